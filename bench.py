@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of ComA's dense hot path on MI355X (contract: see the round brief).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload inpaint|contact]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload inpaint|contact] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Both forms work for N > 1: started as a plain `python bench.py --gpus N` (no WORLD_SIZE in the environment) the script re-executes
@@ -12,7 +12,11 @@ Primary workload (`metric` / `value`, BASELINE.json config 2): SD-1.5 inpaint 51
 (UNet batch 16 with classifier-free guidance), fixed mask.  One "step" = one whole image batch with inputs resident in HBM:
 masked-image VAE encode, 50 x (UNet hipGraph + CFG / DDIM kernel), VAE decode to uint8.  `value` = images/s summed over all ranks
 (weak scaling: independent image batches, no data-path collective), time = MAX over ranks between two barrier + synchronize pairs.
-Further sections on the same line, every rank taking part (only rank 0 prints):
+A plain run sets up, warms up, times the K steps and prints the headline line; nothing else.
+--dump-outputs DIR: after the timed steps, what the primary workload's last step returned is written as DIR/<name>.npy (float32; a
+fixed, seeded sample of any array that would push the total past 64 MB), so that two builds can be compared output for output.
+--full adds, on the same line, the primary workload's roofline (per-launch profile, vendor GEMM, VAE graphs) and these sections,
+every rank taking part (only rank 0 prints):
   secondary        ComA K1-K3 accumulation at config 4's per-GPU slice (H=10475 x O=180 x N=250 bins, 64 samples per step), K steps and
                    then ONE all-reduce(SUM) of the state when N > 1 (timed inside, reported as final_allreduce_ms)
   occupancy        config 5's per-GPU row share (H=1310, R=128, S=2000) through the fused pass + all-reduce(MAX) when N > 1
@@ -96,6 +100,26 @@ def cpu_baseline_inpaint():
                       f"CPU, {torch.get_num_threads()} threads): {dt:.2f} s, EXTRAPOLATED x50 steps; VAE ignored"}
 
 
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, arrays, rank, world):
+    """--dump-outputs: `arrays` (name -> tensor, what the timed path returned in its last step) written as <out_dir>/<name>.npy,
+    float64 kept, everything else as float32; with more than one rank each writes <name>_rank<r>.npy.  An array larger than its share
+    of the 64 MB budget is written as a fixed, seeded sample of its flattened elements: the same positions for the same shape in every
+    run, so dumps of two builds compare element for element."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // (len(arrays) * world) - 1024          # room for the .npy header
+    for name, t in arrays.items():
+        dtype = torch.float64 if t.dtype == torch.float64 else torch.float32
+        a = t.detach()
+        keep = share // (8 if dtype == torch.float64 else 4)
+        if a.numel() > keep:
+            idx = np.unique(np.random.default_rng(0).integers(0, a.numel(), size=keep))
+            a = a.reshape(-1)[torch.from_numpy(idx).to(a.device)]
+        np.save(os.path.join(out_dir, f"{name}_rank{rank}.npy" if world > 1 else f"{name}.npy"), a.to(dtype).cpu().numpy())
+
+
 def bench_inpaint(args, dev, world, rank):
     """BASELINE.json config 2: SD-1.5 inpaint 512x512, 50 DDIM steps, batch 8, fixed mask, CFG 11 (UNet batch 16),
     seeded random fp16 weights of the SD-1.5-inpainting shapes, synthetic prompt embeddings / image / mask.  One step =
@@ -133,12 +157,28 @@ def bench_inpaint(args, dev, world, rank):
     barrier()
     dt = time.perf_counter() - t0
     assert out.shape == (B, 512, 512, 3) and out.dtype == torch.uint8
+    if args.dump_outputs and args.workload == "inpaint":
+        dump_outputs(args.dump_outputs, {"images": out}, rank, world)
     t = torch.tensor([dt], dtype=torch.float64, device=dev)
     if world > 1:
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
     dt = float(t.item())
     res = None
     if rank == 0:
+        value = world * B * args.steps / dt
+        flops_img = (pipe.unet.g.flops * 50 + pipe.vae.dec.g.flops + pipe.vae.enc.g.flops) / B
+        res = {
+            "metric": "HOI images/sec (50-step SD-1.5 inpaint, 512x512, fixed mask, CFG; BASELINE metric part 1)",
+            "value": value, "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f16", "data": "synthetic",
+            "config": {"workload": f"SD-1.5-inpaint 512x512, 50 DDIM steps, batch {B} images per GPU per step (UNet batch {2 * B}), "
+                                   "fixed centred 256^2 mask, guidance 11, 1 VAE encode + 1 VAE decode per image "
+                                   "(BASELINE.json config 2); random-init weights of the SD-1.5-inpainting architecture",
+                       "parallelism": f"independent image batches on {world} GPU(s), no collective"},
+            "tflop_per_image": flops_img / 1e12, "achieved_tflops_whole_loop": value / world * flops_img / 1e12,
+        }
+    if rank == 0 and args.full:
         # roofline of the dominant kernel (the implicit-GEMM conv/linear kernel): per-launch HIP-event timing of the
         # UNet launch list, outside the timed region, same process
         prof = pipe.unet.g.profile(reps=2)
@@ -152,7 +192,6 @@ def bench_inpaint(args, dev, world, rank):
         attn = [(fl, ms) for tag, fl, ms in prof if tag.startswith("attention")]
         tot_ms = sum(ms for _, _, ms in prof)
         g_fl, g_ms = sum(f for f, _ in gemm), sum(m for _, m in gemm)
-        flops_img = (pipe.unet.g.flops * 50 + pipe.vae.dec.g.flops + pipe.vae.enc.g.flops) / B
         vendor = vendor_gemm_reference(dev)
         # the two VAE graphs on their own (outside the timed region): 1 + 1 of them per image in this workload, 21 + 21 per image in the
         # adaptive loop, where they are ~ 43 % of the time
@@ -167,17 +206,7 @@ def bench_inpaint(args, dev, world, rank):
             e.record()
             torch.cuda.synchronize()
             vae_ms[name] = a.elapsed_time(e) / 3
-        value = world * B * args.steps / dt
-        res = {
-            "metric": "HOI images/sec (50-step SD-1.5 inpaint, 512x512, fixed mask, CFG; BASELINE metric part 1)",
-            "value": value, "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f16", "data": "synthetic",
-            "config": {"workload": f"SD-1.5-inpaint 512x512, 50 DDIM steps, batch {B} images per GPU per step (UNet batch {2 * B}), "
-                                   "fixed centred 256^2 mask, guidance 11, 1 VAE encode + 1 VAE decode per image "
-                                   "(BASELINE.json config 2); random-init weights of the SD-1.5-inpainting architecture",
-                       "parallelism": f"independent image batches on {world} GPU(s), no collective"},
-            "tflop_per_image": flops_img / 1e12, "achieved_tflops_whole_loop": value / world * flops_img / 1e12,
+        res.update({
             "roofline": {"bound": "mfma", "kernel": "sd::conv_gemm_kernel<WM,WN,TN,BK,STAGES> (all conv3x3/1x1/linear launches of one UNet forward)",
                          "achieved": g_fl / g_ms / 1e9, "peak": MFMA_F16_PEAK_TFLOPS, "unit": "TFLOP/s",
                          "frac": g_fl / g_ms / 1e9 / MFMA_F16_PEAK_TFLOPS, "launches": n_gemm,
@@ -198,7 +227,7 @@ def bench_inpaint(args, dev, world, rank):
                          "attention": {"achieved": sum(f for f, _ in attn) / sum(m for _, m in attn) / 1e9, "unit": "TFLOP/s"}},
             "vae": dict(vae_ms, batch=B, what="VAE decoder / encoder hipGraph at 512 x 512, HIP events, mean of 3 replays "
                                               "(every ResNet convolution = halo-patch convolution with the GroupNorm + SiLU folded in)"),
-        }
+        })
     del pipe
     torch.cuda.empty_cache()
     return res
@@ -238,7 +267,7 @@ def bench_contact(args, dev, world, rank):
     g0 = torch.Generator(device=dev).manual_seed(99)           # the object is the same on every rank
     on = torch.nn.functional.normalize(torch.randn([O, 3], generator=g0, device=dev), dim=-1)
     ov = on * 0.2 + torch.tensor([0.0, -0.15, 0.3], device=dev)
-    steps, warmup = args.contact_steps, 2
+    steps, warmup = args.contact_steps, (args.warmup if args.workload == "contact" else 2)
 
     def barrier():
         if world > 1:
@@ -267,6 +296,8 @@ def bench_contact(args, dev, world, rank):
         t_ar = time.perf_counter() - t1
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and args.workload == "contact":
+        dump_outputs(args.dump_outputs, {k: getattr(coma, k) for k in coma._STATE_KEYS}, rank, world)
     kern_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
     t = torch.tensor([dt], dtype=torch.float64, device=dev)
     if world > 1:
@@ -550,10 +581,14 @@ def main():
     ap.add_argument("--human-res", type=int, default=10475)
     ap.add_argument("--obj-res", type=int, default=180)
     ap.add_argument("--normal-res", type=int, default=250)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
-    ap.add_argument("--skip", default="", help="comma-separated sections to leave out: occupancy, adaptive (profiling runs: rocprofv3 --pmc "
-                    "segfaults under hipGraph replay on this image, and the adaptive loop always replays graphs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the primary workload's last timed step returned to DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true", help="also measure the primary workload's roofline, the secondary workload, occupancy, "
+                    "the adaptive loops and the CPU baselines (off: a plain run does only what the headline figure needs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: leave out the secondary workload and the further sections")
+    ap.add_argument("--skip", default="", help="with --full: comma-separated sections to leave out: occupancy, adaptive (profiling runs: "
+                    "rocprofv3 --pmc segfaults under hipGraph replay, and the adaptive loop always replays graphs)")
     ap.add_argument("--eager", action="store_true", help="launch kernels one by one instead of replaying the hipGraph "
                     "(profiling aid: rocprofv3 --pmc segfaults under graph replay on this image)")
     ap.add_argument("--ddim-steps", type=int, default=50, help="only for profiling runs; the metric is defined at 50")
@@ -599,8 +634,9 @@ def main():
 
     if args.workload == "contact":
         args.contact_steps = args.steps
-    inp = None if (args.workload == "contact" and args.no_secondary) else bench_inpaint(args, dev, world, rank)
-    con = None if (args.workload == "inpaint" and args.no_secondary) else bench_contact(args, dev, world, rank)
+    secondary = args.full and not args.no_secondary
+    inp = bench_inpaint(args, dev, world, rank) if (args.workload == "inpaint" or secondary) else None
+    con = bench_contact(args, dev, world, rank) if (args.workload == "contact" or secondary) else None
     occ = ada = ada_b1 = ada_pr = None
     skip = set(filter(None, args.skip.split(",")))
     def section(fn):
@@ -623,7 +659,7 @@ def main():
             os._exit(3)
 
     primary_so_far = (inp if args.workload == "inpaint" else con) if rank == 0 else None
-    if not args.no_secondary:          # collective sections: every rank enters them, rank 0 gets the record
+    if secondary:                      # collective sections: every rank enters them, rank 0 gets the record
         if "occupancy" not in skip:
             occ = section(bench_occupancy)
         if "adaptive" not in skip:
@@ -634,15 +670,16 @@ def main():
             if "pointrend" not in skip:
                 ada_pr = section(bench_adaptive_pointrend)
     if rank == 0:
-        primary, secondary = (inp, con) if args.workload == "inpaint" else (con, inp)
+        primary, sec_rec = (inp, con) if args.workload == "inpaint" else (con, inp)
         out = dict(primary)
-        if world == 1 and not args.no_cpu_baseline:
+        cpu = args.full and world == 1 and not args.no_cpu_baseline
+        if cpu:
             out["cpu_baseline"] = cpu_baseline_inpaint() if args.workload == "inpaint" else cpu_baseline()
-        if not args.no_secondary:
+        if secondary:
             out["occupancy"], out["adaptive_loop"], out["adaptive_loop_b1"], out["adaptive_loop_pointrend"] = occ, ada, ada_b1, ada_pr
-        if secondary is not None:
-            sec = dict(secondary)
-            if world == 1 and not args.no_cpu_baseline:
+        if sec_rec is not None:
+            sec = dict(sec_rec)
+            if cpu:
                 sec["cpu_baseline"] = cpu_baseline() if args.workload == "inpaint" else cpu_baseline_inpaint()
             out["secondary"] = sec
         print(json.dumps(out), flush=True)

@@ -10,7 +10,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/prof_$TAG
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-CMD="python $REPO/bench.py --no-cpu-baseline $*"
+CMD="python $REPO/bench.py --full --no-cpu-baseline $*"
 # pass 1: kernel trace + stats (no counters)
 # (the adaptive sections run in child processes since r6, which would write their own trace files over this one: left out here;
 #  the segmentation plan has its own pass below)

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -13,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
         "dtype", "data", "config", "roofline"}
 SMALL = ["--steps", "1", "--warmup", "0", "--ddim-steps", "3", "--contact-steps", "1", "--samples", "4", "--human-res", "512",
-         "--no-cpu-baseline"]
+         "--no-cpu-baseline", "--full"]
 
 
 def _last_json(out):
@@ -38,6 +39,20 @@ def test_single_gpu_line(hip_lib):
     seg = pr["segmentation"]
     assert seg["forward_ms"] > 0 and 0 < seg["roofline"]["frac"] < 1 and seg["roofline"]["peak"] == 157.3
     assert seg["detections_per_image_after_the_last_loop"] == seg["detections_cap"] == 4
+
+
+def test_plain_run_is_the_headline_and_dumps_the_last_step(hip_lib, tmp_path):
+    """Without --full the line carries the primary workload's figure and nothing that needs runs of its own; --dump-outputs writes
+    the images the last timed step returned."""
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "0", "--ddim-steps", "3", "--dump-outputs",
+                        str(tmp_path)], cwd=ROOT, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = _last_json(r.stdout)
+    assert KEYS - {"roofline"} <= set(line) and line["steps"] == 2 and line["value"] > 0
+    assert abs(line["value"] * line["ms_per_step"] / 1e3 - 8) < 1e-6          # 8 images per step, ms_per_step = one of the 2 timed steps
+    assert not {"roofline", "vae", "secondary", "occupancy", "adaptive_loop", "cpu_baseline"} & set(line)
+    img = np.load(tmp_path / "images.npy")
+    assert img.dtype == np.float32 and img.shape == (8, 512, 512, 3) and img.min() >= 0 and img.max() <= 255 and img.std() > 0
 
 
 @pytest.mark.parametrize("launcher", ["torchrun", "self"])

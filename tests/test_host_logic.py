@@ -366,3 +366,19 @@ def test_bench_starts_itself_for_more_than_one_gpu():
     env2 = dict(env, WORLD_SIZE="2", RANK="0", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "4"], cwd=ROOT, env=env2, capture_output=True, text=True, timeout=300)
     assert r.returncode != 0 and "WORLD_SIZE=2" in r.stderr
+
+
+def test_bench_dump_outputs_budget_and_sample(tmp_path):
+    """bench.py --dump-outputs: arrays that fit are written whole as float32 (float64 kept); one that would push the total past 64 MB
+    becomes a seeded sample of its elements, the same positions in every run."""
+    import bench
+    small = torch.arange(24, dtype=torch.uint8).reshape(2, 3, 4)
+    wide = torch.arange(3, dtype=torch.float64)
+    big = torch.arange(10_000_000, dtype=torch.float32)          # 40 MB, every value its own position
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"small": small, "wide": wide, "big": big}, rank=0, world=1)
+    s, w, b = (np.load(tmp_path / "a" / f"{n}.npy") for n in ("small", "wide", "big"))
+    assert s.dtype == np.float32 and np.array_equal(s, small.numpy()) and w.dtype == np.float64 and np.array_equal(w, wide.numpy())
+    assert b.dtype == np.float32 and 0 < b.size < big.numel() and (np.diff(b) > 0).all() and 0 <= b[0] and b[-1] < big.numel()
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64_000_000
+    assert np.array_equal(b, np.load(tmp_path / "b" / "big.npy"))
