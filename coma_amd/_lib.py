@@ -17,6 +17,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # than most of the effects being measured); the product and the tests use the in-tree library
 LIB_PATH = os.environ.get("COMA_HIP_LIB") or os.path.join(_HERE, "libcoma_hip.so")
 ABI_VERSION = 8                  # = COMA_ABI_VERSION of include/coma_hip.h: bumped with every change of the SIGNATURES table below
+# (not for the text-tower functions: they were only added, no existing signature changed, and a library without them is refused by
+# lib() anyway -- getattr of a missing symbol fails)
 
 _lib = None
 
@@ -92,6 +94,9 @@ SIGNATURES = {
     "sd_unet_forward": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "sd_vae_decode": (_i, [_vp, _vp, _vp, _vp]),
     "sd_vae_encode": (_i, [_vp, _vp, _vp, _vp]),
+    "sd_text_encode": (_i, [_vp, _vp, _vp, _vp]),
+    "sd_text_embed_f16": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp]),
+    "sd_attention_causal_f16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp]),
     "sd_mask_adapt_batched": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _d, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     # include/seg_hip.h
     "seg_conv_gemm_f32": (_i, [_vp, _vp]),

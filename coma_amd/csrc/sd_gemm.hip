@@ -15,7 +15,7 @@
 // 128 x 64 to 256 x 320 / 512 x 128 (table at the kernel).  K tiles of 32 or 64 reach LDS by LDS-DMA
 // (`buffer_load_dwordx4 ... offen lds`) into unpadded XOR-swizzled rows, 2-4 stages with counted vmcnt waits and one raw
 // s_barrier per K tile; zero padding is the buffer range check.  The epilogue fuses bias, per-(batch) bias (time
-// embedding), residual add, SiLU, GEGLU (value/gate columns interleaved per wave at weight-prep time) and, on request,
+// embedding), residual add, SiLU / quick GELU, GEGLU (value/gate columns interleaved per wave at weight-prep time) and, on request,
 // per-32-row column sums / sums of squares of the stored tensor (the consumer's GroupNorm statistics).
 #include <hip/hip_fp16.h>
 
@@ -88,6 +88,7 @@ __device__ __forceinline__ void dbg_stamp(const GemmArgs& g, int slot) {
 }
 
 __device__ __forceinline__ float silu(float x) { return x / (1.0f + __expf(-x)); }
+__device__ __forceinline__ float quick_gelu(float x) { return x / (1.0f + __expf(-1.702f * x)); }     // x * sigmoid(1.702 x) (CLIP MLP)
 // gelu_erf2: see sd_gelu.h
 __device__ __forceinline__ int kappa16(int j) { return (j & ~12) | ((j & 4) << 1) | ((j & 8) >> 1); }
 // SD_EPI_PERM32_N: position p = 8g + e of every group of 32 columns holds key 16 (e >> 2) + 4g + (e & 3)
@@ -98,6 +99,7 @@ __device__ __forceinline__ float epilogue_value(const GemmArgs& g, float v, int 
   if (g.bias) v += (float)g.bias[(g.epi & SD_EPI_BIAS_ROWS) ? row : col];
   if (g.bias_bn) v += (float)g.bias_bn[(long long)(row / g.rows_per_batch) * g.ldbb + col];
   if (g.epi & SD_EPI_SILU) v = silu(v);
+  if (g.epi & SD_EPI_QUICK_GELU) v = quick_gelu(v);
   if (resp) v += (float)resp[(long long)row * g.ldr + col];
   return v;
 }
@@ -350,6 +352,10 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, AccQ accq, _Flo
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] = silu(v[e]);
           }
+          if (g.epi & SD_EPI_QUICK_GELU) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = quick_gelu(v[e]);
+          }
           if (resp) {
             const half8 r8 = __builtin_bit_cast(half8, pf[t][k]);
 #pragma unroll
@@ -446,6 +452,10 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, AccQ accq, _Flo
           if (g.epi & SD_EPI_SILU) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] = silu(v[e]);
+          }
+          if (g.epi & SD_EPI_QUICK_GELU) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = quick_gelu(v[e]);
           }
           if (resp) {
             const half8 r8 = *reinterpret_cast<const half8*>(resp + (long long)row * g.ldr + col);
@@ -975,6 +985,8 @@ extern "C" int sd_conv_gemm_f16(const sd_conv_gemm_desc* d_in, void* stream) {
   const bool geglu = (d->epi & SD_EPI_GEGLU) != 0;
   g.ldo = d->ldo > 0 ? d->ldo : (geglu ? d->n / 2 : d->n);
   g.sa = d->stride_a; g.sw = d->stride_w; g.so = d->stride_out; g.sr = d->stride_res;
+  if ((d->epi & SD_EPI_QUICK_GELU) && (d->epi & (SD_EPI_GEGLU | SD_EPI_SILU)))
+    return fail(COMA_E_INVALID, "sd_conv_gemm_f16: SD_EPI_QUICK_GELU takes no GEGLU / SiLU");
   if (geglu && (d->n % 128 != 0 || d->bias_bn || d->res))
     return fail(COMA_E_INVALID, "sd_conv_gemm_f16: GEGLU needs N %% 128 == 0 and no residual / batch bias");
   // ---- tile configuration

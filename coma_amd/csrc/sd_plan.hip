@@ -9,8 +9,8 @@
 // constants) to ONE file; sd_model_load rebuilds all of it in library-owned device memory, so that a caller without Python runs
 //     sd_model_load("unet.sdm", &m); sd_unet_set_context(m, ctx, s); sd_unet_forward(m, x_in, t, eps, s);
 // replaces: the nn.Module objects the reference pipeline calls -- self.unet(...) (utils/adaptive_mask_inpainting.py:1001-1007),
-// self.vae.decode (:1086, :1112), self.vae.encode (:677-680).  Which layer follows which is decided by whoever records the plan
-// (coma_amd/sd/unet.py, vae.py); the library owns execution.
+// self.vae.decode (:1086, :1112), self.vae.encode (:677-680), self.text_encoder (:459-482).  Which layer follows which is decided by
+// whoever records the plan (coma_amd/sd/unet.py, vae.py, text.py); the library owns execution.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -135,6 +135,11 @@ static int launch(const PlanRec& r, void* st) {
                                  (int)i[6], p[5], (int)i[7], (float*)p[6], st);
     case PK_CONV_C3:
       return sd_conv3x3_c3_f16(p[0], (int)i[0], p[1], p[2], (int)i[1], (int)i[2], (int)i[3], (int)i[4], p[3], (int)i[5], (float*)p[4], st);
+    case PK_TEXT_EMBED:
+      return sd_text_embed_f16((const int32_t*)p[0], (int)i[0], (int)i[1], p[1], (int)i[2], p[2], (int)i[3], (int)i[4], p[3], st);
+    case PK_ATTN_CAUSAL:
+      return sd_attention_causal_f16(p[0], p[1], p[2], p[3], (int)i[0], (int)i[1], (int)i[2], (int)i[3], (int)i[4], (int)i[5], (int)i[6], (int)i[7],
+                                     (float)f[0], st);
     case PK_COPY:
       return sd_copy_d2d(p[0], p[1], (size_t)i[0], st);
     case PK_SEG:
@@ -521,4 +526,7 @@ extern "C" int sd_vae_decode(void* model, const void* z, void* image_out, void* 
 }
 extern "C" int sd_vae_encode(void* model, const void* image, void* moments_out, void* stream) {
   return sd::forward(model, "encode", "x", image, nullptr, nullptr, "moments", moments_out, stream);
+}
+extern "C" int sd_text_encode(void* model, const int32_t* ids, void* out, void* stream) {
+  return sd::forward(model, "text", "ids", ids, nullptr, nullptr, "text_out", out, stream);
 }

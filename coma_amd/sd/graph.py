@@ -214,8 +214,8 @@ class LaunchGraph:
                      tag=f"groupnorm B={batch} hw={hw} C={c0 + c1}")
         return out
 
-    def layernorm(self, x, gamma, beta, out, *, rows, c):
-        self.add(lambda: ops.layernorm(x, gamma, beta, out, rows=rows, c=c), tag=f"layernorm rows={rows} C={c}")
+    def layernorm(self, x, gamma, beta, out, *, rows, c, eps=1e-5):
+        self.add(lambda: ops.layernorm(x, gamma, beta, out, rows=rows, c=c, eps=eps), tag=f"layernorm rows={rows} C={c}")
         return out
 
     def attention(self, q, k, vt, out, *, batch, heads, lq, lk, d, ldq, ldk, ldv, ldo, vt_perm16=False):
@@ -288,6 +288,18 @@ class LaunchGraph:
                                           colstats=cs, ldo=out.shape[-1]),
                  flops=2 * batch * hw * n * 9 * c, tag=f"conv3x3(halo) B={batch} {h}x{w_} C={c} n={n}",
                  nbytes=2 * batch * hw * (c + n * (2 if res is not None else 1)) + 2 * n * 9 * c)
+        return out
+
+    def attention_causal(self, q, k, v, out, *, seqs, heads, len_, d, ldq, ldk, ldv, ldo):
+        self.add(lambda: ops.attention_causal(q, k, v, out, seqs=seqs, heads=heads, len_=len_, d=d, ldq=ldq, ldk=ldk, ldv=ldv, ldo=ldo,
+                                              scale=d ** -0.5),
+                 flops=2 * seqs * heads * len_ * (len_ + 1) * d, tag=f"attention(causal) S={seqs} h={heads} L={len_} d={d}")
+        return out
+
+    def text_embed(self, ids, tok_emb, pos_emb, out, *, seqs, len_):
+        vocab, width = tok_emb.shape
+        self.add(lambda: ops.text_embed(ids, tok_emb, pos_emb, out, seqs=seqs, len_=len_, vocab=vocab, n_pos=pos_emb.shape[0], width=width),
+                 tag=f"text embedding S={seqs} L={len_} C={width}", nbytes=2 * 2 * seqs * len_ * width)
         return out
 
     def attention_wide(self, q, k, vt, out, *, batch, heads, lq, lk, d, ldq, ldk, ldv, ldo):

@@ -116,3 +116,6 @@ class SdModel:
 
     def vae_encode(self, image=None, moments_out=None):
         _lib.check(_lib.lib().sd_vae_encode(self.h, self._ptr(image), self._ptr(moments_out), _lib.stream_ptr(self.device)), "sd_vae_encode")
+
+    def text_encode(self, ids=None, out=None):
+        _lib.check(_lib.lib().sd_text_encode(self.h, self._ptr(ids), self._ptr(out), _lib.stream_ptr(self.device)), "sd_text_encode")

@@ -8,7 +8,7 @@ import torch
 
 from .. import _lib
 
-EPI_NONE, EPI_GEGLU, EPI_SILU, EPI_BIAS_ROWS, EPI_PERM16_N, EPI_PERM32_N = 0, 1, 2, 4, 8, 16
+EPI_NONE, EPI_GEGLU, EPI_SILU, EPI_BIAS_ROWS, EPI_PERM16_N, EPI_PERM32_N, EPI_QUICK_GELU = 0, 1, 2, 4, 8, 16, 32
 F16 = torch.float16
 
 
@@ -99,6 +99,23 @@ def attention(q, k, vt, out, *, batch, heads, lq, lk, d, ldq, ldk, ldv, ldo, sca
     rc = _lib.lib().sd_attention_f16(_p(q, "q"), _p(k, "k"), _p(vt, "vt"), _p(out, "out"), batch, heads, lq, lk, d, ldq, ldk,
                                      ldv, ldo, scale, flags, _stream(out))
     _lib.check(rc, "sd_attention_f16")
+    return out
+
+
+def attention_causal(q, k, v, out, *, seqs, heads, len_, d, ldq, ldk, ldv, ldo, scale):
+    """Causal self-attention of the text tower (d = 64, len_ <= 128); q / k / v are views of one fused product (their first element
+    pointers are what the kernel reads, each with its own leading dimension), V not transposed."""
+    rc = _lib.lib().sd_attention_causal_f16(_p(q, "q"), _p(k, "k"), _p(v, "v"), _p(out, "out"), seqs, heads, len_, d, ldq, ldk, ldv, ldo, scale,
+                                            _stream(out))
+    _lib.check(rc, "sd_attention_causal_f16")
+    return out
+
+
+def text_embed(ids, tok_emb, pos_emb, out, *, seqs, len_, vocab, n_pos, width):
+    """out[s * len_ + p] = tok_emb[ids[s, p]] + pos_emb[p] (ids int32; the kernel clamps ids into [0, vocab))."""
+    rc = _lib.lib().sd_text_embed_f16(_p(ids, "ids", torch.int32), seqs, len_, _p(tok_emb, "tok_emb"), vocab, _p(pos_emb, "pos_emb"), n_pos, width,
+                                      _p(out, "out"), _stream(out))
+    _lib.check(rc, "sd_text_embed_f16")
     return out
 
 

@@ -10,10 +10,13 @@ plugin itself:
   * the x0 decode runs only on steps where the mask is actually re-estimated (or the visualiser is on): the
     reference decodes every step (:1028) but consumes the image only there (:1031, :1051) -- outputs are identical;
   * dilation (cv2.dilate 3x3 x k == (2k+1)^2 box max), AND with the default mask, binarisation, masked image and the
-    nearest 8x mask down-sample are one kernel (sd_mask_adapt); the re-encode is the VAE-encoder graph.
-Third-party pieces that cannot exist offline (CLIP text encoder, PointRend / SAM) stay plug-ins: prompts can be
-given as ``prompt_embeds`` / ``negative_prompt_embeds`` and any callable ``image_u8_HWC -> {"mask": u8[H,W], ...}``
-can be registered as the mask model.
+    nearest 8x mask down-sample are one kernel (sd_mask_adapt); the re-encode is the VAE-encoder graph;
+  * the CLIP text tower of a real checkpoint is transformers' CLIPTextModel when transformers imports (as in the reference), and
+    otherwise our own recorded tower (coma_amd/sd/text.py: HipCLIPTextModel, a hipGraph of HIP kernels) with the built-in CLIP BPE
+    tokenizer (coma_amd/sd/tokenizer.py); either pair can also be passed as ``text_encoder=`` / ``tokenizer=``.
+Prompts can also be given as ``prompt_embeds`` / ``negative_prompt_embeds`` (the random-weight path has no tokenizer), and the
+third-party mask model (PointRend / SAM) stays a plug-in: any callable ``image_u8_HWC -> {"mask": u8[H,W], ...}`` can be
+registered as the mask model.
 """
 from __future__ import annotations
 
@@ -235,11 +238,24 @@ class AdaptiveMaskInpaintPipeline:
         sch = DDIMScheduler(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear", clip_sample=False,
                             set_alpha_to_one=False)
         tok = enc = None
-        if os.path.isdir(os.path.join(weights_dir, "text_encoder")) and os.path.isdir(os.path.join(weights_dir, "tokenizer")):
-            # the checkpoint's own CLIP text tower (transformers; third party, as in the reference :26, :459-482)
-            from transformers import CLIPTextModel, CLIPTokenizer
-            tok = CLIPTokenizer.from_pretrained(os.path.join(weights_dir, "tokenizer"))
-            enc = CLIPTextModel.from_pretrained(os.path.join(weights_dir, "text_encoder"), torch_dtype=torch.float16).to(dev).eval()
+        text_dir, tok_dir = os.path.join(weights_dir, "text_encoder"), os.path.join(weights_dir, "tokenizer")
+        if os.path.isdir(text_dir) and os.path.isdir(tok_dir):
+            # the checkpoint's own CLIP text tower: transformers' when it imports (third party, as in the reference :26, :459-482),
+            # else the device tower recorded from the same files and the built-in tokenizer
+            try:
+                from transformers import CLIPTextModel, CLIPTokenizer
+            except ImportError:
+                CLIPTextModel = CLIPTokenizer = None
+            if CLIPTextModel is not None:
+                tok = CLIPTokenizer.from_pretrained(tok_dir)
+                enc = CLIPTextModel.from_pretrained(text_dir, torch_dtype=torch.float16).to(dev).eval()
+                print("text encoder: transformers CLIPTextModel (eager fp16)", flush=True)
+            else:
+                from .text import HipCLIPTextModel
+                from .tokenizer import CLIPTokenizer as BuiltinCLIPTokenizer
+                tok = BuiltinCLIPTokenizer.from_pretrained(tok_dir)
+                enc = HipCLIPTextModel.from_pretrained(text_dir, capacity=batch_size, device=dev)
+                print("text encoder: HipCLIPTextModel (device tower; transformers is not importable)", flush=True)
         return cls(vae, unet, sch, text_encoder=enc, tokenizer=tok, device=dev)
 
     def to(self, device):

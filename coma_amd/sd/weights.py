@@ -16,6 +16,9 @@ UNET_CFG = dict(in_channels=9, out_channels=4, block_out_channels=(320, 640, 128
                 down_has_attn=(True, True, True, False), up_has_attn=(False, True, True, True))
 VAE_CFG = dict(latent_channels=4, block_out_channels=(128, 256, 512, 512), layers_per_block=2, groups=32,
                scaling_factor=0.18215)
+# the SD-1.x text tower (transformers CLIPTextModel, `text_encoder/config.json` of every SD-1.5 checkpoint)
+TEXT_CFG = dict(vocab_size=49408, hidden_size=768, intermediate_size=3072, num_hidden_layers=12, num_attention_heads=12,
+                max_position_embeddings=77, hidden_act="quick_gelu", layer_norm_eps=1e-5)
 
 
 # ------------------------------------------------------------------ shape tables
@@ -137,6 +140,80 @@ def vae_shapes(cfg=VAE_CFG):
     s["encoder.conv_out.weight"] = (2 * lc, ch[-1], 3, 3)
     s["encoder.conv_out.bias"] = (2 * lc,)
     return s
+
+
+def check_text_config(config):
+    """The text tower the kernels were built for: CLIPTextModel with quick_gelu, heads of 64 and at most 128 positions (sd_attention_causal_f16).
+    Anything else (SD-2's OpenCLIP tower: gelu, 1024 wide) is a ValueError.  Returns the config with the defaults of TEXT_CFG filled in."""
+    cfg = dict(TEXT_CFG)
+    cfg.update({k: v for k, v in dict(config).items() if k in TEXT_CFG or k in ("architectures", "model_type")})
+    arch = cfg.get("architectures")
+    if arch is not None and not any(a in ("CLIPTextModel", "CLIPTextModelWithProjection") for a in arch):
+        raise ValueError(f"text encoder: unsupported architecture {arch} (only CLIPTextModel)")
+    if cfg.get("model_type", "clip_text_model") not in ("clip_text_model", "clip"):
+        raise ValueError(f"text encoder: unsupported model_type {cfg['model_type']!r} (only clip_text_model)")
+    if cfg["hidden_act"] != "quick_gelu":
+        raise ValueError(f"text encoder: hidden_act {cfg['hidden_act']!r} is not supported (only quick_gelu, the SD-1.x CLIP tower)")
+    C, H = int(cfg["hidden_size"]), int(cfg["num_attention_heads"])
+    if H <= 0 or C % H or C // H != 64:
+        raise ValueError(f"text encoder: head dim {C / max(H, 1):g} is not supported (hidden {C} / {H} heads must be 64)")
+    if not 1 <= int(cfg["max_position_embeddings"]) <= 128:
+        raise ValueError(f"text encoder: {cfg['max_position_embeddings']} positions are not supported (at most 128)")
+    if C > 2048 or int(cfg["intermediate_size"]) % 64 or int(cfg["intermediate_size"]) <= 0:
+        raise ValueError(f"text encoder: hidden {C} / intermediate {cfg['intermediate_size']} not supported (hidden <= 2048, intermediate % 64 == 0)")
+    if int(cfg["num_hidden_layers"]) <= 0 or int(cfg["vocab_size"]) <= 0:
+        raise ValueError("text encoder: no layers or an empty vocabulary")
+    return cfg
+
+
+def text_shapes(config=TEXT_CFG):
+    """CLIPTextModel parameters under transformers' key names WITHOUT the `text_model.` prefix (position_ids is a buffer, not listed)."""
+    cfg = check_text_config(config)
+    C, I = cfg["hidden_size"], cfg["intermediate_size"]
+    s = {"embeddings.token_embedding.weight": (cfg["vocab_size"], C),
+         "embeddings.position_embedding.weight": (cfg["max_position_embeddings"], C),
+         "final_layer_norm.weight": (C,), "final_layer_norm.bias": (C,)}
+    for i in range(cfg["num_hidden_layers"]):
+        p = f"encoder.layers.{i}"
+        for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
+            s[f"{p}.self_attn.{n}.weight"] = (C, C)
+            s[f"{p}.self_attn.{n}.bias"] = (C,)
+        for n in ("layer_norm1", "layer_norm2"):
+            s[f"{p}.{n}.weight"] = (C,)
+            s[f"{p}.{n}.bias"] = (C,)
+        s[f"{p}.mlp.fc1.weight"] = (I, C)
+        s[f"{p}.mlp.fc1.bias"] = (I,)
+        s[f"{p}.mlp.fc2.weight"] = (C, I)
+        s[f"{p}.mlp.fc2.bias"] = (C,)
+    return s
+
+
+def strip_text_prefix(state):
+    """Real SD-1.5 repositories store `text_model.<key>`; transformers 5 `save_pretrained` writes `<key>`: both map to `<key>`."""
+    return {(k[len("text_model."):] if k.startswith("text_model.") else k): v for k, v in state.items()}
+
+
+def load_text_encoder(text_dir, device="cpu", dtype=torch.float16):
+    """(config, state) of a checkpoint's `text_encoder/`: config.json, then model.safetensors or else pytorch_model.bin (read with
+    torch.load(weights_only=True)); fp16 or fp32 tensors, keys with or without `text_model.`, position_ids ignored.  A wrong architecture,
+    a missing tensor or one of another shape is a ValueError."""
+    import json
+    import os
+    with open(os.path.join(text_dir, "config.json")) as f:
+        cfg = check_text_config(json.load(f))
+    st_path, bin_path = os.path.join(text_dir, "model.safetensors"), os.path.join(text_dir, "pytorch_model.bin")
+    if os.path.exists(st_path):
+        from safetensors.torch import load_file
+        raw = load_file(st_path)
+    elif os.path.exists(bin_path):
+        raw = torch.load(bin_path, map_location="cpu", weights_only=True)
+    else:
+        raise ValueError(f"text encoder: neither model.safetensors nor pytorch_model.bin in {text_dir}")
+    state = check_state(strip_text_prefix(raw), text_shapes(cfg), "CLIP text encoder")
+    for k, v in state.items():
+        if v.dtype not in (torch.float16, torch.float32):
+            raise ValueError(f"text encoder: {k} is {v.dtype} (fp16 or fp32 expected)")
+    return cfg, {k: v.to(dtype).to(device) for k, v in state.items()}
 
 
 # ------------------------------------------------------------------ seeded random parameters

@@ -34,6 +34,7 @@ extern "C" {
                                columns whose source row is >= n hold a clamped finite row */
 #define SD_EPI_PERM32_N 16  /* position p = 8g + e of every group of 32 output columns holds the product with W row 16 (e >> 2) + 4g + (e & 3):
                                the V^T layout sd_attention_wide_f16 reads (one 16-byte LDS load per 16x16x32 MFMA operand).  n % 32 == 0 */
+#define SD_EPI_QUICK_GELU 32 /* out = a * sigmoid(1.702 a), a = acc + bias (CLIP's quick_gelu, fc1 of the text tower); not with GEGLU / SiLU */
 /* bits 20..27 select kernel variants for tuning runs (scripts/time_gemm.py): 20 = generic 128x128 tiles only, 21 = 128x320
  * tile, 22 = tile DMA in one burst, 23 = 4-wave 128x320 tile, 24..27 = forced split-K factor, 28 = tap-major K order for 3x3.  Results agree to
  * fp32 summation order.  Process-wide overrides for A/B runs inside a captured graph (read once): SD_GEMM_TUNE / SD_GEMM_TUNE_1X1 / SD_GEMM_TUNE_3X3 =
@@ -137,6 +138,25 @@ int sd_attention_f16(const void* q, const void* k, const void* vt, void* out, in
  * tiles of 64 keys alternate through two single-buffered 64 KB LDS regions.  out = softmax(q k^T * scale) v. */
 int sd_attention_wide_f16(const void* q, const void* k, const void* vt, void* out, int batch, int heads, int lq, int lk, int d,
                           int ldq, int ldk, int ldv, int ldo, float scale, void* stream);
+
+/* Token + position embedding of the CLIP text tower: out fp16 [seqs * len, width], row s * len + p = tok_emb[ids[s, p]] + pos_emb[p]
+ * (summed in fp32, rounded once).  ids int32 [seqs, len]; tok_emb fp16 [vocab, width]; pos_emb fp16 [n_pos, width] (n_pos >= len);
+ * width % 8 == 0, tables and output 16-byte aligned.  Ids out of [0, vocab): the KERNEL clamps every id into [0, vocab), so a bad id
+ * can never read outside the table; the Python host (coma_amd/sd/text.py) rejects such ids before they reach the device.
+ * replaces: CLIPTextEmbeddings (token_embedding + position_embedding) inside transformers' CLIPTextModel,
+ *           utils/adaptive_mask_inpainting.py:459-482. */
+int sd_text_embed_f16(const int32_t* ids, int seqs, int len, const void* tok_emb, int vocab, const void* pos_emb, int n_pos, int width,
+                      void* out, void* stream);
+
+/* Causal multi-head self-attention over short sequences (the CLIP text tower): for every sequence s, head h and query i < len,
+ *   out[s*len + i, h*d : (h+1)*d] = sum_{j <= i} softmax_j(scale * q_i . k_j) v_j
+ * with q / k / v read in place from [seqs * len, ld*] fp16 matrices (head h at columns [h*d, (h+1)*d)) -- typically the three column
+ * blocks of ONE fused q|k|v product, each with its own leading dimension; V is NOT transposed.  d = 64, 1 <= len <= 128, ld* >= heads*d,
+ * ldq / ldk / ldv multiples of 8, q / k / v 16-byte aligned.  One workgroup per (sequence, head), K and V staged in LDS, fp32 scores and
+ * an exact masked softmax over the whole row, fp16 output; keys after i are never read (the result at i does not depend on them).
+ * A separate kernel from sd_attention_f16 (the UNet's).  replaces: CLIPAttention with the causal mask inside CLIPTextModel. */
+int sd_attention_causal_f16(const void* q, const void* k, const void* v, void* out, int seqs, int heads, int len, int d, int ldq, int ldk,
+                            int ldv, int ldo, float scale, void* stream);
 
 /* Only the per-(sample, channel) affine table of a GroupNorm: fp32 [batch][c0][2] = (scale, shift) at the start of `stats` (same
  * scratch size as sd_groupnorm_f16), from the producer's column sums (colstats0 != NULL: fp32 [batch * hw / rows_per_slot][2][c0], rows_per_slot
@@ -323,7 +343,7 @@ int sd_mask_adapt_batched(const uint8_t* seg, const uint8_t* default_mask, int b
  * Models: the launch list and the hipGraph of a network live in the library (coma_amd/csrc/sd_plan.hip).
  * A model = a registry of device buffers + named bindings (inputs / outputs) + named plans (recorded launch lists).
  * Recording: between sd_model_record_begin and sd_model_record_end every sd_* LAUNCH entry point called on the thread
- * (sd_conv_gemm_f16, sd_groupnorm*_f16, sd_layernorm_f16, sd_attention_f16, sd_softmax_f16,
+ * (sd_conv_gemm_f16, sd_groupnorm*_f16, sd_layernorm_f16, sd_attention_f16, sd_attention_causal_f16, sd_text_embed_f16, sd_softmax_f16,
  * sd_timestep_embedding_f16, sd_copy_d2d) appends its arguments to the plan instead of launching; arguments are validated when
  * the plan first runs.  sd_model_run launches the list eagerly on `stream`; sd_model_replay captures it once into a hipGraph (on a
  * private stream, nothing executes during capture) and launches the graph on `stream`.
@@ -351,7 +371,7 @@ int sd_model_load(const char* path, void** model);
 /* dst[0:bytes) = src[0:bytes), device to device, on `stream` (recordable: the duplicated CFG halves of the UNet). */
 int sd_copy_d2d(void* dst, const void* src, size_t bytes, void* stream);
 
-/* The three networks of the inpainting loop as entry points over a model (recorded by coma_amd/sd/{unet,vae}.py or loaded from a
+/* The four networks of the inpainting loop as entry points over a model (recorded by coma_amd/sd/{unet,vae,text}.py or loaded from a
  * file).  Inputs are copied device-to-device into the model's bound buffers, the plan's hipGraph is launched, the result is copied
  * out; a NULL input / output pointer means "already in place / leave it in the bound buffer" (sd_model_binding gives the address).
  *   sd_unet_set_context  plan "context": ctx fp16 [2B,77,768] -> cross-attention K / V^T of every block   (once per prompt)
@@ -362,11 +382,15 @@ int sd_copy_d2d(void* dst, const void* src, size_t bytes, void* stream);
  *   sd_vae_decode        plan "decode":  z fp16 [B, h*w, 64] (4 valid channels, already divided by scaling_factor)
  *                                        -> image fp16 [B*8h*8w, 64] (3 valid channels)     replaces: self.vae.decode, :1086, :1112
  *   sd_vae_encode        plan "encode":  x fp16 [B, H*W, 64] (3 valid channels in [-1,1]) -> moments fp16 [B*h*w, 64] (mean 4 | logvar 4)
- *                                        replaces: self.vae.encode(image).latent_dist (before .sample), :677-680 */
+ *                                        replaces: self.vae.encode(image).latent_dist (before .sample), :677-680
+ *   sd_text_encode       plan "text":    ids int32 [S, 77] (S = the capacity the model was recorded at) -> text_out fp16 [S, 77, 768]
+ *                                        (last_hidden_state of the CLIP text tower: the UNet context of sd_unet_set_context)
+ *                                        replaces: self.text_encoder(text_input_ids)[0], :459-482 */
 int sd_unet_set_context(void* model, const void* ctx, void* stream);
 int sd_unet_forward(void* model, const void* x_in, const float* timesteps, void* eps_out, void* stream);
 int sd_vae_decode(void* model, const void* z, void* image_out, void* stream);
 int sd_vae_encode(void* model, const void* image, void* moments_out, void* stream);
+int sd_text_encode(void* model, const int32_t* ids, void* out, void* stream);
 
 #ifdef __cplusplus
 }
