@@ -831,15 +831,7 @@ using namespace sd;
 
 extern "C" int sd_attention_f16(const void* q, const void* k, const void* vt, void* out, int batch, int heads, int lq,
                                 int lk, int d, int ldq, int ldk, int ldv, int ldo, float scale, int vt_perm16, void* stream) {
-  if (sd::plan_recording()) {
-    sd::PlanRec r{};
-    r.kind = sd::PK_ATTN;
-    r.p[0] = (void*)q; r.p[1] = (void*)k; r.p[2] = (void*)vt; r.p[3] = out;
-    const int64_t is[10] = {batch, heads, lq, lk, d, ldq, ldk, ldv, ldo, vt_perm16};
-    for (int j = 0; j < 10; ++j) r.i[j] = is[j];
-    r.f[0] = scale;
-    return sd::plan_record(r);
-  }
+  if (sd::plan_recording()) return sd::record<sd::PK_ATTN>(q, k, vt, out, batch, heads, lq, lk, d, ldq, ldk, ldv, ldo, scale, vt_perm16);
   if (!q || !k || !vt || !out) return fail(COMA_E_INVALID, "sd_attention_f16: null pointer");
   if (batch <= 0 || heads <= 0 || lq <= 0 || lk <= 0) return fail(COMA_E_INVALID, "sd_attention_f16: bad sizes");
   if (d % 8 || d <= 0 || d > 160) return fail(COMA_E_INVALID, "sd_attention_f16: head dim %d unsupported (multiple of 8, <= 160)", d);
@@ -897,15 +889,7 @@ extern "C" int sd_attention_f16(const void* q, const void* k, const void* vt, vo
 
 extern "C" int sd_attention_wide_f16(const void* q, const void* k, const void* vt, void* out, int batch, int heads, int lq, int lk, int d,
                                      int ldq, int ldk, int ldv, int ldo, float scale, void* stream) {
-  if (sd::plan_recording()) {
-    sd::PlanRec r{};
-    r.kind = sd::PK_ATTN_WIDE;
-    r.p[0] = (void*)q; r.p[1] = (void*)k; r.p[2] = (void*)vt; r.p[3] = out;
-    const int64_t is[9] = {batch, heads, lq, lk, d, ldq, ldk, ldv, ldo};
-    for (int j = 0; j < 9; ++j) r.i[j] = is[j];
-    r.f[0] = scale;
-    return sd::plan_record(r);
-  }
+  if (sd::plan_recording()) return sd::record<sd::PK_ATTN_WIDE>(q, k, vt, out, batch, heads, lq, lk, d, ldq, ldk, ldv, ldo, scale);
   if (!q || !k || !vt || !out) return fail(COMA_E_INVALID, "sd_attention_wide_f16: null pointer");
   if (batch <= 0 || heads <= 0 || lq <= 0 || lk <= 0 || lk % BKV) return fail(COMA_E_INVALID, "sd_attention_wide_f16: bad sizes (lk must be a multiple of 64)");
   if (d != 512 && d != 256 && d != 128) return fail(COMA_E_INVALID, "sd_attention_wide_f16: head dim %d unsupported (128, 256 or 512)", d);

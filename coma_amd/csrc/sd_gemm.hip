@@ -868,22 +868,7 @@ extern "C" int sd_debug_timestamps(unsigned long long* host_dst, int n_blocks) {
 }
 
 extern "C" int sd_conv_gemm_f16(const sd_conv_gemm_desc* d_in, void* stream) {
-  if (sd::plan_recording()) {
-    if (!d_in) return sd::fail(COMA_E_INVALID, "sd_conv_gemm_f16: null descriptor");
-    const sd_conv_gemm_desc& d = *d_in;
-    sd::PlanRec r{};
-    r.kind = sd::PK_CONV;
-    void* ps[10] = {(void*)d.a0, (void*)d.a1, (void*)d.w, (void*)d.bias, (void*)d.bias_bn, (void*)d.res, d.out, d.workspace, d.colstats, d.out_t};
-    for (int k = 0; k < 10; ++k) r.p[k] = ps[k];
-    const int64_t is[22] = {d.c0, d.c1, d.batch, d.in_h, d.in_w, d.out_h, d.out_w, d.taps, d.stride, d.upsample, d.pad, d.n, d.ldbb, d.ldr, d.ldo,
-                            d.epi, d.nbatch_z, d.stride_a, d.stride_w, d.stride_out, d.stride_res, (int64_t)d.workspace_bytes};
-    for (int k = 0; k < 22; ++k) r.i[k] = is[k];
-    if (d.out_t && (d.n_split < 0 || d.n_split >= (1 << 20) || d.ldo_t < 0 || d.ldo_t >= (1 << 20) || d.rows_per_sample < 0 || d.rows_per_sample >= (1 << 20)))
-      return sd::fail(COMA_E_INVALID, "sd_conv_gemm_f16: out_t sizes out of range");
-    if (d.phase < 0 || d.phase > 4) return sd::fail(COMA_E_INVALID, "sd_conv_gemm_f16: phase must be 0..4");
-    r.i[22] = (int64_t)d.n_split | ((int64_t)d.ldo_t << 20) | ((int64_t)d.rows_per_sample << 40) | ((int64_t)d.phase << 60);    // three 20-bit fields + the phase
-    return sd::plan_record(r);
-  }
+  if (sd::plan_recording()) return sd::record_conv(d_in);
   if (!d_in) return fail(COMA_E_INVALID, "sd_conv_gemm_f16: null descriptor");
   // SD_GEMM_TUNE=<mask> (or _1X1 / _3X3 for those launches only): OR tuning-knob bits (SD_EPI_TUNING_MASK) into every launch -- lets a dispatch rule be A/B-tested inside the
   // captured UNet (scripts/time_unet.py), where cache state differs from a layer timed alone (profiles/r02_notes.md section 14)

@@ -408,13 +408,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(HaloArgs a) {
 extern "C" int sd_conv3x3_halo_f16(const void* x, int c, const float* gn_affine, int silu, const void* w, const void* bias, const void* res,
                                    int ldr, int batch, int h, int w_, int n, void* out, int ldo, float* colstats, void* stream) {
   using namespace sd::hc;
-  if (sd::plan_recording()) {
-    sd::PlanRec r{};
-    r.kind = sd::PK_CONV_HALO;
-    r.p[0] = (void*)x; r.p[1] = (void*)gn_affine; r.p[2] = (void*)w; r.p[3] = (void*)bias; r.p[4] = (void*)res; r.p[5] = out; r.p[6] = colstats;
-    r.i[0] = c; r.i[1] = silu; r.i[2] = ldr; r.i[3] = batch; r.i[4] = h; r.i[5] = w_; r.i[6] = n; r.i[7] = ldo;
-    return sd::plan_record(r);
-  }
+  if (sd::plan_recording()) return sd::record<sd::PK_CONV_HALO>(x, c, gn_affine, silu, w, bias, res, ldr, batch, h, w_, n, out, ldo, colstats);
   if (!x || !w || !out) return fail(COMA_E_INVALID, "sd_conv3x3_halo_f16: null pointer");
   if (n <= 0 || n % kN || n > 4 * kN) return fail(COMA_E_INVALID, "sd_conv3x3_halo_f16: n = %d (built for 128, 256, 384 and 512 output channels)", n);
   if (c <= 0 || c % kChunk || c > kMaxC) return fail(COMA_E_INVALID, "sd_conv3x3_halo_f16: c = %d (a multiple of 64, at most %d)", c, kMaxC);

@@ -451,13 +451,7 @@ using namespace sd;
 // scratch layout (floats): [batch*C*2] affine table, then [batch*nchunk*groups*2] partial sums
 extern "C" int sd_groupnorm_f16(const void* x0, const void* x1, int c0, int c1, int batch, int hw, int groups, float eps,
                                 const void* gamma, const void* beta, int silu, void* out, float* stats, void* stream) {
-  if (sd::plan_recording()) {
-    sd::PlanRec r{};
-    r.kind = sd::PK_GN;
-    r.p[0] = (void*)x0; r.p[1] = (void*)x1; r.p[2] = (void*)gamma; r.p[3] = (void*)beta; r.p[4] = out; r.p[5] = stats;
-    r.i[0] = c0; r.i[1] = c1; r.i[2] = batch; r.i[3] = hw; r.i[4] = groups; r.i[5] = silu; r.f[0] = eps;
-    return sd::plan_record(r);
-  }
+  if (sd::plan_recording()) return sd::record<sd::PK_GN>(x0, x1, c0, c1, batch, hw, groups, eps, gamma, beta, silu, out, stats);
   if (!x0 || !gamma || !beta || !out || !stats) return fail(COMA_E_INVALID, "sd_groupnorm_f16: null pointer");
   if (c1 > 0 && !x1) return fail(COMA_E_INVALID, "sd_groupnorm_f16: x1 missing");
   const int C = c0 + c1;
@@ -484,12 +478,7 @@ extern "C" int sd_groupnorm_f16(const void* x0, const void* x1, int c0, int c1, 
 
 extern "C" int sd_layernorm_f16(const void* x, int64_t rows, int c, float eps, const void* gamma, const void* beta,
                                 void* out, void* stream) {
-  if (sd::plan_recording()) {
-    sd::PlanRec r{};
-    r.kind = sd::PK_LN;
-    r.p[0] = (void*)x; r.p[1] = (void*)gamma; r.p[2] = (void*)beta; r.p[3] = out; r.i[0] = rows; r.i[1] = c; r.f[0] = eps;
-    return sd::plan_record(r);
-  }
+  if (sd::plan_recording()) return sd::record<sd::PK_LN>(x, rows, c, eps, gamma, beta, out);
   if (!x || !gamma || !beta || !out) return fail(COMA_E_INVALID, "sd_layernorm_f16: null pointer");
   if (rows <= 0 || c <= 0 || c % 8 || c > 2048) return fail(COMA_E_INVALID, "sd_layernorm_f16: bad shape c=%d", c);
 #define SD_LN_LAUNCH(R_, CH_)                                                                                                  \
@@ -513,12 +502,7 @@ extern "C" int sd_layernorm_f16(const void* x, int64_t rows, int c, float eps, c
 }
 
 extern "C" int sd_softmax_f16(void* x, int64_t rows, int n, int ld, float scale, void* stream) {
-  if (sd::plan_recording()) {
-    sd::PlanRec r{};
-    r.kind = sd::PK_SOFTMAX;
-    r.p[0] = x; r.i[0] = rows; r.i[1] = n; r.i[2] = ld; r.f[0] = scale;
-    return sd::plan_record(r);
-  }
+  if (sd::plan_recording()) return sd::record<sd::PK_SOFTMAX>(x, rows, n, ld, scale);
   if (!x) return fail(COMA_E_INVALID, "sd_softmax_f16: null pointer");
   if (rows <= 0 || n <= 0 || ld < n) return fail(COMA_E_INVALID, "sd_softmax_f16: bad shape");
   hipLaunchKernelGGL(softmax_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, (_Float16*)x, n, ld, scale);
@@ -528,14 +512,8 @@ extern "C" int sd_softmax_f16(void* x, int64_t rows, int n, int ld, float scale,
 extern "C" int sd_groupnorm_colstats_f16(const void* x0, const void* x1, int c0, int c1, int batch, int hw, int groups, float eps,
                                          const void* gamma, const void* beta, int silu, void* out, float* stats,
                                          const float* colstats0, const float* colstats1, void* stream) {
-  if (sd::plan_recording()) {
-    sd::PlanRec r{};
-    r.kind = sd::PK_GN_COLSTATS;
-    r.p[0] = (void*)x0; r.p[1] = (void*)x1; r.p[2] = (void*)gamma; r.p[3] = (void*)beta; r.p[4] = out; r.p[5] = stats;
-    r.p[6] = (void*)colstats0; r.p[7] = (void*)colstats1;
-    r.i[0] = c0; r.i[1] = c1; r.i[2] = batch; r.i[3] = hw; r.i[4] = groups; r.i[5] = silu; r.f[0] = eps;
-    return sd::plan_record(r);
-  }
+  if (sd::plan_recording()) return sd::record<sd::PK_GN_COLSTATS>(x0, x1, c0, c1, batch, hw, groups, eps, gamma, beta, silu, out, stats, colstats0,
+                                                                  colstats1);
   if (!x0 || !gamma || !beta || !out || !stats || !colstats0) return fail(COMA_E_INVALID, "sd_groupnorm_colstats_f16: null pointer");
   if (c1 > 0 && (!x1 || !colstats1)) return fail(COMA_E_INVALID, "sd_groupnorm_colstats_f16: second source incomplete");
   const int C = c0 + c1;
@@ -556,13 +534,7 @@ extern "C" int sd_groupnorm_colstats_f16(const void* x0, const void* x1, int c0,
 // affine themselves (sd_xfront_f16).
 extern "C" int sd_groupnorm_table_f16(const void* x0, int c0, int batch, int hw, int groups, float eps, const void* gamma, const void* beta,
                                       float* stats, const float* colstats0, int rows_per_slot, void* stream) {
-  if (sd::plan_recording()) {
-    sd::PlanRec r{};
-    r.kind = sd::PK_GN_TABLE;
-    r.p[0] = (void*)x0; r.p[1] = (void*)gamma; r.p[2] = (void*)beta; r.p[3] = stats; r.p[4] = (void*)colstats0;
-    r.i[0] = c0; r.i[1] = batch; r.i[2] = hw; r.i[3] = groups; r.i[4] = rows_per_slot; r.f[0] = eps;
-    return sd::plan_record(r);
-  }
+  if (sd::plan_recording()) return sd::record<sd::PK_GN_TABLE>(x0, c0, batch, hw, groups, eps, gamma, beta, stats, colstats0, rows_per_slot);
   if (!x0 || !gamma || !beta || !stats) return fail(COMA_E_INVALID, "sd_groupnorm_table_f16: null pointer");
   if (rows_per_slot == 0) rows_per_slot = 32;
   const int C = c0;
@@ -590,13 +562,7 @@ extern "C" int sd_groupnorm_table_f16(const void* x0, int c0, int batch, int hw,
 // (sd_winograd_input_f16 with gn_affine: norm1 of the UNet's up-block ResNets, whose input is [hidden | skip]).
 extern "C" int sd_groupnorm_table_cat_f16(int c0, int c1, int batch, int hw, int groups, float eps, const void* gamma, const void* beta, float* stats,
                                           const float* colstats0, const float* colstats1, void* stream) {
-  if (sd::plan_recording()) {
-    sd::PlanRec r{};
-    r.kind = sd::PK_GN_TABLE_CAT;
-    r.p[0] = (void*)gamma; r.p[1] = (void*)beta; r.p[2] = stats; r.p[3] = (void*)colstats0; r.p[4] = (void*)colstats1;
-    r.i[0] = c0; r.i[1] = c1; r.i[2] = batch; r.i[3] = hw; r.i[4] = groups; r.f[0] = eps;
-    return sd::plan_record(r);
-  }
+  if (sd::plan_recording()) return sd::record<sd::PK_GN_TABLE_CAT>(c0, c1, batch, hw, groups, eps, gamma, beta, stats, colstats0, colstats1);
   if (!gamma || !beta || !stats || !colstats0 || (c1 > 0 && !colstats1)) return fail(COMA_E_INVALID, "sd_groupnorm_table_cat_f16: null pointer");
   const int C = c0 + c1;
   if (batch <= 0 || hw <= 0 || hw % 32 || groups <= 0 || groups > GN_MAX_GROUPS || c0 <= 0 || c1 < 0 || C % groups || c0 % 8 || c1 % 8 || C > GN_MAX_C ||

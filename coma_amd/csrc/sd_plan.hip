@@ -68,84 +68,153 @@ static void drop_graph(Plan& p) {
   p.graph = nullptr;
 }
 
-// ---- replay of one record: the public entry point with its arguments unpacked (this thread is not recording here)
-static int launch(const PlanRec& r, void* st) {
+// ---- the records that do not follow argument order: pack and unpack side by side
+// PK_CONV: the descriptor; n_split, ldo_t, rows_per_sample (20 bits each) and the phase (3 bits) share i[22]
+int record_conv(const sd_conv_gemm_desc* d_in) {
+  if (!d_in) return fail(COMA_E_INVALID, "sd_conv_gemm_f16: null descriptor");
+  const sd_conv_gemm_desc& d = *d_in;
+  PlanRec r{};
+  r.kind = PK_CONV;
+  void* ps[10] = {(void*)d.a0, (void*)d.a1, (void*)d.w, (void*)d.bias, (void*)d.bias_bn, (void*)d.res, d.out, d.workspace, d.colstats, d.out_t};
+  for (int k = 0; k < 10; ++k) r.p[k] = ps[k];
+  const int64_t is[22] = {d.c0, d.c1, d.batch, d.in_h, d.in_w, d.out_h, d.out_w, d.taps, d.stride, d.upsample, d.pad, d.n, d.ldbb, d.ldr, d.ldo,
+                          d.epi, d.nbatch_z, d.stride_a, d.stride_w, d.stride_out, d.stride_res, (int64_t)d.workspace_bytes};
+  for (int k = 0; k < 22; ++k) r.i[k] = is[k];
+  if (d.out_t && (d.n_split < 0 || d.n_split >= (1 << 20) || d.ldo_t < 0 || d.ldo_t >= (1 << 20) || d.rows_per_sample < 0 || d.rows_per_sample >= (1 << 20)))
+    return fail(COMA_E_INVALID, "sd_conv_gemm_f16: out_t sizes out of range");
+  if (d.phase < 0 || d.phase > 4) return fail(COMA_E_INVALID, "sd_conv_gemm_f16: phase must be 0..4");
+  r.i[22] = (int64_t)d.n_split | ((int64_t)d.ldo_t << 20) | ((int64_t)d.rows_per_sample << 40) | ((int64_t)d.phase << 60);
+  return plan_record(r);
+}
+static int replay_conv(const PlanRec& r, void* st) {
+  void* const* p = r.p;
+  const int64_t* i = r.i;
+  sd_conv_gemm_desc d;
+  memset(&d, 0, sizeof d);
+  d.a0 = p[0]; d.a1 = p[1]; d.w = p[2]; d.bias = p[3]; d.bias_bn = p[4]; d.res = p[5]; d.out = p[6]; d.workspace = p[7];
+  d.colstats = (float*)p[8];
+  d.c0 = (int)i[0]; d.c1 = (int)i[1]; d.batch = (int)i[2]; d.in_h = (int)i[3]; d.in_w = (int)i[4]; d.out_h = (int)i[5]; d.out_w = (int)i[6];
+  d.taps = (int)i[7]; d.stride = (int)i[8]; d.upsample = (int)i[9]; d.pad = (int)i[10]; d.n = (int)i[11]; d.ldbb = (int)i[12];
+  d.ldr = (int)i[13]; d.ldo = (int)i[14]; d.epi = (int)i[15]; d.nbatch_z = (int)i[16]; d.stride_a = i[17]; d.stride_w = i[18];
+  d.stride_out = i[19]; d.stride_res = i[20]; d.workspace_bytes = (size_t)i[21];
+  d.out_t = p[9]; d.n_split = (int)(i[22] & 0xfffff); d.ldo_t = (int)((i[22] >> 20) & 0xfffff); d.rows_per_sample = (int)((i[22] >> 40) & 0xfffff);
+  d.phase = (int)((i[22] >> 60) & 7);
+  return sd_conv_gemm_f16(&d, st);
+}
+
+// SEG_OP_CONV: the descriptor
+int record_seg_conv(const seg_conv_desc* d) {
+  PlanRec r{};
+  r.kind = PK_SEG;
+  r.i[0] = SEG_OP_CONV;
+  r.p[0] = (void*)d->x; r.p[1] = (void*)d->w; r.p[2] = (void*)d->bias; r.p[3] = (void*)d->res; r.p[4] = d->out; r.p[5] = (void*)d->m_dev;
+  r.i[1] = d->batch; r.i[2] = d->in_h; r.i[3] = d->in_w; r.i[4] = d->c; r.i[5] = d->ldx; r.i[6] = d->n; r.i[7] = d->kpad; r.i[8] = d->kh;
+  r.i[9] = d->kw; r.i[10] = d->stride; r.i[11] = d->pad; r.i[12] = d->out_h; r.i[13] = d->out_w; r.i[14] = d->ldr; r.i[15] = d->res_mode;
+  r.i[16] = d->ldo; r.i[17] = d->relu; r.i[18] = d->rows_per_item; r.i[19] = d->tile; r.i[20] = d->unit_rows;
+  r.p[6] = d->workspace; r.i[21] = d->split_k; r.i[22] = (int64_t)d->workspace_bytes;
+  return plan_record(r);
+}
+static int replay_seg_conv(const PlanRec& r, void* st) {
+  void* const* p = r.p;
+  const int64_t* i = r.i;
+  seg_conv_desc d{};
+  d.x = p[0]; d.w = p[1]; d.bias = p[2]; d.res = p[3]; d.out = p[4]; d.m_dev = p[5];
+  d.batch = (int)i[1]; d.in_h = (int)i[2]; d.in_w = (int)i[3]; d.c = (int)i[4]; d.ldx = (int)i[5]; d.n = (int)i[6]; d.kpad = (int)i[7]; d.kh = (int)i[8];
+  d.kw = (int)i[9]; d.stride = (int)i[10]; d.pad = (int)i[11]; d.out_h = (int)i[12]; d.out_w = (int)i[13]; d.ldr = (int)i[14]; d.res_mode = (int)i[15];
+  d.ldo = (int)i[16]; d.relu = (int)i[17]; d.rows_per_item = (int)i[18]; d.tile = (int)i[19]; d.unit_rows = (int)i[20];
+  d.workspace = p[6]; d.split_k = (int)i[21]; d.workspace_bytes = (size_t)i[22];
+  return seg_conv_gemm_f32(&d, st);
+}
+
+// SEG_OP_RPN_SELECT_LEVELS: host arrays of 1 .. 6 levels (the caller checked n_levels), copied into fixed slots
+int record_rpn_select_levels(const void* const* preds, const void* const* cell_anchors, const int* fh, const int* fw, int n_levels, int first_stride,
+                             int ld, int batch, int pre_topk, float img_h, float img_w, int cap, void* cand_keys, void* cand_boxes,
+                             void* cand_group, void* key_scratch) {
+  PlanRec r{};
+  r.kind = PK_SEG;
+  r.i[0] = SEG_OP_RPN_SELECT_LEVELS;
+  for (int l = 0; l < n_levels; ++l) { r.p[l] = (void*)preds[l]; r.p[6 + l] = (void*)cell_anchors[l]; r.i[8 + l] = fh[l]; r.i[14 + l] = fw[l]; }
+  r.p[12] = cand_keys; r.p[13] = cand_boxes; r.p[14] = cand_group; r.p[15] = key_scratch;
+  r.i[1] = n_levels; r.i[2] = first_stride; r.i[3] = ld; r.i[4] = batch; r.i[5] = pre_topk; r.i[6] = cap; r.f[0] = img_h; r.f[1] = img_w;
+  return plan_record(r);
+}
+static int replay_rpn_select_levels(const PlanRec& r, void* st) {
   void* const* p = r.p;
   const int64_t* i = r.i;
   const double* f = r.f;
+  const void* preds[6]; const void* cells[6]; int fh[6], fw[6];
+  for (int l = 0; l < (int)i[1]; ++l) { preds[l] = p[l]; cells[l] = p[6 + l]; fh[l] = (int)i[8 + l]; fw[l] = (int)i[14 + l]; }
+  return seg_rpn_select_levels(preds, cells, fh, fw, (int)i[1], (int)i[2], (int)i[3], (int)i[4], (int)i[5], (float)f[0], (float)f[1], (int)i[6], p[12], p[13],
+                               p[14], p[15], st);
+}
+
+// PK_WINO_IN: v in p[2], gn_affine in p[3] -- the reverse of argument order
+int winograd_input_stored(const void* x0, const void* x1, void* v, const float* gn_affine, int c0, int c1, int batch, int h, int w, int upsample,
+                          int silu, float vscale, void* stream) {
+  return sd_winograd_input_f16(x0, x1, c0, c1, batch, h, w, upsample, gn_affine, silu, vscale, v, stream);
+}
+
+// PK_XCHAIN: debug_out / debug_stage are not recorded; a replay passes nullptr, 0
+int xattn_chain_stored(const void* attn1_out, const void* h, const void* wo1, const void* bo1, const void* gamma2, const void* beta2,
+                       const void* wq2, const void* k2, const void* vt2, const void* wo2, const void* bo2, const void* gamma3, const void* beta3,
+                       void* h2, void* n3, int64_t rows, int rows_per_sample, int lk, int ldv2, float eps, void* stream) {
+  return sd_xattn_chain_f16(attn1_out, h, wo1, bo1, gamma2, beta2, wq2, k2, vt2, wo2, bo2, gamma3, beta3, h2, n3, rows, rows_per_sample, lk, ldv2,
+                            eps, nullptr, 0, stream);
+}
+
+// ---- replay of one record: the public entry point with its arguments unpacked (this thread is not recording here).  One line per
+// kind / SEG_OP_*: replay<> calls the entry<> of sd_plan.h, the hand-written records their unpack above.
+static int launch_seg(const PlanRec& r, void* st) {
+  const int op = (int)r.i[0];
+  switch (op) {
+    case SEG_OP_CONV: return replay_seg_conv(r, st);
+    case SEG_OP_RESIZE: return replay<PK_SEG, SEG_OP_RESIZE>(r, st);
+    case SEG_OP_MAXPOOL: return replay<PK_SEG, SEG_OP_MAXPOOL>(r, st);
+    case SEG_OP_SUBSAMPLE: return replay<PK_SEG, SEG_OP_SUBSAMPLE>(r, st);
+    case SEG_OP_MEMSET: return replay<PK_SEG, SEG_OP_MEMSET>(r, st);
+    case SEG_OP_RPN_SELECT: return replay<PK_SEG, SEG_OP_RPN_SELECT>(r, st);
+    case SEG_OP_SORT: return replay<PK_SEG, SEG_OP_SORT>(r, st);
+    case SEG_OP_NMS: return replay<PK_SEG, SEG_OP_NMS>(r, st);
+    case SEG_OP_ROI_ALIGN: return replay<PK_SEG, SEG_OP_ROI_ALIGN>(r, st);
+    case SEG_OP_BOX_PREDICT: return replay<PK_SEG, SEG_OP_BOX_PREDICT>(r, st);
+    case SEG_OP_FINALIZE: return replay<PK_SEG, SEG_OP_FINALIZE>(r, st);
+    case SEG_OP_POINT_SAMPLE: return replay<PK_SEG, SEG_OP_POINT_SAMPLE>(r, st);
+    case SEG_OP_UPSAMPLE2X: return replay<PK_SEG, SEG_OP_UPSAMPLE2X>(r, st);
+    case SEG_OP_TOPK_POINTS: return replay<PK_SEG, SEG_OP_TOPK_POINTS>(r, st);
+    case SEG_OP_POINT_LOGIT: return replay<PK_SEG, SEG_OP_POINT_LOGIT>(r, st);
+    case SEG_OP_PASTE: return replay<PK_SEG, SEG_OP_PASTE>(r, st);
+    case SEG_OP_RPN_SELECT_LEVELS: return replay_rpn_select_levels(r, st);
+    default: return fail(COMA_E_INVALID, "seg plan: unknown operator %d", op);
+  }
+}
+
+static int launch(const PlanRec& r, void* st) {
   switch (r.kind) {
-    case PK_CONV: {
-      sd_conv_gemm_desc d;
-      memset(&d, 0, sizeof d);
-      d.a0 = p[0]; d.a1 = p[1]; d.w = p[2]; d.bias = p[3]; d.bias_bn = p[4]; d.res = p[5]; d.out = p[6]; d.workspace = p[7];
-      d.colstats = (float*)p[8];
-      d.c0 = (int)i[0]; d.c1 = (int)i[1]; d.batch = (int)i[2]; d.in_h = (int)i[3]; d.in_w = (int)i[4]; d.out_h = (int)i[5]; d.out_w = (int)i[6];
-      d.taps = (int)i[7]; d.stride = (int)i[8]; d.upsample = (int)i[9]; d.pad = (int)i[10]; d.n = (int)i[11]; d.ldbb = (int)i[12];
-      d.ldr = (int)i[13]; d.ldo = (int)i[14]; d.epi = (int)i[15]; d.nbatch_z = (int)i[16]; d.stride_a = i[17]; d.stride_w = i[18];
-      d.stride_out = i[19]; d.stride_res = i[20]; d.workspace_bytes = (size_t)i[21];
-      d.out_t = p[9]; d.n_split = (int)(i[22] & 0xfffff); d.ldo_t = (int)((i[22] >> 20) & 0xfffff); d.rows_per_sample = (int)((i[22] >> 40) & 0xfffff);
-      d.phase = (int)((i[22] >> 60) & 7);
-      return sd_conv_gemm_f16(&d, st);
-    }
-    case PK_GN:
-      return sd_groupnorm_f16(p[0], p[1], (int)i[0], (int)i[1], (int)i[2], (int)i[3], (int)i[4], (float)f[0], p[2], p[3], (int)i[5], p[4],
-                              (float*)p[5], st);
-    case PK_GN_COLSTATS:
-      return sd_groupnorm_colstats_f16(p[0], p[1], (int)i[0], (int)i[1], (int)i[2], (int)i[3], (int)i[4], (float)f[0], p[2], p[3], (int)i[5],
-                                       p[4], (float*)p[5], (const float*)p[6], (const float*)p[7], st);
-    case PK_LN:
-      return sd_layernorm_f16(p[0], i[0], (int)i[1], (float)f[0], p[1], p[2], p[3], st);
-    case PK_ATTN:
-      return sd_attention_f16(p[0], p[1], p[2], p[3], (int)i[0], (int)i[1], (int)i[2], (int)i[3], (int)i[4], (int)i[5], (int)i[6], (int)i[7],
-                              (int)i[8], (float)f[0], (int)i[9], st);
-    case PK_SOFTMAX:
-      return sd_softmax_f16(p[0], i[0], (int)i[1], (int)i[2], (float)f[0], st);
-    case PK_TEMB:
-      return sd_timestep_embedding_f16((const float*)p[0], (int)i[0], (int)i[1], p[1], st);
-    case PK_ATTN_WIDE:
-      return sd_attention_wide_f16(p[0], p[1], p[2], p[3], (int)i[0], (int)i[1], (int)i[2], (int)i[3], (int)i[4], (int)i[5], (int)i[6], (int)i[7],
-                                   (int)i[8], (float)f[0], st);
-    case PK_XCHAIN:
-      return sd_xattn_chain_f16(p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], p[9], p[10], p[11], p[12], p[13], p[14], i[0], (int)i[1],
-                                (int)i[2], (int)i[3], (float)f[0], nullptr, 0, st);
-    case PK_XFRONT:
-      return sd_xfront_f16(p[0], (const float*)p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], p[9], p[10], i[0], (int)i[1], (int)i[2], (float)f[0], st);
-    case PK_GN_TABLE:
-      return sd_groupnorm_table_f16(p[0], (int)i[0], (int)i[1], (int)i[2], (int)i[3], (float)f[0], p[1], p[2], (float*)p[3], (const float*)p[4], (int)i[4], st);
-    case PK_XTAIL:
-      return sd_xtail_f16(p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], p[9], (float*)p[10], i[0], st);
-    case PK_CONV_SMALL_N:
-      return sd_conv3x3_small_n_f16(p[0], (const float*)p[1], (int)i[0], p[2], p[3], (int)i[1], (int)i[2], (int)i[3], (int)i[4], (int)i[5], p[4],
-                                    (int)i[6], st);
-    case PK_WINO_IN:
-      return sd_winograd_input_f16(p[0], p[1], (int)i[0], (int)i[1], (int)i[2], (int)i[3], (int)i[4], (int)i[5], (const float*)p[3], (int)i[6], (float)f[0], p[2], st);
-    case PK_WINO_OUT:
-      return sd_winograd_output_f16(p[0], (int)i[0], (int)i[1], (int)i[2], (int)i[3], (int)i[4], p[1], p[2], (int)i[5], p[3], (int)i[6], p[4],
-                                    (int)i[7], (int)i[8], (float)f[0], (float*)p[5], st);
-    case PK_GN_WINO_IN:
-      return sd_gn_winograd_input_f16(p[0], p[1], (int)i[0], (int)i[1], p[2], (int)i[2], p[3], p[4], (int)i[3], (int)i[4], (int)i[5], (int)i[6],
-                                      (int)i[7], (float)f[0], p[5], p[6], (int)i[8], (float)f[1], p[7], st);
-    case PK_IM2COL_C3:
-      return sd_im2col3x3_c3_f16(p[0], (int)i[0], (int)i[1], (int)i[2], (int)i[3], p[1], st);
-    case PK_GN_TABLE_CAT:
-      return sd_groupnorm_table_cat_f16((int)i[0], (int)i[1], (int)i[2], (int)i[3], (int)i[4], (float)f[0], p[0], p[1], (float*)p[2], (const float*)p[3],
-                                        (const float*)p[4], st);
-    case PK_CONV_HALO:
-      return sd_conv3x3_halo_f16(p[0], (int)i[0], (const float*)p[1], (int)i[1], p[2], p[3], p[4], (int)i[2], (int)i[3], (int)i[4], (int)i[5],
-                                 (int)i[6], p[5], (int)i[7], (float*)p[6], st);
-    case PK_CONV_C3:
-      return sd_conv3x3_c3_f16(p[0], (int)i[0], p[1], p[2], (int)i[1], (int)i[2], (int)i[3], (int)i[4], p[3], (int)i[5], (float*)p[4], st);
-    case PK_TEXT_EMBED:
-      return sd_text_embed_f16((const int32_t*)p[0], (int)i[0], (int)i[1], p[1], (int)i[2], p[2], (int)i[3], (int)i[4], p[3], st);
-    case PK_ATTN_CAUSAL:
-      return sd_attention_causal_f16(p[0], p[1], p[2], p[3], (int)i[0], (int)i[1], (int)i[2], (int)i[3], (int)i[4], (int)i[5], (int)i[6], (int)i[7],
-                                     (float)f[0], st);
-    case PK_COPY:
-      return sd_copy_d2d(p[0], p[1], (size_t)i[0], st);
-    case PK_SEG:
-      return seg_replay(r, st);
-    default:
-      return fail(COMA_E_INVALID, "sd plan: unknown launch kind %d", r.kind);
+    case PK_CONV: return replay_conv(r, st);
+    case PK_GN: return replay<PK_GN>(r, st);
+    case PK_GN_COLSTATS: return replay<PK_GN_COLSTATS>(r, st);
+    case PK_LN: return replay<PK_LN>(r, st);
+    case PK_ATTN: return replay<PK_ATTN>(r, st);
+    case PK_SOFTMAX: return replay<PK_SOFTMAX>(r, st);
+    case PK_TEMB: return replay<PK_TEMB>(r, st);
+    case PK_COPY: return replay<PK_COPY>(r, st);
+    case PK_ATTN_WIDE: return replay<PK_ATTN_WIDE>(r, st);
+    case PK_XCHAIN: return replay<PK_XCHAIN>(r, st);
+    case PK_XFRONT: return replay<PK_XFRONT>(r, st);
+    case PK_GN_TABLE: return replay<PK_GN_TABLE>(r, st);
+    case PK_XTAIL: return replay<PK_XTAIL>(r, st);
+    case PK_CONV_SMALL_N: return replay<PK_CONV_SMALL_N>(r, st);
+    case PK_WINO_IN: return replay<PK_WINO_IN>(r, st);
+    case PK_WINO_OUT: return replay<PK_WINO_OUT>(r, st);
+    case PK_GN_WINO_IN: return replay<PK_GN_WINO_IN>(r, st);
+    case PK_IM2COL_C3: return replay<PK_IM2COL_C3>(r, st);
+    case PK_GN_TABLE_CAT: return replay<PK_GN_TABLE_CAT>(r, st);
+    case PK_CONV_HALO: return replay<PK_CONV_HALO>(r, st);
+    case PK_CONV_C3: return replay<PK_CONV_C3>(r, st);
+    case PK_SEG: return launch_seg(r, st);
+    case PK_TEXT_EMBED: return replay<PK_TEXT_EMBED>(r, st);
+    case PK_ATTN_CAUSAL: return replay<PK_ATTN_CAUSAL>(r, st);
+    default: return fail(COMA_E_INVALID, "sd plan: unknown launch kind %d", r.kind);
   }
 }
 
@@ -165,11 +234,7 @@ static Model* as_model(void* m) { return static_cast<Model*>(m); }
 using namespace sd;
 
 extern "C" int sd_copy_d2d(void* dst, const void* src, size_t bytes, void* stream) {
-  if (plan_recording()) {
-    PlanRec r{};
-    r.kind = PK_COPY; r.p[0] = dst; r.p[1] = const_cast<void*>(src); r.i[0] = (int64_t)bytes;
-    return plan_record(r);
-  }
+  if (plan_recording()) return record<PK_COPY>(dst, src, bytes);
   if (!dst || !src || bytes == 0) return fail(COMA_E_INVALID, "sd_copy_d2d: bad args");
   if (hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess)
     return fail(COMA_E_LAUNCH, "sd_copy_d2d: hipMemcpyAsync failed");

@@ -306,13 +306,7 @@ __global__ __launch_bounds__(256) void conv3x3_c3_kernel(const _Float16* __restr
 extern "C" int sd_conv3x3_small_n_f16(const void* x, const float* gn_affine, int silu, const void* w, const void* bias, int batch, int h,
                                       int w_, int c, int n, void* out, int ldo, void* stream) {
   using namespace sd::sc;
-  if (sd::plan_recording()) {
-    sd::PlanRec r{};
-    r.kind = sd::PK_CONV_SMALL_N;
-    r.p[0] = (void*)x; r.p[1] = (void*)gn_affine; r.p[2] = (void*)w; r.p[3] = (void*)bias; r.p[4] = out;
-    r.i[0] = silu; r.i[1] = batch; r.i[2] = h; r.i[3] = w_; r.i[4] = c; r.i[5] = n; r.i[6] = ldo;
-    return sd::plan_record(r);
-  }
+  if (sd::plan_recording()) return sd::record<sd::PK_CONV_SMALL_N>(x, gn_affine, silu, w, bias, batch, h, w_, c, n, out, ldo);
   if (!x || !w || !out) return fail(COMA_E_INVALID, "sd_conv3x3_small_n_f16: null pointer");
   if (c != 128 && c != 320) return fail(COMA_E_INVALID, "sd_conv3x3_small_n_f16: c = %d (built for 128 and 320 input channels)", c);
   if (n < 1 || n > 4 || batch <= 0 || h <= 0 || w_ <= 0 || ldo < 8 || ldo % 8)
@@ -330,12 +324,7 @@ extern "C" int sd_conv3x3_small_n_f16(const void* x, const float* gn_affine, int
 
 extern "C" int sd_im2col3x3_c3_f16(const void* x, int ldx, int batch, int h, int w_, void* out, void* stream) {
   using namespace sd::sc;
-  if (sd::plan_recording()) {
-    sd::PlanRec r{};
-    r.kind = sd::PK_IM2COL_C3;
-    r.p[0] = (void*)x; r.p[1] = out; r.i[0] = ldx; r.i[1] = batch; r.i[2] = h; r.i[3] = w_;
-    return sd::plan_record(r);
-  }
+  if (sd::plan_recording()) return sd::record<sd::PK_IM2COL_C3>(x, ldx, batch, h, w_, out);
   if (!x || !out) return fail(COMA_E_INVALID, "sd_im2col3x3_c3_f16: null pointer");
   if (ldx < 4 || ldx % 4 || batch <= 0 || h <= 0 || w_ <= 0) return fail(COMA_E_INVALID, "sd_im2col3x3_c3_f16: bad shape ldx=%d batch=%d h=%d w=%d", ldx, batch, h, w_);
   const long long M = (long long)batch * h * w_;
@@ -348,13 +337,7 @@ extern "C" int sd_im2col3x3_c3_f16(const void* x, int ldx, int batch, int h, int
 extern "C" int sd_conv3x3_c3_f16(const void* x, int ldx, const void* w32, const void* bias, int batch, int h, int w_, int n, void* out, int ldo,
                                  float* colstats, void* stream) {
   using namespace sd::sc;
-  if (sd::plan_recording()) {
-    sd::PlanRec r{};
-    r.kind = sd::PK_CONV_C3;
-    r.p[0] = (void*)x; r.p[1] = (void*)w32; r.p[2] = (void*)bias; r.p[3] = out; r.p[4] = colstats;
-    r.i[0] = ldx; r.i[1] = batch; r.i[2] = h; r.i[3] = w_; r.i[4] = n; r.i[5] = ldo;
-    return sd::plan_record(r);
-  }
+  if (sd::plan_recording()) return sd::record<sd::PK_CONV_C3>(x, ldx, w32, bias, batch, h, w_, n, out, ldo, colstats);
   if (!x || !w32 || !out) return fail(COMA_E_INVALID, "sd_conv3x3_c3_f16: null pointer");
   if (n != 128) return fail(COMA_E_INVALID, "sd_conv3x3_c3_f16: n = %d (built for 128 output channels)", n);
   if (ldx < 4 || ldx % 4 || batch <= 0 || batch > 65535 || h <= 0 || w_ <= 0 || h % kTile || w_ % kTile || ldo < n || ldo % 8)

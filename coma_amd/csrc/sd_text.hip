@@ -124,13 +124,7 @@ static_assert(PK_TEXT_EMBED == PK_SEG + 1 && PK_ATTN_CAUSAL == PK_SEG + 2 && PK_
 
 extern "C" int sd_text_embed_f16(const int32_t* ids, int seqs, int len, const void* tok_emb, int vocab, const void* pos_emb, int n_pos,
                                  int width, void* out, void* stream) {
-  if (plan_recording()) {
-    PlanRec r{};
-    r.kind = PK_TEXT_EMBED;
-    r.p[0] = (void*)ids; r.p[1] = (void*)tok_emb; r.p[2] = (void*)pos_emb; r.p[3] = out;
-    r.i[0] = seqs; r.i[1] = len; r.i[2] = vocab; r.i[3] = n_pos; r.i[4] = width;
-    return plan_record(r);
-  }
+  if (plan_recording()) return record<PK_TEXT_EMBED>(ids, seqs, len, tok_emb, vocab, pos_emb, n_pos, width, out);
   if (!ids || !tok_emb || !pos_emb || !out) return fail(COMA_E_INVALID, "sd_text_embed_f16: null pointer");
   if (seqs <= 0 || len <= 0 || vocab <= 0 || n_pos < len || width <= 0 || width % 8)
     return fail(COMA_E_INVALID, "sd_text_embed_f16: bad sizes (seqs=%d len=%d vocab=%d n_pos=%d width=%d; n_pos >= len, width %% 8 == 0)", seqs, len,
@@ -144,13 +138,7 @@ extern "C" int sd_text_embed_f16(const int32_t* ids, int seqs, int len, const vo
 
 extern "C" int sd_attention_causal_f16(const void* q, const void* k, const void* v, void* out, int seqs, int heads, int len, int d, int ldq,
                                        int ldk, int ldv, int ldo, float scale, void* stream) {
-  if (plan_recording()) {
-    PlanRec r{};
-    r.kind = PK_ATTN_CAUSAL;
-    r.p[0] = (void*)q; r.p[1] = (void*)k; r.p[2] = (void*)v; r.p[3] = out;
-    r.i[0] = seqs; r.i[1] = heads; r.i[2] = len; r.i[3] = d; r.i[4] = ldq; r.i[5] = ldk; r.i[6] = ldv; r.i[7] = ldo; r.f[0] = scale;
-    return plan_record(r);
-  }
+  if (plan_recording()) return record<PK_ATTN_CAUSAL>(q, k, v, out, seqs, heads, len, d, ldq, ldk, ldv, ldo, scale);
   if (!q || !k || !v || !out) return fail(COMA_E_INVALID, "sd_attention_causal_f16: null pointer");
   if (d != CA_D) return fail(COMA_E_INVALID, "sd_attention_causal_f16: head dim must be %d (got %d)", CA_D, d);
   if (len < 1 || len > CA_MAXL) return fail(COMA_E_INVALID, "sd_attention_causal_f16: sequence length must be 1..%d (got %d)", CA_MAXL, len);

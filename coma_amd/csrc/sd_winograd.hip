@@ -444,13 +444,7 @@ extern "C" {
 int sd_winograd_input_f16(const void* x0, const void* x1, int c0, int c1, int batch, int h, int w, int upsample, const float* gn_affine,
                           int silu, float vscale, void* v, void* stream) {
   using namespace sd;
-  if (plan_recording()) {
-    PlanRec r{};
-    r.kind = PK_WINO_IN;
-    r.p[0] = (void*)x0; r.p[1] = (void*)x1; r.p[2] = v; r.p[3] = (void*)gn_affine;
-    r.i[0] = c0; r.i[1] = c1; r.i[2] = batch; r.i[3] = h; r.i[4] = w; r.i[5] = upsample; r.i[6] = silu; r.f[0] = vscale;
-    return plan_record(r);
-  }
+  if (plan_recording()) return record<PK_WINO_IN>(x0, x1, v, gn_affine, c0, c1, batch, h, w, upsample, silu, vscale);
   if (upsample != 0 && upsample != 1) return fail(COMA_E_INVALID, "sd_winograd_input_f16: upsample must be 0 or 1");
   if (!x0 || !v) return fail(COMA_E_INVALID, "sd_winograd_input_f16: null pointer");
   if (!(vscale > 0.0f)) return fail(COMA_E_INVALID, "sd_winograd_input_f16: vscale must be positive");
@@ -474,13 +468,7 @@ int sd_winograd_weight_f16(const void* w, int n, int c, float uscale, void* u, v
 int sd_winograd_output_f16(const void* m, int ldm, int batch, int h, int w, int n, const void* bias, const void* bias_bn, int ldbb,
                            const void* res, int ldr, void* out, int ldo, int silu, float mscale, float* colstats, void* stream) {
   using namespace sd;
-  if (plan_recording()) {
-    PlanRec r{};
-    r.kind = PK_WINO_OUT;
-    r.p[0] = (void*)m; r.p[1] = (void*)bias; r.p[2] = (void*)bias_bn; r.p[3] = (void*)res; r.p[4] = out; r.p[5] = colstats;
-    r.i[0] = ldm; r.i[1] = batch; r.i[2] = h; r.i[3] = w; r.i[4] = n; r.i[5] = ldbb; r.i[6] = ldr; r.i[7] = ldo; r.i[8] = silu; r.f[0] = mscale;
-    return plan_record(r);
-  }
+  if (plan_recording()) return record<PK_WINO_OUT>(m, ldm, batch, h, w, n, bias, bias_bn, ldbb, res, ldr, out, ldo, silu, mscale, colstats);
   if (!m || !out) return fail(COMA_E_INVALID, "sd_winograd_output_f16: null pointer");
   if (!(mscale > 0.0f)) return fail(COMA_E_INVALID, "sd_winograd_output_f16: mscale must be positive");
   if (n <= 0 || n % 8 || ldm % 8 || batch <= 0 || (h & 1) || (w & 1)) return fail(COMA_E_INVALID, "sd_winograd_output_f16: bad shape");
@@ -505,14 +493,8 @@ int sd_gn_winograd_input_f16(const void* x0, const void* x1, int c0, int c1, con
                              int ldbb, int batch, int h, int w, int groups, float eps, const void* gamma, const void* beta, int silu, float mscale,
                              void* v, void* stream) {
   using namespace sd;
-  if (plan_recording()) {
-    PlanRec r{};
-    r.kind = PK_GN_WINO_IN;
-    r.p[0] = (void*)x0; r.p[1] = (void*)x1; r.p[2] = (void*)m; r.p[3] = (void*)bias; r.p[4] = (void*)bias_bn; r.p[5] = (void*)gamma;
-    r.p[6] = (void*)beta; r.p[7] = v;
-    r.i[0] = c0; r.i[1] = c1; r.i[2] = ldm; r.i[3] = ldbb; r.i[4] = batch; r.i[5] = h; r.i[6] = w; r.i[7] = groups; r.i[8] = silu; r.f[0] = eps; r.f[1] = mscale;
-    return plan_record(r);
-  }
+  if (plan_recording()) return record<PK_GN_WINO_IN>(x0, x1, c0, c1, m, ldm, bias, bias_bn, ldbb, batch, h, w, groups, eps, gamma, beta, silu,
+                                                     mscale, v);
   if ((!x0 && !m) || !gamma || !beta || !v) return fail(COMA_E_INVALID, "sd_gn_winograd_input_f16: null pointer");
   if (m && !(mscale > 0.0f)) return fail(COMA_E_INVALID, "sd_gn_winograd_input_f16: mscale must be positive");
   if (m && (x0 || x1 || c1)) return fail(COMA_E_INVALID, "sd_gn_winograd_input_f16: either NHWC sources or plane products, not both");

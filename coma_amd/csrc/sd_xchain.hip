@@ -589,15 +589,8 @@ extern "C" int sd_xattn_chain_f16(const void* attn1_out, const void* h, const vo
                                   const void* gamma3, const void* beta3, void* h2, void* n3, int64_t rows, int rows_per_sample, int lk,
                                   int ldv2, float eps, void* debug_out, int debug_stage, void* stream) {
   using namespace sd;
-  if (plan_recording()) {
-    PlanRec r{};
-    r.kind = PK_XCHAIN;
-    const void* ps[15] = {attn1_out, h, wo1, bo1, gamma2, beta2, wq2, k2, vt2, wo2, bo2, gamma3, beta3, h2, n3};
-    for (int k = 0; k < 15; ++k) r.p[k] = const_cast<void*>(ps[k]);
-    r.i[0] = rows; r.i[1] = rows_per_sample; r.i[2] = lk; r.i[3] = ldv2;
-    r.f[0] = eps;
-    return plan_record(r);
-  }
+  if (plan_recording()) return record<PK_XCHAIN>(attn1_out, h, wo1, bo1, gamma2, beta2, wq2, k2, vt2, wo2, bo2, gamma3, beta3, h2, n3, rows,
+                                                 rows_per_sample, lk, ldv2, eps);
   if (!attn1_out || !h || !wo1 || !bo1 || !gamma2 || !beta2 || !wq2 || !k2 || !vt2 || !wo2 || !bo2 || !gamma3 || !beta3 || !h2 || !n3)
     return fail(COMA_E_INVALID, "sd_xattn_chain_f16: null pointer");
   if (rows <= 0 || rows_per_sample <= 0 || rows % rows_per_sample || rows_per_sample % xc::TM || lk <= 0 || lk > 96 || ldv2 < 80 || ldv2 % 8 ||
@@ -621,14 +614,7 @@ extern "C" int sd_xfront_f16(const void* x, const float* gn_affine, const void* 
                              const void* wqk, const void* wv, void* h, void* qk, void* vt, int64_t rows, int rows_per_sample, int ldv, float eps,
                              void* stream) {
   using namespace sd;
-  if (plan_recording()) {
-    PlanRec r{};
-    r.kind = PK_XFRONT;
-    const void* ps[11] = {x, gn_affine, wpi, bpi, gamma1, beta1, wqk, wv, h, qk, vt};
-    for (int k = 0; k < 11; ++k) r.p[k] = const_cast<void*>(ps[k]);
-    r.i[0] = rows; r.i[1] = rows_per_sample; r.i[2] = ldv; r.f[0] = eps;
-    return plan_record(r);
-  }
+  if (plan_recording()) return record<PK_XFRONT>(x, gn_affine, wpi, bpi, gamma1, beta1, wqk, wv, h, qk, vt, rows, rows_per_sample, ldv, eps);
   if (!x || !gn_affine || !wpi || !bpi || !gamma1 || !beta1 || !wqk || !wv || !h || !qk || !vt) return fail(COMA_E_INVALID, "sd_xfront_f16: null pointer");
   if (rows <= 0 || rows_per_sample <= 0 || rows % rows_per_sample || rows_per_sample % xc::TM || ldv < rows_per_sample || ldv % 8 ||
       rows * xc::C * 4 >= 0x80000000LL)

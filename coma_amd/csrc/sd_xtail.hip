@@ -350,14 +350,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void xtail_kernel(Args g) {
 extern "C" int sd_xtail_f16(const void* n3, const void* h2, const void* x, const void* w1, const void* b1, const void* w2, const void* b2,
                             const void* wpo, const void* bpo, void* out, float* colstats, int64_t rows, void* stream) {
   using namespace sd;
-  if (plan_recording()) {
-    PlanRec r{};
-    r.kind = PK_XTAIL;
-    const void* ps[11] = {n3, h2, x, w1, b1, w2, b2, wpo, bpo, out, colstats};
-    for (int k = 0; k < 11; ++k) r.p[k] = const_cast<void*>(ps[k]);
-    r.i[0] = rows;
-    return plan_record(r);
-  }
+  if (plan_recording()) return record<PK_XTAIL>(n3, h2, x, w1, b1, w2, b2, wpo, bpo, out, colstats, rows);
   if (!n3 || !h2 || !x || !w1 || !b1 || !w2 || !b2 || !wpo || !bpo || !out) return fail(COMA_E_INVALID, "sd_xtail_f16: null pointer");
   if (rows <= 0 || rows % xt::TM || rows * xt::C * 2 >= 0x80000000LL)
     return fail(COMA_E_INVALID, "sd_xtail_f16: bad sizes (C = 320, rows a multiple of 128, tensors below 2 GiB)");

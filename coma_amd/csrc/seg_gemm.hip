@@ -493,17 +493,7 @@ static int launch_gemm(GemmArgs& a, hipStream_t st, int force_split, size_t ws_b
 extern "C" int seg_conv_gemm_f32(const seg_conv_desc* d, void* stream) {
   using namespace seg;
   if (!d) return fail(COMA_E_INVALID, "seg_conv_gemm_f32: null descriptor");
-  if (sd::plan_recording()) {
-    sd::PlanRec r{};
-    r.kind = sd::PK_SEG;
-    r.i[0] = SEG_OP_CONV;
-    r.p[0] = (void*)d->x; r.p[1] = (void*)d->w; r.p[2] = (void*)d->bias; r.p[3] = (void*)d->res; r.p[4] = d->out; r.p[5] = (void*)d->m_dev;
-    r.i[1] = d->batch; r.i[2] = d->in_h; r.i[3] = d->in_w; r.i[4] = d->c; r.i[5] = d->ldx; r.i[6] = d->n; r.i[7] = d->kpad; r.i[8] = d->kh;
-    r.i[9] = d->kw; r.i[10] = d->stride; r.i[11] = d->pad; r.i[12] = d->out_h; r.i[13] = d->out_w; r.i[14] = d->ldr; r.i[15] = d->res_mode;
-    r.i[16] = d->ldo; r.i[17] = d->relu; r.i[18] = d->rows_per_item; r.i[19] = d->tile; r.i[20] = d->unit_rows;
-    r.p[6] = d->workspace; r.i[21] = d->split_k; r.i[22] = (int64_t)d->workspace_bytes;
-    return sd::plan_record(r);
-  }
+  if (sd::plan_recording()) return sd::record_seg_conv(d);
   if (!d->x || !d->w || !d->out) return fail(COMA_E_INVALID, "seg_conv_gemm_f32: null pointer");
   if (d->batch <= 0 || d->in_h <= 0 || d->in_w <= 0 || d->out_h <= 0 || d->out_w <= 0 || d->n <= 0)
     return fail(COMA_E_INVALID, "seg_conv_gemm_f32: batch=%d in=%dx%d out=%dx%d n=%d", d->batch, d->in_h, d->in_w, d->out_h, d->out_w, d->n);

@@ -911,26 +911,13 @@ __global__ __launch_bounds__(256) void paste_kernel(const float* logits, int s, 
 
 using namespace seg;
 
-#define SEG_REC_BEGIN(OP) \
-  if (sd::plan_recording()) { \
-    sd::PlanRec r{}; \
-    r.kind = sd::PK_SEG; \
-    r.i[0] = OP;
-#define SEG_REC_END \
-    return sd::plan_record(r); \
-  }
-
 static inline unsigned blocks_for(long long n, int per) { return (unsigned)((n + per - 1) / per); }
 
 extern "C" int seg_resize_normalize_u8(const void* src, int batch, int h, int w, int new_h, int new_w, int pad_h, int pad_w, const void* bounds_x,
                                        const void* kk_x, int ksize_x, const void* bounds_y, const void* kk_y, int ksize_y, float mean0, float mean1,
                                        float mean2, void* tmp, void* resized, void* out, void* stream) {
-  SEG_REC_BEGIN(SEG_OP_RESIZE)
-    r.p[0] = (void*)src; r.p[1] = (void*)bounds_x; r.p[2] = (void*)kk_x; r.p[3] = (void*)bounds_y; r.p[4] = (void*)kk_y; r.p[5] = tmp; r.p[6] = resized;
-    r.p[7] = out;
-    r.i[1] = batch; r.i[2] = h; r.i[3] = w; r.i[4] = new_h; r.i[5] = new_w; r.i[6] = pad_h; r.i[7] = pad_w; r.i[8] = ksize_x; r.i[9] = ksize_y;
-    r.f[0] = mean0; r.f[1] = mean1; r.f[2] = mean2;
-  SEG_REC_END
+  if (sd::plan_recording()) return sd::record<sd::PK_SEG, SEG_OP_RESIZE>(src, batch, h, w, new_h, new_w, pad_h, pad_w, bounds_x, kk_x, ksize_x,
+                                                                         bounds_y, kk_y, ksize_y, mean0, mean1, mean2, tmp, resized, out);
   if (!src || !bounds_x || !kk_x || !bounds_y || !kk_y || !tmp || !out) return fail(COMA_E_INVALID, "seg_resize_normalize_u8: null pointer");
   if (batch <= 0 || h <= 0 || w <= 0 || new_h <= 0 || new_w <= 0 || pad_h < new_h || pad_w < new_w || ksize_x <= 0 || ksize_y <= 0)
     return fail(COMA_E_INVALID, "seg_resize_normalize_u8: bad sizes");
@@ -944,9 +931,7 @@ extern "C" int seg_resize_normalize_u8(const void* src, int batch, int h, int w,
 }
 
 extern "C" int seg_maxpool3x3s2_f32(const void* x, int batch, int h, int w, int c, void* out, void* stream) {
-  SEG_REC_BEGIN(SEG_OP_MAXPOOL)
-    r.p[0] = (void*)x; r.p[1] = out; r.i[1] = batch; r.i[2] = h; r.i[3] = w; r.i[4] = c;
-  SEG_REC_END
+  if (sd::plan_recording()) return sd::record<sd::PK_SEG, SEG_OP_MAXPOOL>(x, batch, h, w, c, out);
   if (!x || !out || batch <= 0 || h <= 0 || w <= 0 || c <= 0 || c % 4) return fail(COMA_E_INVALID, "seg_maxpool3x3s2_f32: bad args");
   const int oh = (h - 1) / 2 + 1, ow = (w - 1) / 2 + 1;
   const long long n = (long long)batch * oh * ow * (c / 4);
@@ -956,9 +941,7 @@ extern "C" int seg_maxpool3x3s2_f32(const void* x, int batch, int h, int w, int 
 }
 
 extern "C" int seg_subsample2_f32(const void* x, int batch, int h, int w, int c, void* out, void* stream) {
-  SEG_REC_BEGIN(SEG_OP_SUBSAMPLE)
-    r.p[0] = (void*)x; r.p[1] = out; r.i[1] = batch; r.i[2] = h; r.i[3] = w; r.i[4] = c;
-  SEG_REC_END
+  if (sd::plan_recording()) return sd::record<sd::PK_SEG, SEG_OP_SUBSAMPLE>(x, batch, h, w, c, out);
   if (!x || !out || batch <= 0 || h <= 0 || w <= 0 || c <= 0 || c % 4) return fail(COMA_E_INVALID, "seg_subsample2_f32: bad args");
   const int oh = (h - 1) / 2 + 1, ow = (w - 1) / 2 + 1;
   const long long n = (long long)batch * oh * ow * (c / 4);
@@ -968,9 +951,7 @@ extern "C" int seg_subsample2_f32(const void* x, int batch, int h, int w, int c,
 }
 
 extern "C" int seg_memset(void* dst, int byte, size_t bytes, void* stream) {
-  SEG_REC_BEGIN(SEG_OP_MEMSET)
-    r.p[0] = dst; r.i[1] = byte; r.i[2] = (int64_t)bytes;
-  SEG_REC_END
+  if (sd::plan_recording()) return sd::record<sd::PK_SEG, SEG_OP_MEMSET>(dst, byte, bytes);
   if (!dst || bytes == 0) return fail(COMA_E_INVALID, "seg_memset: bad args");
   // a kernel, not hipMemsetAsync: inside the captured plan a memset NODE sat between kernel nodes, and replays of that graph hung the
   // queue about once in three processes (profiles/r06_notes.md 2); a fill kernel is an ordinary node of the chain
@@ -983,11 +964,8 @@ extern "C" int seg_memset(void* dst, int byte, size_t bytes, void* stream) {
 extern "C" int seg_rpn_select(const void* pred, int ld, int batch, int fh, int fw, int stride, const void* cell_anchors, int level, int anchor_base,
                               int pre_topk, float img_h, float img_w, int cand_offset, int cap, void* cand_keys, void* cand_boxes, void* cand_group,
                               void* stream) {
-  SEG_REC_BEGIN(SEG_OP_RPN_SELECT)
-    r.p[0] = (void*)pred; r.p[1] = (void*)cell_anchors; r.p[2] = cand_keys; r.p[3] = cand_boxes; r.p[4] = cand_group;
-    r.i[1] = ld; r.i[2] = batch; r.i[3] = fh; r.i[4] = fw; r.i[5] = stride; r.i[6] = level; r.i[7] = anchor_base; r.i[8] = pre_topk; r.i[9] = cand_offset;
-    r.i[10] = cap; r.f[0] = img_h; r.f[1] = img_w;
-  SEG_REC_END
+  if (sd::plan_recording()) return sd::record<sd::PK_SEG, SEG_OP_RPN_SELECT>(pred, ld, batch, fh, fw, stride, cell_anchors, level, anchor_base,
+                                                                             pre_topk, img_h, img_w, cand_offset, cap, cand_keys, cand_boxes, cand_group);
   if (!pred || !cell_anchors || !cand_keys || !cand_boxes || !cand_group) return fail(COMA_E_INVALID, "seg_rpn_select: null pointer");
   if (ld < 15 || batch <= 0 || fh <= 0 || fw <= 0 || pre_topk <= 0 || cand_offset < 0 || cand_offset + pre_topk > cap)
     return fail(COMA_E_INVALID, "seg_rpn_select: bad sizes (ld=%d, offset=%d, topk=%d, cap=%d)", ld, cand_offset, pre_topk, cap);
@@ -1000,11 +978,8 @@ extern "C" int seg_rpn_select_levels(const void* const* preds, const void* const
                                      int ld, int batch, int pre_topk, float img_h, float img_w, int cap, void* cand_keys, void* cand_boxes,
                                      void* cand_group, void* key_scratch, void* stream) {
   if (!preds || !cell_anchors || !fh || !fw || n_levels <= 0 || n_levels > 6) return fail(COMA_E_INVALID, "seg_rpn_select_levels: 1 .. 6 levels, got %d", n_levels);
-  SEG_REC_BEGIN(SEG_OP_RPN_SELECT_LEVELS)
-    for (int l = 0; l < n_levels; ++l) { r.p[l] = (void*)preds[l]; r.p[6 + l] = (void*)cell_anchors[l]; r.i[8 + l] = fh[l]; r.i[14 + l] = fw[l]; }
-    r.p[12] = cand_keys; r.p[13] = cand_boxes; r.p[14] = cand_group; r.p[15] = key_scratch;
-    r.i[1] = n_levels; r.i[2] = first_stride; r.i[3] = ld; r.i[4] = batch; r.i[5] = pre_topk; r.i[6] = cap; r.f[0] = img_h; r.f[1] = img_w;
-  SEG_REC_END
+  if (sd::plan_recording()) return sd::record_rpn_select_levels(preds, cell_anchors, fh, fw, n_levels, first_stride, ld, batch, pre_topk, img_h,
+                                                                img_w, cap, cand_keys, cand_boxes, cand_group, key_scratch);
   if (!cand_keys || !cand_boxes || !cand_group) return fail(COMA_E_INVALID, "seg_rpn_select_levels: null pointer");
   if (ld < 15 || batch <= 0 || pre_topk <= 0 || first_stride <= 0) return fail(COMA_E_INVALID, "seg_rpn_select_levels: bad sizes (ld=%d, batch=%d, topk=%d)", ld, batch, pre_topk);
   RpnLevels L{};
@@ -1030,10 +1005,7 @@ extern "C" int seg_rpn_select_levels(const void* const* preds, const void* const
 
 extern "C" int seg_sort_candidates(const void* keys, const void* boxes, const void* group, int batch, int cap, void* s_boxes, void* s_scores,
                                    void* s_group, void* s_src, void* n_valid, void* stream) {
-  SEG_REC_BEGIN(SEG_OP_SORT)
-    r.p[0] = (void*)keys; r.p[1] = (void*)boxes; r.p[2] = (void*)group; r.p[3] = s_boxes; r.p[4] = s_scores; r.p[5] = s_group; r.p[6] = s_src; r.p[7] = n_valid;
-    r.i[1] = batch; r.i[2] = cap;
-  SEG_REC_END
+  if (sd::plan_recording()) return sd::record<sd::PK_SEG, SEG_OP_SORT>(keys, boxes, group, batch, cap, s_boxes, s_scores, s_group, s_src, n_valid);
   if (!keys || !boxes || !group || !s_boxes || !s_scores || !s_group || !s_src || !n_valid) return fail(COMA_E_INVALID, "seg_sort_candidates: null pointer");
   if (batch <= 0 || cap < 64 || cap > 8192 || (cap & (cap - 1))) return fail(COMA_E_INVALID, "seg_sort_candidates: cap=%d (a power of two in [64, 8192])", cap);
   const size_t lds = (size_t)cap * 10;
@@ -1048,11 +1020,8 @@ extern "C" int seg_sort_candidates(const void* keys, const void* boxes, const vo
 extern "C" int seg_nms(const void* s_boxes, const void* s_scores, const void* s_group, const void* s_src, const void* n_valid, int batch, int cap,
                        float thresh, int max_keep, void* mask_ws, void* keep_pos, void* out_boxes, void* out_scores, void* out_group, void* out_src,
                        void* out_count, void* stream) {
-  SEG_REC_BEGIN(SEG_OP_NMS)
-    r.p[0] = (void*)s_boxes; r.p[1] = (void*)s_scores; r.p[2] = (void*)s_group; r.p[3] = (void*)s_src; r.p[4] = (void*)n_valid; r.p[5] = mask_ws; r.p[6] = keep_pos;
-    r.p[7] = out_boxes; r.p[8] = out_scores; r.p[9] = out_group; r.p[10] = out_src; r.p[11] = out_count;
-    r.i[1] = batch; r.i[2] = cap; r.i[3] = max_keep; r.f[0] = thresh;
-  SEG_REC_END
+  if (sd::plan_recording()) return sd::record<sd::PK_SEG, SEG_OP_NMS>(s_boxes, s_scores, s_group, s_src, n_valid, batch, cap, thresh, max_keep,
+                                                                      mask_ws, keep_pos, out_boxes, out_scores, out_group, out_src, out_count);
   if (!s_boxes || !s_scores || !s_group || !s_src || !n_valid || !mask_ws || !keep_pos || !out_boxes || !out_scores || !out_group || !out_src || !out_count)
     return fail(COMA_E_INVALID, "seg_nms: null pointer");
   if (batch <= 0 || cap < 64 || cap > 8192 || cap % 64 || max_keep <= 0) return fail(COMA_E_INVALID, "seg_nms: cap=%d max_keep=%d", cap, max_keep);
@@ -1067,10 +1036,7 @@ extern "C" int seg_nms(const void* s_boxes, const void* s_scores, const void* s_
 
 extern "C" int seg_roi_align_f32(const void* p2, const void* p3, const void* p4, const void* p5, int h2, int w2, int c, const void* boxes,
                                  const void* count, int batch, int R, int out_size, void* out, void* level, void* stream) {
-  SEG_REC_BEGIN(SEG_OP_ROI_ALIGN)
-    r.p[0] = (void*)p2; r.p[1] = (void*)p3; r.p[2] = (void*)p4; r.p[3] = (void*)p5; r.p[4] = (void*)boxes; r.p[5] = (void*)count; r.p[6] = out; r.p[7] = level;
-    r.i[1] = h2; r.i[2] = w2; r.i[3] = c; r.i[4] = batch; r.i[5] = R; r.i[6] = out_size;
-  SEG_REC_END
+  if (sd::plan_recording()) return sd::record<sd::PK_SEG, SEG_OP_ROI_ALIGN>(p2, p3, p4, p5, h2, w2, c, boxes, count, batch, R, out_size, out, level);
   if (!p2 || !p3 || !p4 || !p5 || !boxes || !count || !out) return fail(COMA_E_INVALID, "seg_roi_align_f32: null pointer");
   if (h2 <= 0 || w2 <= 0 || h2 % 8 || w2 % 8 || c <= 0 || c % 4 || batch <= 0 || R <= 0 || out_size <= 0)
     return fail(COMA_E_INVALID, "seg_roi_align_f32: bad sizes (p2 is %d x %d: multiples of 8, so that p3..p5 are exact halves)", h2, w2);
@@ -1086,10 +1052,8 @@ extern "C" int seg_roi_align_f32(const void* p2, const void* p3, const void* p4,
 extern "C" int seg_box_predict(const void* pred, int ld, const void* proposals, const void* count, int batch, int R, float img_h, float img_w,
                                float score_thresh, int cap, void* cand_keys, void* cand_boxes, void* cand_group, void* cand_count, void* probs,
                                void* stream) {
-  SEG_REC_BEGIN(SEG_OP_BOX_PREDICT)
-    r.p[0] = (void*)pred; r.p[1] = (void*)proposals; r.p[2] = (void*)count; r.p[3] = cand_keys; r.p[4] = cand_boxes; r.p[5] = cand_group; r.p[6] = cand_count;
-    r.p[7] = probs; r.i[1] = ld; r.i[2] = batch; r.i[3] = R; r.i[4] = cap; r.f[0] = img_h; r.f[1] = img_w; r.f[2] = score_thresh;
-  SEG_REC_END
+  if (sd::plan_recording()) return sd::record<sd::PK_SEG, SEG_OP_BOX_PREDICT>(pred, ld, proposals, count, batch, R, img_h, img_w, score_thresh,
+                                                                              cap, cand_keys, cand_boxes, cand_group, cand_count, probs);
   if (!pred || !proposals || !count || !cand_keys || !cand_boxes || !cand_group || !cand_count) return fail(COMA_E_INVALID, "seg_box_predict: null pointer");
   if (ld < 401 || batch <= 0 || R <= 0 || cap <= 0) return fail(COMA_E_INVALID, "seg_box_predict: bad sizes");
   const int n = batch * R;
@@ -1101,10 +1065,7 @@ extern "C" int seg_box_predict(const void* pred, int ld, const void* proposals, 
 
 extern "C" int seg_finalize_detections(const void* det_boxes, const void* count, int batch, int R, float img_h, float img_w, int out_h, int out_w,
                                        void* out_boxes, void* valid, void* stream) {
-  SEG_REC_BEGIN(SEG_OP_FINALIZE)
-    r.p[0] = (void*)det_boxes; r.p[1] = (void*)count; r.p[2] = out_boxes; r.p[3] = valid; r.i[1] = batch; r.i[2] = R; r.i[3] = out_h; r.i[4] = out_w;
-    r.f[0] = img_h; r.f[1] = img_w;
-  SEG_REC_END
+  if (sd::plan_recording()) return sd::record<sd::PK_SEG, SEG_OP_FINALIZE>(det_boxes, count, batch, R, img_h, img_w, out_h, out_w, out_boxes, valid);
   if (!det_boxes || !count || !out_boxes || !valid || batch <= 0 || R <= 0) return fail(COMA_E_INVALID, "seg_finalize_detections: bad args");
   const int n = batch * R;
   hipLaunchKernelGGL(finalize_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float*)det_boxes, (const int*)count, R,
@@ -1115,11 +1076,8 @@ extern "C" int seg_finalize_detections(const void* det_boxes, const void* count,
 extern "C" int seg_point_sample_f32(const void* feat, int fh, int fw, int c, int per_roi, float feat_scale, const void* boxes, const void* count,
                                     int batch, int R, const void* coords, int P, int grid_side, void* out, int ldo, int col0, int n_copies,
                                     long long copy_stride, void* stream) {
-  SEG_REC_BEGIN(SEG_OP_POINT_SAMPLE)
-    r.p[0] = (void*)feat; r.p[1] = (void*)boxes; r.p[2] = (void*)count; r.p[3] = (void*)coords; r.p[4] = out;
-    r.i[1] = fh; r.i[2] = fw; r.i[3] = c; r.i[4] = per_roi; r.i[5] = batch; r.i[6] = R; r.i[7] = P; r.i[8] = grid_side; r.i[9] = ldo; r.i[10] = col0;
-    r.i[11] = n_copies; r.i[12] = copy_stride; r.f[0] = feat_scale;
-  SEG_REC_END
+  if (sd::plan_recording()) return sd::record<sd::PK_SEG, SEG_OP_POINT_SAMPLE>(feat, fh, fw, c, per_roi, feat_scale, boxes, count, batch, R,
+                                                                               coords, P, grid_side, out, ldo, col0, n_copies, copy_stride);
   if (!feat || !count || !out || (!per_roi && !boxes)) return fail(COMA_E_INVALID, "seg_point_sample_f32: null pointer");
   if (fh <= 0 || fw <= 0 || c <= 0 || c % 4 || batch <= 0 || R <= 0 || P <= 0 || (!coords && grid_side * grid_side != P) || ldo < col0 + c || ldo % 4 ||
       col0 % 4 || n_copies < 1 || copy_stride % 4)
@@ -1133,9 +1091,7 @@ extern "C" int seg_point_sample_f32(const void* feat, int fh, int fw, int c, int
 }
 
 extern "C" int seg_upsample2x_f32(const void* x, const void* count, int batch, int R, int s, void* out, void* stream) {
-  SEG_REC_BEGIN(SEG_OP_UPSAMPLE2X)
-    r.p[0] = (void*)x; r.p[1] = (void*)count; r.p[2] = out; r.i[1] = batch; r.i[2] = R; r.i[3] = s;
-  SEG_REC_END
+  if (sd::plan_recording()) return sd::record<sd::PK_SEG, SEG_OP_UPSAMPLE2X>(x, count, batch, R, s, out);
   if (!x || !count || !out || batch <= 0 || R <= 0 || s <= 0) return fail(COMA_E_INVALID, "seg_upsample2x_f32: bad args");
   const long long n = (long long)batch * R * 4 * s * s;
   hipLaunchKernelGGL(upsample2x_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, (const float*)x, (const int*)count, R, s, (float*)out, n);
@@ -1143,9 +1099,7 @@ extern "C" int seg_upsample2x_f32(const void* x, const void* count, int batch, i
 }
 
 extern "C" int seg_topk_points(const void* logits, const void* count, int batch, int R, int s, int k, void* idx, void* coords, void* stream) {
-  SEG_REC_BEGIN(SEG_OP_TOPK_POINTS)
-    r.p[0] = (void*)logits; r.p[1] = (void*)count; r.p[2] = idx; r.p[3] = coords; r.i[1] = batch; r.i[2] = R; r.i[3] = s; r.i[4] = k;
-  SEG_REC_END
+  if (sd::plan_recording()) return sd::record<sd::PK_SEG, SEG_OP_TOPK_POINTS>(logits, count, batch, R, s, k, idx, coords);
   if (!logits || !count || !idx || !coords || batch <= 0 || R <= 0 || s <= 0 || k <= 0 || k > s * s) return fail(COMA_E_INVALID, "seg_topk_points: bad args");
   hipLaunchKernelGGL(topk_points_kernel, dim3(batch * R), dim3(1024), 0, (hipStream_t)stream, (const float*)logits, (const int*)count, R, s, k, (int*)idx,
                      (float*)coords);
@@ -1154,10 +1108,7 @@ extern "C" int seg_topk_points(const void* logits, const void* count, int batch,
 
 extern "C" int seg_point_logit_scatter(const void* x, int ldx, int kdim, const void* w, const void* bias, const void* classes, const void* count,
                                        int batch, int R, int P, const void* idx, void* map, int s, void* stream) {
-  SEG_REC_BEGIN(SEG_OP_POINT_LOGIT)
-    r.p[0] = (void*)x; r.p[1] = (void*)w; r.p[2] = (void*)bias; r.p[3] = (void*)classes; r.p[4] = (void*)count; r.p[5] = (void*)idx; r.p[6] = map;
-    r.i[1] = ldx; r.i[2] = kdim; r.i[3] = batch; r.i[4] = R; r.i[5] = P; r.i[6] = s;
-  SEG_REC_END
+  if (sd::plan_recording()) return sd::record<sd::PK_SEG, SEG_OP_POINT_LOGIT>(x, ldx, kdim, w, bias, classes, count, batch, R, P, idx, map, s);
   if (!x || !w || !bias || !classes || !count || !map || ldx < kdim || kdim <= 0 || batch <= 0 || R <= 0 || P <= 0 || s <= 0 || (!idx && P != s * s))
     return fail(COMA_E_INVALID, "seg_point_logit_scatter: bad args");
   const long long n = (long long)batch * R * P;
@@ -1168,10 +1119,8 @@ extern "C" int seg_point_logit_scatter(const void* x, int ldx, int kdim, const v
 
 extern "C" int seg_paste_masks(const void* logits, int s, const void* out_boxes, const void* valid, const void* classes, const void* count, int batch,
                                int R, int out_h, int out_w, int cat_id, void* masks, void* merged, void* stream) {
-  SEG_REC_BEGIN(SEG_OP_PASTE)
-    r.p[0] = (void*)logits; r.p[1] = (void*)out_boxes; r.p[2] = (void*)valid; r.p[3] = (void*)classes; r.p[4] = (void*)count; r.p[5] = masks; r.p[6] = merged;
-    r.i[1] = s; r.i[2] = batch; r.i[3] = R; r.i[4] = out_h; r.i[5] = out_w; r.i[6] = cat_id;
-  SEG_REC_END
+  if (sd::plan_recording()) return sd::record<sd::PK_SEG, SEG_OP_PASTE>(logits, s, out_boxes, valid, classes, count, batch, R, out_h, out_w,
+                                                                        cat_id, masks, merged);
   if (!logits || !out_boxes || !valid || !classes || !count || !merged || s <= 0 || batch <= 0 || R <= 0 || out_h <= 0 || out_w <= 0)
     return fail(COMA_E_INVALID, "seg_paste_masks: bad args");
   hipLaunchKernelGGL(paste_kernel, dim3(blocks_for((long long)out_h * out_w, 256), batch), dim3(256), 0, (hipStream_t)stream, (const float*)logits, s,
@@ -1179,58 +1128,3 @@ extern "C" int seg_paste_masks(const void* logits, int s, const void* out_boxes,
                      (unsigned char*)merged);
   return check_launch("seg::paste_kernel");
 }
-
-// ---- replay of a recorded launch (sd_plan.hip: PK_SEG)
-namespace sd {
-int seg_replay(const PlanRec& r, void* st) {
-  void* const* p = r.p;
-  const int64_t* i = r.i;
-  const double* f = r.f;
-  switch ((int)i[0]) {
-    case SEG_OP_CONV: {
-      seg_conv_desc d{};
-      d.x = p[0]; d.w = p[1]; d.bias = p[2]; d.res = p[3]; d.out = p[4]; d.m_dev = p[5];
-      d.batch = (int)i[1]; d.in_h = (int)i[2]; d.in_w = (int)i[3]; d.c = (int)i[4]; d.ldx = (int)i[5]; d.n = (int)i[6]; d.kpad = (int)i[7]; d.kh = (int)i[8];
-      d.kw = (int)i[9]; d.stride = (int)i[10]; d.pad = (int)i[11]; d.out_h = (int)i[12]; d.out_w = (int)i[13]; d.ldr = (int)i[14]; d.res_mode = (int)i[15];
-      d.ldo = (int)i[16]; d.relu = (int)i[17]; d.rows_per_item = (int)i[18]; d.tile = (int)i[19]; d.unit_rows = (int)i[20];
-      d.workspace = p[6]; d.split_k = (int)i[21]; d.workspace_bytes = (size_t)i[22];
-      return seg_conv_gemm_f32(&d, st);
-    }
-    case SEG_OP_RESIZE:
-      return seg_resize_normalize_u8(p[0], (int)i[1], (int)i[2], (int)i[3], (int)i[4], (int)i[5], (int)i[6], (int)i[7], p[1], p[2], (int)i[8], p[3], p[4],
-                                     (int)i[9], (float)f[0], (float)f[1], (float)f[2], p[5], p[6], p[7], st);
-    case SEG_OP_MAXPOOL: return seg_maxpool3x3s2_f32(p[0], (int)i[1], (int)i[2], (int)i[3], (int)i[4], p[1], st);
-    case SEG_OP_SUBSAMPLE: return seg_subsample2_f32(p[0], (int)i[1], (int)i[2], (int)i[3], (int)i[4], p[1], st);
-    case SEG_OP_MEMSET: return seg_memset(p[0], (int)i[1], (size_t)i[2], st);
-    case SEG_OP_RPN_SELECT:
-      return seg_rpn_select(p[0], (int)i[1], (int)i[2], (int)i[3], (int)i[4], (int)i[5], p[1], (int)i[6], (int)i[7], (int)i[8], (float)f[0], (float)f[1],
-                            (int)i[9], (int)i[10], p[2], p[3], p[4], st);
-    case SEG_OP_RPN_SELECT_LEVELS: {
-      const void* preds[6]; const void* cells[6]; int fh[6], fw[6];
-      for (int l = 0; l < (int)i[1]; ++l) { preds[l] = p[l]; cells[l] = p[6 + l]; fh[l] = (int)i[8 + l]; fw[l] = (int)i[14 + l]; }
-      return seg_rpn_select_levels(preds, cells, fh, fw, (int)i[1], (int)i[2], (int)i[3], (int)i[4], (int)i[5], (float)f[0], (float)f[1], (int)i[6], p[12], p[13],
-                                   p[14], p[15], st);
-    }
-    case SEG_OP_SORT: return seg_sort_candidates(p[0], p[1], p[2], (int)i[1], (int)i[2], p[3], p[4], p[5], p[6], p[7], st);
-    case SEG_OP_NMS:
-      return seg_nms(p[0], p[1], p[2], p[3], p[4], (int)i[1], (int)i[2], (float)f[0], (int)i[3], p[5], p[6], p[7], p[8], p[9], p[10], p[11], st);
-    case SEG_OP_ROI_ALIGN:
-      return seg_roi_align_f32(p[0], p[1], p[2], p[3], (int)i[1], (int)i[2], (int)i[3], p[4], p[5], (int)i[4], (int)i[5], (int)i[6], p[6], p[7], st);
-    case SEG_OP_BOX_PREDICT:
-      return seg_box_predict(p[0], (int)i[1], p[1], p[2], (int)i[2], (int)i[3], (float)f[0], (float)f[1], (float)f[2], (int)i[4], p[3], p[4], p[5], p[6], p[7], st);
-    case SEG_OP_FINALIZE:
-      return seg_finalize_detections(p[0], p[1], (int)i[1], (int)i[2], (float)f[0], (float)f[1], (int)i[3], (int)i[4], p[2], p[3], st);
-    case SEG_OP_POINT_SAMPLE:
-      return seg_point_sample_f32(p[0], (int)i[1], (int)i[2], (int)i[3], (int)i[4], (float)f[0], p[1], p[2], (int)i[5], (int)i[6], p[3], (int)i[7], (int)i[8],
-                                  p[4], (int)i[9], (int)i[10], (int)i[11], (long long)i[12], st);
-    case SEG_OP_UPSAMPLE2X: return seg_upsample2x_f32(p[0], p[1], (int)i[1], (int)i[2], (int)i[3], p[2], st);
-    case SEG_OP_TOPK_POINTS: return seg_topk_points(p[0], p[1], (int)i[1], (int)i[2], (int)i[3], (int)i[4], p[2], p[3], st);
-    case SEG_OP_POINT_LOGIT:
-      return seg_point_logit_scatter(p[0], (int)i[1], (int)i[2], p[1], p[2], p[3], p[4], (int)i[3], (int)i[4], (int)i[5], p[5], p[6], (int)i[6], st);
-    case SEG_OP_PASTE:
-      return seg_paste_masks(p[0], (int)i[1], p[1], p[2], p[3], p[4], (int)i[2], (int)i[3], (int)i[4], (int)i[5], (int)i[6], p[5], p[6], st);
-    default:
-      return coma::fail(COMA_E_INVALID, "seg plan: unknown operator %d", (int)i[0]);
-  }
-}
-}  // namespace sd

@@ -342,10 +342,9 @@ int sd_mask_adapt_batched(const uint8_t* seg, const uint8_t* default_mask, int b
 /* ------------------------------------------------------------------------------------------------------------------
  * Models: the launch list and the hipGraph of a network live in the library (coma_amd/csrc/sd_plan.hip).
  * A model = a registry of device buffers + named bindings (inputs / outputs) + named plans (recorded launch lists).
- * Recording: between sd_model_record_begin and sd_model_record_end every sd_* LAUNCH entry point called on the thread
- * (sd_conv_gemm_f16, sd_groupnorm*_f16, sd_layernorm_f16, sd_attention_f16, sd_attention_causal_f16, sd_text_embed_f16, sd_softmax_f16,
- * sd_timestep_embedding_f16, sd_copy_d2d) appends its arguments to the plan instead of launching; arguments are validated when
- * the plan first runs.  sd_model_run launches the list eagerly on `stream`; sd_model_replay captures it once into a hipGraph (on a
+ * Recording: between sd_model_record_begin and sd_model_record_end every recordable LAUNCH entry point called on the thread
+ * (sd_conv_gemm_f16 and the others of the replay table in coma_amd/csrc/sd_plan.h, the seg_* launches of include/seg_hip.h included)
+ * appends its arguments to the plan instead of launching; arguments are validated when the plan first runs.  sd_model_run launches the list eagerly on `stream`; sd_model_replay captures it once into a hipGraph (on a
  * private stream, nothing executes during capture) and launches the graph on `stream`.
  * sd_model_save / sd_model_load: ONE file with the registry, the bindings, the plans and the contents of the SD_BUF_PERSISTENT
  * buffers (weights, constants); a loaded model owns its device memory (freed by sd_model_destroy), a recorded one borrows the
