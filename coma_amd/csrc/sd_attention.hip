@@ -22,7 +22,6 @@
 // quarter rate ~510 cycles, ~75 more full-rate instructions); the staging is kept off the VALU entirely.
 #include <hip/hip_fp16.h>
 
-#include <cstdlib>
 #include <type_traits>
 #include <utility>
 
@@ -49,7 +48,6 @@ struct AttnArgs {
   int heads, lq, lk, d;
   int ldq, ldk, ldv, ldo;
   float scale_log2;   // scale * log2(e)
-  int no_spec;        // attention_sp_kernel: track the maximum on every key tile from the start (A/B aid, SD_ATTN_SPEC=0)
 };
 
 typedef __attribute__((address_space(3))) void* lptr_t;
@@ -596,30 +594,26 @@ __global__ __launch_bounds__(256, 1) void attention_sp_kernel(AttnArgs a) {
         }
     }
   };
-  if (a.no_spec) {
-    run_pass(std::true_type{});
-  } else {
-    run_pass(std::false_type{});
-    bool bad = false;
+  run_pass(std::false_type{});
+  bool bad = false;
 #pragma unroll
-    for (int sq = 0; sq < NQ; ++sq) bad |= !(o[sq][1][4] < 3.0e38f);       // inf / NaN denominator (row 40 of O^T; every lane checks its own)
-    if (__syncthreads_or(bad ? 1 : 0)) {
-      // a weight overflowed fp16 somewhere in this workgroup: start over with the maximum tracked on every tile
+  for (int sq = 0; sq < NQ; ++sq) bad |= !(o[sq][1][4] < 3.0e38f);       // inf / NaN denominator (row 40 of O^T; every lane checks its own)
+  if (__syncthreads_or(bad ? 1 : 0)) {
+    // a weight overflowed fp16 somewhere in this workgroup: start over with the maximum tracked on every tile
 #pragma unroll
-      for (int sq = 0; sq < NQ; ++sq) {
-        m_run[sq] = 0.0f;
-        if (hh) qf[sq][2][0] = (_Float16)0.0f;
+    for (int sq = 0; sq < NQ; ++sq) {
+      m_run[sq] = 0.0f;
+      if (hh) qf[sq][2][0] = (_Float16)0.0f;
 #pragma unroll
-        for (int t = 0; t < 2; ++t)
+      for (int t = 0; t < 2; ++t)
 #pragma unroll
-          for (int r = 0; r < 16; ++r) { o[sq][t][r] = 0.0f; s[sq][t][r] = 0.0f; }
+        for (int r = 0; r < 16; ++r) { o[sq][t][r] = 0.0f; s[sq][t][r] = 0.0f; }
 #pragma unroll
-        for (int st = 0; st < 4; ++st)
+      for (int st = 0; st < 4; ++st)
 #pragma unroll
-          for (int j = 0; j < 8; ++j) pf[sq][st][j] = (_Float16)0.0f;
-      }
-      run_pass(std::true_type{});
+        for (int j = 0; j < 8; ++j) pf[sq][st][j] = (_Float16)0.0f;
     }
+    run_pass(std::true_type{});
   }
 
   // ---- normalise by the ones row (row 40 = register 4 of the second 32-row tile, hh = 0 lane) and store
@@ -844,16 +838,12 @@ extern "C" int sd_attention_f16(const void* q, const void* k, const void* vt, vo
   a.q = (const _Float16*)q; a.k = (const _Float16*)k; a.vt = (const _Float16*)vt; a.out = (_Float16*)out;
   a.heads = heads; a.lq = lq; a.lk = lk; a.d = d; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
   a.scale_log2 = scale * 1.4426950408889634f;
-  static const int spec_env = [] { const char* e = getenv("SD_ATTN_SPEC"); return e ? atoi(e) : 1; }();
-  a.no_spec = !spec_env;
   hipStream_t s = (hipStream_t)stream;
   // software-pipelined kernel: d = 40, whole key tiles (at least two), V^T key-permuted; by default only when 256-query blocks
-  // fill the chip.  vt_perm16 bit 1 forces it wherever it is legal, bit 2 forbids it (tests / A-B timing); SD_ATTN_V=1 forbids
-  // it process-wide.
-  static const int sp_mode = [] { const char* e = getenv("SD_ATTN_V"); return e ? atoi(e) : 2; }();
+  // fill the chip.  vt_perm16 bit 1 forces it wherever it is legal, bit 2 forbids it (tests / A-B timing).
   const bool sp_legal = d == 40 && (vt_perm16 & 1) && lk % BKV == 0 && lk >= 2 * BKV;
   // (r5: from ONE block per CU on -- UNet batch 2, one image per pipeline call: 75 us against 97 us for the r2 kernel; it was two per CU)
-  const bool sp_auto = sp_mode >= 2 && !(vt_perm16 & 4) && (long long)batch * heads * ((lq + 255) / 256) >= 256;
+  const bool sp_auto = !(vt_perm16 & 4) && (long long)batch * heads * ((lq + 255) / 256) >= 256;
   if (sp_legal && ((vt_perm16 & 2) || sp_auto)) {
     // (HQ = 2, 128 queries per wave, measured slower -- 585 vs 487 us -- and is not instantiated: it needs 460 registers)
     dim3 g2((unsigned)((lq + 255) / 256), (unsigned)heads, (unsigned)batch);
@@ -863,10 +853,10 @@ extern "C" int sd_attention_f16(const void* q, const void* k, const void* vt, vo
   vt_perm16 &= 1;
   // 64 queries per wave once there are enough blocks to fill the chip -- unless there are only a few key tiles (the 77-token cross
   // attention): then a block is all prologue / epilogue latency and more resident blocks (QT = 1: ~100 registers) hide it better
-  static const int xqt1 = [] { const char* e = getenv("SD_ATTN_XQT1"); return e ? atoi(e) : 1; }();   // 38.5 -> 34.9 us at lq = 4096, lk = 77
+  // (38.5 -> 34.9 us at lq = 4096, lk = 77)
   // r5: ... and at d = 80 (the 32 x 32 level: 73.4 -> 64.4 us; 254 registers) once 256-query blocks fill the chip twice
   const bool two80 = d == 80 && lq >= 1024 && lk >= 256 && (long long)batch * heads * ((lq + 255) / 256) >= 512;
-  const bool two = (lq >= 1024 && d == 40 && !(xqt1 && lk <= 128)) || two80;
+  const bool two = (lq >= 1024 && d == 40 && lk > 128) || two80;
   dim3 grid((unsigned)((lq + (two ? 255 : 127)) / (two ? 256 : 128)), (unsigned)heads, (unsigned)batch);
 #define SD_ATTN_LAUNCH(KS, DVT, QT, ONES)                                                                       \
   do {                                                                                                          \
@@ -901,13 +891,11 @@ extern "C" int sd_attention_wide_f16(const void* q, const void* k, const void* v
   a.q = (const _Float16*)q; a.k = (const _Float16*)k; a.vt = (const _Float16*)vt; a.out = (_Float16*)out;
   a.heads = heads; a.lq = lq; a.lk = lk; a.d = d; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
   a.scale_log2 = scale * 1.4426950408889634f;
-  a.no_spec = 0;
   const size_t lds = (size_t)2 * BKV * d * sizeof(_Float16);          // K tile + V^T tile
   hipStream_t s = (hipStream_t)stream;
   // 128 queries per workgroup (8 waves) from one full round of such workgroups on (VAE batch 8: 470 -> 300 us; half a round -- batch 4 -- is a tie,
-  // below it the 64-query form wins by 8 - 10 %); SD_WIDE_NW = 4 / 8 forces either (A/B timing)
-  static const int nw_env = [] { const char* e = getenv("SD_WIDE_NW"); return e ? atoi(e) : 0; }();
-  const bool eight = nw_env ? nw_env == 8 : (long long)batch * heads * ((lq + 127) / 128) >= 256;
+  // below it the 64-query form wins by 8 - 10 %)
+  const bool eight = (long long)batch * heads * ((lq + 127) / 128) >= 256;
 #define SD_WIDE_LAUNCH(DT, NW)                                                                                                \
   do {                                                                                                                        \
     static coma::LdsOptIn lds_opt;                                                                                            \

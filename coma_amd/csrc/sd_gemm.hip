@@ -19,9 +19,7 @@
 // per-32-row column sums / sums of squares of the stored tensor (the consumer's GroupNorm statistics).
 #include <hip/hip_fp16.h>
 
-#include <cstdlib>
 #include <type_traits>
-#include <vector>
 
 #include "common.h"
 #include "sd_gelu.h"
@@ -40,10 +38,15 @@ typedef float float4v __attribute__((ext_vector_type(4)));
 
 constexpr int BKMIN = 32;   // source channel counts must be multiples of this (and of 64 for the deep-K variant)
 
-// Tuning aid (SD_GEMM_DBG=1): blocks 0..DBG_BLOCKS-1 record s_memtime at kernel entry, first tile landed, end of the K loop and
-// end of the epilogue; read back with sd_debug_timestamps().
+// K walked tap-major for a 3x3 launch (set by the dispatcher on GemmArgs::epi only; not one of the caller's SD_EPI_* flags)
+constexpr int EPI_TAPMAJOR = 1 << 28;
+
+#ifdef GEMM_DBG
+// Tuning aid, compiled in with -DGEMM_DBG (scripts/build_variant.sh): blocks 0..DBG_BLOCKS-1 record the shader clock at kernel
+// entry, first tile landed, end of the K loop and end of the epilogue; read back with sd_debug_timestamps().
 constexpr int DBG_BLOCKS = 4096;
 __device__ unsigned long long g_dbg_stamps[DBG_BLOCKS * 4];
+#endif
 
 struct GemmArgs {
   const _Float16* a0;
@@ -67,7 +70,9 @@ struct GemmArgs {
   int ksplit;                 // >1: blockIdx.z selects a K range and fp32 partials go to `partial`
   float* partial;             // [ksplit][M][N] fp32
   long long sa, sw, so, sr;   // per-blockIdx.z strides in elements (batched mode, ksplit == 1)
-  unsigned long long* dbg;    // nullptr unless SD_GEMM_DBG is set
+#ifdef GEMM_DBG
+  unsigned long long* dbg;    // g_dbg_stamps
+#endif
   _Float16* out_t;            // optional: columns >= n_split leave transposed per sample, keys in the PERM16 order (sd_conv_gemm_desc.out_t)
   int n_split, ldo_t, rps;
   // Sub-pixel phase of `conv3x3(nearest-upsample-x2(x))` (sd_conv_gemm_desc.phase): taps = 4 is a 2 x 2 window over the SOURCE whose origin
@@ -83,9 +88,13 @@ __device__ __forceinline__ long long out_row(const GemmArgs& g, int m) {
   return g.phase ? 2LL * m + ((long long)(m >> g.ph_wshift) << (g.ph_wshift + 1)) + g.ph_rowoff : (long long)m;
 }
 
+#ifdef GEMM_DBG
 __device__ __forceinline__ void dbg_stamp(const GemmArgs& g, int slot) {
-  if (g.dbg && blockIdx.y == 0 && blockIdx.x < DBG_BLOCKS && threadIdx.x == 0) g.dbg[blockIdx.x * 4 + slot] = __builtin_readcyclecounter();
+  if (blockIdx.y == 0 && blockIdx.x < DBG_BLOCKS && threadIdx.x == 0) g.dbg[blockIdx.x * 4 + slot] = __builtin_readcyclecounter();
 }
+#else
+#define dbg_stamp(g, slot) ((void)0)
+#endif
 
 __device__ __forceinline__ float silu(float x) { return x / (1.0f + __expf(-x)); }
 __device__ __forceinline__ float quick_gelu(float x) { return x / (1.0f + __expf(-1.702f * x)); }     // x * sigmoid(1.702 x) (CLIP MLP)
@@ -598,7 +607,7 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_gemm_kernel(GemmArgs g) {
   // the same (pixel, channel-chunk) lines shifted by one pixel -- ~50 KB per workgroup that stays in L2 -- where the
   // tap-major order re-fetched the whole 164 KB activation tile of the workgroup per tap (working set of an XCD 5 MB > L2:
   // rocprofv3 showed 9x the activation bytes on the fabric).  The sum over K is the same set of products in another order.
-  const bool tapminor = g.taps == 9 && !g.upsample && !(g.epi & (1 << 28));
+  const bool tapminor = g.taps == 9 && !g.upsample && !(g.epi & EPI_TAPMAJOR);
   int ld_tap, ld_ci;
   if (tapminor) {
     ld_tap = __builtin_amdgcn_readfirstlane(kt0 % 9);
@@ -860,43 +869,21 @@ using namespace sd;
 
 extern "C" size_t sd_conv_gemm_workspace_bytes(void) { return (size_t)64 << 20; }
 
+#ifdef GEMM_DBG
+// [n_blocks][4] stamps of the most recent launch (synchronises the device); not part of the product ABI
 extern "C" int sd_debug_timestamps(unsigned long long* host_dst, int n_blocks) {
   if (!host_dst || n_blocks <= 0 || n_blocks > DBG_BLOCKS) return fail(COMA_E_INVALID, "sd_debug_timestamps: bad arguments");
   if (hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(g_dbg_stamps), (size_t)n_blocks * 4 * sizeof(unsigned long long)) != hipSuccess)
     return fail(COMA_E_LAUNCH, "sd_debug_timestamps: copy failed");
   return COMA_OK;
 }
+#endif
 
 extern "C" int sd_conv_gemm_f16(const sd_conv_gemm_desc* d_in, void* stream) {
   if (sd::plan_recording()) return sd::record_conv(d_in);
   if (!d_in) return fail(COMA_E_INVALID, "sd_conv_gemm_f16: null descriptor");
-  // SD_GEMM_TUNE=<mask> (or _1X1 / _3X3 for those launches only): OR tuning-knob bits (SD_EPI_TUNING_MASK) into every launch -- lets a dispatch rule be A/B-tested inside the
-  // captured UNet (scripts/time_unet.py), where cache state differs from a layer timed alone (profiles/r02_notes.md section 14)
-  static const int tune_env = getenv("SD_GEMM_TUNE") ? (int)strtol(getenv("SD_GEMM_TUNE"), nullptr, 0) & SD_EPI_TUNING_MASK : 0;
+  if (d_in->epi & ~SD_EPI_ALL) return fail(COMA_E_INVALID, "sd_conv_gemm_f16: epi 0x%x holds bits outside SD_EPI_ALL", d_in->epi);
   sd_conv_gemm_desc d_copy = *d_in;
-  static const int tune1_env = getenv("SD_GEMM_TUNE_1X1") ? (int)strtol(getenv("SD_GEMM_TUNE_1X1"), nullptr, 0) & SD_EPI_TUNING_MASK : 0;
-  static const int tune9_env = getenv("SD_GEMM_TUNE_3X3") ? (int)strtol(getenv("SD_GEMM_TUNE_3X3"), nullptr, 0) & SD_EPI_TUNING_MASK : 0;
-  d_copy.epi |= tune_env | (d_in->taps == 1 ? tune1_env : tune9_env);
-  {   // SD_GEMM_FORCE="N,K,mask;N,K,mask;...": knob bits for the launches with that N and K only (K = taps * channels)
-    struct Force { int n, k, mask; };
-    static const std::vector<Force> forced = [] {
-      std::vector<Force> v;
-      const char* e = getenv("SD_GEMM_FORCE");
-      while (e && *e) {
-        Force f{0, 0, 0};
-        char* end = nullptr;
-        f.n = (int)strtol(e, &end, 0); if (*end != ',') break;
-        f.k = (int)strtol(end + 1, &end, 0); if (*end != ',') break;
-        f.mask = (int)strtol(end + 1, &end, 0) & SD_EPI_TUNING_MASK;
-        v.push_back(f);
-        e = *end == ';' ? end + 1 : end;
-        if (*end != ';') break;
-      }
-      return v;
-    }();
-    for (const Force& f : forced)
-      if (f.n == d_in->n && f.k == d_in->taps * (d_in->c0 + d_in->c1)) d_copy.epi |= f.mask;
-  }
   // a plain product with more than 65536 rows given as batch x 1 x 1: the kernel keeps the sample index in 16 bits, so fold a power of
   // two of the rows into the "image" (same row order; not with a per-sample bias, whose index is the sample)
   if (d_copy.taps == 1 && d_copy.in_h == 1 && d_copy.in_w == 1 && d_copy.out_h == 1 && d_copy.out_w == 1 && d_copy.batch > 65536 && !d_copy.bias_bn &&
@@ -912,7 +899,7 @@ extern "C" int sd_conv_gemm_f16(const sd_conv_gemm_desc* d_in, void* stream) {
   if (phase) {
     // sub-pixel phase of conv3x3(nearest-upsample-x2(x)): a 2 x 2 window over the source, rows scattered to the output pixels of that parity
     if (d->taps != 4 || d->stride != 1 || d->upsample || d->out_h != d->in_h || d->out_w != d->in_w || (d->in_w & (d->in_w - 1)) ||
-        (d->nbatch_z > 1) || d->res || d->bias_bn || d->out_t || (d->epi & ~SD_EPI_TUNING_MASK) || d->n % 8 ||
+        (d->nbatch_z > 1) || d->res || d->bias_bn || d->out_t || d->epi || d->n % 8 ||
         (d->ldo > 0 && d->ldo % 8))
       return fail(COMA_E_INVALID, "sd_conv_gemm_f16: a phase launch needs taps = 4, stride 1, out = in size, in_w a power of two, n %% 8 == 0 and "
                                   "a plain epilogue (bias, optional colstats)");
@@ -981,33 +968,29 @@ extern "C" int sd_conv_gemm_f16(const sd_conv_gemm_desc* d_in, void* stream) {
   const bool deep = g.K >= 1024 && k64;
   // 256 x 320 tile: N a multiple of 320 (every layer of the SD UNet), enough rows to fill the chip with 1 block / CU
   // ... or z-batched plain products whose tiles fill it together (the 16 plane products of a Winograd convolution at the 16 x 16 level:
-  // 4 x 4 tiles x 16 planes = one block per CU, where the generic 128 x 128 tile needs 2.5 rounds; SD_GEMM_ZBIG=0 switches it off for A/B)
-  static const bool zbig_on = !getenv("SD_GEMM_ZBIG") || atoi(getenv("SD_GEMM_ZBIG")) != 0;
-  const bool zplain = nz > 1 && zbig_on && d->taps == 1 && !d->colstats && !d->out_t &&
-                      !(d->epi & ~SD_EPI_TUNING_MASK);
-  const bool big = !geglu && (nz == 1 || zplain) && k64 && g.N % 320 == 0 && (long long)((g.M + 255) / 256) * (g.N / 320) * nz >= 192 &&
-                   !(d->epi & ((1 << 20) | (1 << 21)));
+  // 4 x 4 tiles x 16 planes = one block per CU, where the generic 128 x 128 tile needs 2.5 rounds)
+  const bool zplain = nz > 1 && d->taps == 1 && !d->colstats && !d->out_t && !d->epi;
+  const bool big = !geglu && (nz == 1 || zplain) && k64 && g.N % 320 == 0 && (long long)((g.M + 255) / 256) * (g.N / 320) * nz >= 192;
   // GEGLU (needs an even number of MFMA column tiles per wave): 256 x 256, 8 waves, wave tile 64 x 128
-  const bool big_geglu = geglu && nz == 1 && k64 && g.N % 256 == 0 && g.M >= 256 * 16 && !(d->epi & (1 << 20));
+  const bool big_geglu = geglu && nz == 1 && k64 && g.N % 256 == 0 && g.M >= 256 * 16;
   // VAE widths (128 / 256 / 512 channels at up to 512 x 512 pixels): 256 x 256 and 256 x 128 tiles, 8 waves
-  const bool big256 = !geglu && !big && nz == 1 && k64 && g.N % 256 == 0 && g.M >= 256 * 128 && !(d->epi & (1 << 20));
-  const bool big128 = !geglu && !big && !big256 && nz == 1 && k64 && g.N % 128 == 0 && g.M >= 256 * 256 && !(d->epi & (1 << 20));
+  const bool big256 = !geglu && !big && nz == 1 && k64 && g.N % 256 == 0 && g.M >= 256 * 128;
+  const bool big128 = !geglu && !big && !big256 && nz == 1 && k64 && g.N % 128 == 0 && g.M >= 256 * 256;
   // 256 x 128 with FOUR waves (wave tile 64 x 128), BK = 32, 3 stages = 72 KiB of LDS, so that two independent blocks share a CU
   // (one block's epilogue and barriers run under the other's K loop): the 128-channel 3x3 convs of the VAE at 512 x 512
   // (K = 1152, where the output pass is a quarter of the launch).  800 TF/s isolated, the same as 512 x 128 with 8 waves (789) and
   // +15 % over 128 x 128; at K >= 2304 and for N >= 256 the 8-wave tiles win by 10-15 % (profiles/r02_notes.md section 10)
-  const bool tall128 = big128 && g.K <= 1152 && !(d->epi & (1 << 20));
+  const bool tall128 = big128 && g.K <= 1152;
   // 128 x 320, 4 waves (wave tile 64 x 160): mid-size M where 256-row tiles would leave CUs idle
   // ... and, split in two along K, for the deep 3x3 convs at 16 x 16 (M = 4096, N = 1280, K >= 11520): 32 x 4 tiles x 2 splits = one
   // block per CU, where 128 x 128 tiles leave 320 blocks for 512 slots (+4 % at K = 11520, +15 % at K = 23040, profiles/r02_notes.md 12)
   const bool midsk = !big && !geglu && nz == 1 && k64 && g.N % 320 == 0 && g.N >= 1280 && g.M >= 4096 && g.M < 128 * 64 && g.K >= 8192 &&
                      !d->colstats && d->workspace && d->workspace_bytes >= (size_t)2 * g.M * g.N * sizeof(float) &&
-                     (long long)((g.M + 127) / 128) * (g.N / 320) * 2 <= 256 && !(d->epi & ((1 << 20) | (1 << 21)));
-  const bool mid = (!big && !big256 && !big128 && !geglu && nz == 1 && g.N % 320 == 0 && (g.M >= 128 * 64 || (d->epi & (1 << 21))) &&
-                    (g.N <= 640 || (d->epi & (1 << 21))) && !(d->epi & (1 << 20))) || midsk;
+                     (long long)((g.M + 127) / 128) * (g.N / 320) * 2 <= 256;
+  const bool mid = (!big && !big256 && !big128 && !geglu && nz == 1 && g.N % 320 == 0 && g.M >= 128 * 64 && g.N <= 640) || midsk;
   // 128 x 320 with EIGHT waves (wave tile 32 x 160, two waves per SIMD) instead of four: the partner wave covers each
-  // wave's LDS-read / DMA-issue latency, which the 4-wave tile leaves exposed (knob 23 selects the 4-wave form)
-  const bool mid8 = mid && k64 && g.K >= 256 && !(d->epi & (1 << 23));
+  // wave's LDS-read / DMA-issue latency, which the 4-wave tile leaves exposed
+  const bool mid8 = mid && k64 && g.K >= 256;
   const bool wide = g.N % 128 == 0 || g.N > 256;
   const int bm = ((big || big_geglu || big256 || big128) ? 256 : 128);
   const int bn = (big || mid) ? 320 : ((big_geglu || big256) ? 256 : ((wide || big128) ? 128 : 64));
@@ -1016,15 +999,15 @@ extern "C" int sd_conv_gemm_f16(const sd_conv_gemm_desc* d_in, void* stream) {
   // split-K when the tile grid cannot fill the chip: as many splits as keep every block resident at once (2 per CU,
   // 512 in total -- a partial second round costs more than it buys), at least 384 of K per split
   g.ksplit = 1;
-  static const bool dbg_on = getenv("SD_GEMM_DBG") != nullptr;
-  g.dbg = nullptr;
-  if (dbg_on) { void* p = nullptr; if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_dbg_stamps)) == hipSuccess) g.dbg = (unsigned long long*)p; }
+#ifdef GEMM_DBG
+  if (hipGetSymbolAddress((void**)&g.dbg, HIP_SYMBOL(g_dbg_stamps)) != hipSuccess) return fail(COMA_E_LAUNCH, "sd_conv_gemm_f16: no g_dbg_stamps");
+#endif
   g.partial = (float*)d->workspace;
   g.colstats = (float*)d->colstats;
   g.out_t = (_Float16*)d->out_t; g.n_split = d->n_split; g.ldo_t = d->ldo_t; g.rps = d->rows_per_sample;
   if (g.out_t) {
     if (geglu || nz != 1 || d->taps != 1 || d->c1 > 0 || d->bias || d->bias_bn || d->res || d->colstats ||
-        (d->epi & ~SD_EPI_TUNING_MASK) || d->n_split <= 0 || d->n_split % 640 || (d->n - d->n_split) <= 0 || (d->n - d->n_split) % 640 ||
+        d->epi || d->n_split <= 0 || d->n_split % 640 || (d->n - d->n_split) <= 0 || (d->n - d->n_split) % 640 ||
         g.M % 32 || d->rows_per_sample <= 0 || d->rows_per_sample % 32 || g.M % d->rows_per_sample || d->ldo_t % 8 || d->ldo_t < d->rows_per_sample ||
         g.ldo < d->n_split || g.ldo % 8)
       return fail(COMA_E_INVALID, "sd_conv_gemm_f16: out_t needs a plain linear (no bias / residual / GEGLU / statistics / batching), n_split and "
@@ -1039,7 +1022,7 @@ extern "C" int sd_conv_gemm_f16(const sd_conv_gemm_desc* d_in, void* stream) {
   // second N tile re-reads A from L2 anyway and the order is neutral to -10 %, profiles/r02_notes.md).  The 8-wave 128 x 320 tile
   // follows the same rule so that a half-batch launch of such a layer (the shared CFG prefix) accumulates in the same order as the
   // full-batch one and stays bit-identical to it.
-  if (!((big || mid8) && gy == 1)) g.epi |= (1 << 28);
+  if (!((big || mid8) && gy == 1)) g.epi |= EPI_TAPMAJOR;
   const long long blocks = (long long)gx * gy;
   const int nk = g.K / bk;
   const int min_tiles = 384 / bk;
@@ -1049,16 +1032,14 @@ extern "C" int sd_conv_gemm_f16(const sd_conv_gemm_desc* d_in, void* stream) {
     if (s > 16) s = 16;
     while (s > 1 && (size_t)s * g.M * g.N * sizeof(float) > d->workspace_bytes) --s;
     if (s > 1) g.ksplit = s;
-    const int force = (d->epi >> 24) & 15;      // tuning knob: forced split factor
-    if (force && (size_t)force * g.M * g.N * sizeof(float) <= d->workspace_bytes) g.ksplit = force > nk ? nk : force;
   }
   const long long lin_blocks = gx >= 16 ? 8LL * ((gx + 7) / 8) * gy : (long long)gx * gy;   // XCD-banded order (see kernel)
   if (lin_blocks > 0x7fffffffLL) return fail(COMA_E_INVALID, "sd_conv_gemm_f16: grid too large");
   dim3 grid((unsigned)lin_blocks, (unsigned)(g.ksplit > 1 ? g.ksplit : nz));
   hipStream_t st = (hipStream_t)stream;
   // DMA issue spread over the K steps of a tile (3x3: +0.5 % of a UNet forward) or in one burst (1x1: +0.6 %) -- both measured inside the
-  // captured forward; knob 22 forces the burst
-  const bool spread = !(d->epi & (1 << 22)) && d->taps == 9;
+  // captured forward
+  const bool spread = d->taps == 9;
 #define GEMM_LAUNCH(WM_, WN_, TN_, BK_, ST_, SP_, TM_, THREADS_)                                                                  \
   do {                                                                                                                           \
     if (m16) hipLaunchKernelGGL((conv_gemm_kernel<WM_, WN_, TN_, BK_, ST_, SP_, TM_, true>), grid, dim3(THREADS_), 0, st, g);    \
@@ -1066,10 +1047,8 @@ extern "C" int sd_conv_gemm_f16(const sd_conv_gemm_desc* d_in, void* stream) {
   } while (0)
   // 16x16x32 MFMAs in the K loop of every launch with K >= 256 (measured inside the captured graphs, A B A B: UNet forward -0.2 ms from the
   // 3x3 convolutions -- the power-limited ones -- and another -0.45 ms from the 1x1 / linear launches, most of it at K = 320; VAE decode
-  // -0.65 ms).  SD_GEMM_M16 / SD_GEMM_M16_1X1 = <minimum K, 0 = off> override the rule for A/B runs.
-  static const int m16_env = getenv("SD_GEMM_M16") ? atoi(getenv("SD_GEMM_M16")) : 256;
-  static const int m16_1x1 = getenv("SD_GEMM_M16_1X1") ? atoi(getenv("SD_GEMM_M16_1X1")) : 256;
-  const bool m16 = (d->taps == 9 ? (m16_env && g.K >= m16_env) : (m16_1x1 && g.K >= m16_1x1));
+  // -0.65 ms)
+  const bool m16 = g.K >= 256;
   if (big && spread) GEMM_LAUNCH(4, 2, 5, 64, 2, true, 2, 512);
   else if (wide && deep && spread && !big_geglu && !big256 && !big128 && !mid) GEMM_LAUNCH(2, 2, 2, 64, 2, true, 2, 256);
   else if (big) GEMM_LAUNCH(4, 2, 5, 64, 2, false, 2, 512);

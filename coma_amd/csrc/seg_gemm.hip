@@ -57,7 +57,7 @@ struct GemmArgs {
   long long M;
   const float* zeros;                        // 16 bytes of zeros in global memory
   float* ws; int splits, nk_per, ws_ld;      // split-K: slab z of the workspace is [gx * BM][ws_ld] raw partial sums
-  int gx, gy, band;                                                  // row / column tiles (the grid is 1-D: see the tile order in the kernel)
+  int gx, gy;                                                        // row / column tiles (the grid is 1-D: see the tile order in the kernel)
 };
 
 template <int WM, int WN, int TM, int TN, bool UNI, bool PRE>
@@ -78,11 +78,10 @@ __global__ __launch_bounds__(256, (WM * TM * WN * TN <= 8 ? 3 : 2)) void conv_ge
   {
     const int T = a.gx * a.gy, L = (int)blockIdx.x;
     const int xcd = L & 7, slot = L >> 3, q = T >> 3, r = T & 7;
-    tile_id = a.band ? xcd * q + (xcd < r ? xcd : r) + slot : L;
+    tile_id = xcd * q + (xcd < r ? xcd : r) + slot;
   }
-  int tmx, tnx;
-  if (a.band) { tmx = tile_id / a.gy; tnx = tile_id - tmx * a.gy; }       // banded: column tiles of one row band adjacent
-  else { tnx = tile_id / a.gx; tmx = tile_id - tnx * a.gx; }             // plain: row tiles fastest (the order of a 2-D grid)
+  // (the tile indices are wave-uniform: readfirstlane pins them to SGPRs, which also saves the compiler two more live scalar registers)
+  const int tmx = __builtin_amdgcn_readfirstlane(tile_id / a.gy), tnx = __builtin_amdgcn_readfirstlane(tile_id - tmx * a.gy);
   const int m0 = tmx * BM;                               // M < 2^31 - BM (checked by the launcher): row arithmetic in 32 bits
   const int n0 = tnx * BN;
   const int Mv = (int)a.M;
@@ -470,12 +469,9 @@ static int launch_gemm(GemmArgs& a, hipStream_t st, int force_split, size_t ws_b
     a.splits = (nk + a.nk_per - 1) / a.nk_per;            // every slice non-empty
   }
   a.gx = (int)gx; a.gy = gy;
-  static const int band_env = getenv("SEG_XCD_BAND") ? atoi(getenv("SEG_XCD_BAND")) : -1;      // A/B aid: 0 = plain order, 1 = banded everywhere
-  a.band = band_env >= 0 ? band_env : 1;
-  static const int pre_env = getenv("SEG_EPI_PREFETCH") ? atoi(getenv("SEG_EPI_PREFETCH")) : 1;  // A/B aid: 0 = residual read inside the epilogue
-  // (only for K <= 128: from K = 256 on the K loop hides the epilogue of the co-resident workgroup anyway, and the 254-register kernel
-  // is the slower one -- res5.x.conv3, K = 512: 124 us without, 146 us with)
-  if (a.res_mode != 0 && a.splits == 1 && nk <= 4 && pre_env)
+  // the residual is requested before the epilogue only for K <= 128: from K = 256 on the K loop hides the epilogue of the co-resident
+  // workgroup anyway, and the 254-register kernel is the slower one (res5.x.conv3, K = 512: 124 us without, 146 us with)
+  if (a.res_mode != 0 && a.splits == 1 && nk <= 4)
     hipLaunchKernelGGL((conv_gemm_f32_kernel<WM, WN, TM, TN, UNI, true>), dim3((unsigned)(gx * gy), 1, 1), dim3(256), lds, st, a);
   else
     hipLaunchKernelGGL((conv_gemm_f32_kernel<WM, WN, TM, TN, UNI, false>), dim3((unsigned)(gx * gy), 1, (unsigned)a.splits), dim3(256), lds, st, a);

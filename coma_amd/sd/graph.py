@@ -13,10 +13,9 @@ from . import ops
 from .model import BUF_ZEROED, SdModel
 
 F16 = torch.float16
-_TORCH_GRAPH = __import__("os").environ.get("SD_TORCH_GRAPH") == "1"
 # GroupNorm statistics ride on the producer's epilogue from this many output rows on (below, the GEMMs are split-K launches whose reduce pass
-# owns the epilogue, and a one-launch GroupNorm is as cheap as the finalize + apply pair); SD_GN_STATS_MIN_M=<rows> for A/B runs
-GN_STATS_MIN_M = int(__import__("os").environ.get("SD_GN_STATS_MIN_M", 16384))
+# owns the epilogue, and a one-launch GroupNorm is as cheap as the finalize + apply pair)
+GN_STATS_MIN_M = 16384
 
 
 class LaunchGraph:
@@ -354,18 +353,6 @@ class LaunchGraph:
         self.model.run(self.plan)
 
     def replay(self):
-        if _TORCH_GRAPH:                          # A/B aid (SD_TORCH_GRAPH=1): torch.cuda.CUDAGraph over the Python closures
-            if getattr(self, "_tg", None) is None:
-                s = torch.cuda.Stream(self.device)
-                s.wait_stream(torch.cuda.current_stream(self.device))
-                with torch.cuda.stream(s):
-                    self.run()
-                torch.cuda.current_stream(self.device).wait_stream(s)
-                torch.cuda.synchronize(self.device)
-                self._tg = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self._tg):
-                    self.run()
-            return self._tg.replay()
         if not self._recorded:
             self.capture()            # recorded, then run eagerly once: that run IS this call's execution (no second pass over the step)
             self.model.prepare(self.plan)      # the hipGraph is captured and instantiated now (nothing executes), so the next call only launches

@@ -19,8 +19,6 @@ their consumer GEMMs (0.2-0.7 ms SLOWER per forward in three rounds of A/B), Ups
 """
 from __future__ import annotations
 
-import os
-
 import torch
 
 from . import ops
@@ -45,7 +43,7 @@ WINOGRAD_MAX_H = 32         # ResNet 3x3 convolutions of feature maps up to 32 x
 
 class HipUNet2DConditionModel:
     def __init__(self, state, batch, height=64, width=64, ctx_len=77, device="cuda", cfg=UNET_CFG, use_graph=True,
-                 cfg_shared_prefix=False, fuse_xchain=True, fuse_xfront=True, fuse_xtail=True, fuse_qkv=True, winograd_max_h=None,
+                 cfg_shared_prefix=False, fuse_xchain=True, fuse_xfront=True, fuse_xtail=True, fuse_qkv=True, winograd_max_h=WINOGRAD_MAX_H,
                  winograd_min_batch=8, xtail_min_rows=XTAIL_MIN_ROWS):
         """cfg_shared_prefix: the caller guarantees that the two halves of the batch carry IDENTICAL sample and timestep
         (classifier-free guidance: [uncond | cond] differ only in the text context, utils/adaptive_mask_inpainting.py:990).
@@ -62,9 +60,9 @@ class HipUNet2DConditionModel:
         self.fuse_xfront = fuse_xfront      # C = 320 blocks: norm, proj_in, norm1, to_q | to_k, to_v^T in one launch (sd_xfront_f16)
         self.fuse_qkv = fuse_qkv            # C = 640 / 1280 blocks: to_q | to_k | to_v one GEMM, V^T written transposed by its epilogue (sd_conv_gemm_desc.out_t)
         self.fuse_xtail = fuse_xtail        # C = 320 blocks: ff (GEGLU, Linear) + residual, proj_out + residual in one launch (sd_xtail_f16)
-        # ResNet 3x3 convolutions of feature maps up to this edge run as Winograd F(2x2,3x3) (0 = never; SD_WINOGRAD=<edge> for A/B runs), from
+        # ResNet 3x3 convolutions of feature maps up to this edge run as Winograd F(2x2,3x3) (0 = never), from
         # this UNet batch on (at batch 2 -- one image per call -- the plane products are a few tiles each and the direct form is 0.7 % faster)
-        self.winograd_max_h = int(os.environ.get("SD_WINOGRAD", WINOGRAD_MAX_H)) if winograd_max_h is None else int(winograd_max_h)
+        self.winograd_max_h = int(winograd_max_h)
         self.winograd_min_batch = int(winograd_min_batch)
         self.xtail_min_rows = int(xtail_min_rows)
         self.cfg_shared_prefix = bool(cfg_shared_prefix) and batch % 2 == 0 and cfg["down_has_attn"][0]

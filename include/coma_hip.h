@@ -28,9 +28,7 @@ extern "C" {
 
 /* bumped whenever ANY exported signature of coma_hip.h / sd_hip.h / seg_hip.h changes; coma_amd/_lib.py refuses a library that
  * reports another value (a stale build loaded through COMA_HIP_LIB would otherwise be called with mismatched argument lists) */
-#define COMA_ABI_VERSION 8   /* the text-tower entry points (sd_text_embed_f16, sd_attention_causal_f16, sd_text_encode) only ADDED functions and
-                                left every existing signature as it was, so the version stays 8; a library built before them still fails
-                                to load here, because it lacks their symbols (coma_amd/_lib.py binds every function of the table) */
+#define COMA_ABI_VERSION 9   /* 9: sd_debug_timestamps removed, sd_conv_gemm_f16 refuses epi bits outside SD_EPI_ALL */
 
 #define COMA_OK 0
 #define COMA_E_INVALID (-1) /* bad argument (null pointer, non-positive size, unsupported shape) */

@@ -35,11 +35,9 @@ extern "C" {
 #define SD_EPI_PERM32_N 16  /* position p = 8g + e of every group of 32 output columns holds the product with W row 16 (e >> 2) + 4g + (e & 3):
                                the V^T layout sd_attention_wide_f16 reads (one 16-byte LDS load per 16x16x32 MFMA operand).  n % 32 == 0 */
 #define SD_EPI_QUICK_GELU 32 /* out = a * sigmoid(1.702 a), a = acc + bias (CLIP's quick_gelu, fc1 of the text tower); not with GEGLU / SiLU */
-/* bits 20..27 select kernel variants for tuning runs (scripts/time_gemm.py): 20 = generic 128x128 tiles only, 21 = 128x320
- * tile, 22 = tile DMA in one burst, 23 = 4-wave 128x320 tile, 24..27 = forced split-K factor, 28 = tap-major K order for 3x3.  Results agree to
- * fp32 summation order.  Process-wide overrides for A/B runs inside a captured graph (read once): SD_GEMM_TUNE / SD_GEMM_TUNE_1X1 / SD_GEMM_TUNE_3X3 =
- * <mask of these bits>, SD_GEMM_FORCE="N,K,mask;...", SD_GEMM_M16 / SD_GEMM_M16_1X1 = <minimum K for the 16x16x32 K loop, 0 = 32x32x16 everywhere>. */
-#define SD_EPI_TUNING_MASK 0x1ff00000
+/* every flag above; sd_conv_gemm_f16 refuses (COMA_E_INVALID) an epi with any other bit set.  The kernel, tile and split-K factor
+ * of a launch are a function of the descriptor alone. */
+#define SD_EPI_ALL (SD_EPI_GEGLU | SD_EPI_SILU | SD_EPI_BIAS_ROWS | SD_EPI_PERM16_N | SD_EPI_PERM32_N | SD_EPI_QUICK_GELU)
 
 /* out[m, n] = sum_k A[m, k] * W[n, k] (+ epilogue) with A gathered from one or two NHWC sources:
  *   m = (b, oy, ox), k = (tap, ci);  taps = 9: 3x3, zero pad 1;  taps = 1: 1x1 / linear;  taps = 4: one sub-pixel phase (see `phase`)
@@ -91,10 +89,6 @@ typedef struct sd_conv_gemm_desc {
 
 int sd_conv_gemm_f16(const sd_conv_gemm_desc* desc, void* stream);
 size_t sd_conv_gemm_workspace_bytes(void); /* recommended workspace size */
-/* Tuning aid: with SD_GEMM_DBG set in the environment, the first 4096 workgroups of every sd_conv_gemm_f16 launch record the
- * shader clock at {entry, first K tile landed, end of the K loop, end of the epilogue}; this copies [n_blocks][4] u64 stamps of the
- * most recent launch to the host (synchronises the device). */
-int sd_debug_timestamps(unsigned long long* host_dst, int n_blocks);
 
 /* GroupNorm (+ optional SiLU) over NHWC fp16, reading the channel concatenation of two sources and writing one
  * tensor [batch, hw, c0+c1].  replaces: nn.GroupNorm(groups, C, eps) + nn.SiLU in diffusers ResnetBlock2D /

@@ -1,10 +1,9 @@
 #!/usr/bin/env python3
-"""Per-phase cycle breakdown of conv_gemm launches (tuning aid): SD_GEMM_DBG=1 python scripts/phase_gemm.py
-For each shape: kernel time (HIP events), and per workgroup the shader-clock cycles spent in
+"""Per-phase cycle breakdown of conv_gemm launches (tuning aid; needs the -DGEMM_DBG build: scripts/build_variant.sh gemm_dbg -DGEMM_DBG,
+run with COMA_HIP_LIB=coma_amd/_ab/gemm_dbg.so).  For each shape: kernel time (HIP events), and per workgroup the shader-clock cycles spent in
 prologue (entry -> first K tile landed), K loop, epilogue; plus the effective clock = cycles(first entry -> last exit) / time."""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("SD_GEMM_DBG", "1")
 import numpy as np
 import torch
 from coma_amd import _lib
@@ -13,7 +12,7 @@ dev = "cuda:0"
 WS = torch.empty(96 << 20, dtype=torch.float32, device=dev)
 
 
-def run(M, N, K, taps=1, hw=None, epi=0, res=True, knob=0):
+def run(M, N, K, taps=1, hw=None, epi=0, res=True):
     C_ = K // taps
     if taps == 9:
         B, H = M // hw, int(hw ** 0.5)
@@ -26,18 +25,20 @@ def run(M, N, K, taps=1, hw=None, epi=0, res=True, knob=0):
     r = torch.randn(M, N, device=dev).half() if res and not (epi & 1) else None
     out = torch.empty(M, N // 2 if epi & 1 else N, device=dev, dtype=torch.float16)
     for _ in range(3):
-        ops.conv_gemm(x, w, out, bias=b, res=r, epi=epi | knob, workspace=WS, **kw)
+        ops.conv_gemm(x, w, out, bias=b, res=r, epi=epi, workspace=WS, **kw)
     torch.cuda.synchronize()
     a, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record()
     reps = 10
     for _ in range(reps):
-        ops.conv_gemm(x, w, out, bias=b, res=r, epi=epi | knob, workspace=WS, **kw)
+        ops.conv_gemm(x, w, out, bias=b, res=r, epi=epi, workspace=WS, **kw)
     e.record(); torch.cuda.synchronize()
     us = a.elapsed_time(e) / reps * 1e3
     nb = 4096
     st = np.zeros((nb, 4), dtype=np.uint64)
-    _lib.check(_lib.lib().sd_debug_timestamps(st.ctypes.data_as(C.c_void_p), nb), "dbg")
+    lib = _lib.lib()
+    lib.sd_debug_timestamps.restype = C.c_int
+    _lib.check(lib.sd_debug_timestamps(st.ctypes.data_as(C.c_void_p), nb), "sd_debug_timestamps")
     st = st.astype(np.int64)
     ok = (st[:, 3] > st[:, 0]) & (st[:, 0] > 0)
     # only blocks of the last launch: their entry stamps lie within one kernel duration of the newest exit
@@ -64,8 +65,7 @@ SH = [(65536, 320, 320, 1, None, 0), (65536, 320, 1280, 1, None, 0), (65536, 320
 if os.environ.get("TAIL"):      # the short-K launches of the C = 640 / 1280 transformer blocks
     SH = [(16384, 640, 640, 1, None, 0), (4096, 1280, 1280, 1, None, 0), (16384, 1920, 640, 1, None, 0), (4096, 3840, 1280, 1, None, 0),
           (16384, 640, 2560, 1, None, 0), (4096, 1280, 5120, 1, None, 0), (16384, 5120, 640, 1, None, 1), (4096, 10240, 1280, 1, None, 1)]
-knob = sum(1 << int(b) for b in sys.argv[1].split("+")) if len(sys.argv) > 1 else 0
 for sh in SH:
     if os.environ.get("GEGLU_ONLY") and not sh[5]:
         continue
-    run(*sh, knob=knob)
+    run(*sh)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Time sd_attention_f16 at the UNet's self-attention shapes and check it against torch fp32 (tuning aid).
-   python scripts/time_attention.py            # env SD_ATTN_V=1|2 picks the kernel generation where both apply"""
+   python scripts/time_attention.py"""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

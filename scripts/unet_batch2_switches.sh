@@ -11,8 +11,6 @@ for rep in 1 2; do
   echo "== --no-xtail";              $T --no-xtail | tail -1
   echo "== --no-qkv";                $T --no-qkv | tail -1
   echo "== winograd from batch 2";   $T --wino-min-batch=2 | tail -1
-  echo "== GN stats from M=8192";    SD_GN_STATS_MIN_M=8192 $T | tail -1
-  echo "== GN stats from M=2048";    SD_GN_STATS_MIN_M=2048 $T | tail -1
   echo "== eager (no graph)";        $T --eager | tail -1
 done
 echo "== per-class breakdown, batch 2"
