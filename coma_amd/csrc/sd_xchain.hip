@@ -250,6 +250,8 @@ __global__ __launch_bounds__(NW * 64, 2) void xchain_kernel(Args g) {
     };
     half8 kf[9], vf[10];
     // fragments of head hd: K[key = 32 t + l31][dd = 16 ks + 8 hh ..] (dd >= 40: zero), V^T[dd = 32 t + l31][keys of chunk 2 st + hh].
+    // P.V covers key positions 0 .. 79 (5 chunks of 16: vf, pf below), so the entry point accepts lk <= 80; the third score tile exists
+    // for keys 64 .. 79 only.
     // One register set each: the NEXT head's K is requested as soon as this head's QK^T has consumed the registers, the next V^T as
     // soon as P.V has -- both are in flight under the rest of the head (register budget: 256 with two waves per SIMD).
     auto fetch_k = [&](int hd) {
@@ -593,9 +595,9 @@ extern "C" int sd_xattn_chain_f16(const void* attn1_out, const void* h, const vo
                                                  rows_per_sample, lk, ldv2, eps);
   if (!attn1_out || !h || !wo1 || !bo1 || !gamma2 || !beta2 || !wq2 || !k2 || !vt2 || !wo2 || !bo2 || !gamma3 || !beta3 || !h2 || !n3)
     return fail(COMA_E_INVALID, "sd_xattn_chain_f16: null pointer");
-  if (rows <= 0 || rows_per_sample <= 0 || rows % rows_per_sample || rows_per_sample % xc::TM || lk <= 0 || lk > 96 || ldv2 < 80 || ldv2 % 8 ||
+  if (rows <= 0 || rows_per_sample <= 0 || rows % rows_per_sample || rows_per_sample % xc::TM || lk <= 0 || lk > 80 || ldv2 < 80 || ldv2 % 8 ||
       rows * xc::C * 2 >= 0x80000000LL)
-    return fail(COMA_E_INVALID, "sd_xattn_chain_f16: bad sizes (C = 320, rows per sample a multiple of 64, at most 96 keys, ldv2 >= 80)");
+    return fail(COMA_E_INVALID, "sd_xattn_chain_f16: bad sizes (C = 320, rows per sample a multiple of 64, at most 80 keys, ldv2 >= 80)");
   xc::Args g;
   g.a = (const _Float16*)attn1_out; g.h = (const _Float16*)h; g.wo1 = (const _Float16*)wo1; g.bo1 = (const _Float16*)bo1;
   g.g2 = (const _Float16*)gamma2; g.b2 = (const _Float16*)beta2; g.wq = (const _Float16*)wq2; g.k2 = (const _Float16*)k2;

@@ -259,7 +259,7 @@ class HipUNet2DConditionModel:
         g.attention(qk, qk.view(-1)[C:], vt, a, batch=B, heads=heads, lq=L, lk=L, d=d, ldq=2 * C, ldk=2 * C, ldv=ldv, ldo=C, vt_perm16=True)
         Lk, cd = self.ctx_len, self.ctx_dim
         ldv2 = (Lk + 15) // 16 * 16
-        xchain = self.fuse_xchain and C == 320 and L % 64 == 0 and Lk <= 96
+        xchain = self.fuse_xchain and C == 320 and L % 64 == 0 and Lk <= 80     # the kernel multiplies 80 key positions (5 chunks of 16)
 
         def context_kv(Bf):
             """K / V^T of the text context for this block (per-prompt graph)."""

@@ -185,9 +185,9 @@ int sd_xtail_f16(const void* n3, const void* h2, const void* x, const void* w1, 
 
 /* The row-local middle of a BasicTransformerBlock at C = 320 (8 heads of 40) in ONE launch:
  *   h1 = attn1_out Wo1^T + bo1 + h;  n2 = LayerNorm(h1; gamma2, beta2);  q2 = n2 Wq2^T;
- *   a2 = softmax(q2 K2^T / sqrt(40)) V2 per head over the lk <= 96 text tokens;  h2 = a2 Wo2^T + bo2 + h1;  n3 = LayerNorm(h2; gamma3, beta3)
+ *   a2 = softmax(q2 K2^T / sqrt(40)) V2 per head over the lk <= 80 text tokens;  h2 = a2 Wo2^T + bo2 + h1;  n3 = LayerNorm(h2; gamma3, beta3)
  * attn1_out, h: fp16 [rows, 320];  weights fp16 [320, 320] (nn.Linear layout);  k2 fp16 [rows / rows_per_sample, lk, 320];
- * vt2 fp16 [samples, 320, ldv2] = V2 transposed, keys in the SD_EPI_PERM16_N order (ldv2 >= 80, pad columns finite);
+ * vt2 fp16 [samples, 320, ldv2] = V2 transposed, keys in the SD_EPI_PERM16_N order (ldv2 >= 80, a multiple of 8; pad columns finite);
  * outputs h2, n3: fp16 [rows, 320] (h2 is also used as scratch for h1).  rows_per_sample a multiple of 64.
  * debug_out / debug_stage (tests): when debug_out != NULL the kernel stops after stage 1 (h1), 2 (n2), 3 (q2) or 4 (a2) and
  * writes that [rows, 320] tensor there.

@@ -382,3 +382,45 @@ def test_bench_dump_outputs_budget_and_sample(tmp_path):
     assert b.dtype == np.float32 and 0 < b.size < big.numel() and (np.diff(b) > 0).all() and 0 <= b[0] and b[-1] < big.numel()
     assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64_000_000
     assert np.array_equal(b, np.load(tmp_path / "b" / "big.npy"))
+
+
+def test_rowtile_reference_chain_reproduces_the_oracle_transformer():
+    """tests/rowtile_ref.py (the float64 truth of the C = 320 row-tile kernel tests) is tied to the project's oracle: for one sample of
+    64 tokens, 77 context tokens and random weights, xfront -> self-attention (oracle attention_ref) -> xchain -> xtail with
+    exact=True reproduces oracle.sd_oracle.transformer_ref to 1e-5 relative (fp32 oracle against the fp64 helper)."""
+    from coma_amd.sd import weights
+    from oracle import sd_oracle as so
+    from tests import rowtile_ref as rr
+    C, L, LK, CD, heads = 320, 64, 77, 768, 8
+    p, t = "blk", "blk.transformer_blocks.0"
+    shapes = {p + ".norm.weight": (C,), p + ".norm.bias": (C,), p + ".proj_in.weight": (C, C, 1, 1), p + ".proj_in.bias": (C,),
+              p + ".proj_out.weight": (C, C, 1, 1), p + ".proj_out.bias": (C,), t + ".ff.net.0.proj.weight": (8 * C, C),
+              t + ".ff.net.0.proj.bias": (8 * C,), t + ".ff.net.2.weight": (C, 4 * C), t + ".ff.net.2.bias": (C,)}
+    for n in ("norm1", "norm2", "norm3"):
+        shapes.update({f"{t}.{n}.weight": (C,), f"{t}.{n}.bias": (C,)})
+    for a, kv in (("attn1", C), ("attn2", CD)):
+        shapes.update({f"{t}.{a}.to_q.weight": (C, C), f"{t}.{a}.to_k.weight": (C, kv), f"{t}.{a}.to_v.weight": (C, kv),
+                       f"{t}.{a}.to_out.0.weight": (C, C), f"{t}.{a}.to_out.0.bias": (C,)})
+    s = weights.random_state(shapes, seed=5, gain=1.5)
+    g = torch.Generator().manual_seed(6)
+    x, ctx = (torch.randn(1, C, 8, 8, generator=g) * 2 + 0.5).half(), torch.randn(1, LK, CD, generator=g).half()
+    ref = so.transformer_ref(x.float(), ctx.float(), s, p, heads)[0].reshape(C, L).t()
+    xr = x[0].reshape(C, L).t().contiguous()                                         # token-major [L, C], what the kernels see
+    w = lambda n: s[n].reshape(s[n].shape[0], -1) if s[n].dim() == 4 else s[n]
+    fr = rr.xfront(xr, w(p + ".norm.weight"), w(p + ".norm.bias"), w(p + ".proj_in.weight"), w(p + ".proj_in.bias"), w(t + ".norm1.weight"),
+                   w(t + ".norm1.bias"), w(t + ".attn1.to_q.weight"), w(t + ".attn1.to_k.weight"), w(t + ".attn1.to_v.weight"),
+                   rows_per_sample=L, gn_eps=1e-6, exact=True)
+    a1 = so.attention_ref(fr["qk"][None, :, :C], fr["qk"][None, :, C:], fr["v"][None], heads, (C // heads) ** -0.5)[0]
+    k2, v2 = ctx.double() @ w(t + ".attn2.to_k.weight").double().t(), ctx.double() @ w(t + ".attn2.to_v.weight").double().t()
+    ch = rr.xchain(a1, fr["h"], w(t + ".attn1.to_out.0.weight"), w(t + ".attn1.to_out.0.bias"), w(t + ".norm2.weight"), w(t + ".norm2.bias"),
+                   w(t + ".attn2.to_q.weight"), k2, v2, w(t + ".attn2.to_out.0.weight"), w(t + ".attn2.to_out.0.bias"),
+                   w(t + ".norm3.weight"), w(t + ".norm3.bias"), rows_per_sample=L, exact=True)
+    out = rr.xtail(ch["n3"], ch["h2"], xr, w(t + ".ff.net.0.proj.weight"), w(t + ".ff.net.0.proj.bias"), w(t + ".ff.net.2.weight"),
+                   w(t + ".ff.net.2.bias"), w(p + ".proj_out.weight"), w(p + ".proj_out.bias"), exact=True)
+    err, scale = float((out - ref.double()).abs().max()), float(ref.abs().max())
+    assert err <= 1e-5 * scale, (err, scale)
+    # a row subset is the same rows of the full result (the kernels are local to a token row), and the fp16 restatement is near it
+    sub = rr.xchain(a1, fr["h"], w(t + ".attn1.to_out.0.weight"), w(t + ".attn1.to_out.0.bias"), w(t + ".norm2.weight"), w(t + ".norm2.bias"),
+                    w(t + ".attn2.to_q.weight"), k2, v2, w(t + ".attn2.to_out.0.weight"), w(t + ".attn2.to_out.0.bias"),
+                    w(t + ".norm3.weight"), w(t + ".norm3.bias"), rows_per_sample=L, exact=False, rows=[3, 40])
+    assert 0 < float(rr.row_error(sub["n3"], ch["n3"][[3, 40]]).max()) < 1e-2

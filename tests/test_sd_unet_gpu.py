@@ -138,6 +138,21 @@ def test_unet_benchmark_shape_matches_fp32_reference(setup):
         assert r <= REL_L2 and c >= COS, (i, r, c)
 
 
+def test_context_longer_than_the_chain_kernel_takes_the_unfused_path(setup):
+    """sd_xattn_chain_f16 multiplies 80 key positions, so its rule in unet.py is Lk <= 80: a UNet built for 96 context tokens has no
+    `xchain` launch (the 77-token one has) and matches the fp32 reference at 16 x 16 through sd_attention_f16."""
+    state, sample, _, t, _, UNet = setup
+    from coma_amd.sd import weights
+    assert any(tag.startswith("xchain") for tag, _ in UNet(state, batch=2, height=16, width=16, device=DEV).g.tags)
+    ctx = torch.randn(2, 96, 768, generator=torch.Generator().manual_seed(41)).half().float()
+    unet = UNet(state, batch=2, height=16, width=16, ctx_len=96, device=DEV, use_graph=True)
+    assert not any(tag.startswith("xchain") for tag, _ in unet.g.tags)
+    out = unet(sample.to(DEV), t.to(DEV), encoder_hidden_states=ctx.to(DEV), return_dict=False)[0]
+    ref = so.unet_ref(state, sample, t, ctx, weights.UNET_CFG)
+    rel, cos = _metrics(out, ref)
+    assert rel <= REL_L2 and cos >= COS, (rel, cos)
+
+
 def test_row_tile_fusions_agree_with_the_unfused_graph(setup):
     """The C = 320 row-tile kernels (sd_xfront_f16, sd_xattn_chain_f16, sd_xtail_f16) and the one-launch q | k | v projection
     (sd_conv_gemm_desc.out_t) against the SAME network with every one of them switched off, at the 64 x 64 level where they are used
