@@ -5,13 +5,23 @@ Mirrors the two writers of the reference, `src/coma/downsample_human.py:17-77` a
   * nearest vertex  -> coma_nearest_vertex_i64 (bit-exact argmin, utils/coma.py:87-91);
   * vertex normals  -> coma_vertex_normals_f64 (area-weighted, ascending-face accumulation like open3d; parity unpinned --
     open3d is absent from the build image);
-  * the point sampler: open3d's Poisson-disk elimination is third party and out of scope; points are either
-    SUPPLIED (what a maintainer with open3d exports once) or drawn by the seeded area-weighted uniform sampler below.
+  * the point sampler: open3d's own Poisson-disk point set is third party (SURVEY.md 8b-4) and is never silently replaced;
+    for simplify_method="poisson_disk" points are SUPPLIED (what a maintainer with open3d exports once; sampler="supplied", the
+    default, which raises without them) or, only when the caller opts in with sampler="device", drawn by sample_poisson_disk
+    below; simplify_method="uniform" draws with the seeded area-weighted uniform sampler.
+
+sample_poisson_disk is weighted sample elimination (Yuksel 2015), the method behind open3d's sample_points_poisson_disk, run by
+coma_sample_eliminate_f64 bit-identically to its NumPy restatement (tests/sample_elim_ref.py).  Parity with open3d's own point set
+is UNPINNED: open3d draws its candidates with another RNG, and the constants below are quoted from memory of its source.  What is
+pinned is the algorithm as include/coma_hip.h states it.
 """
 from __future__ import annotations
 
 import numpy as np
 
+import torch
+
+from . import _lib
 from .coma import nearest_vertex_indices
 from .ingest import vertex_normals_batch
 
@@ -47,24 +57,76 @@ def sample_uniform(vertices, faces, vertex_normals, number_of_points, seed=0):
     return pts, np.divide(nrm, n, out=np.zeros_like(nrm), where=n > 0)
 
 
-def _points(vertices, faces, normals, number_of_points, points, point_normals, simplify_method, seed):
+# [3rd-party, from memory of open3d's source, unpinned]: the constants of TriangleMesh::SamplePointsPoissonDisk.  They are
+# arguments all the way down to the kernel, so a maintainer with open3d at hand can correct them here without touching it.
+POISSON_INIT_FACTOR = 5      # candidates drawn per requested point
+POISSON_ALPHA = 8.0          # weight exponent (the kernel refuses any other value: ((t*t)^2)^2 needs no pow)
+POISSON_BETA = 0.5           # r_min = r_max * beta * (1 - (N/M)^gamma)
+POISSON_GAMMA = 1.5
+
+
+def poisson_radii(area, number_of_points, number_of_candidates, beta=POISSON_BETA, gamma=POISSON_GAMMA):
+    """(r_max, r_min) of the elimination for N points kept out of M candidates on a surface of area A, in f64."""
+    n, m = float(number_of_points), float(number_of_candidates)
+    r_max = 2.0 * float(np.sqrt((float(area) / n) / (2.0 * np.sqrt(3.0))))
+    return r_max, r_max * beta * (1.0 - (n / m) ** gamma)
+
+
+def sample_eliminate(points, n_keep, r_max, r_min, alpha=POISSON_ALPHA, device="cuda"):
+    """coma_sample_eliminate_f64: indices (ascending, i64 [n_keep]) of the candidates that survive weighted sample elimination."""
+    L = _lib.lib()
+    pts = torch.tensor(np.ascontiguousarray(np.asarray(points, dtype=np.float64)), device=device)
+    assert pts.dim() == 2 and pts.shape[1] == 3
+    M = pts.shape[0]
+    ws = torch.empty([max(1, int(L.coma_sample_eliminate_workspace_bytes(M)) // 8)], dtype=torch.float64, device=pts.device)
+    keep = torch.empty([max(0, int(n_keep))], dtype=torch.int64, device=pts.device)
+    rc = L.coma_sample_eliminate_f64(_lib.ptr(pts, torch.float64), M, int(n_keep), float(r_max), float(r_min), float(alpha),
+                                     _lib.ptr(ws), _lib.ptr(keep, torch.int64), _lib.stream_ptr(pts.device))
+    _lib.check(rc, "coma_sample_eliminate_f64")
+    return keep.cpu().numpy()
+
+
+def sample_poisson_disk(vertices, faces, vertex_normals, number_of_points, seed=0, device="cuda", init_factor=POISSON_INIT_FACTOR):
+    """Blue-noise surface samples: init_factor * N seeded uniform candidates (sample_uniform, same seed semantics) thinned to N by
+    weighted sample elimination on the device.  Returns the kept points and their normals in ascending candidate order.
+    NOT open3d's point set (see the module docstring): same method, another RNG, constants unpinned."""
+    n = int(number_of_points)
+    m = int(init_factor) * n
+    pts, nrm = sample_uniform(vertices, faces, vertex_normals, m, seed)
+    a, b, c = (np.asarray(vertices, dtype=np.float64)[faces[:, k]] for k in range(3))
+    area = float((0.5 * np.linalg.norm(np.cross(b - a, c - a), axis=1)).sum())
+    r_max, r_min = poisson_radii(area, n, m)
+    keep = sample_eliminate(pts, n, r_max, r_min, POISSON_ALPHA, device=device)
+    return pts[keep], nrm[keep]
+
+
+SAMPLERS = ("supplied", "device")
+
+
+def _points(vertices, faces, normals, number_of_points, points, point_normals, simplify_method, seed, sampler="supplied", device="cuda"):
+    assert sampler in SAMPLERS, f"sampler: '{sampler}' not in {SAMPLERS}"
     if points is not None:
         points = np.asarray(points, dtype=np.float64)
         assert point_normals is not None and len(point_normals) == len(points), "supplied points need their normals"
         return points, np.asarray(point_normals, dtype=np.float64)
     if simplify_method != "uniform":
+        if sampler == "device":
+            return sample_poisson_disk(vertices, faces, normals, number_of_points, seed, device)
         raise NotImplementedError("Poisson-disk sampling is open3d's (third party): pass points=/point_normals= exported from it, "
+                                  "opt in to the device sampler with sampler='device' (same method, not open3d's point set), "
                                   "or use simplify_method='uniform'")
     return sample_uniform(vertices, faces, normals, number_of_points, seed)
 
 
-def downsample_human(vertices, faces, number_of_points, points=None, point_normals=None, simplify_method="uniform", seed=42, device="cuda"):
+def downsample_human(vertices, faces, number_of_points, points=None, point_normals=None, simplify_method="uniform", seed=42, device="cuda",
+                     sampler="supplied"):
     """downsample_human.py:29-77 -> the dict it pickles as smplx_star_downsampled_{N}.pickle."""
     vertices, faces = np.asarray(vertices), np.asarray(faces).astype(np.int64)
     V = len(vertices)
     normals = vertex_normals_batch(vertices, faces, device=device)[0]
     if number_of_points < V:
-        pts, nrm = _points(vertices.astype(np.float64), faces, normals, number_of_points, points, point_normals, simplify_method, seed)
+        pts, nrm = _points(vertices.astype(np.float64), faces, normals, number_of_points, points, point_normals, simplify_method, seed,
+                           sampler, device)
         indices = [int(i) for i in nearest_vertex_indices(pts, vertices.astype(np.float64), device=device)]
     else:
         pts, nrm, indices = vertices.astype(np.float64), normals, list(range(V))
@@ -74,11 +136,11 @@ def downsample_human(vertices, faces, number_of_points, points=None, point_norma
 
 
 def downsample_object(supercategory, category, asset_id, vertices, faces, number_of_points, points=None, point_normals=None,
-                      simplify_method="uniform", seed=42, device="cuda"):
+                      simplify_method="uniform", seed=42, device="cuda", sampler="supplied"):
     """downsample_objects.py:17-62 -> the dict it pickles as {asset_id}_{N}.pickle."""
     vertices, faces = np.asarray(vertices, dtype=np.float64), np.asarray(faces).astype(np.int64)
     normals = vertex_normals_batch(vertices, faces, device=device)[0]
-    pts, nrm = _points(vertices, faces, normals, number_of_points, points, point_normals, simplify_method, seed)
+    pts, nrm = _points(vertices, faces, normals, number_of_points, points, point_normals, simplify_method, seed, sampler, device)
     indices = [int(i) for i in nearest_vertex_indices(pts, vertices, device=device)]
     keep = np.array([d for d in range(len(nrm)) if nrm[d].sum() != 0], dtype=np.int64)   # zero-normal samples are dropped (:30-38)
     return {"supercategory": supercategory, "category": category, "asset_id": asset_id, "V": vertices.shape[0], "F": faces.shape[0],

@@ -168,6 +168,21 @@ int coma_ransac_mse_f64(const double* views, const double* tri, const int* cand_
 int coma_vertex_normals_f64(const double* verts, const int32_t* faces, const int32_t* vf_offsets, const int32_t* vf_faces,
                             int S, int V, int F, double eps, double* normals, void* stream);
 
+/* Weighted sample elimination (Yuksel 2015), the method behind open3d's sample_points_poisson_disk; opt-in sampler of the
+ * down-sampling writers (coma_amd/downsample.py::sample_poisson_disk).  Parity with open3d's own point set is UNPINNED (another
+ * RNG draws its candidates, and the constants the host passes are quoted from memory); what is pinned is this definition:
+ * d_ij = sqrt(((xi-xj)^2 + (yi-yj)^2) + (zi-zj)^2); pairs with d_ij >= r_max contribute nothing; w_ij = ((t*t)^2)^2 with
+ * t = 1 - max(d_ij, r_min)/r_max; w_i = sum over j != i in ascending j; until n_keep points are alive the alive point of largest
+ * w is removed (lowest index on equal w) and every alive neighbour j gets one w_j -= w_ij.  All f64, no FMA: bit-identical to
+ * tests/sample_elim_ref.py.
+ * points f64 [M,3] -> keep_idx i64 [n_keep], the surviving indices in ascending order.  workspace: device buffer of
+ * coma_sample_eliminate_workspace_bytes(M) bytes, 8-byte aligned.  Refused (COMA_E_INVALID, keep_idx untouched): M outside
+ * [1, 65536], n_keep outside [1, M], alpha != 8, r_max <= 0, r_min outside [0, r_max).  n_keep == M returns 0..M-1 without
+ * running the loop.  The loop runs in ONE workgroup (no waiting between workgroups). */
+size_t coma_sample_eliminate_workspace_bytes(int M);
+int coma_sample_eliminate_f64(const double* points, int M, int n_keep, double r_max, double r_min, double alpha, void* workspace,
+                              int64_t* keep_idx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,9 @@
 The reference builds the SMPL-X "star" pose mesh itself (smplx + model files: third party, absent here); this CLI takes that
 mesh as --mesh_pth (the reference's own ./constants/mesh/smplx_star.pickle {vertices, faces}, or an .obj) and, optionally,
 the sampled points exported from open3d (--points_pth: .npz with points [N,3] and normals [N,3]).  Index map, normals and
-the zero-normal filter run through coma_amd (HIP)."""
+the zero-normal filter run through coma_amd (HIP).  --sampler device opts in to the project's own Poisson-disk sampler
+(weighted sample elimination on the device: open3d's method, NOT its point set -- parity unpinned); the default, supplied,
+refuses poisson_disk without --points_pth."""
 import argparse
 import os
 import pickle
@@ -33,7 +35,9 @@ def downsample_smplx(args, device="cuda"):
         z = np.load(args.points_pth)
         pts, nrm = z["points"], z["normals"]
     n = args.num_human_downsample_points
-    to_save = downsample_human(vertices, faces, n, points=pts, point_normals=nrm, simplify_method=args.simplify_method, seed=args.seed, device=device)
+    sampler = getattr(args, "sampler", "supplied")
+    to_save = downsample_human(vertices, faces, n, points=pts, point_normals=nrm, simplify_method=args.simplify_method, seed=args.seed, device=device,
+                               sampler=sampler)
     name = f"smplx_star_downsampled_{n}.pickle" if n < len(vertices) else "smplx_star_downsampled_FULL.pickle"
     save_pth = os.path.join(args.save_dir, name)
     if not args.skip_done or not os.path.exists(save_pth):
@@ -55,6 +59,8 @@ def build_parser():
     p.add_argument("--mesh_pth", type=str, default="./constants/mesh/smplx_star.pickle")
     p.add_argument("--points_pth", type=str, default=None, help=".npz {points, normals}; required for poisson_disk")
     p.add_argument("--save_dir", type=str, default="./constants/mesh")
+    p.add_argument("--sampler", choices=["supplied", "device"], default="supplied",
+                   help="poisson_disk without --points_pth: 'device' runs the project's sample elimination (not open3d's point set)")
     return p
 
 
@@ -62,6 +68,7 @@ if __name__ == "__main__":
     args = build_parser().parse_args()
     from utils.reproducibility import seed_everything
     seed_everything(args.seed)
+    print(f"sampler: {args.sampler}")
     for n in args.num_human_downsample_points_list:
         args.num_human_downsample_points = n
         print(downsample_smplx(args))
