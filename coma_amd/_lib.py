@@ -18,7 +18,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("COMA_HIP_LIB") or os.path.join(_HERE, "libcoma_hip.so")
 ABI_VERSION = 9                  # = COMA_ABI_VERSION of include/coma_hip.h: bumped with every change of the SIGNATURES table below
 # (not for the text-tower functions: they were only added, no existing signature changed, and a library without them is refused by
-# lib() anyway -- getattr of a missing symbol fails; the same holds for the two coma_sample_eliminate_* functions)
+# lib() anyway -- getattr of a missing symbol fails; the same holds for the two coma_sample_eliminate_* functions and for the
+# coma_raster_* / coma_silhouette_iou functions)
 
 _lib = None
 
@@ -47,6 +48,10 @@ SIGNATURES = {
     "coma_vertex_normals_f64": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _d, _vp, _vp]),
     "coma_sample_eliminate_workspace_bytes": (C.c_size_t, [_i]),
     "coma_sample_eliminate_f64": (_i, [_vp, _i, _i, _d, _d, _d, _vp, _vp, _vp]),
+    "coma_raster_workspace_bytes": (C.c_size_t, [_i, _i]),
+    "coma_raster_depth_f64": (_i, [_vp, _i, _vp, _i, C.POINTER(_d), C.POINTER(_d), _d, _i, _i, _vp, _vp, _vp]),
+    "coma_raster_status": (_i, [_vp, _vp]),
+    "coma_silhouette_iou": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     # include/sd_hip.h
     "sd_conv_gemm_f16": (_i, [_vp, _vp]),
     "sd_conv_gemm_workspace_bytes": (C.c_size_t, []),

@@ -183,6 +183,52 @@ size_t coma_sample_eliminate_workspace_bytes(int M);
 int coma_sample_eliminate_f64(const double* points, int M, int n_keep, double r_max, double r_min, double alpha, void* workspace,
                               int64_t* keep_idx, void* stream);
 
+/* Depth initialisation's silhouette test: an orthographic nearest-depth map per mesh and one compare-and-count pass.
+ * replaces: the Blender scene build and the 2*retrieval_range + 1 instance-segmentation renders of
+ *           src/generation/initialize_depth.py:134-201 (select_human), and get_rendered_human_segmap / compute_IoU of
+ *           src/generation/compute_metrics.py:39-112.  The candidates differ only by a shift along the viewing axis of an
+ *           orthographic camera, so they share one screen footprint: two depth maps (human, asset) answer all K of them.
+ * Blender's own render is UNPINNED (bpy is not available to this project); what is pinned, bit for bit against the NumPy
+ * restatement tests/raster_ref.py, is this rule set (all f64, no FMA, sums in the order written):
+ *   camera space   c = diag(1,-1,-1) R^T (p - t) as in utils/blenderproc.py:183-196: d = p - t; c.x = (R00 d0 + R10 d1) + R20 d2;
+ *                  c.y = -((R01 d0 + R11 d1) + R21 d2); c.z = -((R02 d0 + R12 d1) + R22 d2) is the depth, larger is farther.
+ *   pixel          u = c.x s + W/2, v = c.y s + H/2 (x to the right, y down), s = max(W, H) / scale: Blender's ortho scale spans
+ *                  the LARGER side, the max(cam_resolution) of initialize_depth.py:312-314.  [3rd-party, unpinned] for W != H:
+ *                  utils/blenderproc.py:196 scales x by W and y by H, which agrees only for the square images the pipeline uses.
+ *   snapping       U = floor(u 256 + 0.5), V = floor(v 256 + 0.5) as integers (1/256-pixel grid).  A non-finite vertex (or depth)
+ *                  or |U|, |V| > 2^25 refuses the call; below that every edge function is exact in int64 and in f64.
+ *   coverage       pixel (i, j) is sampled at (256 i + 128, 256 j + 128); integer edge functions
+ *                  e_PQ(x, y) = (Qx - Px)(y - Py) - (Qy - Py)(x - Px); area = e_AB(C); area < 0 swaps B and C (both windings are
+ *                  drawn), area == 0 is skipped; with e0 = e_BC, e1 = e_CA, e2 = e_AB a sample is covered when every e > 0, or
+ *                  e == 0 on an edge P->Q with Qy < Py, or Qy == Py and Qx > Px (top-left rule: a shared edge is hit exactly once).
+ *   depth          z = ((e0 zA + e1 zB) + e2 zC) / area; a NaN (only when |z| 2^53 overflows) is not drawn.
+ *   resolve        key(z) = bits ^ (sign ? all ones : 2^63), an order-preserving u64; 64-bit atomic minimum per pixel, so the map
+ *                  does not depend on the order of arrival; the empty key is all ones.
+ * verts f64 [V,3] world space, faces i32 [F,3] (device); R f64[9] row-major camera-to-world rotation and t f64[3] camera position
+ * are HOST pointers read during the call; depth_key u64 [H,W]; workspace: coma_raster_workspace_bytes(V, F) bytes of device
+ * scratch, 16-byte aligned.  W, H in [1, 8192].
+ * Refusals.  Arguments the host can see (null pointer, sizes, scale, camera) return COMA_E_INVALID before anything is launched.
+ * The vertex and face DATA live on the device and no entry point here synchronises with the host, so those refusals are taken on
+ * the device: the first kernel records them in the workspace, every later kernel then does nothing (depth_key is left untouched),
+ * and coma_raster_status(workspace, stream) -- the one call that waits for the stream -- returns COMA_E_INVALID with the text.
+ * !! coma_raster_depth_f64 RETURNING COMA_OK DOES NOT MEAN THE MAP WAS DRAWN.  A C caller MUST call coma_raster_status on the same
+ * !! workspace and stream before it reads depth_key or hands it to coma_silhouette_iou: after a refusal depth_key still holds
+ * !! whatever it held before the call (uninitialised memory for a fresh buffer), and nothing else reports that. */
+size_t coma_raster_workspace_bytes(int V, int F);
+int coma_raster_depth_f64(const double* verts, int V, const int32_t* faces, int F, const double* R, const double* t, double scale,
+                          int W, int H, void* workspace, uint64_t* depth_key, void* stream);
+int coma_raster_status(const void* workspace, void* stream);
+
+/* Compare and count.  human_key / asset_key u64 [H,W] from coma_raster_depth_f64 (asset_key NULL = no asset), offsets f64 [K]
+ * (device; the shift of candidate k along the viewing axis, added to the decoded human depth), gt u8 [H,W] (non-zero = person).
+ * A pixel belongs to candidate k when the human key is not empty and (the asset key is empty or zh + offsets[k] < za).  The test
+ * is strict, so the asset wins an exact tie ([unpinned] against Blender, which has no defined order for coincident surfaces).
+ * visible[k] = #pixels of candidate k, inter[k] = #(candidate and gt), uni[k] = #(candidate or gt): i64 [K], overwritten; integer
+ * counts, so the order of the reduction cannot matter.  masks u8 [K,H,W] (0 / 255) is written when non-NULL.  K in [1, 64].
+ * The host forms IoU = inter / uni (src/generation/initialize_depth.py:175-178).  No host synchronisation. */
+int coma_silhouette_iou(const uint64_t* human_key, const uint64_t* asset_key, const double* offsets, int K, const uint8_t* gt,
+                        int W, int H, int64_t* visible, int64_t* inter, int64_t* uni, uint8_t* masks, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
