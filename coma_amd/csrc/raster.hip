@@ -19,29 +19,12 @@
 //
 // coma_silhouette_iou: zero the 3K counters, then one pass over the pixels; a wave handles 64 consecutive pixels, each candidate's
 // predicate is reduced by ballot + popcount, accumulated per workgroup in LDS and flushed with 3K integer atomics per workgroup.
-#include "common.h"
+#include "raster_common.h"
 
 namespace coma {
 
-constexpr int kSmallMax = 256;          // pixel centres in a bounding box that one lane still walks by itself
-constexpr int kTile = 16;               // screen tile of the work-list kernel: 16 x 16 pixels = 256 threads
-constexpr int kRasterMaxDim = 8192;     // W, H: box corners are packed into 16 bits each
-constexpr int kRasterMaxPrims = 1 << 24;
 constexpr int kIouMaxK = 64;
-constexpr double kSnapLimit = 33554432.0;   // 2^25 in 1/256-pixel units: every edge function stays below 2^53
 constexpr unsigned long long kEmptyKey = ~0ull;
-constexpr size_t kHeaderBytes = 64;
-enum { kBadNonFinite = 1, kBadRange = 2, kBadFace = 4 };
-
-struct RasterCam {
-  double r[9], t[3];   // camera-to-world rotation (row-major) and position
-  double s, hw, hh;    // pixels per world unit, W/2, H/2
-};
-
-struct SnapVert {
-  int x, y;            // 1/256-pixel units
-  double z;            // camera-space depth, larger is farther
-};
 
 __device__ __forceinline__ unsigned long long depth_key(double z) {
   const unsigned long long b = (unsigned long long)__double_as_longlong(z);
@@ -52,56 +35,10 @@ __device__ __forceinline__ double key_depth(unsigned long long k) {
   return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
 }
 
-// edge function of P -> Q at (px, py): exact in int64 below the snap limit
-__device__ __forceinline__ long long edge_fn(int Px, int Py, int Qx, int Qy, int px, int py) {
-  return (long long)(Qx - Px) * (long long)(py - Py) - (long long)(Qy - Py) * (long long)(px - Px);
-}
-
-// a sample ON the edge P -> Q belongs to the triangle only when the edge is a left edge (runs upwards, y is down) or a top edge
-__device__ __forceinline__ bool edge_owns_ties(int Px, int Py, int Qx, int Qy) {
-  const int dx = Qx - Px, dy = Qy - Py;
-  return dy < 0 || (dy == 0 && dx > 0);
-}
-
-struct RasterTri {
-  int ax, ay, bx, by, cx, cy;
-  double za, zb, zc, area;
-  bool t0, t1, t2;
-  int x0, y0, x1, y1;   // inclusive pixel box, clipped to the screen; empty when x0 > x1 or y0 > y1
-};
-
-// false: nothing to draw (zero area, or no pixel centre of the screen inside the bounding box)
-__device__ __forceinline__ bool raster_tri_load(const SnapVert* __restrict__ sv, const int* __restrict__ faces, int f, int W, int H,
-                                                RasterTri& t) {
-  const int ia = faces[3 * (int64_t)f + 0];
-  int ib = faces[3 * (int64_t)f + 1], ic = faces[3 * (int64_t)f + 2];
-  SnapVert A = sv[ia], B = sv[ib], C = sv[ic];
-  long long area = edge_fn(A.x, A.y, B.x, B.y, C.x, C.y);
-  if (area == 0) return false;
-  if (area < 0) {   // the other winding: swap two vertices
-    const SnapVert T = B;
-    B = C, C = T, area = -area;
-  }
-  t.ax = A.x, t.ay = A.y, t.bx = B.x, t.by = B.y, t.cx = C.x, t.cy = C.y;
-  t.za = A.z, t.zb = B.z, t.zc = C.z, t.area = (double)area;
-  t.t0 = edge_owns_ties(B.x, B.y, C.x, C.y), t.t1 = edge_owns_ties(C.x, C.y, A.x, A.y), t.t2 = edge_owns_ties(A.x, A.y, B.x, B.y);
-  const int mnx = min(A.x, min(B.x, C.x)), mxx = max(A.x, max(B.x, C.x));
-  const int mny = min(A.y, min(B.y, C.y)), mxy = max(A.y, max(B.y, C.y));
-  // pixel i is sampled at 256 i + 128: first i with 256 i + 128 >= mn, last i with 256 i + 128 <= mx (>> is a floor)
-  t.x0 = max(0, (mnx + 127) >> 8), t.x1 = min(W - 1, (mxx - 128) >> 8);
-  t.y0 = max(0, (mny + 127) >> 8), t.y1 = min(H - 1, (mxy - 128) >> 8);
-  return t.x0 <= t.x1 && t.y0 <= t.y1;
-}
-
 // key of the triangle at pixel (x, y), or the empty key when the centre is not covered
 __device__ __forceinline__ unsigned long long raster_sample(const RasterTri& t, int x, int y) {
-  const int px = 256 * x + 128, py = 256 * y + 128;
-  const long long e0 = edge_fn(t.bx, t.by, t.cx, t.cy, px, py);
-  const long long e1 = edge_fn(t.cx, t.cy, t.ax, t.ay, px, py);
-  const long long e2 = edge_fn(t.ax, t.ay, t.bx, t.by, px, py);
-  const bool in = (e0 > 0 || (e0 == 0 && t.t0)) && (e1 > 0 || (e1 == 0 && t.t1)) && (e2 > 0 || (e2 == 0 && t.t2));
-  if (!in) return kEmptyKey;
-  const double z = (((double)e0 * t.za + (double)e1 * t.zb) + (double)e2 * t.zc) / t.area;
+  double z;
+  if (!raster_cover_depth(t, x, y, z)) return kEmptyKey;
   if (z != z) return kEmptyKey;   // only when |depth| * 2^53 overflows: such a sample is not drawn
   return depth_key(z);
 }
@@ -241,6 +178,16 @@ __global__ __launch_bounds__(256) void iou_count_kernel(const unsigned long long
   }
 }
 
+int raster_reset_launch(int* hdr, hipStream_t st) {
+  hipLaunchKernelGGL(raster_reset_kernel, dim3(1), dim3(64), 0, st, hdr);
+  return check_launch("raster_reset_kernel");
+}
+
+int raster_setup_launch(const double* verts, int V, const int* faces, int F, const RasterCam& cam, SnapVert* sv, int* hdr, hipStream_t st) {
+  hipLaunchKernelGGL(raster_setup_kernel, dim3((unsigned)(((V > F ? V : F) + 255) / 256)), dim3(256), 0, st, verts, V, faces, F, cam, sv, hdr);
+  return check_launch("raster_setup_kernel");
+}
+
 }  // namespace coma
 
 using namespace coma;
@@ -270,10 +217,8 @@ extern "C" int coma_raster_depth_f64(const double* verts, int V, const int32_t* 
   int4* big = (int4*)(sv + V);
   hipStream_t st = (hipStream_t)stream;
   const int64_t n = (int64_t)W * H;
-  hipLaunchKernelGGL(raster_reset_kernel, dim3(1), dim3(64), 0, st, hdr);
-  if (int rc = check_launch("raster_reset_kernel")) return rc;
-  hipLaunchKernelGGL(raster_setup_kernel, dim3((unsigned)(((V > F ? V : F) + 255) / 256)), dim3(256), 0, st, verts, V, faces, F, cam, sv, hdr);
-  if (int rc = check_launch("raster_setup_kernel")) return rc;
+  if (int rc = raster_reset_launch(hdr, st)) return rc;
+  if (int rc = raster_setup_launch(verts, V, faces, F, cam, sv, hdr, st)) return rc;
   const unsigned fill_blocks = (unsigned)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
   hipLaunchKernelGGL(raster_fill_kernel, dim3(fill_blocks), dim3(256), 0, st, (unsigned long long*)depth_key, n, hdr);
   if (int rc = check_launch("raster_fill_kernel")) return rc;

@@ -29,6 +29,9 @@ extern "C" {
 /* bumped whenever ANY exported signature of coma_hip.h / sd_hip.h / seg_hip.h changes; coma_amd/_lib.py refuses a library that
  * reports another value (a stale build loaded through COMA_HIP_LIB would otherwise be called with mismatched argument lists) */
 #define COMA_ABI_VERSION 9   /* 9: sd_debug_timestamps removed, sd_conv_gemm_f16 refuses epi bits outside SD_EPI_ALL */
+/* The version counts CHANGES of existing signatures, not additions: a function that is only added (the text tower, the sample
+ * elimination, the rasteriser, the mesh volume functions) leaves it alone, because a library without it already fails to load
+ * (coma_amd/_lib.py binds every declared name). */
 
 #define COMA_OK 0
 #define COMA_E_INVALID (-1) /* bad argument (null pointer, non-positive size, unsupported shape) */
@@ -228,6 +231,55 @@ int coma_raster_status(const void* workspace, void* stream);
  * The host forms IoU = inter / uni (src/generation/initialize_depth.py:175-178).  No host synchronisation. */
 int coma_silhouette_iou(const uint64_t* human_key, const uint64_t* asset_key, const double* offsets, int K, const uint8_t* gt,
                         int W, int H, int64_t* visible, int64_t* inter, int64_t* uni, uint8_t* masks, void* stream);
+
+/* Signed volume of a triangle mesh: sum over the faces of det[a b c] / 6, what trimesh's `volume` gives for a closed mesh
+ * (src/generation/compute_metrics.py:97, the denominator of the intersection ratio).  All f64, no FMA:
+ * det = (ax (by cz - bz cy) - ay (bx cz - bz cx)) + az (bx cy - by cx); the sum has a FIXED shape (each thread adds its faces in
+ * ascending order, a tree per workgroup, the partials in block order, a tree over them) and is divided by 6 once, so two calls
+ * give the same bits; against a sum in another order it is within F 2^-52 sum|det| / 6.
+ * verts f64 [V,3], faces i32 [F,3], out f64 [1] (device); workspace: coma_mesh_volume_workspace_bytes(F) bytes, 8-byte aligned.
+ * A face index outside [0, V) is not followed and makes the result NaN.  No host synchronisation. */
+size_t coma_mesh_volume_workspace_bytes(int F);
+int coma_mesh_volume_f64(const double* verts, int V, const int32_t* faces, int F, double* out, void* workspace, void* stream);
+
+/* Intersection volume of two meshes by columns: every crossing of a grid cell's column with either surface, then one sweep.
+ * replaces: the Blender boolean of src/generation/compute_metrics.py:86-99 (trimesh.boolean.intersection(engine="blender").volume),
+ *           the numerator of `interscetion_ratio`.  Blender's boolean is UNPINNED; what is pinned, bit for bit against the NumPy
+ *           restatement tests/volume_ref.py, is this rule set:
+ *   columns, grid  columns run along world +z over an axis-aligned xy grid of square cells: origin (x0, y0), s cells per world
+ *                  unit, W x H cells, W, H in [1, 8192].  In the camera convention above this is R = diag(1,-1,-1),
+ *                  t = (x0, y0, 0), W/2 = H/2 = 0: u = (x - x0) s, v = (y - y0) s, depth = z.
+ *   snapping, coverage, depth   the rasteriser's rules above, unchanged (the same device functions): U = floor(u 256 + 0.5),
+ *                  sample at (256 i + 128, 256 j + 128), int64 edge functions, area = e_AB(C), area < 0 swaps B and C, area == 0
+ *                  is skipped, top-left rule, z = ((e0 zA + e1 zB) + e2 zC) / area in f64.
+ *   crossing       every covered (column, triangle) pair yields one crossing (Z, sigma): Z = floor((z s) 256 + 0.5) as int64 -- the
+ *                  quantum of the xy grid; sigma = +1 when the area BEFORE the swap was > 0, -1 when it was < 0.  A non-finite z or
+ *                  |Z| > 2^40 refuses the call.
+ *   sweep          per column the crossings of mesh A and of mesh B are sorted by Z.  Going up, n_A -= sigma at each crossing of A,
+ *                  n_B likewise.  Between two consecutive events Z_k < Z_k+1 the column is inside A iff n_A != 0, inside B iff
+ *                  n_B != 0, inside both iff both.  The order among equal Z cannot matter: the interval between them is empty.
+ *   result         three int64 sums of interval lengths over all columns, sums = {L_AB, L_A, L_B}, accumulated with integer
+ *                  atomics: independent of the order of arrival.  The host forms volume = L / (256 s^3).  col_ab i64 [H,W]
+ *                  (optional) is each column's share of L_AB.
+ * Validity: the rule set measures a volume for CLOSED, consistently oriented meshes (either orientation: n != 0, not n > 0).  For an
+ * open or inconsistently oriented mesh the result is still deterministic but it is not a volume.
+ * capacity is the number of crossings (A plus B) the workspace has room for, in [1, 2^31 - 1]: the total depends on the data, so
+ * the caller chooses it.  workspace: coma_column_crossings_workspace_bytes(...) bytes of device scratch, 16-byte aligned (0 for
+ * sizes the call would refuse).  sums i64 [3] (device).
+ * Refusals follow coma_raster_depth_f64: what the host can see returns COMA_E_INVALID before any launch; what lives on the device
+ * (non-finite vertex, coordinate beyond 2^25 sub-cell units, face index out of range, the Z range, capacity exceeded) is recorded in
+ * the workspace, the later kernels idle, sums and col_ab are left untouched, and coma_intersection_status(workspace, stream,
+ * needed) -- the one call that waits for the stream -- returns COMA_E_INVALID with the text.  *needed (HOST pointer, may be NULL)
+ * receives the number of crossings counted (0 when the call was refused before they were counted): after a capacity refusal it is
+ * the capacity to call again with.
+ * !! coma_intersection_columns RETURNING COMA_OK DOES NOT MEAN THE SUMS WERE WRITTEN.  A C caller MUST call
+ * !! coma_intersection_status on the same workspace and stream before it reads sums or col_ab: after a refusal they still hold
+ * !! whatever they held before the call (uninitialised memory for a fresh buffer), and nothing else reports that. */
+size_t coma_column_crossings_workspace_bytes(int VA, int FA, int VB, int FB, int W, int H, int64_t capacity);
+int coma_intersection_columns(const double* vertsA, int VA, const int32_t* facesA, int FA, const double* vertsB, int VB,
+                              const int32_t* facesB, int FB, double x0, double y0, double s, int W, int H, int64_t capacity,
+                              void* workspace, int64_t* sums, int64_t* col_ab, void* stream);
+int coma_intersection_status(const void* workspace, void* stream, int64_t* needed);
 
 #ifdef __cplusplus
 }
