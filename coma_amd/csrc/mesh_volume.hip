@@ -19,23 +19,15 @@
 //               walk them upwards keeping n_A and n_B, add up the interval lengths; wave reduction, three integer atomics per wave
 //   finish   -> sums = the header's three accumulators, unless the call was refused
 //
+// Everything up to the fill is columns_crossings_launch (declared in columns_common.h), which depth_opt.hip calls as well.
+//
 // coma_mesh_volume_f64: per-face determinants summed in a fixed shape (grid-stride per thread, LDS tree per workgroup, partials in
 // block order, one workgroup over the partials), so two calls give the same bits.
-#include "raster_common.h"
+#include "columns_common.h"
 
 namespace coma {
 
-constexpr int kSortMax = 16;                       // crossings per column sorted in LDS: 256 lanes x 16 x 8 B = 32 KiB
-constexpr int kScanItems = 4;                      // columns per thread of the scan kernels
-constexpr int kScanBlock = 256 * kScanItems;
-constexpr long long kZLimit = 1ll << 40;
-constexpr long long kMaxCapacity = 0x7fffffffll;   // offsets are 32-bit
 constexpr int kVolumeBlocks = 256;
-enum { kBadDepth = 8, kBadCapacity = 16 };
-// header, as 16 ints: [0] status, [1] / [2] length of the work list of A / B, [3] a refused depth was met, then int64 at byte 16:
-// crossings counted, 24 / 32 / 40: L_AB, L_A, L_B.  The count kernels test hdr[0] before their barriers, so nothing may change it
-// while they run: they raise hdr[3], and the scan folds it into the status word.
-enum { kHdrNeeded = 2, kHdrSums = 3 };             // in units of int64
 
 // Z of a covered sample; false (and the status word set) when the rule set refuses it
 __device__ __forceinline__ bool crossing_z(double z, double s, long long& Z, int* __restrict__ hdr) {
@@ -46,10 +38,6 @@ __device__ __forceinline__ bool crossing_z(double z, double s, long long& Z, int
   }
   Z = (long long)q;
   return true;
-}
-
-__device__ __forceinline__ long long pack_crossing(long long Z, int mesh, bool flipped) {
-  return Z * 4 + (mesh << 1) + (flipped ? 0 : 1);
 }
 
 __global__ __launch_bounds__(256) void columns_zero_kernel(unsigned* __restrict__ cnt, int64_t n, const int* __restrict__ hdr) {
@@ -240,11 +228,6 @@ __device__ __forceinline__ void sort_and_sweep(long long* p, int stride, int n, 
   }
 }
 
-__device__ __forceinline__ long long wave_sum(long long v) {
-  for (int d = kWave / 2; d > 0; d >>= 1) v += __shfl_down(v, d, kWave);
-  return v;
-}
-
 __global__ __launch_bounds__(256) void columns_sweep_kernel(const unsigned* __restrict__ ends, long long* __restrict__ entries, int64_t n,
                                                             long long* __restrict__ col_ab, int* __restrict__ hdr) {
   __shared__ long long lds[kSortMax * 256];   // entry k of lane t at [k * 256 + t]: consecutive lanes, consecutive banks
@@ -317,30 +300,52 @@ __global__ __launch_bounds__(256) void volume_final_kernel(const double* __restr
 
 static int volume_blocks(int F) { return (F + 255) / 256 < kVolumeBlocks ? (F + 255) / 256 : kVolumeBlocks; }
 
-struct ColumnsLayout {
-  size_t sv_a, sv_b, big_a, big_b, cnt, block_sums, entries, total;
-  int scan_blocks;
-};
+int columns_crossings_launch(const double* const verts[2], const int V[2], const int* const faces[2], const int F[2], double x0, double y0,
+                             double s, int W, int H, long long capacity, char* ws, const ColumnsLayout& l, hipStream_t st) {
+  int* hdr = (int*)ws;
+  SnapVert* sv[2] = {(SnapVert*)(ws + l.sv_a), (SnapVert*)(ws + l.sv_b)};
+  int4* big[2] = {(int4*)(ws + l.big_a), (int4*)(ws + l.big_b)};
+  unsigned* cnt = (unsigned*)(ws + l.cnt);
+  unsigned long long* block_sums = (unsigned long long*)(ws + l.block_sums);
+  long long* entries = (long long*)(ws + l.entries);
+  RasterCam cam = {};
+  cam.r[0] = 1.0, cam.r[4] = -1.0, cam.r[8] = -1.0;   // u = x - x0, v = y - y0, depth = z
+  cam.t[0] = x0, cam.t[1] = y0, cam.t[2] = 0.0;
+  cam.s = s, cam.hw = 0.0, cam.hh = 0.0;
+  const int64_t n = (int64_t)W * H;
+  const unsigned pix_blocks = (unsigned)((n + 255) / 256);
+  const int tiles_x = (W + kTile - 1) / kTile, tiles_y = (H + kTile - 1) / kTile;
+  const int tiles = tiles_x * tiles_y;
+  const int slices = tiles >= 2048 ? 1 : (2048 / tiles > 32 ? 32 : 2048 / tiles);
 
-static ColumnsLayout columns_layout(int VA, int FA, int VB, int FB, int W, int H, long long capacity) {
-  ColumnsLayout l;
-  const size_t n = (size_t)W * H;
-  auto up = [](size_t x) { return (x + 15) / 16 * 16; };
-  l.scan_blocks = (int)((n + kScanBlock - 1) / kScanBlock);
-  l.sv_a = kHeaderBytes;
-  l.sv_b = l.sv_a + (size_t)VA * sizeof(SnapVert);
-  l.big_a = l.sv_b + (size_t)VB * sizeof(SnapVert);
-  l.big_b = l.big_a + (size_t)FA * sizeof(int4);
-  l.cnt = l.big_b + (size_t)FB * sizeof(int4);
-  l.block_sums = up(l.cnt + n * sizeof(unsigned));
-  l.entries = up(l.block_sums + (size_t)l.scan_blocks * sizeof(unsigned long long));
-  l.total = l.entries + (size_t)capacity * sizeof(long long);
-  return l;
-}
-
-static bool columns_sizes_ok(int VA, int FA, int VB, int FB, int W, int H, long long capacity) {
-  return VA >= 1 && VA <= kRasterMaxPrims && FA >= 1 && FA <= kRasterMaxPrims && VB >= 1 && VB <= kRasterMaxPrims && FB >= 1 &&
-         FB <= kRasterMaxPrims && W >= 1 && W <= kRasterMaxDim && H >= 1 && H <= kRasterMaxDim && capacity >= 1 && capacity <= kMaxCapacity;
+  if (int rc = raster_reset_launch(hdr, st)) return rc;
+  for (int m = 0; m < 2; ++m)
+    if (int rc = raster_setup_launch(verts[m], V[m], faces[m], F[m], cam, sv[m], hdr, st)) return rc;
+  hipLaunchKernelGGL(columns_zero_kernel, dim3(pix_blocks < 2048 ? pix_blocks : 2048), dim3(256), 0, st, cnt, n, hdr);
+  if (int rc = check_launch("columns_zero_kernel")) return rc;
+  for (int m = 0; m < 2; ++m) {
+    hipLaunchKernelGGL(columns_bin_kernel<false>, dim3((unsigned)((F[m] + 255) / 256)), dim3(256), 0, st, sv[m], faces[m], F[m], W, H, s, m, cnt,
+                       entries, capacity, big[m], hdr);
+    if (int rc = check_launch("columns_bin_kernel<count>")) return rc;
+    hipLaunchKernelGGL(columns_tile_kernel<false>, dim3((unsigned)tiles, (unsigned)slices), dim3(256), 0, st, sv[m], faces[m], W, H, tiles_x, s, m, cnt,
+                       entries, capacity, big[m], hdr);
+    if (int rc = check_launch("columns_tile_kernel<count>")) return rc;
+  }
+  hipLaunchKernelGGL(scan_sums_kernel, dim3((unsigned)l.scan_blocks), dim3(256), 0, st, cnt, n, block_sums, hdr);
+  if (int rc = check_launch("scan_sums_kernel")) return rc;
+  hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(256), 0, st, block_sums, l.scan_blocks, capacity, hdr);
+  if (int rc = check_launch("scan_top_kernel")) return rc;
+  hipLaunchKernelGGL(scan_offsets_kernel, dim3((unsigned)l.scan_blocks), dim3(256), 0, st, cnt, n, block_sums, hdr);
+  if (int rc = check_launch("scan_offsets_kernel")) return rc;
+  for (int m = 0; m < 2; ++m) {
+    hipLaunchKernelGGL(columns_bin_kernel<true>, dim3((unsigned)((F[m] + 255) / 256)), dim3(256), 0, st, sv[m], faces[m], F[m], W, H, s, m, cnt,
+                       entries, capacity, big[m], hdr);
+    if (int rc = check_launch("columns_bin_kernel<fill>")) return rc;
+    hipLaunchKernelGGL(columns_tile_kernel<true>, dim3((unsigned)tiles, (unsigned)slices), dim3(256), 0, st, sv[m], faces[m], W, H, tiles_x, s, m, cnt,
+                       entries, capacity, big[m], hdr);
+    if (int rc = check_launch("columns_tile_kernel<fill>")) return rc;
+  }
+  return COMA_OK;
 }
 
 }  // namespace coma
@@ -380,52 +385,15 @@ extern "C" int coma_intersection_columns(const double* vertsA, int VA, const int
   const ColumnsLayout l = columns_layout(VA, FA, VB, FB, W, H, capacity);
   char* ws = (char*)workspace;
   int* hdr = (int*)ws;
-  SnapVert* sv[2] = {(SnapVert*)(ws + l.sv_a), (SnapVert*)(ws + l.sv_b)};
-  int4* big[2] = {(int4*)(ws + l.big_a), (int4*)(ws + l.big_b)};
-  unsigned* cnt = (unsigned*)(ws + l.cnt);
-  unsigned long long* block_sums = (unsigned long long*)(ws + l.block_sums);
-  long long* entries = (long long*)(ws + l.entries);
   const double* verts[2] = {vertsA, vertsB};
   const int* faces[2] = {facesA, facesB};
   const int V[2] = {VA, VB}, F[2] = {FA, FB};
-  RasterCam cam = {};
-  cam.r[0] = 1.0, cam.r[4] = -1.0, cam.r[8] = -1.0;   // u = x - x0, v = y - y0, depth = z
-  cam.t[0] = x0, cam.t[1] = y0, cam.t[2] = 0.0;
-  cam.s = s, cam.hw = 0.0, cam.hh = 0.0;
   hipStream_t st = (hipStream_t)stream;
   const int64_t n = (int64_t)W * H;
   const unsigned pix_blocks = (unsigned)((n + 255) / 256);
-  const int tiles_x = (W + kTile - 1) / kTile, tiles_y = (H + kTile - 1) / kTile;
-  const int tiles = tiles_x * tiles_y;
-  const int slices = tiles >= 2048 ? 1 : (2048 / tiles > 32 ? 32 : 2048 / tiles);
-
-  if (int rc = raster_reset_launch(hdr, st)) return rc;
-  for (int m = 0; m < 2; ++m)
-    if (int rc = raster_setup_launch(verts[m], V[m], faces[m], F[m], cam, sv[m], hdr, st)) return rc;
-  hipLaunchKernelGGL(columns_zero_kernel, dim3(pix_blocks < 2048 ? pix_blocks : 2048), dim3(256), 0, st, cnt, n, hdr);
-  if (int rc = check_launch("columns_zero_kernel")) return rc;
-  for (int m = 0; m < 2; ++m) {
-    hipLaunchKernelGGL(columns_bin_kernel<false>, dim3((unsigned)((F[m] + 255) / 256)), dim3(256), 0, st, sv[m], faces[m], F[m], W, H, s, m, cnt,
-                       entries, (long long)capacity, big[m], hdr);
-    if (int rc = check_launch("columns_bin_kernel<count>")) return rc;
-    hipLaunchKernelGGL(columns_tile_kernel<false>, dim3((unsigned)tiles, (unsigned)slices), dim3(256), 0, st, sv[m], faces[m], W, H, tiles_x, s, m, cnt,
-                       entries, (long long)capacity, big[m], hdr);
-    if (int rc = check_launch("columns_tile_kernel<count>")) return rc;
-  }
-  hipLaunchKernelGGL(scan_sums_kernel, dim3((unsigned)l.scan_blocks), dim3(256), 0, st, cnt, n, block_sums, hdr);
-  if (int rc = check_launch("scan_sums_kernel")) return rc;
-  hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(256), 0, st, block_sums, l.scan_blocks, (long long)capacity, hdr);
-  if (int rc = check_launch("scan_top_kernel")) return rc;
-  hipLaunchKernelGGL(scan_offsets_kernel, dim3((unsigned)l.scan_blocks), dim3(256), 0, st, cnt, n, block_sums, hdr);
-  if (int rc = check_launch("scan_offsets_kernel")) return rc;
-  for (int m = 0; m < 2; ++m) {
-    hipLaunchKernelGGL(columns_bin_kernel<true>, dim3((unsigned)((F[m] + 255) / 256)), dim3(256), 0, st, sv[m], faces[m], F[m], W, H, s, m, cnt,
-                       entries, (long long)capacity, big[m], hdr);
-    if (int rc = check_launch("columns_bin_kernel<fill>")) return rc;
-    hipLaunchKernelGGL(columns_tile_kernel<true>, dim3((unsigned)tiles, (unsigned)slices), dim3(256), 0, st, sv[m], faces[m], W, H, tiles_x, s, m, cnt,
-                       entries, (long long)capacity, big[m], hdr);
-    if (int rc = check_launch("columns_tile_kernel<fill>")) return rc;
-  }
+  unsigned* cnt = (unsigned*)(ws + l.cnt);
+  long long* entries = (long long*)(ws + l.entries);
+  if (int rc = columns_crossings_launch(verts, V, faces, F, x0, y0, s, W, H, (long long)capacity, ws, l, st)) return rc;
   hipLaunchKernelGGL(columns_sweep_kernel, dim3(pix_blocks), dim3(256), 0, st, cnt, entries, n, (long long*)col_ab, hdr);
   if (int rc = check_launch("columns_sweep_kernel")) return rc;
   hipLaunchKernelGGL(columns_finish_kernel, dim3(1), dim3(64), 0, st, hdr, (long long*)sums);

@@ -81,6 +81,19 @@ def parallel_slice(n_items, parallel_num, parallel_idx):
 MAX_REACH_CELLS = 65536.0        # half of the 2^25 / 256 = 131 072 cells the device lets a vertex lie from the grid origin
 
 
+def _overlap_grid(vertsA, vertsB, resolution, axes):
+    """The grid over the xy overlap of the two bounding boxes; None when the boxes are disjoint (or only touch) on one of `axes`."""
+    a, b = np.asarray(vertsA, dtype=np.float64), np.asarray(vertsB, dtype=np.float64)
+    lo, hi = np.maximum(a.min(axis=0), b.min(axis=0)), np.minimum(a.max(axis=0), b.max(axis=0))
+    if not (hi[:axes] > lo[:axes]).all():
+        return None
+    ex, ey = float(hi[0] - lo[0]), float(hi[1] - lo[1])
+    reach = max(float(np.abs(m[:, :2] - lo[:2]).max()) for m in (a, b))
+    s = min(resolution / max(ex, ey), MAX_REACH_CELLS / reach)
+    W, H = max(1, math.ceil(ex * s)), max(1, math.ceil(ey * s))
+    return float(lo[0]), float(lo[1]), float(s), int(min(W, resolution)), int(min(H, resolution))
+
+
 def overlap_grid(vertsA, vertsB, resolution):
     """The grid laid over the xy overlap of the two bounding boxes: (x0, y0, s, W, H) with `resolution` square cells along the
     longer side and ceil(shorter side in those cells) along the other, or None when the boxes are disjoint (or only touch) on any
@@ -89,15 +102,14 @@ def overlap_grid(vertsA, vertsB, resolution):
     the cells may not be arbitrarily small against the meshes: s is capped at MAX_REACH_CELLS / (largest |x - x0|, |y - y0| of any
     vertex).  The cap binds only when the overlap is thinner than resolution / 65536 of the meshes' extent (two boxes that graze);
     the grid then has fewer than `resolution` cells, each still under 1 / 65536 of that extent."""
-    a, b = np.asarray(vertsA, dtype=np.float64), np.asarray(vertsB, dtype=np.float64)
-    lo, hi = np.maximum(a.min(axis=0), b.min(axis=0)), np.minimum(a.max(axis=0), b.max(axis=0))
-    if not (hi > lo).all():
-        return None
-    ex, ey = float(hi[0] - lo[0]), float(hi[1] - lo[1])
-    reach = max(float(np.abs(m[:, :2] - lo[:2]).max()) for m in (a, b))
-    s = min(resolution / max(ex, ey), MAX_REACH_CELLS / reach)
-    W, H = max(1, math.ceil(ex * s)), max(1, math.ceil(ey * s))
-    return float(lo[0]), float(lo[1]), float(s), int(min(W, resolution)), int(min(H, resolution))
+    return _overlap_grid(vertsA, vertsB, resolution, 3)
+
+
+def overlap_grid_xy(vertsA, vertsB, resolution):
+    """overlap_grid() for a mesh A that slides along z (the depth optimisation, coma_amd/depth_opt.py): the same grid and the same cap
+    on the scale, but only x and y decide whether the boxes meet; the z extent does not enter, because the footprint of A never
+    changes while its depth does.  None when the boxes are disjoint (or only touch) in x or y."""
+    return _overlap_grid(vertsA, vertsB, resolution, 2)
 
 
 # ---- device ----

@@ -281,6 +281,62 @@ int coma_intersection_columns(const double* vertsA, int VA, const int32_t* faces
                               void* workspace, int64_t* sums, int64_t* col_ab, void* stream);
 int coma_intersection_status(const void* workspace, void* stream, int64_t* needed);
 
+/* Depth optimisation: one scalar d, the displacement of the human along the camera's front vector, moved by Adam under a multiview
+ * joint term and a collision term.
+ * replaces: the optimisation loop of src/generation/optimize_depth.py:689-780.  Its optimiser holds the displacement alone (:695), so
+ *           the body model's output is the same in every epoch: vertices V0 + d f, joints J0 + d f.
+ * COAP's collision loss (a learned occupancy network, :752-753) is UNPINNED and NOT reproduced (its checkpoint is not available to
+ * this project).  The collision term here is geometric: the intersection ratio L_AB / L_A of the column rule set above, in [0, 1],
+ * as a function of d; that is what --w_collision weights.  What is pinned, bit for bit against the NumPy restatement
+ * tests/shift_ref.py, is this rule set:
+ *   frame          the host rotates both meshes into the camera-aligned frame p' = p R (f64; R the camera's rotation, so the front
+ *                  vector R[:, 2] becomes +z) and lays the grid over the xy overlap of the two bounding boxes; the z extent does not
+ *                  enter, because the human slides along it and its footprint never changes.
+ *   crossings      columns, grid, snapping, coverage, depth and crossing (Z, sigma) are those of coma_intersection_columns, from the
+ *                  same kernels; mesh A is the human.  Per column the crossings are then sorted by (mesh, Z) and kept: A's list,
+ *                  then B's.  L_A and L_B are the interval lengths inside A and inside B (the sweep's, for one mesh at a time).
+ *   shift          Delta = floor((d s) 256 + 0.5) as int64, |Delta| clamped to 2^42 (nothing can overlap beyond; a NaN counts as
+ *                  beyond).  L_AB(Delta) is the L_AB of the sweep above after Delta is added to every Z of A.  It is an integer,
+ *                  piecewise-linear function whose breakpoints lie on integers.
+ *   slope          S2(Delta) = L_AB(Delta + 1) - L_AB(Delta - 1): an exact central difference, no tie rule.
+ *   collision      ratio(d) = L_AB(Delta) / L_A, d ratio / dd = (S2(Delta) (256 s)) / (2 L_A) in f64; both 0 when L_A == 0.
+ *   multiview      joints = J0 + d f (x = J0x + d fx, ...).  Per inlier n with the view record w of coma_dlt_score_f64:
+ *                  cx = ((x mr0 + y mr3) + z mr6) - tmr0, px = cx / scale max(res) + res_x / 2, rx = px - xy[n][j][0], likewise y;
+ *                  ax = ((fx mr0 + fy mr3) + fz mr6) / scale max(res), likewise ay.  sq_n = sum_j (rx rx + ry ry) and
+ *                  gr_n = sum_j (rx ax + ry ay), j ascending.  multiview_joint_loss (:371-400) sums over the joints and averages over
+ *                  the two coordinates (torch.mean(torch.sum(., axis=1)) on [1, J, 2]; not a mean over joints): loss_n = 0.5 sq_n,
+ *                  with the analytic gradient gr_n.  Over the views: 256 partial sums (partial t adds views t, t + 256, ... in
+ *                  ascending order), a tree lds[t] + lds[t + h] for h = 128 ... 1, then / N.
+ *   Adam           torch's form in f64, no FMA: g = w_multiview g_mv + w_collision (d ratio / dd); m = b1 m + (1 - b1) g;
+ *                  v = b2 v + ((1 - b2) g) g; p1 = p1 b1, p2 = p2 b2 (running products from 1); d = d - ((lr / (1 - p1)) m) /
+ *                  (sqrt(v) / sqrt(1 - p2) + 1e-8); b1 = 0.9, b2 = 0.999.  w_refview of the reference is not in its loss (:757).
+ * coma_shift_columns_prepare: arguments, capacity and refusals exactly as coma_intersection_columns; workspace:
+ *   coma_shift_columns_workspace_bytes(...) bytes, 16-byte aligned; it holds the sorted lists until the next prepare.  lengths i64 [2]
+ *   (device, may be NULL) = {L_A, L_B}.  Refusals are recorded on the device, the later kernels idle (lengths untouched), and
+ *   coma_shift_columns_status(workspace, stream, needed) is the one call that waits.
+ * coma_shift_profile: d f64 [K] (device), K in [1, 64] -> L i64 [K,3] = L_AB at Delta - 1, Delta, Delta + 1 (device), integer atomics.
+ *   Left untouched when the workspace holds a refused call.  No host synchronisation.
+ * coma_depth_optimize_f64: workspace (a prepared shift workspace, or NULL: no collision term; w_collision == 0 has the same
+ *   effect), views f64 [n_views,28], joints0 f64 [J,3], cand_view i32 [N], cand_xy f64 [N,J,2] (device; N == 0: no multiview term),
+ *   front f64 [3] (HOST pointer, read during the call), E epochs in [1, 4096].  Per epoch one profile kernel (K = 1, d read from traj)
+ *   and one single-workgroup step kernel are enqueued; no host synchronisation.  traj f64 [E+1] = d before epoch 0 ... after epoch
+ *   E - 1; Ltraj i64 [E,3] the profile at traj[e] (written when the collision term is on); losses f64 [E,2] = {multiview loss,
+ *   ratio} at traj[e], unweighted.  state: coma_depth_optimize_state_bytes() bytes of device scratch, 8-byte aligned, where the step
+ *   kernels keep m, v, p1, p2 between launches.  A d that is not finite is recorded there and the later epochs idle;
+ *   coma_depth_optimize_status(state, stream, epoch) -- which waits -- then returns COMA_E_INVALID and the epoch (HOST pointer, may be
+ *   NULL) after which it happened; so it does when the workspace holds a refused call (nothing is written then). */
+size_t coma_shift_columns_workspace_bytes(int VA, int FA, int VB, int FB, int W, int H, int64_t capacity);
+int coma_shift_columns_prepare(const double* vertsA, int VA, const int32_t* facesA, int FA, const double* vertsB, int VB,
+                               const int32_t* facesB, int FB, double x0, double y0, double s, int W, int H, int64_t capacity,
+                               void* workspace, int64_t* lengths, void* stream);
+int coma_shift_columns_status(const void* workspace, void* stream, int64_t* needed);
+int coma_shift_profile(const void* workspace, const double* d, int K, int64_t* L, void* stream);
+size_t coma_depth_optimize_state_bytes(void);
+int coma_depth_optimize_f64(const void* workspace, const double* views, int n_views, const double* joints0, const double* front,
+                            const int32_t* cand_view, const double* cand_xy, int N, int J, double d0, double lr, double w_multiview,
+                            double w_collision, int E, double* traj, int64_t* Ltraj, double* losses, void* state, void* stream);
+int coma_depth_optimize_status(const void* state, void* stream, int* epoch);
+
 #ifdef __cplusplus
 }
 #endif
