@@ -19,7 +19,8 @@ LIB_PATH = os.environ.get("COMA_HIP_LIB") or os.path.join(_HERE, "libcoma_hip.so
 ABI_VERSION = 9                  # = COMA_ABI_VERSION of include/coma_hip.h: bumped with every change of the SIGNATURES table below
 # (not for the text-tower functions: they were only added, no existing signature changed, and a library without them is refused by
 # lib() anyway -- getattr of a missing symbol fails; the same holds for the two coma_sample_eliminate_* functions and for the
-# coma_raster_* / coma_silhouette_iou functions, and for the mesh volume functions of csrc/mesh_volume.hip and the depth-optimisation functions of csrc/depth_opt.hip)
+# coma_raster_* / coma_silhouette_iou functions, and for the mesh volume functions of csrc/mesh_volume.hip and the depth-optimisation functions of csrc/depth_opt.hip,
+# and for the two coma_app_objective_* functions of csrc/app_objective.hip)
 
 _lib = None
 
@@ -64,6 +65,8 @@ SIGNATURES = {
     "coma_depth_optimize_state_bytes": (C.c_size_t, []),
     "coma_depth_optimize_f64": (_i, [_vp, _vp, _i, _vp, C.POINTER(_d), _vp, _vp, _i, _i, _d, _d, _d, _d, _i, _vp, _vp, _vp, _vp, _vp]),
     "coma_depth_optimize_status": (_i, [_vp, _vp, C.POINTER(_i)]),
+    "coma_app_objective_workspace_bytes": (C.c_size_t, [_i, _i, _i]),
+    "coma_app_objective_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _fp3, _fp3, _fp3, _d, _vp, _vp, _i, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     # include/sd_hip.h
     "sd_conv_gemm_f16": (_i, [_vp, _vp]),
     "sd_conv_gemm_workspace_bytes": (C.c_size_t, []),

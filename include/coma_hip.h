@@ -337,6 +337,53 @@ int coma_depth_optimize_f64(const void* workspace, const double* views, int n_vi
                             double w_collision, int E, double* traj, int64_t* Ltraj, double* losses, void* state, void* stream);
 int coma_depth_optimize_status(const void* state, void* stream, int* epoch);
 
+/* The optimisation app's ComA objective: the orientation term and the contact term of one posed mesh, unweighted, and their
+ * gradients with respect to the vertices, in one pass (the app never needs a loss without its gradient).
+ * replaces: src/application/optimize.py:274-289 (compute_vertex_normals :118-152, normalize_vectors_torch, the column
+ *           reference_object_vertex_index of canonicalize_a_wrt_b_to_p :69-115) and the loss lines :295-296 (chamfer_distance
+ *           :155-164), forward and backward, inside the 2000-iteration loop of :252-307.  SMPL-X, VPoser, the angle prior and COAP
+ *           stay with the caller: its autograd continues from the two gradients returned here.
+ * PINNED against the reference's own functions and loss lines, executed on the CPU in f64 (tests/golden/app_objective_golden.npz),
+ * through the f64 restatement tests/app_ref.py.  Rule set:
+ *   normals        N_h = sum over the faces incident to h, ascending face index, of (v1 - v0) x (v2 - v0): the three index_add calls
+ *                  of :124-150 add this same vector to each corner.  Three normalisations follow in the reference's order:
+ *                  n1 = N / max(|N|, 1e-6) (F.normalize(eps=1e-6)), n2 = n1 / (|n1| + eps) (:277), a = n2 / (|n2| + eps) (:73).
+ *   canonicalise   for the one column b the map a -> f is linear, f = M a, M built on the host in f64 from b^ = b / (|b| + eps) and
+ *                  p^, s^ likewise: with c = B p^, B the b_cross of :92-98 as written (B[0][0] = b0 is set, B[2][1] = b0 is not),
+ *                  M = c c^T / (1 + b^.p^) + (b^.p^) I + p^ b^^T - b^ p^^T; when 1 + b^.p^ < eps it is the replacer
+ *                  M = 2 s^ s^^T - I instead.  Then f^ = f / |f|.  |p^.s^| > 1e-8 refuses the call (the reference asserts it).
+ *                  With one eps in both places, 1 + b^.p^ >= about 2 eps even for b = -p, so the replacer needs eps > about 0.62.
+ *   orientation    term = (1 / V) sum_h nan_to_num(1 - (GT_h . f^_h + 1) / 2).  A vertex whose share is NaN -- its normal sum is
+ *                  zero (no incident face, or only degenerate ones), or f is -- contributes 0 to the term and nothing to the
+ *                  gradient.  DEVIATION: the reference gives a zero gradient for a vertex without faces and NaN gradients around a
+ *                  degenerate fan (0 * inf in the backward of its square roots).
+ *   contact        A = verts[selected], B = targets (the object points obj_verts[corresponding_object_indices], duplicates kept):
+ *                  term = mean_i min_j |A_i - B_j| + mean_j min_i |A_i - B_j|.  The argmin is taken over f32 distances
+ *                  sqrt((dx^2 + dy^2) + dz^2) of coordinate differences, the FIRST minimum wins a tie; the winning distance is then
+ *                  taken again in f64.  The gradient follows the argmin; a zero distance has zero gradient (as cdist's backward).
+ *                  k == 0: the term is 0, its gradient zero, nothing of it is launched (the reference raises on an empty min).
+ *                  `selected` must hold DISTINCT rows (np.nonzero gives them so): two equal entries write one gradient row twice.
+ *   gradients      analytic.  g_h = d term / d N_h through f / |f| and the three normalisations; back to the vertices by a GATHER over
+ *                  the CSR table: per incident face G = (g_f0 + g_f1) + g_f2, d/dv1 = (v2 - v0) x G, d/dv2 = G x (v1 - v0),
+ *                  d/dv0 = -(d/dv1 + d/dv2), the slot of h taken, faces ascending.  The contact term's second direction is a scan
+ *                  over j ascending for the rows whose argmin is i.  No floating-point atomics anywhere; the sums of the two terms
+ *                  are per-workgroup trees whose partials one workgroup adds in block order: two calls give the same bits.
+ *   precision      inputs and outputs are f32; everything per vertex and every sum is evaluated in f64 (the work is latency-bound),
+ *                  so the outputs are the f32 rounding of the rule set.  Only the k x k argmin search is f32.
+ * verts f32 [V,3]; faces i32 [F,3]; vf_offsets i32 [V+1] / vf_faces i32 [3F] as for coma_vertex_normals_f64; orientation_gt f32 [V,3];
+ * obj_normal / principle_vec / sub_principle_vec: HOST pointers, 3 floats each, read during the call; selected i32 [k]; targets
+ * f32 [k,3] (both may be NULL when k == 0); terms f32 [2] = {orientation, contact}; grad_orientation, grad_contact f32 [V,3],
+ * overwritten; workspace: coma_app_objective_workspace_bytes(V, F, k) bytes of device scratch, 16-byte aligned (0 for sizes the call
+ * would refuse).  Refused before any launch: a null pointer, V or F <= 0, k < 0 or k > V, eps < 0, a workspace too small.  A face,
+ * table or selected index outside its range (device data the call cannot see) is not followed and makes the term it feeds NaN.
+ * Seven kernel launches and one memset on the caller's stream; no host synchronisation. */
+size_t coma_app_objective_workspace_bytes(int V, int F, int k);
+int coma_app_objective_f32(const float* verts, const int32_t* faces, const int32_t* vf_offsets, const int32_t* vf_faces, int V, int F,
+                           const float* orientation_gt, const float* obj_normal, const float* principle_vec,
+                           const float* sub_principle_vec, double eps, const int32_t* selected, const float* targets, int k,
+                           float* terms, float* grad_orientation, float* grad_contact, void* workspace, size_t workspace_bytes,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

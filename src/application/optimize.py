@@ -1,0 +1,179 @@
+"""Optimisation app: fit an SMPL-X pose to an object under a learned ComA state -- the one program of the reference that uses a
+learned state -- with ComA's own objective on the device (coma_amd.app.ComaObjective) and the third-party models as hooks.
+
+CLI surface, parameter set, initial values and loss composition of the reference's ``src/application/optimize.py``:
+  * flags and defaults of :321-339 (unknown flags are rejected); principle / sub-principle vectors (0,0,1) / (0,1,0) and reference
+    object vertex 0 as its __main__ passes them (:348-350);
+  * parameters and initial values of :236-250: Adam over global_orient (0), transl (3, 1, 0), both hand poses (0) and the pose
+    embedding (the decoder's encoding of the T-pose); betas, expression, eye and jaw poses fixed;
+  * loss = pose-prior + angle-prior + contact + orientation (:292-298), the last two from ONE device evaluation per iteration, its
+    gradient with respect to the vertices handed to torch's autograd, which continues into the body model;
+  * output {save_dir}/{supercategory}/{category}/optimized.obj (:317), written by a plain v / f writer (the reference writes through
+    open3d, absent here; its file also carries vertex normals).
+The hooks own their torch arithmetic; the optimiser stays torch.optim.Adam beside them:
+  * body_model(betas=, global_orient=, body_pose=, left_hand_pose=, right_hand_pose=, transl=, expression=, jaw_pose=, leye_pose=,
+    reye_pose=, return_verts=True, return_full_pose=True) -> object with .vertices [1,V,3]; it also has .faces [F,3].  Default:
+    smplx.create(BODY_MOCAP_PATH, model_type="smplx", num_pca_comps=45), imported when first needed;
+  * pose_decoder with .encode(pose [1,63]).mean and .decode(embedding, output_type="aa").  Default: the reference's VPoser loader
+    (utils.vposer), which this repository does not carry -- a clear error says so;
+  * angle_prior(body_pose [1,63]) -> tensor, summed.  Default: likewise.
+--use_collision is REFUSED: COAP (a learned occupancy network with a downloaded checkpoint) is unpinned and not reproduced, as in the
+depth stage.  One flag is added: --num_iters (the reference's loop count, 2000, is a literal there).
+"""
+import argparse
+import os
+import pickle
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+BODY_MOCAP_PATH = "imports/hand4whole/common/utils_hand4whole/human_model_files/"
+DEFAULT_BETAS = [[-0.00982137, 0.03693837, 0.0949352, -0.01299302, 0.00492086, -0.04505398, -0.0008909, -0.00054313, 0.03646483, -0.00803524]]
+COLLISION_REFUSAL = ("--use_collision is not supported: the reference's collision term is COAP's (a learned occupancy network whose "
+                     "checkpoint is not available to this project); run without it")
+
+
+def default_body_model(device):
+    try:
+        import smplx
+    except ImportError as exc:
+        raise RuntimeError("optimize: the `smplx` package is needed for the body model (pass body_model=... to run without it)") from exc
+    return smplx.create(model_path=BODY_MOCAP_PATH, model_type="smplx", num_pca_comps=45).to(device)
+
+
+def default_pose_decoder(device):
+    try:
+        from utils.vposer.model_loader import load_vposer
+    except ImportError as exc:
+        raise RuntimeError("optimize: VPoser (utils.vposer of the reference, third party) is needed for the pose embedding "
+                           "(pass pose_decoder=... to run without it)") from exc
+    vposer = load_vposer("imports/vposer", vp_model="snapshot").to(device=device)
+    vposer.eval()
+    return vposer
+
+
+def default_angle_prior(device):
+    try:
+        from utils.vposer.prior import create_prior
+    except ImportError as exc:
+        raise RuntimeError("optimize: the angle prior (utils.vposer.prior of the reference, third party) is needed "
+                           "(pass angle_prior=... to run without it)") from exc
+    return create_prior(prior_type="angle").to(device)
+
+
+def write_obj(pth, vertices, faces):
+    """Plain Wavefront OBJ: `v x y z` lines, then 1-based `f a b c` lines; coordinates with 9 significant digits (f32 round-trips)."""
+    vertices, faces = np.asarray(vertices, dtype=np.float64).reshape(-1, 3), np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    with open(pth, "w") as fh:
+        for v in vertices:
+            fh.write(f"v {v[0]:.9g} {v[1]:.9g} {v[2]:.9g}\n")
+        for f in faces:
+            fh.write(f"f {f[0] + 1} {f[1] + 1} {f[2] + 1}\n")
+
+
+def fit(objective_loss, body_model, pose_decoder, angle_prior, lr, body_pose_weight, bending_prior_weight, pprior_weight, scale_factor,
+        num_iters=2000, device="cuda", dtype=None, record=False):
+    """The loop of :236-307 around any `objective_loss(vertices [1,V,3]) -> scalar` (the weighted orientation + contact terms).
+    Returns dict(vertices [V,3] of the last iteration's forward, as the reference saves them; losses; trajectory = global_orient and
+    transl after every step, [num_iters + 1, 6], when record)."""
+    import torch
+    dtype = dtype or torch.float32
+    mk = lambda x: torch.as_tensor(np.asarray(x, dtype=np.float64)).to(device=device, dtype=dtype)
+    t_pose_embedding = pose_decoder.encode(mk(np.zeros((1, 63)))).mean
+    pose_embedding = t_pose_embedding.clone().detach().requires_grad_(True)
+    betas, expression = mk(DEFAULT_BETAS), mk(np.zeros((1, 10)))
+    leye_pose, reye_pose = mk(np.zeros((1, 3))), mk(np.zeros((1, 3)))
+    global_orient = torch.nn.Parameter(mk([[0.0, 0.0, 0.0]]), requires_grad=True)
+    transl = torch.nn.Parameter(mk([[3.0, 1.0, 0.0]]), requires_grad=True)
+    left_hand_pose = torch.nn.Parameter(mk(np.zeros((1, 45))), requires_grad=True)
+    right_hand_pose = torch.nn.Parameter(mk(np.zeros((1, 45))), requires_grad=True)
+    jaw_pose = torch.nn.Parameter(mk(np.zeros((1, 3))))
+    optimizer = torch.optim.Adam([global_orient, transl, left_hand_pose, right_hand_pose, pose_embedding], lr=lr)
+    state = lambda: torch.cat([global_orient.detach().reshape(-1), transl.detach().reshape(-1)]).cpu().numpy().astype(np.float64)
+    losses, trajectory = [], [state()] if record else []
+    vertices = None
+    for _ in range(num_iters):
+        optimizer.zero_grad()
+        body_pose = pose_decoder.decode(pose_embedding, output_type="aa").view(1, -1)
+        output = body_model(betas=betas, global_orient=global_orient, body_pose=body_pose, left_hand_pose=left_hand_pose,
+                            right_hand_pose=right_hand_pose, transl=transl, expression=expression, jaw_pose=jaw_pose, leye_pose=leye_pose,
+                            reye_pose=reye_pose, return_verts=True, return_full_pose=True)
+        vertices = output.vertices * scale_factor
+        pprior_loss = (pose_embedding.pow(2).sum() * body_pose_weight ** 2) * pprior_weight
+        angle_prior_loss = torch.sum(angle_prior(body_pose)) * bending_prior_weight
+        loss = pprior_loss + angle_prior_loss + objective_loss(vertices)
+        loss.backward()
+        optimizer.step()
+        if record:
+            losses.append(float(loss.detach()))
+            trajectory.append(state())
+    return dict(vertices=None if vertices is None else vertices.detach().reshape(-1, 3).cpu().numpy(), losses=losses, trajectory=trajectory)
+
+
+def optimize_smpl(supercategory, category, coma_path, asset_downsample_pth, eps, principle_vec, sub_principle_vec, reference_object_vertex_index,
+                  lr, body_pose_weight, bending_prior_weight, pprior_weight, orientation_weight, contact_weight, contact_threshold, scale_factor,
+                  use_collision, save_dir="", num_iters=2000, body_model=None, pose_decoder=None, angle_prior=None, device="cuda", record=False):
+    """The reference's optimize_smpl with the three third-party models as hooks (None = the reference's own, imported lazily).
+    coma_path / asset_downsample_pth: the pickles, or the dicts they hold.  Writes {save_dir}/{supercategory}/{category}/optimized.obj
+    and returns fit()'s dict plus the faces and the path."""
+    if use_collision:
+        raise NotImplementedError(COLLISION_REFUSAL)
+    from coma_amd.app import ComaObjective
+    body_model = body_model if body_model is not None else default_body_model(device)
+    pose_decoder = pose_decoder if pose_decoder is not None else default_pose_decoder(device)
+    angle_prior = angle_prior if angle_prior is not None else default_angle_prior(device)
+    faces = np.asarray(body_model.faces).astype(np.int64)
+    objective = ComaObjective.from_state(coma_path, asset_downsample_pth, faces, reference_object_vertex_index, contact_threshold,
+                                         principle_vec, sub_principle_vec, eps, device)
+    out = fit(lambda vertices: objective.loss(vertices, orientation_weight, contact_weight), body_model, pose_decoder, angle_prior, lr,
+              body_pose_weight, bending_prior_weight, pprior_weight, scale_factor, num_iters, device, record=record)
+    out["faces"] = faces
+    out["path"] = None
+    if out["vertices"] is not None:
+        directory = os.path.join(save_dir, supercategory, category)
+        os.makedirs(directory, exist_ok=True)
+        out["path"] = os.path.join(directory, "optimized.obj")
+        write_obj(out["path"], out["vertices"], faces)
+    return out
+
+
+def build_parser():
+    p = argparse.ArgumentParser(allow_abbrev=False)
+    p.add_argument("--supercategory", type=str)
+    p.add_argument("--category", type=str)
+    p.add_argument("--coma_path", type=str)
+    p.add_argument("--save_dir", type=str, default="output/")
+    p.add_argument("--asset_downsample_pth", type=str)
+    p.add_argument("--eps", type=float, default=1e-6)
+    p.add_argument("--lr", type=float, default=1e-2)
+    p.add_argument("--body_pose_weight", type=float, default=10000)
+    p.add_argument("--bending_prior_weight", type=float, default=31700)
+    p.add_argument("--pprior_weight", type=float, default=1e-6)
+    p.add_argument("--orientation_weight", type=float, default=1e12)
+    p.add_argument("--contact_weight", type=float, default=2.6e11)
+    p.add_argument("--contact_threshold", type=float, default=0.3)
+    p.add_argument("--scale_factor", type=float, default=0.84)
+    p.add_argument("--use_collision", action="store_true", help="refused: COAP is not reproduced")
+    p.add_argument("--num_iters", type=int, default=2000, help="Adam iterations (a literal 2000 in the reference)")
+    return p
+
+
+def main(args, body_model=None, pose_decoder=None, angle_prior=None):
+    if args.use_collision:
+        raise SystemExit(COLLISION_REFUSAL)
+    return optimize_smpl(supercategory=args.supercategory, category=args.category, coma_path=args.coma_path,
+                         asset_downsample_pth=args.asset_downsample_pth, eps=args.eps, principle_vec=[0, 0, 1], sub_principle_vec=[0, 1, 0],
+                         reference_object_vertex_index=0, lr=args.lr, body_pose_weight=args.body_pose_weight,
+                         bending_prior_weight=args.bending_prior_weight, pprior_weight=args.pprior_weight,
+                         orientation_weight=args.orientation_weight, contact_weight=args.contact_weight,
+                         contact_threshold=args.contact_threshold, scale_factor=args.scale_factor, use_collision=args.use_collision,
+                         save_dir=args.save_dir, num_iters=args.num_iters, body_model=body_model, pose_decoder=pose_decoder,
+                         angle_prior=angle_prior)
+
+
+if __name__ == "__main__":
+    main(build_parser().parse_args())
