@@ -20,7 +20,7 @@ ABI_VERSION = 9                  # = COMA_ABI_VERSION of include/coma_hip.h: bum
 # (not for the text-tower functions: they were only added, no existing signature changed, and a library without them is refused by
 # lib() anyway -- getattr of a missing symbol fails; the same holds for the two coma_sample_eliminate_* functions and for the
 # coma_raster_* / coma_silhouette_iou functions, and for the mesh volume functions of csrc/mesh_volume.hip and the depth-optimisation functions of csrc/depth_opt.hip,
-# and for the two coma_app_objective_* functions of csrc/app_objective.hip)
+# and for the two coma_app_objective_* functions of csrc/app_objective.hip and the coma_smplx_* functions of csrc/smplx.hip)
 
 _lib = None
 
@@ -67,6 +67,15 @@ SIGNATURES = {
     "coma_depth_optimize_status": (_i, [_vp, _vp, C.POINTER(_i)]),
     "coma_app_objective_workspace_bytes": (C.c_size_t, [_i, _i, _i]),
     "coma_app_objective_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _fp3, _fp3, _fp3, _d, _vp, _vp, _i, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "coma_smplx_workspace_bytes": (C.c_size_t, [_i, _i]),
+    "coma_smplx_shape_state_bytes": (C.c_size_t, [_i, _i]),
+    "coma_smplx_saved_bytes": (C.c_size_t, [_i, _i]),
+    "coma_smplx_shape_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, C.c_size_t, _vp]),
+    "coma_smplx_forward_f32": (_i, [_vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_size_t,
+                                    _vp, C.c_size_t, _vp]),
+    "coma_smplx_backward_f32": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _i, _vp, _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t,
+                                     _vp]),
+    "coma_smplx_extra_joints_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     # include/sd_hip.h
     "sd_conv_gemm_f16": (_i, [_vp, _vp]),
     "sd_conv_gemm_workspace_bytes": (C.c_size_t, []),

@@ -1,0 +1,290 @@
+"""The SMPL-X body model on MI355X: linear blend skinning forward and backward by the library's own kernels
+(coma_amd/csrc/smplx.hip; rule set in include/coma_hip.h, restated in tests/smplx_ref.py).
+
+`DeviceSMPLX` has the call shape of the third-party `smplx` package's model object, which is what the `body_model` hooks of
+src/application/optimize.py and src/generation/optimize_depth.py call: keyword tensors in, an object with .vertices [1,V,3],
+.joints, .full_pose and .faces out.  `.vertices` is the output of a torch.autograd.Function whose backward is the device backward, so
+a pose decoder or a prior on the other side of the hook keeps differentiating through torch.
+
+Deviations from the package, all refused or stated rather than silently different:
+  * NO gradient with respect to betas or expression (the call raises if either requires grad) and none through `.joints`;
+  * batch size 1 only;
+  * the package's table of vertex ids for the extra joints (nose, eyes, ears, toes, heels, finger tips) is not shipped: it is taken
+    from `smplx.vertex_ids` when that package imports, may be passed in, and otherwise `.joints` is [J posed joints | landmarks] and
+    `extra_joint_source` says "landmarks only";
+  * no dynamic face contour, no joint mapper.
+There is no CPU path.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from types import SimpleNamespace
+
+import numpy as np
+import torch
+
+from . import _lib
+
+SHAPE_SPACE_DIM, EXPRESSION_SPACE_DIM = 300, 100
+MAX_JOINTS = 64
+# the package's order of the extra joints (vertex_joint_selector.py): face and feet, then the finger tips of both hands
+_FACE_FEET = ("nose", "reye", "leye", "rear", "lear", "LBigToe", "LSmallToe", "LHeel", "RBigToe", "RSmallToe", "RHeel")
+_TIPS = ("thumb", "index", "middle", "ring", "pinky")
+
+
+def _package_vertex_ids():
+    try:
+        from smplx.vertex_ids import vertex_ids
+    except ImportError:
+        return None
+    table = vertex_ids["smplx"]
+    return [table[n] for n in _FACE_FEET] + [table[side + n] for side in ("l", "r") for n in _TIPS]
+
+
+def _row(x, n, name):
+    """A call argument as a host f32 vector [n] and whether it requires grad; batch size 1 only."""
+    if x is None:
+        return None
+    if not torch.is_tensor(x):
+        x = torch.as_tensor(np.asarray(x, dtype=np.float32))
+    if x.dim() == 2 and x.shape[0] != 1:
+        raise ValueError(f"{name}: batch size {x.shape[0]}; DeviceSMPLX handles batch size 1 only")
+    if x.numel() != n:
+        raise ValueError(f"{name}: expected {n} numbers ([1,{n}]), got shape {tuple(x.shape)}")
+    return x
+
+
+class DeviceSMPLX:
+    def __init__(self, model, n_pca=45, flat_hand_mean=False, use_pca=True, device="cuda", num_betas=10, num_expression_coeffs=10,
+                 extra_joint_vertex_ids=None):
+        """model: a dict of arrays with the keys of an SMPL-X model file (v_template, shapedirs, posedirs, J_regressor, kintree_table,
+        weights, f, hands_components{l,r}, hands_mean{l,r}, lmk_faces_idx, lmk_bary_coords)."""
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise _lib.ComaHipError(f"DeviceSMPLX needs a HIP device (got {dev}); there is no CPU path")
+        need = ("v_template", "shapedirs", "posedirs", "J_regressor", "kintree_table", "weights", "f", "hands_componentsl", "hands_componentsr",
+                "hands_meanl", "hands_meanr", "lmk_faces_idx", "lmk_bary_coords")
+        missing = [k for k in need if k not in model]
+        if missing:
+            raise KeyError(f"DeviceSMPLX: the model lacks {missing}")
+        f32 = lambda a: np.ascontiguousarray(np.asarray(a), dtype=np.float32)
+        v_template = f32(model["v_template"]).reshape(-1, 3)
+        V = int(v_template.shape[0])
+        J_regressor = f32(model["J_regressor"])
+        J = int(J_regressor.shape[0])
+        if J_regressor.shape != (J, V):
+            raise ValueError(f"J_regressor: expected [J,{V}], got {J_regressor.shape}")
+        if not 5 <= J <= MAX_JOINTS:
+            raise ValueError(f"DeviceSMPLX: {J} joints; between 5 and {MAX_JOINTS} are supported")
+        # shape directions [:, :, :num_betas]; expression directions from 300 on, or 10:20 in a file with fewer than 400 directions
+        sd = np.asarray(model["shapedirs"])
+        if sd.ndim < 3:
+            sd = sd[:, :, None]
+        num_betas = min(num_betas, 10) if sd.shape[-1] < SHAPE_SPACE_DIM else min(num_betas, SHAPE_SPACE_DIM)
+        if sd.shape[-1] < SHAPE_SPACE_DIM + EXPRESSION_SPACE_DIM:
+            start, end = 10, 20
+        else:
+            start, end = SHAPE_SPACE_DIM, SHAPE_SPACE_DIM + num_expression_coeffs
+        shape_dirs, expr_dirs = sd[:, :, :num_betas], sd[:, :, start:end]
+        self.num_betas, self.num_expression_coeffs = int(shape_dirs.shape[-1]), int(expr_dirs.shape[-1])
+        shapedirs = f32(np.concatenate([shape_dirs, expr_dirs], -1))
+        if shapedirs.shape[:2] != (V, 3) or shapedirs.shape[-1] < 1:
+            raise ValueError(f"shapedirs: expected [{V},3,NB >= 1], got {shapedirs.shape}")
+        pd = np.asarray(model["posedirs"])
+        P = 9 * (J - 1)
+        if pd.shape != (V, 3, P):
+            raise ValueError(f"posedirs: expected [{V},3,{P}], got {pd.shape}")
+        posedirs = f32(pd.reshape(-1, P).T)                         # [P, 3V], the layout the package keeps too
+        weights = f32(model["weights"])
+        if weights.shape != (V, J):
+            raise ValueError(f"weights: expected [{V},{J}], got {weights.shape}")
+        parents = np.asarray(model["kintree_table"])[0].astype(np.int64).copy()
+        parents[0] = -1
+        if parents.shape != (J,) or any(not 0 <= parents[i] < i for i in range(1, J)):
+            raise ValueError("kintree_table: every joint after the root needs a parent with a smaller index")
+        hd = int(np.asarray(model["hands_meanl"]).size)
+        if hd % 3 or 2 * hd > 3 * (J - 5) or np.asarray(model["hands_meanr"]).size != hd:
+            raise ValueError(f"hands_mean: {hd} entries per hand do not fit {J} joints")
+        self.use_pca, self.flat_hand_mean = bool(use_pca), bool(flat_hand_mean)
+        self.num_pca_comps = int(n_pca) if use_pca else 0
+        comps = None
+        if use_pca:
+            cl, cr = f32(model["hands_componentsl"])[:n_pca], f32(model["hands_componentsr"])[:n_pca]
+            if cl.shape != (n_pca, hd) or cr.shape != (n_pca, hd):
+                raise ValueError(f"hands_components: expected at least [{n_pca},{hd}], got {cl.shape} and {cr.shape}")
+            comps = np.stack([cl, cr])
+        mean = np.zeros(3 * J, np.float32)
+        if not flat_hand_mean and hd:
+            mean[3 * J - 2 * hd:3 * J - hd], mean[3 * J - hd:] = f32(model["hands_meanl"]).reshape(-1), f32(model["hands_meanr"]).reshape(-1)
+        self.faces = np.asarray(model["f"]).astype(np.int64).reshape(-1, 3)
+        lmk_faces = np.asarray(model["lmk_faces_idx"]).astype(np.int64).reshape(-1)
+        lmk_bary = f32(model["lmk_bary_coords"]).reshape(-1, 3)
+        if extra_joint_vertex_ids is None:
+            extra_joint_vertex_ids = _package_vertex_ids()
+            self.extra_joint_source = "landmarks only" if extra_joint_vertex_ids is None else "smplx.vertex_ids"
+        else:
+            self.extra_joint_source = "caller"
+        ids = np.asarray([] if extra_joint_vertex_ids is None else list(extra_joint_vertex_ids), dtype=np.int64).reshape(-1)
+        idx = np.concatenate([np.repeat(ids[:, None], 3, 1), self.faces[lmk_faces]])
+        if idx.size and (idx.min() < 0 or idx.max() >= V):
+            raise IndexError(f"extra joints: vertex indices must lie in [0, {V}), got [{idx.min()}, {idx.max()}]")
+        w = np.concatenate([np.tile(np.float32([1, 0, 0]), (len(ids), 1)), lmk_bary]).astype(np.float32)
+
+        self.V, self.J, self.P, self.hand_dim, self.device = V, J, P, hd, dev
+        self.num_lead = 3 * J - 2 * hd                                  # axis-angle entries before the hands
+        self.num_body = self.num_lead - 12                               # body_pose entries
+        self.hand_size = self.num_pca_comps if use_pca else hd          # entries of one hand's argument
+        self.num_theta = self.num_lead + 2 * self.hand_size
+        self.num_extra = int(idx.shape[0])
+        # host copies (read by the tests) and their device uploads
+        self.host = dict(v_template=v_template, shapedirs=shapedirs, posedirs=posedirs, J_regressor=J_regressor, weights=weights,
+                         parents=parents, hand_components=comps, pose_mean=mean, extra_index=idx, extra_weight=w)
+        self._parents = (C.c_int32 * J)(*[int(p) for p in parents])
+        self._uploaded = False                                           # the device is first touched by the first call
+        self._shape_key, self._shape_source, self._shape_version = None, None, None
+        self.shape_stage_runs = 0                                        # how often the shape stage ran (tests count it)
+
+    @classmethod
+    def from_file(cls, model_path, gender="neutral", num_pca_comps=45, flat_hand_mean=False, use_pca=True, device="cuda", num_betas=10,
+                  num_expression_coeffs=10, extra_joint_vertex_ids=None):
+        """model_path: the model file itself, or -- the path rule of the package's `create(model_path, model_type="smplx")` -- a
+        directory whose `smplx/` sub-directory holds SMPLX_{GENDER}.npz; read with NumPy alone."""
+        pth = model_path
+        if os.path.isdir(pth):
+            pth = os.path.join(pth, "smplx")
+            if os.path.isdir(pth):
+                pth = os.path.join(pth, f"SMPLX_{gender.upper()}.npz")
+        if not os.path.exists(pth):
+            raise FileNotFoundError(f"DeviceSMPLX: {pth} does not exist")
+        with np.load(pth, allow_pickle=True) as data:
+            model = {k: data[k] for k in data.files}
+        return cls(model, n_pca=num_pca_comps, flat_hand_mean=flat_hand_mean, use_pca=use_pca, device=device, num_betas=num_betas,
+                   num_expression_coeffs=num_expression_coeffs, extra_joint_vertex_ids=extra_joint_vertex_ids)
+
+    def _upload(self):
+        if self._uploaded:
+            return
+        if self.device.index is None:                                    # "cuda" means the current device; tensors report cuda:N
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        h, dev = self.host, self.device
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        self._v_template, self._shapedirs, self._posedirs = up(h["v_template"]), up(h["shapedirs"]), up(h["posedirs"])
+        self._J_regressor, self._weights, self._mean = up(h["J_regressor"]), up(h["weights"]), up(h["pose_mean"])
+        self._comps = up(h["hand_components"]) if h["hand_components"] is not None and self.hand_dim else None
+        self._extra_index, self._extra_weight = (up(h["extra_index"].astype(np.int32)), up(h["extra_weight"])) if self.num_extra else (None, None)
+        L = _lib.lib()
+        self._ws_bytes, self._shape_bytes, self._saved_bytes = (int(f(self.V, self.J)) for f in (
+            L.coma_smplx_workspace_bytes, L.coma_smplx_shape_state_bytes, L.coma_smplx_saved_bytes))
+        self._ws = torch.empty([self._ws_bytes], dtype=torch.uint8, device=dev)
+        self._shape_state = torch.empty([self._shape_bytes], dtype=torch.uint8, device=dev)
+        self._uploaded = True
+
+    # ---- the three device calls ----
+    def _shape_stage(self, betas, expression):
+        """Re-run only when the coefficients differ from the last call's.  The same tensor objects at the same version counter (the
+        app passes its fixed betas every iteration) are not looked at again, so nothing is read back from the device for them;
+        anything else is compared on the host copy made here (one device-to-host copy when the coefficients live on the device).
+        LIMITATION: a write that does not move the version counter -- through `.data`, or from outside torch -- is not seen on the
+        same-tensor path; pass a new tensor, or write in place through torch."""
+        for x, name in ((betas, "betas"), (expression, "expression")):     # looked at on every call, whichever path follows
+            if torch.is_tensor(x) and x.requires_grad:
+                raise _lib.ComaHipError(f"DeviceSMPLX: {name} requires grad, and the device body model has no gradient with respect to {name}")
+        source = (betas, expression)
+        version = tuple(x._version if torch.is_tensor(x) else None for x in source)
+        if self._shape_source is not None and version == self._shape_version and all(
+                (x is None and y is None) or (torch.is_tensor(x) and x is y) for x, y in zip(source, self._shape_source)):
+            return
+        parts = []
+        for x, n, name in ((betas, self.num_betas, "betas"), (expression, self.num_expression_coeffs, "expression")):
+            x = _row(x, n, name)
+            if x is None:
+                parts.append(np.zeros(n, np.float32))
+                continue
+            parts.append(x.detach().to(torch.float32).reshape(-1).cpu().numpy())
+        coef = np.ascontiguousarray(np.concatenate(parts), dtype=np.float32)
+        self._upload()
+        key = coef.tobytes()
+        self._shape_source, self._shape_version = source, version
+        if key == self._shape_key:
+            return
+        d_coef = torch.from_numpy(coef).to(self.device)
+        f32 = torch.float32
+        with _lib.on_device(self.device) as stream:
+            rc = _lib.lib().coma_smplx_shape_f32(_lib.ptr(self._v_template, f32), _lib.ptr(self._shapedirs, f32), _lib.ptr(d_coef, f32),
+                                                 _lib.ptr(self._J_regressor, f32), self.V, self.J, int(coef.size), _lib.ptr(self._shape_state),
+                                                 self._shape_bytes, stream)
+        _lib.check(rc, "coma_smplx_shape_f32")
+        self._shape_key = key
+        self.shape_stage_runs += 1
+
+    def _forward(self, theta, transl):
+        """theta f32 [num_theta], transl f32 [3] or None (device) -> vertices [V,3], joints [J + extra, 3], full_pose [3J], saved."""
+        f32, dev = torch.float32, self.device
+        vertices = torch.empty([self.V, 3], dtype=f32, device=dev)
+        joints = torch.empty([self.J + self.num_extra, 3], dtype=f32, device=dev)
+        full_pose = torch.empty([3 * self.J], dtype=f32, device=dev)
+        saved = torch.empty([self._saved_bytes], dtype=torch.uint8, device=dev)
+        L = _lib.lib()
+        with _lib.on_device(dev) as stream:
+            rc = L.coma_smplx_forward_f32(_lib.ptr(theta, f32, "theta"), _lib.ptr(transl, f32, "transl"), _lib.ptr(self._posedirs, f32),
+                                          _lib.ptr(self._weights, f32), self._parents, _lib.ptr(self._comps, f32), _lib.ptr(self._mean, f32), self.V,
+                                          self.J, self.hand_dim, self.num_pca_comps, _lib.ptr(self._shape_state), _lib.ptr(vertices),
+                                          _lib.ptr(joints), _lib.ptr(full_pose), _lib.ptr(saved), self._saved_bytes, _lib.ptr(self._ws),
+                                          self._ws_bytes, stream)
+            if rc == 0 and self.num_extra:
+                rc = L.coma_smplx_extra_joints_f32(_lib.ptr(vertices), _lib.ptr(transl, f32), _lib.ptr(self._extra_index, torch.int32),
+                                                   _lib.ptr(self._extra_weight, f32), self.V, self.num_extra,
+                                                   C.c_void_p(joints.data_ptr() + 12 * self.J), stream)
+        _lib.check(rc, "coma_smplx_forward_f32")
+        return vertices, joints, full_pose, saved
+
+    def _backward(self, grad_vertices, saved):
+        f32, dev = torch.float32, self.device
+        g_theta = torch.empty([self.num_theta], dtype=f32, device=dev)
+        g_transl = torch.empty([3], dtype=f32, device=dev)
+        with _lib.on_device(dev) as stream:
+            rc = _lib.lib().coma_smplx_backward_f32(_lib.ptr(grad_vertices, f32, "grad_vertices"), _lib.ptr(self._posedirs, f32),
+                                                    _lib.ptr(self._weights, f32), self._parents, _lib.ptr(self._comps, f32), self.V, self.J,
+                                                    self.hand_dim, self.num_pca_comps, _lib.ptr(self._shape_state), _lib.ptr(saved),
+                                                    self._saved_bytes, _lib.ptr(g_theta), _lib.ptr(g_transl), _lib.ptr(self._ws), self._ws_bytes,
+                                                    stream)
+        _lib.check(rc, "coma_smplx_backward_f32")
+        return g_theta, g_transl
+
+    def __call__(self, betas=None, global_orient=None, body_pose=None, left_hand_pose=None, right_hand_pose=None, transl=None, expression=None,
+                 jaw_pose=None, leye_pose=None, reye_pose=None, return_verts=True, return_full_pose=False, **unused):
+        """The package's call: every argument [1, n] (None = zeros).  Gradients flow from .vertices to the seven pose arguments and
+        transl; betas and expression must not require grad."""
+        sizes = (("global_orient", global_orient, 3), ("body_pose", body_pose, self.num_body), ("jaw_pose", jaw_pose, 3),
+                 ("leye_pose", leye_pose, 3), ("reye_pose", reye_pose, 3), ("left_hand_pose", left_hand_pose, self.hand_size),
+                 ("right_hand_pose", right_hand_pose, self.hand_size), ("transl", transl, 3))
+        rows = [(name, _row(x, n, name), n) for name, x, n in sizes]          # shapes first: nothing has touched the device yet
+        self._shape_stage(betas, expression)
+        parts = []
+        for name, x, n in rows:
+            if x is None:
+                x = None if name == "transl" else torch.zeros([n], dtype=torch.float32, device=self.device)
+            elif not x.is_cuda or x.device != self.device:
+                raise _lib.ComaHipError(f"{name} must live on {self.device} (got {x.device}); there is no CPU path")
+            parts.append(x if x is None else x.reshape(-1).to(torch.float32))
+        transl = parts.pop()
+        theta = torch.cat(parts)
+        vertices, joints, full_pose = _SkinFunction.apply(self, theta, transl)
+        return SimpleNamespace(vertices=vertices[None] if return_verts else None, joints=joints[None],
+                               full_pose=full_pose[None] if return_full_pose else None, faces=self.faces, betas=betas, expression=expression,
+                               global_orient=global_orient, body_pose=body_pose, jaw_pose=jaw_pose, transl=transl)
+
+
+class _SkinFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, model, theta, transl):
+        vertices, joints, full_pose, saved = model._forward(theta.detach().contiguous(), None if transl is None else transl.detach().contiguous())
+        ctx.model, ctx.saved, ctx.has_transl = model, saved, transl is not None
+        ctx.mark_non_differentiable(joints, full_pose)
+        return vertices, joints, full_pose
+
+    @staticmethod
+    def backward(ctx, grad_vertices, _grad_joints, _grad_full_pose):
+        g_theta, g_transl = ctx.model._backward(grad_vertices.to(torch.float32).contiguous(), ctx.saved)
+        return None, g_theta, (g_transl if ctx.has_transl else None)

@@ -1,0 +1,583 @@
+// The SMPL-X body model -- linear blend skinning of a template over a joint tree -- forward and backward, for gfx950.
+// replaces: the third-party `smplx` package behind the `body_model` hook of src/application/optimize.py (called and differentiated
+// in every one of its 2000 iterations, several dozen eager launches each way) and of src/generation/optimize_depth.py, by three
+// launches forward and three backward on the caller's stream.  Rule set: include/coma_hip.h; restated in f64 in tests/smplx_ref.py.
+//
+// In the project's own words.  The packed parameters theta are axis-angle vectors for the leading joints followed by the
+// coefficients of the two hands; the hands' axis-angles are the coefficients times the model's hand components, and the model's
+// mean pose is added to all of it.  Every joint's axis-angle r becomes a rotation by Rodrigues' formula with the angle taken as the
+// norm of (r + 1e-8), the epsilon added to each component: the formula and its derivative stay finite at r = 0, which is where the
+// app starts.  The shape stage (once per betas) moves the template along the shape directions and regresses the rest joints from
+// it.  The pose stage walks the tree from the root, G_i = G_parent [R_i | J_i - J_parent], and takes the rest pose out again:
+// A_i = [G_i.R | G_i.t - G_i.R J_i].  The skinning stage adds the pose-dependent offsets (the entries of R_i - I for i >= 1 times
+// `posedirs`) to the shaped template, blends the A_i with the vertex's weights and applies the blend.  The backward walks all of
+// that in reverse from dL/dvertices to dL/dtheta and dL/dtransl; betas, expression and the joint outputs get NO gradient.
+//
+// Everything is evaluated in f64 on f32 inputs (as the rest of the per-vertex code of this library: V = 10 475 and a 55-joint
+// chain are latency- and bandwidth-bound, the f64 rate does not show), so the outputs are the f32 rounding of the rule set.  The
+// one large operand is posedirs [P, 3V] (61 MB): forward reads it with threads along the 3V axis and the P rows split over
+// kPSplit workgroups per column block, so that about a thousand workgroups keep loads in flight; backward reads the same rows as
+// P dot products, one workgroup each.  No transposed copy.  No floating-point atomics: every sum over vertices is per-workgroup
+// (fixed order inside), then one fixed-order pass over the workgroups, so two calls give the same bits.
+#include "common.h"
+
+#include <cmath>
+
+namespace coma {
+namespace {
+
+constexpr int kMaxJ = 64;         // joints (the chain kernels keep the whole tree in LDS)
+constexpr int kBlock = 256;
+constexpr int kTile = 128;        // vertices (and threads) per skinning workgroup: weights tile 128 x 64 f32 = 32 KB of LDS
+constexpr int kPSplit = 8;        // splits of the P rows of posedirs in the forward
+constexpr int kMaxRows = (9 * (kMaxJ - 1) + kPSplit - 1) / kPSplit;
+constexpr int kMaxPca = 64;
+
+struct Tree { int32_t parent[kMaxJ]; };
+
+__device__ __forceinline__ double block_sum(double v, double* lds) {   // lds[t] + lds[t + h], h = 128 ... 1
+  const int t = threadIdx.x;
+  lds[t] = v;
+  __syncthreads();
+  for (int h = kBlock / 2; h >= 1; h >>= 1) {
+    if (t < h) lds[t] = lds[t] + lds[t + h];
+    __syncthreads();
+  }
+  return lds[0];
+}
+
+// ---- shape stage ----
+__global__ __launch_bounds__(kBlock) void smplx_shape_kernel(const float* __restrict__ v_template, const float* __restrict__ shapedirs,
+                                                            const float* __restrict__ coef, int n3, int NB, double* __restrict__ v_shaped) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n3) return;
+  double acc = 0.0;
+  for (int l = 0; l < NB; ++l) acc = acc + (double)coef[l] * (double)shapedirs[(int64_t)i * NB + l];
+  v_shaped[i] = (double)v_template[i] + acc;
+}
+
+// one workgroup per (joint, coordinate pair is folded: three sums in one pass)
+__global__ __launch_bounds__(kBlock) void smplx_jrest_kernel(const float* __restrict__ J_regressor, const double* __restrict__ v_shaped, int V,
+                                                            double* __restrict__ j_rest) {
+  __shared__ double lds[kBlock];
+  const int j = blockIdx.x;
+  double s[3] = {0.0, 0.0, 0.0};
+  for (int v = threadIdx.x; v < V; v += kBlock) {
+    const double w = (double)J_regressor[(int64_t)j * V + v];
+    s[0] = s[0] + w * v_shaped[3 * (int64_t)v];
+    s[1] = s[1] + w * v_shaped[3 * (int64_t)v + 1];
+    s[2] = s[2] + w * v_shaped[3 * (int64_t)v + 2];
+  }
+  for (int c = 0; c < 3; ++c) {
+    const double r = block_sum(s[c], lds);
+    if (threadIdx.x == 0) j_rest[3 * j + c] = r;
+    __syncthreads();
+  }
+}
+
+// ---- pose stage ----
+struct Rod { double a, x, y, z, s, c; };
+
+__device__ __forceinline__ Rod rod_of(const double* r) {
+  const double e = 1e-8;
+  const double x0 = r[0] + e, y0 = r[1] + e, z0 = r[2] + e;
+  Rod q;
+  q.a = sqrt((x0 * x0 + y0 * y0) + z0 * z0);
+  q.x = r[0] / q.a; q.y = r[1] / q.a; q.z = r[2] / q.a;
+  q.s = sin(q.a); q.c = cos(q.a);
+  return q;
+}
+
+// K = [[0,-z,y],[z,0,-x],[-y,x,0]] and K K of the unit-ish direction
+__device__ __forceinline__ void skew(const Rod& q, double* K, double* K2) {
+  K[0] = 0.0; K[1] = -q.z; K[2] = q.y; K[3] = q.z; K[4] = 0.0; K[5] = -q.x; K[6] = -q.y; K[7] = q.x; K[8] = 0.0;
+  K2[0] = -(q.y * q.y + q.z * q.z); K2[1] = q.x * q.y; K2[2] = q.x * q.z;
+  K2[3] = q.x * q.y; K2[4] = -(q.x * q.x + q.z * q.z); K2[5] = q.y * q.z;
+  K2[6] = q.x * q.z; K2[7] = q.y * q.z; K2[8] = -(q.x * q.x + q.y * q.y);
+}
+
+__device__ __forceinline__ void rodrigues(const double* r, double* R) {
+  const Rod q = rod_of(r);
+  double K[9], K2[9];
+  skew(q, K, K2);
+  const double c1 = 1.0 - q.c;
+#pragma unroll
+  for (int e = 0; e < 9; ++e) R[e] = ((e % 4 == 0) ? 1.0 : 0.0) + (q.s * K[e] + c1 * K2[e]);
+}
+
+// dL/dr from dL/dR, the +1e-8 inside the norm included
+__device__ __forceinline__ void rodrigues_backward(const double* r, const double* dR, double* dr) {
+  const Rod q = rod_of(r);
+  double K[9], K2[9], dK[9];
+  skew(q, K, K2);
+  const double c1 = 1.0 - q.c;
+  double da = 0.0;
+#pragma unroll
+  for (int e = 0; e < 9; ++e) da = da + dR[e] * (q.c * K[e] + q.s * K2[e]);
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      double m = 0.0;                                     // (dR K^T + K^T dR)[i][j]
+#pragma unroll
+      for (int k = 0; k < 3; ++k) m = m + (dR[3 * i + k] * K[3 * j + k] + K[3 * k + i] * dR[3 * k + j]);
+      dK[3 * i + j] = q.s * dR[3 * i + j] + c1 * m;
+    }
+  const double dd[3] = {dK[7] - dK[5], dK[2] - dK[6], dK[3] - dK[1]};
+  const double dat = da - ((dd[0] * r[0] + dd[1] * r[1]) + dd[2] * r[2]) / (q.a * q.a);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) dr[k] = dd[k] / q.a + dat * ((r[k] + 1e-8) / q.a);
+}
+
+// R [J,9] and the chain G [J,3x4] in LDS from pose [3J] (LDS) and the rest joints; serial in the joint index (parent[i] < i)
+__device__ __forceinline__ void pose_chain(const double* pose, const double* __restrict__ j_rest, const Tree& tree, int J, double* R, double* G) {
+  const int t = threadIdx.x;
+  if (t < J) rodrigues(pose + 3 * t, R + 9 * t);
+  __syncthreads();
+  if (t < 12) G[t] = (t % 4 < 3) ? R[3 * (t / 4) + t % 4] : j_rest[t / 4];
+  __syncthreads();
+  for (int i = 1; i < J; ++i) {
+    const int p = tree.parent[i];
+    if (t < 12) {
+      const int r = t / 4, c = t % 4;
+      const double* Gp = G + 12 * p + 4 * r;
+      double v;
+      if (c < 3) {
+        v = (Gp[0] * R[9 * i + c] + Gp[1] * R[9 * i + 3 + c]) + Gp[2] * R[9 * i + 6 + c];
+      } else {
+        const double tx = j_rest[3 * i] - j_rest[3 * p], ty = j_rest[3 * i + 1] - j_rest[3 * p + 1], tz = j_rest[3 * i + 2] - j_rest[3 * p + 2];
+        v = ((Gp[0] * tx + Gp[1] * ty) + Gp[2] * tz) + Gp[3];
+      }
+      G[12 * i + t] = v;
+    }
+    __syncthreads();
+  }
+}
+
+struct PoseArgs {
+  const float* theta;
+  const float* comps;     // [2, n_pca, hd]
+  const float* mean;      // [3J] or null
+  const float* transl;    // [3] or null
+  const double* j_rest;
+  int J, hd, n_pca;
+  Tree tree;
+  double* s_pose;         // saved [3J]
+  double* s_A;            // saved [J,12]
+  double* feat;           // workspace [9 (J - 1)]
+  float* joints;          // [J,3]
+  float* full_pose;       // [3J] or null
+};
+
+__global__ __launch_bounds__(kBlock) void smplx_pose_kernel(PoseArgs a) {
+  __shared__ double pose[3 * kMaxJ], R[9 * kMaxJ], G[12 * kMaxJ];
+  const int t = threadIdx.x, J = a.J;
+  const int nb = a.n_pca > 0 ? 3 * J - 2 * a.hd : 3 * J;
+  for (int k = t; k < 3 * J; k += kBlock) {
+    double v;
+    if (k < nb) {
+      v = (double)a.theta[k];
+    } else {
+      const int h = (k - nb) / a.hd, kk = (k - nb) % a.hd;
+      v = 0.0;
+      for (int i = 0; i < a.n_pca; ++i) v = v + (double)a.theta[nb + h * a.n_pca + i] * (double)a.comps[(int64_t)(h * a.n_pca + i) * a.hd + kk];
+    }
+    if (a.mean) v = v + (double)a.mean[k];
+    pose[k] = v;
+    a.s_pose[k] = v;
+    if (a.full_pose) a.full_pose[k] = (float)v;
+  }
+  __syncthreads();
+  pose_chain(pose, a.j_rest, a.tree, J, R, G);
+  for (int q = t; q < 12 * J; q += kBlock) {
+    const int i = q / 12, r = (q % 12) / 4, c = q % 4;
+    const double* Gi = G + 12 * i + 4 * r;
+    double v = Gi[c];
+    if (c == 3) {
+      v = v - ((Gi[0] * a.j_rest[3 * i] + Gi[1] * a.j_rest[3 * i + 1]) + Gi[2] * a.j_rest[3 * i + 2]);
+      a.joints[3 * i + r] = (float)(Gi[3] + (a.transl ? (double)a.transl[r] : 0.0));
+    }
+    a.s_A[q] = v;
+  }
+  for (int q = t; q < 9 * (J - 1); q += kBlock) a.feat[q] = R[9 + q] - ((q % 9) % 4 == 0 ? 1.0 : 0.0);
+}
+
+// ---- skinning stage ----
+// partial pose offsets: part[s][i] = sum over the rows p of split s (ascending) of feat[p] posedirs[p][i]
+__global__ __launch_bounds__(kBlock) void smplx_offsets_kernel(const float* __restrict__ posedirs, const double* __restrict__ feat, int P, int n3,
+                                                              int rows, double* __restrict__ part) {
+  __shared__ double f[kMaxRows];
+  const int s = blockIdx.y;
+  const int p0 = s * rows, p1 = min(P, p0 + rows);
+  for (int p = p0 + threadIdx.x; p < p1; p += kBlock) f[p - p0] = feat[p];
+  __syncthreads();
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n3) return;
+  double acc = 0.0;
+  const float* col = posedirs + i;
+#pragma unroll 8
+  for (int p = p0; p < p1; ++p) acc = acc + f[p - p0] * (double)col[(int64_t)p * n3];
+  part[(int64_t)s * n3 + i] = acc;
+}
+
+struct SkinArgs {
+  const float* weights;     // [V,J]
+  const double* A;          // [J,12]
+  const double* v_shaped;   // [V,3]
+  const double* part;       // [kPSplit][3V]
+  const float* transl;      // [3] or null
+  int V, J;
+  double* v_posed;          // saved [V,3]
+  float* vertices;          // [V,3]
+};
+
+// the weights of a tile of vertices (one contiguous run of the [V,J] table) and the J transforms into LDS
+__device__ __forceinline__ int stage_tile(const float* __restrict__ weights, const double* __restrict__ A, int V, int J, float* Wt, double* Al) {
+  const int v0 = blockIdx.x * kTile, n = min(kTile, V - v0);
+  const float* src = weights + (int64_t)v0 * J;
+  for (int q = threadIdx.x; q < n * J; q += kTile) Wt[q] = src[q];
+  for (int q = threadIdx.x; q < 12 * J; q += kTile) Al[q] = A[q];
+  __syncthreads();
+  return n;
+}
+
+__device__ __forceinline__ void blend(const float* w, const double* Al, int J, double* T) {
+#pragma unroll
+  for (int e = 0; e < 12; ++e) T[e] = 0.0;
+  for (int j = 0; j < J; ++j) {
+    const double wj = (double)w[j];
+#pragma unroll
+    for (int e = 0; e < 12; ++e) T[e] = T[e] + wj * Al[12 * j + e];
+  }
+}
+
+__global__ __launch_bounds__(kTile) void smplx_skin_kernel(SkinArgs a) {
+  __shared__ float Wt[kTile * kMaxJ];
+  __shared__ double Al[12 * kMaxJ];
+  const int n = stage_tile(a.weights, a.A, a.V, a.J, Wt, Al);
+  const int t = threadIdx.x;
+  if (t >= n) return;
+  const int64_t v = (int64_t)blockIdx.x * kTile + t, n3 = 3 * (int64_t)a.V;
+  double vp[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    double off = 0.0;
+    for (int s = 0; s < kPSplit; ++s) off = off + a.part[s * n3 + 3 * v + c];
+    vp[c] = a.v_shaped[3 * v + c] + off;
+    a.v_posed[3 * v + c] = vp[c];
+  }
+  double T[12];
+  blend(Wt + t * a.J, Al, a.J, T);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const double x = ((T[4 * c] * vp[0] + T[4 * c + 1] * vp[1]) + T[4 * c + 2] * vp[2]) + T[4 * c + 3];
+    a.vertices[3 * v + c] = (float)(x + (a.transl ? (double)a.transl[c] : 0.0));
+  }
+}
+
+// ---- backward ----
+struct SkinBwdArgs {
+  const float* weights;
+  const double* A;
+  const double* v_posed;
+  const float* grad;        // dL/dvertices [V,3]
+  int V, J;
+  double* gvp;              // workspace [V,3]: T[:3,:3]^T g
+  double* dA_part;          // workspace [blocks][12 J + 3]: the block's share of dL/dA, then of dL/dtransl
+};
+
+__global__ __launch_bounds__(kTile) void smplx_skin_bwd_kernel(SkinBwdArgs a) {
+  __shared__ float Wt[kTile * kMaxJ];
+  __shared__ double Al[12 * kMaxJ];
+  __shared__ double gl[3 * kTile], vl[4 * kTile];
+  const int n = stage_tile(a.weights, a.A, a.V, a.J, Wt, Al);
+  const int t = threadIdx.x;
+  if (t < n) {
+    const int64_t v = (int64_t)blockIdx.x * kTile + t;
+    const double g[3] = {(double)a.grad[3 * v], (double)a.grad[3 * v + 1], (double)a.grad[3 * v + 2]};
+    double T[12];
+    blend(Wt + t * a.J, Al, a.J, T);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      a.gvp[3 * v + c] = (T[c] * g[0] + T[4 + c] * g[1]) + T[8 + c] * g[2];
+      gl[3 * t + c] = g[c];
+      vl[4 * t + c] = a.v_posed[3 * v + c];
+    }
+    vl[4 * t + 3] = 1.0;
+  }
+  __syncthreads();
+  const int nq = 12 * a.J + 3;
+  double* out = a.dA_part + (int64_t)blockIdx.x * nq;
+  for (int q = t; q < nq; q += kTile) {
+    double acc = 0.0;
+    if (q < 12 * a.J) {
+      const int j = q / 12, r = (q % 12) / 4, c = q % 4;
+      for (int u = 0; u < n; ++u) acc = acc + ((double)Wt[u * a.J + j] * gl[3 * u + r]) * vl[4 * u + c];
+    } else {
+      const int r = q - 12 * a.J;
+      for (int u = 0; u < n; ++u) acc = acc + gl[3 * u + r];
+    }
+    out[q] = acc;
+  }
+}
+
+// dL/dfeature_p = <posedirs[p, :], gvp>: one workgroup per row
+__global__ __launch_bounds__(kBlock) void smplx_feature_bwd_kernel(const float* __restrict__ posedirs, const double* __restrict__ gvp, int n3,
+                                                                  double* __restrict__ dfeat) {
+  __shared__ double lds[kBlock];
+  const float* row = posedirs + (int64_t)blockIdx.x * n3;
+  double acc = 0.0;
+#pragma unroll 4
+  for (int i = threadIdx.x; i < n3; i += kBlock) acc = acc + (double)row[i] * gvp[i];
+  const double s = block_sum(acc, lds);
+  if (threadIdx.x == 0) dfeat[blockIdx.x] = s;
+}
+
+struct PoseBwdArgs {
+  const double* s_pose;
+  const double* j_rest;
+  const float* comps;
+  const double* dA_part;
+  const double* dfeat;
+  int J, hd, n_pca, nblk;
+  Tree tree;
+  float* grad_theta;
+  float* grad_transl;
+};
+
+__global__ __launch_bounds__(kBlock) void smplx_pose_bwd_kernel(PoseBwdArgs a) {
+  __shared__ double pose[3 * kMaxJ], R[9 * kMaxJ], G[12 * kMaxJ], dG[12 * kMaxJ], dR[9 * kMaxJ];
+  const int t = threadIdx.x, J = a.J;
+  for (int k = t; k < 3 * J; k += kBlock) pose[k] = a.s_pose[k];
+  __syncthreads();
+  pose_chain(pose, a.j_rest, a.tree, J, R, G);
+  // dL/dA and dL/dtransl: the workgroups' shares in block order; dA into G's place is not possible (G is needed), so into dR/dG
+  const int nq = 12 * J + 3;
+  double* dA = dG;                                        // dG is built from dA in place below
+  for (int q = t; q < nq; q += kBlock) {
+    double acc = 0.0;
+    for (int b = 0; b < a.nblk; ++b) acc = acc + a.dA_part[(int64_t)b * nq + q];
+    if (q < 12 * J) dA[q] = acc;
+    else a.grad_transl[q - 12 * J] = (float)acc;
+  }
+  __syncthreads();
+  // A = [G.R | G.t - G.R J]: dG.t = dA.t, dG.R = dA.R - dA.t J^T   (each entry reads its own row's dA.t, which is not rewritten)
+  for (int q = t; q < 12 * J; q += kBlock) {
+    const int i = q / 12, r = (q % 12) / 4, c = q % 4;
+    if (c < 3) dG[q] = dA[q] - dA[12 * i + 4 * r + 3] * a.j_rest[3 * i + c];
+  }
+  __syncthreads();
+  for (int i = J - 1; i >= 1; --i) {
+    const int p = a.tree.parent[i];
+    if (t < 9) {                                          // dR_i = G_p.R^T dG_i.R + dL/dfeature
+      const int r = t / 3, c = t % 3;
+      double v = (G[12 * p + r] * dG[12 * i + c] + G[12 * p + 4 + r] * dG[12 * i + 4 + c]) + G[12 * p + 8 + r] * dG[12 * i + 8 + c];
+      dR[9 * i + t] = v + a.dfeat[9 * (i - 1) + t];
+    } else if (t >= 16 && t < 28) {                       // dG_p.R += dG_i.R R_i^T + dG_i.t t_i^T;  dG_p.t += dG_i.t
+      const int e = t - 16, r = e / 4, c = e % 4;
+      const double* di = dG + 12 * i + 4 * r;
+      double add;
+      if (c < 3) {
+        const double tc = a.j_rest[3 * i + c] - a.j_rest[3 * p + c];
+        add = ((di[0] * R[9 * i + 3 * c] + di[1] * R[9 * i + 3 * c + 1]) + di[2] * R[9 * i + 3 * c + 2]) + di[3] * tc;
+      } else {
+        add = di[3];
+      }
+      dG[12 * p + e] = dG[12 * p + e] + add;
+    }
+    __syncthreads();
+  }
+  if (t < 9) dR[t] = dG[4 * (t / 3) + t % 3];
+  __syncthreads();
+  double* dpose = G;                                      // the chain is no longer needed
+  if (t < J) {
+    double dr[3];
+    rodrigues_backward(pose + 3 * t, dR + 9 * t, dr);
+    dpose[3 * t] = dr[0]; dpose[3 * t + 1] = dr[1]; dpose[3 * t + 2] = dr[2];
+  }
+  __syncthreads();
+  const int nb = a.n_pca > 0 ? 3 * J - 2 * a.hd : 3 * J;
+  for (int k = t; k < nb; k += kBlock) a.grad_theta[k] = (float)dpose[k];
+  for (int q = t; q < 2 * a.n_pca; q += kBlock) {           // the hand components transposed
+    const int h = q / a.n_pca;
+    double acc = 0.0;
+    for (int kk = 0; kk < a.hd; ++kk) acc = acc + (double)a.comps[(int64_t)q * a.hd + kk] * dpose[nb + h * a.hd + kk];
+    a.grad_theta[nb + q] = (float)acc;
+  }
+}
+
+// ---- extra joints ----
+__global__ __launch_bounds__(kBlock) void smplx_gather_kernel(const float* __restrict__ vertices, const float* __restrict__ transl,
+                                                             const int32_t* __restrict__ idx, const float* __restrict__ w, int V, int E,
+                                                             float* __restrict__ out) {
+  const int q = blockIdx.x * kBlock + threadIdx.x;
+  if (q >= 3 * E) return;
+  const int e = q / 3, c = q % 3;
+  const double tr = transl ? (double)transl[c] : 0.0;
+  double acc = 0.0;
+  for (int i = 0; i < 3; ++i) {
+    const int v = idx[3 * e + i];
+    const double x = (v >= 0 && v < V) ? (double)vertices[3 * (int64_t)v + c] - tr : (double)NAN;   // an index outside the mesh is not followed
+    acc = acc + (double)w[3 * e + i] * x;
+  }
+  out[q] = (float)(acc + tr);
+}
+
+size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+struct Layout {
+  size_t feat, part, gvp, dA_part, dfeat, total;      // workspace
+  size_t v_shaped, j_rest, shape_total;               // shape state
+  size_t s_pose, s_A, s_vposed, saved_total;          // saved by a forward for its backward
+  int P, rows, nblk, nb3;
+};
+
+Layout layout(int V, int J) {
+  Layout L = {};
+  const size_t n3 = (size_t)3 * V, d = sizeof(double);
+  L.P = 9 * (J - 1);
+  L.rows = (L.P + kPSplit - 1) / kPSplit;
+  L.nblk = (V + kTile - 1) / kTile;
+  L.nb3 = (int)((n3 + kBlock - 1) / kBlock);
+  size_t at = 0;
+  L.feat = at;    at = up16(at + (size_t)(L.P > 0 ? L.P : 1) * d);
+  L.part = at;    at = up16(at + (size_t)kPSplit * n3 * d);
+  L.gvp = at;     at = up16(at + n3 * d);
+  L.dA_part = at; at = up16(at + (size_t)L.nblk * (12 * J + 3) * d);
+  L.dfeat = at;   at = up16(at + (size_t)(L.P > 0 ? L.P : 1) * d);
+  L.total = at;
+  at = 0;
+  L.v_shaped = at; at = up16(at + n3 * d);
+  L.j_rest = at;   at = up16(at + (size_t)3 * J * d);
+  L.shape_total = at;
+  at = 0;
+  L.s_pose = at;   at = up16(at + (size_t)3 * J * d);
+  L.s_A = at;      at = up16(at + (size_t)12 * J * d);
+  L.s_vposed = at; at = up16(at + n3 * d);
+  L.saved_total = at;
+  return L;
+}
+
+constexpr int kMaxV = 1 << 24;
+constexpr int kMaxNB = 1024;
+
+bool sizes_ok(int V, int J) { return V >= 1 && V <= kMaxV && J >= 1 && J <= kMaxJ; }
+
+int check_common(const char* who, int V, int J, int hand_dim, int n_pca, const int32_t* parents, Tree& tree) {
+  if (!sizes_ok(V, J)) return fail(COMA_E_INVALID, "%s: V=%d must lie in [1, %d] and J=%d in [1, %d]", who, V, kMaxV, J, kMaxJ);
+  if (n_pca < 0 || n_pca > kMaxPca) return fail(COMA_E_INVALID, "%s: n_pca=%d outside [0, %d]", who, n_pca, kMaxPca);
+  if (hand_dim < 0 || hand_dim % 3 != 0 || 2 * hand_dim > 3 * (J - 1))
+    return fail(COMA_E_INVALID, "%s: hand_dim=%d must be a multiple of 3 with 2 hand_dim <= 3 (J - 1) = %d", who, hand_dim, 3 * (J - 1));
+  for (int i = 0; i < kMaxJ; ++i) tree.parent[i] = 0;
+  for (int i = 1; i < J; ++i) {
+    if (parents[i] < 0 || parents[i] >= i) return fail(COMA_E_INVALID, "%s: parent %d of joint %d outside [0, %d)", who, parents[i], i, i);
+    tree.parent[i] = parents[i];
+  }
+  return COMA_OK;
+}
+
+int check_buffer(const char* who, const char* what, const void* p, size_t have, size_t need) {
+  if (have < need) return fail(COMA_E_INVALID, "%s: %s of %zu bytes, %zu needed", who, what, have, need);
+  if (((uintptr_t)p & 15) != 0) return fail(COMA_E_INVALID, "%s: %s must be 16-byte aligned", who, what);
+  return COMA_OK;
+}
+
+}  // namespace
+}  // namespace coma
+
+using namespace coma;
+
+extern "C" size_t coma_smplx_workspace_bytes(int V, int J) { return sizes_ok(V, J) ? layout(V, J).total : 0; }
+extern "C" size_t coma_smplx_shape_state_bytes(int V, int J) { return sizes_ok(V, J) ? layout(V, J).shape_total : 0; }
+extern "C" size_t coma_smplx_saved_bytes(int V, int J) { return sizes_ok(V, J) ? layout(V, J).saved_total : 0; }
+
+extern "C" int coma_smplx_shape_f32(const float* v_template, const float* shapedirs, const float* coefficients, const float* J_regressor, int V,
+                                    int J, int NB, void* shape_state, size_t shape_state_bytes, void* stream) {
+  const char* who = "coma_smplx_shape_f32";
+  if (!v_template || !shapedirs || !coefficients || !J_regressor || !shape_state) return fail(COMA_E_INVALID, "%s: null pointer", who);
+  if (!sizes_ok(V, J)) return fail(COMA_E_INVALID, "%s: V=%d must lie in [1, %d] and J=%d in [1, %d]", who, V, kMaxV, J, kMaxJ);
+  if (NB < 1 || NB > kMaxNB) return fail(COMA_E_INVALID, "%s: NB=%d outside [1, %d]", who, NB, kMaxNB);
+  const Layout L = layout(V, J);
+  if (int rc = check_buffer(who, "shape state", shape_state, shape_state_bytes, L.shape_total)) return rc;
+  char* st = (char*)shape_state;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(smplx_shape_kernel, dim3(L.nb3), dim3(kBlock), 0, s, v_template, shapedirs, coefficients, 3 * V, NB, (double*)(st + L.v_shaped));
+  hipLaunchKernelGGL(smplx_jrest_kernel, dim3(J), dim3(kBlock), 0, s, J_regressor, (const double*)(st + L.v_shaped), V, (double*)(st + L.j_rest));
+  return check_launch(who);
+}
+
+extern "C" int coma_smplx_forward_f32(const float* theta, const float* transl, const float* posedirs, const float* weights, const int32_t* parents,
+                                      const float* hand_components, const float* pose_mean, int V, int J, int hand_dim, int n_pca,
+                                      const void* shape_state, float* vertices, float* joints, float* full_pose, void* saved, size_t saved_bytes,
+                                      void* workspace, size_t workspace_bytes, void* stream) {
+  const char* who = "coma_smplx_forward_f32";
+  if (!theta || !posedirs || !weights || !parents || !shape_state || !vertices || !joints || !saved || !workspace)
+    return fail(COMA_E_INVALID, "%s: null pointer", who);
+  if (n_pca > 0 && hand_dim > 0 && !hand_components) return fail(COMA_E_INVALID, "%s: null pointer (hand_components with n_pca > 0)", who);
+  PoseArgs pa = {};
+  if (int rc = check_common(who, V, J, hand_dim, n_pca, parents, pa.tree)) return rc;
+  const Layout L = layout(V, J);
+  if (int rc = check_buffer(who, "saved state", saved, saved_bytes, L.saved_total)) return rc;
+  if (int rc = check_buffer(who, "workspace", workspace, workspace_bytes, L.total)) return rc;
+  if (((uintptr_t)shape_state & 15) != 0) return fail(COMA_E_INVALID, "%s: shape state must be 16-byte aligned", who);
+  const char* st = (const char*)shape_state;
+  char* sv = (char*)saved;
+  char* ws = (char*)workspace;
+  hipStream_t s = (hipStream_t)stream;
+  pa.theta = theta; pa.comps = hand_components; pa.mean = pose_mean; pa.transl = transl; pa.j_rest = (const double*)(st + L.j_rest);
+  pa.J = J; pa.hd = hand_dim; pa.n_pca = n_pca; pa.s_pose = (double*)(sv + L.s_pose); pa.s_A = (double*)(sv + L.s_A);
+  pa.feat = (double*)(ws + L.feat); pa.joints = joints; pa.full_pose = full_pose;
+  hipLaunchKernelGGL(smplx_pose_kernel, dim3(1), dim3(kBlock), 0, s, pa);
+  if (L.P > 0)
+    hipLaunchKernelGGL(smplx_offsets_kernel, dim3(L.nb3, kPSplit), dim3(kBlock), 0, s, posedirs, (const double*)(ws + L.feat), L.P, 3 * V, L.rows,
+                       (double*)(ws + L.part));
+  else if (hipMemsetAsync(ws + L.part, 0, (size_t)kPSplit * 3 * V * sizeof(double), s) != hipSuccess)
+    return fail(COMA_E_LAUNCH, "%s: memset failed", who);
+  SkinArgs sa = {};
+  sa.weights = weights; sa.A = pa.s_A; sa.v_shaped = (const double*)(st + L.v_shaped); sa.part = (const double*)(ws + L.part); sa.transl = transl;
+  sa.V = V; sa.J = J; sa.v_posed = (double*)(sv + L.s_vposed); sa.vertices = vertices;
+  hipLaunchKernelGGL(smplx_skin_kernel, dim3(L.nblk), dim3(kTile), 0, s, sa);
+  return check_launch(who);
+}
+
+extern "C" int coma_smplx_backward_f32(const float* grad_vertices, const float* posedirs, const float* weights, const int32_t* parents,
+                                       const float* hand_components, int V, int J, int hand_dim, int n_pca, const void* shape_state,
+                                       const void* saved, size_t saved_bytes, float* grad_theta, float* grad_transl, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+  const char* who = "coma_smplx_backward_f32";
+  if (!grad_vertices || !posedirs || !weights || !parents || !shape_state || !saved || !grad_theta || !grad_transl || !workspace)
+    return fail(COMA_E_INVALID, "%s: null pointer", who);
+  if (n_pca > 0 && hand_dim > 0 && !hand_components) return fail(COMA_E_INVALID, "%s: null pointer (hand_components with n_pca > 0)", who);
+  PoseBwdArgs pb = {};
+  if (int rc = check_common(who, V, J, hand_dim, n_pca, parents, pb.tree)) return rc;
+  const Layout L = layout(V, J);
+  if (int rc = check_buffer(who, "saved state", saved, saved_bytes, L.saved_total)) return rc;
+  if (int rc = check_buffer(who, "workspace", workspace, workspace_bytes, L.total)) return rc;
+  if (((uintptr_t)shape_state & 15) != 0) return fail(COMA_E_INVALID, "%s: shape state must be 16-byte aligned", who);
+  const char* st = (const char*)shape_state;
+  const char* sv = (const char*)saved;
+  char* ws = (char*)workspace;
+  hipStream_t s = (hipStream_t)stream;
+  SkinBwdArgs sb = {};
+  sb.weights = weights; sb.A = (const double*)(sv + L.s_A); sb.v_posed = (const double*)(sv + L.s_vposed); sb.grad = grad_vertices;
+  sb.V = V; sb.J = J; sb.gvp = (double*)(ws + L.gvp); sb.dA_part = (double*)(ws + L.dA_part);
+  hipLaunchKernelGGL(smplx_skin_bwd_kernel, dim3(L.nblk), dim3(kTile), 0, s, sb);
+  if (L.P > 0)
+    hipLaunchKernelGGL(smplx_feature_bwd_kernel, dim3(L.P), dim3(kBlock), 0, s, posedirs, (const double*)(ws + L.gvp), 3 * V, (double*)(ws + L.dfeat));
+  pb.s_pose = (const double*)(sv + L.s_pose); pb.j_rest = (const double*)(st + L.j_rest); pb.comps = hand_components;
+  pb.dA_part = sb.dA_part; pb.dfeat = (const double*)(ws + L.dfeat); pb.J = J; pb.hd = hand_dim; pb.n_pca = n_pca; pb.nblk = L.nblk;
+  pb.grad_theta = grad_theta; pb.grad_transl = grad_transl;
+  hipLaunchKernelGGL(smplx_pose_bwd_kernel, dim3(1), dim3(kBlock), 0, s, pb);
+  return check_launch(who);
+}
+
+extern "C" int coma_smplx_extra_joints_f32(const float* vertices, const float* transl, const int32_t* vertex_index, const float* vertex_weight,
+                                           int V, int E, float* out, void* stream) {
+  const char* who = "coma_smplx_extra_joints_f32";
+  if (E == 0) return COMA_OK;
+  if (!vertices || !vertex_index || !vertex_weight || !out) return fail(COMA_E_INVALID, "%s: null pointer", who);
+  if (V < 1 || V > kMaxV || E < 0 || E > kMaxV) return fail(COMA_E_INVALID, "%s: bad sizes V=%d E=%d", who, V, E);
+  hipLaunchKernelGGL(smplx_gather_kernel, dim3((3 * E + kBlock - 1) / kBlock), dim3(kBlock), 0, (hipStream_t)stream, vertices, transl, vertex_index,
+                     vertex_weight, V, E, out);
+  return check_launch(who);
+}

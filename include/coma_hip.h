@@ -384,6 +384,61 @@ int coma_app_objective_f32(const float* verts, const int32_t* faces, const int32
                            float* terms, float* grad_orientation, float* grad_contact, void* workspace, size_t workspace_bytes,
                            void* stream);
 
+/* The SMPL-X body model: linear blend skinning of a V-vertex template over a J-joint tree, forward and backward (batch size 1).
+ * replaces: the third-party `smplx` package behind the `body_model` hook of src/application/optimize.py (every iteration, forward
+ *           and backward) and src/generation/optimize_depth.py (once per item), i.e. lbs / batch_rodrigues / batch_rigid_transform and
+ *           the assembly of SMPLX.forward (use_face_contour=False, no joint mapper).
+ * PINNED against that package's own lbs and SMPLX class executed on the CPU in f64 (tests/golden/smplx_golden.npz), through the f64
+ * restatement tests/smplx_ref.py.  Rule set:
+ *   parameters     theta f32 [NT].  n_pca > 0: theta = [3 J - 2 hand_dim axis-angle entries | n_pca left | n_pca right] and the hands'
+ *                  axis-angles are coefficients x hand_components (f32 [2, n_pca, hand_dim], left then right); n_pca == 0: theta is the
+ *                  3 J axis-angle entries themselves.  SMPL-X: J = 55, hand_dim = 45, the leading 75 entries are global_orient 3 |
+ *                  body_pose 63 | jaw 3 | leye 3 | reye 3.  pose = assembled theta + pose_mean (f32 [3J], may be NULL = zeros).
+ *   Rodrigues      per joint r: angle = |r + 1e-8| (the epsilon added to EACH component before the norm), dir = r / angle,
+ *                  K = skew(dir), R = I + sin(angle) K + (1 - cos(angle)) K K.  Finite, with a finite derivative, at r = 0.
+ *   shape stage    v_shaped = v_template + shapedirs . coefficients (shapedirs f32 [V,3,NB], coefficients f32 [NB] = betas followed
+ *                  by expression), J_rest = J_regressor (f32 [J,V]) v_shaped.  Kept in f64 in `shape_state`; re-run only when the
+ *                  coefficients change.
+ *   pose stage     feature = (R_i - I) for i = 1 .. J-1 flattened, P = 9 (J - 1).  G_0 = [R_0 | J_0], G_i = G_parent(i) [R_i | J_i -
+ *                  J_parent(i)] in ascending i; joints_i = G_i.t (+ transl); A_i = [G_i.R | G_i.t - G_i.R J_i].  One workgroup.
+ *   skinning       v_posed = v_shaped + sum_p feature_p posedirs[p, 3v + c] (posedirs f32 [P, 3V], the model's own layout; summed in
+ *                  eight ascending runs of rows whose results are added in ascending order), T = sum_j weights[v, j] A_j (weights
+ *                  f32 [V,J], j ascending), vertex = T [v_posed, 1] (+ transl).
+ *   backward       from g = dL/dvertices f32 [V,3]: dL/dtransl = sum_v g_v; dL/dA_j = sum_v weights[v,j] g_v (x) [v_posed, 1];
+ *                  g_vposed = T.R^T g_v; dL/dfeature_p = <posedirs[p, :], g_vposed>; the chain in descending i; the derivative of
+ *                  the Rodrigues formula with the 1e-8 inside the norm; the hand components transposed.  NO gradient with respect
+ *                  to betas, expression, or through the joints output.  Sums over vertices: per workgroup of 128 vertices in
+ *                  ascending order, then over the workgroups in ascending order; the P dot products as 256 strided partial sums and
+ *                  a tree lds[t] + lds[t + h], h = 128 ... 1.  No floating-point atomics: two calls give the same bits.
+ *   extra joints   out_e = sum_{i<3} vertex_weight[e,i] (vertex[vertex_index[e,i]] - transl) + transl: a vertex pick is index
+ *                  (i, i, i) with weights (1, 0, 0), a static landmark a face's three vertices with its barycentric weights.  The
+ *                  caller lays the result behind the J posed joints: [J | vertex picks | landmarks].  No gradient.
+ *   precision      inputs and outputs are f32; every stage is evaluated in f64 (the work is bandwidth- and latency-bound), so the
+ *                  outputs are the f32 rounding of the rule set.
+ * All pointers are device pointers except `parents` (HOST, i32 [J], read during the call; parents[0] is ignored, parents[i] must lie
+ * in [0, i) for i > 0).  shape_state / saved / workspace: coma_smplx_{shape_state,saved,workspace}_bytes(V, J) bytes, 16-byte aligned
+ * (0 for sizes the calls refuse).  `saved` is written by a forward and read by ITS backward (one per forward in flight); `workspace`
+ * is scratch shared by all calls on one stream.  vertices f32 [V,3], joints f32 [J,3], full_pose f32 [3J] (may be NULL), grad_theta
+ * f32 [NT], grad_transl f32 [3], transl f32 [3] (may be NULL).  Refused before any launch: a null pointer, V outside [1, 2^24], J
+ * outside [1, 64], NB outside [1, 1024], n_pca outside [0, 64], hand_dim not a multiple of 3 or 2 hand_dim > 3 (J - 1), a bad parent, a
+ * buffer too small or misaligned.  A vertex_index outside [0, V) is not followed and gives NaN.  Forward: 3 launches, backward: 3,
+ * shape: 2, extra joints: 1; caller's stream, no allocation, no host synchronisation. */
+size_t coma_smplx_workspace_bytes(int V, int J);
+size_t coma_smplx_shape_state_bytes(int V, int J);
+size_t coma_smplx_saved_bytes(int V, int J);
+int coma_smplx_shape_f32(const float* v_template, const float* shapedirs, const float* coefficients, const float* J_regressor, int V, int J,
+                         int NB, void* shape_state, size_t shape_state_bytes, void* stream);
+int coma_smplx_forward_f32(const float* theta, const float* transl, const float* posedirs, const float* weights, const int32_t* parents,
+                           const float* hand_components, const float* pose_mean, int V, int J, int hand_dim, int n_pca,
+                           const void* shape_state, float* vertices, float* joints, float* full_pose, void* saved, size_t saved_bytes,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int coma_smplx_backward_f32(const float* grad_vertices, const float* posedirs, const float* weights, const int32_t* parents,
+                            const float* hand_components, int V, int J, int hand_dim, int n_pca, const void* shape_state,
+                            const void* saved, size_t saved_bytes, float* grad_theta, float* grad_transl, void* workspace,
+                            size_t workspace_bytes, void* stream);
+int coma_smplx_extra_joints_f32(const float* vertices, const float* transl, const int32_t* vertex_index, const float* vertex_weight, int V,
+                                int E, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

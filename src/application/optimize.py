@@ -18,7 +18,9 @@ The hooks own their torch arithmetic; the optimiser stays torch.optim.Adam besid
     (utils.vposer), which this repository does not carry -- a clear error says so;
   * angle_prior(body_pose [1,63]) -> tensor, summed.  Default: likewise.
 --use_collision is REFUSED: COAP (a learned occupancy network with a downloaded checkpoint) is unpinned and not reproduced, as in the
-depth stage.  One flag is added: --num_iters (the reference's loop count, 2000, is a literal there).
+depth stage.  Two flags are added: --num_iters (the reference's loop count, 2000, is a literal there) and --body_model {smplx,device}
+(default smplx, the hook described above; device = coma_amd.body_model.DeviceSMPLX, the same model files read with NumPy and the
+skinning and its backward run by the library's own kernels).
 """
 import argparse
 import os
@@ -159,12 +161,26 @@ def build_parser():
     p.add_argument("--scale_factor", type=float, default=0.84)
     p.add_argument("--use_collision", action="store_true", help="refused: COAP is not reproduced")
     p.add_argument("--num_iters", type=int, default=2000, help="Adam iterations (a literal 2000 in the reference)")
+    # absent from the namespace unless given (the parsed defaults stay the reference's parameter set); read through body_model_choice()
+    p.add_argument("--body_model", choices=("smplx", "device"), default=argparse.SUPPRESS,
+                   help="smplx (default): the third-party package (the reference's); device: coma_amd.body_model.DeviceSMPLX on the same model files")
     return p
+
+
+def body_model_choice(args):
+    return getattr(args, "body_model", "smplx")
+
+
+def device_body_model(device="cuda"):
+    from coma_amd.body_model import DeviceSMPLX
+    return DeviceSMPLX.from_file(BODY_MOCAP_PATH, num_pca_comps=45, device=device)
 
 
 def main(args, body_model=None, pose_decoder=None, angle_prior=None):
     if args.use_collision:
         raise SystemExit(COLLISION_REFUSAL)
+    if body_model is None and body_model_choice(args) == "device":
+        body_model = device_body_model()
     return optimize_smpl(supercategory=args.supercategory, category=args.category, coma_path=args.coma_path,
                          asset_downsample_pth=args.asset_downsample_pth, eps=args.eps, principle_vec=[0, 0, 1], sub_principle_vec=[0, 1, 0],
                          reference_object_vertex_index=0, lr=args.lr, body_pose_weight=args.body_pose_weight,

@@ -21,6 +21,9 @@ of the loss.  --asset_seg_dir is accepted and unused, as in the reference.
 Three flags are added: --asset_obj_root (as in initialize_depth.py; OBJ assets only), --volume_resolution (cells along the longer
 side of the collision grid) and --perturb_view_num (the reference restricts the inlier search to the reference view's group of
 `view_num` cameras for perturbed categories, from a table this repository does not carry; unset = all views).
+--body_model {smplx,device} (default smplx: the hook above) and --extra_joint_vertex_ids FILE: `device` runs the body model through
+coma_amd.body_model.DeviceSMPLX; the joints this stage reads include the package's 21 vertex picks, whose id table is not shipped, so
+without the package the ids come from FILE (a JSON list) or the run is refused.
 """
 import argparse
 import os
@@ -52,6 +55,40 @@ def default_body_model(smplx_data, smplx_path):
     import torch
     human = smplx.create(model_path=smplx_path, model_type="smplx", num_pca_comps=45)
     params = {k: torch.as_tensor(np.asarray(v)).float() for k, v in smplx_data.items() if k != "transl"}
+    with torch.no_grad():
+        out = human(**params, return_verts=True, return_full_pose=True)
+    return out.vertices[0].cpu().numpy(), out.joints[0].cpu().numpy()
+
+
+_DEVICE_MODELS = {}        # (smplx_path, device, ids) -> DeviceSMPLX: the model file is read and uploaded once, not per item
+NO_VERTEX_IDS = ("optimize_depth: --body_model device needs the 21 extra-joint vertex ids (nose, eyes, ears, toes, heels, finger tips): the "
+                 "joints this stage reads (coma_amd.depth_opt.BODY_INDICES) include them, the table lives in the `smplx` package, which "
+                 "does not import here, and it is not shipped; pass --extra_joint_vertex_ids FILE (a JSON list of 21 vertex ids)")
+
+
+def load_vertex_ids(pth):
+    """The 21 vertex ids of the package's extra joints, in its order, from a JSON list."""
+    import json
+    with open(pth) as fh:
+        ids = [int(i) for i in json.load(fh)]
+    if len(ids) != 21:
+        raise ValueError(f"{pth}: expected a JSON list of 21 vertex ids, got {len(ids)}")
+    return ids
+
+
+def device_body_model(smplx_data, smplx_path, device="cuda", extra_joint_vertex_ids=None):
+    """default_body_model's contract through coma_amd.body_model.DeviceSMPLX (--body_model device): no third-party package.  Refused
+    when the vertex picks among the joints cannot be had: the stage would read face landmarks in their place."""
+    import torch
+    from coma_amd.body_model import DeviceSMPLX
+    key = (os.path.abspath(smplx_path), str(device), None if extra_joint_vertex_ids is None else tuple(extra_joint_vertex_ids))
+    human = _DEVICE_MODELS.get(key)
+    if human is None:
+        human = DeviceSMPLX.from_file(smplx_path, num_pca_comps=45, device=device, extra_joint_vertex_ids=extra_joint_vertex_ids)
+        if human.extra_joint_source == "landmarks only":
+            raise RuntimeError(NO_VERTEX_IDS)
+        _DEVICE_MODELS[key] = human
+    params = {k: torch.as_tensor(np.asarray(v)).float().to(device) for k, v in smplx_data.items() if k != "transl"}
     with torch.no_grad():
         out = human(**params, return_verts=True, return_full_pose=True)
     return out.vertices[0].cpu().numpy(), out.joints[0].cpu().numpy()
@@ -221,10 +258,17 @@ def build_parser():
     p.add_argument("--asset_obj_root", type=str, default="data", help="directory that holds the dataset folders (3D-FUTURE-model, BEHAVE, ...)")
     p.add_argument("--volume_resolution", type=int, default=512, help="cells along the longer side of the collision grid")
     p.add_argument("--perturb_view_num", type=int, default=None, help="cameras per perturbation group (inlier search stays inside the group)")
+    p.add_argument("--body_model", choices=("smplx", "device"), default="smplx",
+                   help="smplx: the third-party package (the reference's); device: coma_amd.body_model.DeviceSMPLX on the same model files")
+    p.add_argument("--extra_joint_vertex_ids", type=str, default=None,
+                   help="with --body_model device and no `smplx` package: a JSON list of the 21 extra-joint vertex ids, in the package's order")
     return p
 
 
 def main(args, body_model=None):
+    if body_model is None and getattr(args, "body_model", "smplx") == "device":
+        ids = load_vertex_ids(args.extra_joint_vertex_ids) if getattr(args, "extra_joint_vertex_ids", None) else None
+        body_model = lambda smplx_data, smplx_path: device_body_model(smplx_data, smplx_path, extra_joint_vertex_ids=ids)
     for name in ("supercategories", "categories", "prompts", "allowed_viewpoint_prompts"):
         if getattr(args, name) is not None:
             setattr(args, name, [x.lower() for x in getattr(args, name)])
