@@ -125,10 +125,11 @@ int sd_layernorm_f16(const void* x, int64_t rows, int c, float eps, const void* 
 int sd_attention_f16(const void* q, const void* k, const void* vt, void* out, int batch, int heads, int lq, int lk,
                      int d, int ldq, int ldk, int ldv, int ldo, float scale, int vt_perm16, void* stream);
 
-/* Fused attention for WIDE heads (32 <= d <= 512, d a multiple of 32; the VAE mid-block: one head of 512 over 4096 tokens,
+/* Fused attention for WIDE heads (d = 128, 256 or 512, any other head dim is refused; the VAE mid-block: one head of 512 over 4096 tokens,
  * diffusers AttentionBlock reached through self.vae.decode / self.vae.encode, utils/adaptive_mask_inpainting.py:1112, :677-680).
  * Same tensors as sd_attention_f16, except: lk must be a multiple of 64 and V^T must be in the SD_EPI_PERM32_N key order
- * (ldv >= lk).  A wave owns 16 queries on v_mfma_f32_16x16x32_f16 (O^T of 512 x 16 is 128 accumulator registers), K and V^T
+ * (ldv >= lk, a multiple of 8; the pad columns lk..ldv-1 must hold finite values, as for sd_attention_f16).  The same leading-dimension
+ * and 2 GiB slice rules apply; violations return an error, nothing is launched.  A wave owns 16 queries on v_mfma_f32_16x16x32_f16 (O^T of 512 x 16 is 128 accumulator registers), K and V^T
  * tiles of 64 keys alternate through two single-buffered 64 KB LDS regions.  out = softmax(q k^T * scale) v. */
 int sd_attention_wide_f16(const void* q, const void* k, const void* vt, void* out, int batch, int heads, int lq, int lk, int d,
                           int ldq, int ldk, int ldv, int ldo, float scale, void* stream);
