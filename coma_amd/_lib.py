@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # COMA_HIP_LIB=<path>: tuning aid -- load another BUILD of the library (A/B of two builds inside one GPU call: box-to-box spread is larger
 # than most of the effects being measured); the product and the tests use the in-tree library
 LIB_PATH = os.environ.get("COMA_HIP_LIB") or os.path.join(_HERE, "libcoma_hip.so")
-ABI_VERSION = 9                  # = COMA_ABI_VERSION of include/coma_hip.h: bumped with every change of the SIGNATURES table below
+ABI_VERSION = 10                 # = COMA_ABI_VERSION of include/coma_hip.h: bumped with every change of the SIGNATURES table below
 # (not for the text-tower functions: they were only added, no existing signature changed, and a library without them is refused by
 # lib() anyway -- getattr of a missing symbol fails; the same holds for the two coma_sample_eliminate_* functions and for the
 # coma_raster_* / coma_silhouette_iou functions, and for the mesh volume functions of csrc/mesh_volume.hip and the depth-optimisation functions of csrc/depth_opt.hip,
@@ -79,6 +79,7 @@ SIGNATURES = {
     # include/sd_hip.h
     "sd_conv_gemm_f16": (_i, [_vp, _vp]),
     "sd_conv_gemm_workspace_bytes": (C.c_size_t, []),
+    "sd_conv_gemm_describe": (_i, [_vp, _vp]),
     "sd_groupnorm_f16": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp, _vp, _vp]),
     "sd_groupnorm_colstats_f16": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "sd_layernorm_f16": (_i, [_vp, _i64, _i, _f, _vp, _vp, _vp, _vp]),

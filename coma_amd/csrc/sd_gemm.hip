@@ -401,7 +401,8 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, AccQ accq, _Flo
               cs[e] += __shfl_xor(cs[e], mask);
               cq[e] += __shfl_xor(cq[e], mask);
             }
-          if (lane < 4 && !oob) {
+          // (a 32-row tile of the block that lies beyond M owns no slot: M % 32 == 0, so a tile is inside or outside as a whole)
+          if (lane < 4 && !oob && m0 + wr * (TM * 32) + i * 32 < g.M) {
             int slot = (m0 + wr * (TM * 32) + i * 32) >> 5;
             if (g.phase) {               // the consumer's GroupNorm sums the slots of a sample in any order: phase p of sample b owns
               const int per = g.rows_per_batch >> 5, b = slot / per;     // slots [4 b per + p per, 4 b per + (p + 1) per)
@@ -879,8 +880,26 @@ extern "C" int sd_debug_timestamps(unsigned long long* host_dst, int n_blocks) {
 }
 #endif
 
-extern "C" int sd_conv_gemm_f16(const sd_conv_gemm_desc* d_in, void* stream) {
-  if (sd::plan_recording()) return sd::record_conv(d_in);
+// The launch lines of the dispatch: X(line, WM, WN, TN, BK, STAGES, SPREAD, TM, THREADS).  conv_gemm_configure picks the line, the launch
+// switch and the choice record (sd_conv_gemm_describe) are both generated from this list.
+#define GEMM_LINES(X)                      \
+  X(0, 4, 2, 5, 64, 2, true, 2, 512)       \
+  X(1, 2, 2, 2, 64, 2, true, 2, 256)       \
+  X(2, 4, 2, 5, 64, 2, false, 2, 512)      \
+  X(3, 4, 2, 4, 64, 2, true, 2, 512)       \
+  X(4, 4, 2, 4, 64, 2, false, 2, 512)      \
+  X(5, 4, 1, 4, 32, 3, false, 2, 256)      \
+  X(6, 4, 2, 2, 64, 2, false, 2, 512)      \
+  X(7, 4, 2, 5, 64, 2, true, 1, 512)       \
+  X(8, 2, 2, 5, 32, 3, false, 2, 256)      \
+  X(9, 2, 2, 2, 64, 2, false, 2, 256)      \
+  X(10, 2, 2, 2, 32, 4, false, 2, 256)     \
+  X(11, 2, 2, 1, 64, 2, false, 2, 256)     \
+  X(12, 2, 2, 1, 32, 4, false, 2, 256)
+
+// Validation and tile selection of sd_conv_gemm_f16, host only: fills the kernel arguments, the launch line (GEMM_LINES), the grid and the
+// choice record.  Launches nothing and dereferences none of the descriptor's data pointers.
+static int conv_gemm_configure(const sd_conv_gemm_desc* d_in, GemmArgs& g, int& line, dim3& grid, sd_conv_gemm_choice& choice) {
   if (!d_in) return fail(COMA_E_INVALID, "sd_conv_gemm_f16: null descriptor");
   if (d_in->epi & ~SD_EPI_ALL) return fail(COMA_E_INVALID, "sd_conv_gemm_f16: epi 0x%x holds bits outside SD_EPI_ALL", d_in->epi);
   sd_conv_gemm_desc d_copy = *d_in;
@@ -916,7 +935,7 @@ extern "C" int sd_conv_gemm_f16(const sd_conv_gemm_desc* d_in, void* stream) {
   if (d->upsample && (d->stride != 1 || d->taps != 9))
     return fail(COMA_E_INVALID, "sd_conv_gemm_f16: upsample only with 3x3 stride 1");
   const int nz = d->nbatch_z > 0 ? d->nbatch_z : 1;
-  GemmArgs g;
+  g = GemmArgs{};
   g.a0 = (const _Float16*)d->a0; g.a1 = (const _Float16*)d->a1; g.c0 = d->c0; g.c1 = d->c1;
   g.in_h = d->in_h; g.in_w = d->in_w; g.out_h = d->out_h; g.out_w = d->out_w;
   g.taps = d->taps; g.stride = d->stride; g.upsample = d->upsample; g.pad = d->taps == 9 ? d->pad : 0;
@@ -951,6 +970,9 @@ extern "C" int sd_conv_gemm_f16(const sd_conv_gemm_desc* d_in, void* stream) {
     if ((d->epi & (SD_EPI_PERM16_N | SD_EPI_GEGLU)) || d->n % 32 || d->res || d->bias_bn || d->colstats)
       return fail(COMA_E_INVALID, "sd_conv_gemm_f16: SD_EPI_PERM32_N needs n %% 32 == 0 and takes no other column-dependent epilogue");
   }
+  // a column bias would be added to output POSITION p, which holds the product with W row kappa(p): refused rather than left undefined
+  if ((d->epi & (SD_EPI_PERM16_N | SD_EPI_PERM32_N)) && d->bias && !(d->epi & SD_EPI_BIAS_ROWS))
+    return fail(COMA_E_INVALID, "sd_conv_gemm_f16: SD_EPI_PERM16_N / SD_EPI_PERM32_N take a bias only with SD_EPI_BIAS_ROWS");
   g.w = (const _Float16*)d->w; g.bias = (const _Float16*)d->bias; g.bias_bn = (const _Float16*)d->bias_bn;
   g.res = (const _Float16*)d->res; g.ldr = d->ldr > 0 ? d->ldr : d->n;
   g.out = (_Float16*)d->out; g.epi = d->epi;
@@ -999,9 +1021,6 @@ extern "C" int sd_conv_gemm_f16(const sd_conv_gemm_desc* d_in, void* stream) {
   // split-K when the tile grid cannot fill the chip: as many splits as keep every block resident at once (2 per CU,
   // 512 in total -- a partial second round costs more than it buys), at least 384 of K per split
   g.ksplit = 1;
-#ifdef GEMM_DBG
-  if (hipGetSymbolAddress((void**)&g.dbg, HIP_SYMBOL(g_dbg_stamps)) != hipSuccess) return fail(COMA_E_LAUNCH, "sd_conv_gemm_f16: no g_dbg_stamps");
-#endif
   g.partial = (float*)d->workspace;
   g.colstats = (float*)d->colstats;
   g.out_t = (_Float16*)d->out_t; g.n_split = d->n_split; g.ldo_t = d->ldo_t; g.rps = d->rows_per_sample;
@@ -1018,6 +1037,9 @@ extern "C" int sd_conv_gemm_f16(const sd_conv_gemm_desc* d_in, void* stream) {
                      (g.bias_bn && (g.res || g.rows_per_batch % 32 || g.ldbb % 8)) || (long long)(g.M + 512) * g.ldo * 2 >= 0x7fffffffLL ||
                      (g.res && (long long)(g.M + 512) * g.ldr * 2 >= 0x7fffffffLL)))
     return fail(COMA_E_INVALID, "sd_conv_gemm_f16: colstats needs M %% 32 == 0, N %% 8 == 0, 16-byte aligned rows, < 2 GiB tensors, no GEGLU / batching");
+  // the phase slot rule (gemm_epilogue) gives sample b the slots [4 b per, 4 (b + 1) per), per = in_h * in_w / 32: a 32-row block must lie in one sample
+  if (g.colstats && phase && g.rows_per_batch % 32)
+    return fail(COMA_E_INVALID, "sd_conv_gemm_f16: colstats of a phase launch needs in_h * in_w %% 32 == 0");
   // tap-minor K order only where it measured faster: the 320-column tiles with a single N tile (+7 % at 64x64, C = 320; elsewhere the
   // second N tile re-reads A from L2 anyway and the order is neutral to -10 %, profiles/r02_notes.md).  The 8-wave 128 x 320 tile
   // follows the same rule so that a half-batch launch of such a layer (the shared CFG prefix) accumulates in the same order as the
@@ -1035,34 +1057,72 @@ extern "C" int sd_conv_gemm_f16(const sd_conv_gemm_desc* d_in, void* stream) {
   }
   const long long lin_blocks = gx >= 16 ? 8LL * ((gx + 7) / 8) * gy : (long long)gx * gy;   // XCD-banded order (see kernel)
   if (lin_blocks > 0x7fffffffLL) return fail(COMA_E_INVALID, "sd_conv_gemm_f16: grid too large");
-  dim3 grid((unsigned)lin_blocks, (unsigned)(g.ksplit > 1 ? g.ksplit : nz));
-  hipStream_t st = (hipStream_t)stream;
+  grid = dim3((unsigned)lin_blocks, (unsigned)(g.ksplit > 1 ? g.ksplit : nz));
   // DMA issue spread over the K steps of a tile (3x3: +0.5 % of a UNet forward) or in one burst (1x1: +0.6 %) -- both measured inside the
   // captured forward
   const bool spread = d->taps == 9;
-#define GEMM_LAUNCH(WM_, WN_, TN_, BK_, ST_, SP_, TM_, THREADS_)                                                                  \
-  do {                                                                                                                           \
-    if (m16) hipLaunchKernelGGL((conv_gemm_kernel<WM_, WN_, TN_, BK_, ST_, SP_, TM_, true>), grid, dim3(THREADS_), 0, st, g);    \
-    else hipLaunchKernelGGL((conv_gemm_kernel<WM_, WN_, TN_, BK_, ST_, SP_, TM_, false>), grid, dim3(THREADS_), 0, st, g);       \
-  } while (0)
+  if (big && spread) line = 0;
+  else if (wide && deep && spread && !big_geglu && !big256 && !big128 && !mid) line = 1;
+  else if (big) line = 2;
+  else if ((big_geglu || big256) && spread) line = 3;
+  else if (big_geglu || big256) line = 4;
+  else if (tall128) line = 5;
+  else if (big128) line = 6;
+  else if (mid8) line = 7;
+  else if (mid) line = 8;
+  else if (wide && deep) line = 9;
+  else if (wide) line = 10;
+  else if (deep) line = 11;
+  else line = 12;
+  choice = sd_conv_gemm_choice{};
+  switch (line) {
+#define GEMM_CHOICE(L_, WM_, WN_, TN_, BK_, ST_, SP_, TM_, THREADS_)                                                             \
+  case L_:                                                                                                                       \
+    choice.bm = WM_ * TM_ * 32; choice.bn = WN_ * TN_ * 32; choice.bk = BK_; choice.stages = ST_; choice.waves = THREADS_ / 64; \
+    choice.tm = TM_; choice.spread = SP_ ? 1 : 0;                                                                                \
+    break;
+    GEMM_LINES(GEMM_CHOICE)
+#undef GEMM_CHOICE
+  }
   // 16x16x32 MFMAs in the K loop of every launch with K >= 256 (measured inside the captured graphs, A B A B: UNet forward -0.2 ms from the
   // 3x3 convolutions -- the power-limited ones -- and another -0.45 ms from the 1x1 / linear launches, most of it at K = 320; VAE decode
   // -0.65 ms)
-  const bool m16 = g.K >= 256;
-  if (big && spread) GEMM_LAUNCH(4, 2, 5, 64, 2, true, 2, 512);
-  else if (wide && deep && spread && !big_geglu && !big256 && !big128 && !mid) GEMM_LAUNCH(2, 2, 2, 64, 2, true, 2, 256);
-  else if (big) GEMM_LAUNCH(4, 2, 5, 64, 2, false, 2, 512);
-  else if ((big_geglu || big256) && spread) GEMM_LAUNCH(4, 2, 4, 64, 2, true, 2, 512);
-  else if (big_geglu || big256) GEMM_LAUNCH(4, 2, 4, 64, 2, false, 2, 512);
-  else if (tall128) GEMM_LAUNCH(4, 1, 4, 32, 3, false, 2, 256);
-  else if (big128) GEMM_LAUNCH(4, 2, 2, 64, 2, false, 2, 512);
-  else if (mid8) GEMM_LAUNCH(4, 2, 5, 64, 2, true, 1, 512);
-  else if (mid) GEMM_LAUNCH(2, 2, 5, 32, 3, false, 2, 256);
-  else if (wide && deep) GEMM_LAUNCH(2, 2, 2, 64, 2, false, 2, 256);
-  else if (wide) GEMM_LAUNCH(2, 2, 2, 32, 4, false, 2, 256);
-  else if (deep) GEMM_LAUNCH(2, 2, 1, 64, 2, false, 2, 256);
-  else GEMM_LAUNCH(2, 2, 1, 32, 4, false, 2, 256);
+  choice.m16 = g.K >= 256 ? 1 : 0;
+  choice.ksplit = g.ksplit;
+  choice.tap_minor = (g.taps == 9 && !g.upsample && !(g.epi & EPI_TAPMAJOR)) ? 1 : 0;      // the K order the kernel walks
+  choice.grid_x = (int)grid.x; choice.grid_y = (int)grid.y;
+  return COMA_OK;
+}
+
+extern "C" int sd_conv_gemm_describe(const sd_conv_gemm_desc* desc, sd_conv_gemm_choice* choice) {
+  if (!choice) return fail(COMA_E_INVALID, "sd_conv_gemm_describe: null choice");
+  GemmArgs g;
+  int line;
+  dim3 grid;
+  return conv_gemm_configure(desc, g, line, grid, *choice);
+}
+
+extern "C" int sd_conv_gemm_f16(const sd_conv_gemm_desc* d_in, void* stream) {
+  if (sd::plan_recording()) return sd::record_conv(d_in);
+  GemmArgs g;
+  int line;
+  dim3 grid;
+  sd_conv_gemm_choice choice;
+  if (const int rc = conv_gemm_configure(d_in, g, line, grid, choice)) return rc;
+#ifdef GEMM_DBG
+  if (hipGetSymbolAddress((void**)&g.dbg, HIP_SYMBOL(g_dbg_stamps)) != hipSuccess) return fail(COMA_E_LAUNCH, "sd_conv_gemm_f16: no g_dbg_stamps");
+#endif
+  hipStream_t st = (hipStream_t)stream;
+  const bool m16 = choice.m16 != 0;
+  switch (line) {
+#define GEMM_LAUNCH(L_, WM_, WN_, TN_, BK_, ST_, SP_, TM_, THREADS_)                                                             \
+  case L_:                                                                                                                       \
+    if (m16) hipLaunchKernelGGL((conv_gemm_kernel<WM_, WN_, TN_, BK_, ST_, SP_, TM_, true>), grid, dim3(THREADS_), 0, st, g);    \
+    else hipLaunchKernelGGL((conv_gemm_kernel<WM_, WN_, TN_, BK_, ST_, SP_, TM_, false>), grid, dim3(THREADS_), 0, st, g);       \
+    break;
+    GEMM_LINES(GEMM_LAUNCH)
 #undef GEMM_LAUNCH
+  }
   if (g.ksplit > 1) {
     const long long n8 = (long long)g.M * (g.N / 8);
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, st, g);

@@ -37,29 +37,58 @@ def _stream(t):
     return _lib.stream_ptr(t.device)
 
 
-def conv_gemm(a0, w, out, *, batch, in_h, in_w, out_h=None, out_w=None, c0, n, a1=None, c1=0, taps=1, stride=1, upsample=0,
-              pad=1, bias=None, bias_bn=None, ldbb=0, res=None, ldr=0, ldo=0, epi=EPI_NONE, nbatch_z=1, stride_a=0, stride_w=0,
-              stride_out=0, stride_res=0, workspace=None, colstats=None,
-              out_t=None, n_split=0, ldo_t=0, rows_per_sample=0, phase=0):
+class ConvGemmChoice(C.Structure):
+    """sd_conv_gemm_choice of include/sd_hip.h: the kernel sd_conv_gemm_f16 runs for a descriptor."""
+    _fields_ = [(k, C.c_int) for k in ("bm", "bn", "bk", "stages", "waves", "tm", "spread", "m16", "ksplit", "tap_minor", "grid_x", "grid_y")]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def _conv_gemm_desc(p, a0, w, out, *, batch, in_h, in_w, out_h=None, out_w=None, c0, n, a1=None, c1=0, taps=1, stride=1, upsample=0,
+                    pad=1, bias=None, bias_bn=None, ldbb=0, res=None, ldr=0, ldo=0, epi=EPI_NONE, nbatch_z=1, stride_a=0, stride_w=0,
+                    stride_out=0, stride_res=0, workspace=None, workspace_bytes=None, colstats=None,
+                    out_t=None, n_split=0, ldo_t=0, rows_per_sample=0, phase=0):
+    """The descriptor of a launch; p(tensor, name, dtype) -> address."""
     d = ConvGemmDesc()
     d.phase = phase
-    d.a0, d.a1, d.c0, d.c1 = _p(a0, "a0"), _p(a1, "a1"), c0, c1
+    d.a0, d.a1, d.c0, d.c1 = p(a0, "a0"), p(a1, "a1"), c0, c1
     d.batch, d.in_h, d.in_w = batch, in_h, in_w
     d.out_h = out_h if out_h is not None else in_h
     d.out_w = out_w if out_w is not None else in_w
     d.taps, d.stride, d.upsample, d.pad, d.n = taps, stride, upsample, pad, n
     d.ldbb = ldbb
-    d.w, d.bias, d.bias_bn, d.res, d.ldr = _p(w, "w"), _p(bias, "bias"), _p(bias_bn, "bias_bn"), _p(res, "res"), ldr
-    d.out, d.ldo, d.epi, d.nbatch_z = _p(out, "out"), ldo, epi, nbatch_z
+    d.w, d.bias, d.bias_bn, d.res, d.ldr = p(w, "w"), p(bias, "bias"), p(bias_bn, "bias_bn"), p(res, "res"), ldr
+    d.out, d.ldo, d.epi, d.nbatch_z = p(out, "out"), ldo, epi, nbatch_z
     d.stride_a, d.stride_w, d.stride_out, d.stride_res = stride_a, stride_w, stride_out, stride_res
     if workspace is not None:
-        d.workspace, d.workspace_bytes = _p(workspace, "workspace", torch.float32), workspace.numel() * 4
+        d.workspace = p(workspace, "workspace", torch.float32)
+        d.workspace_bytes = workspace_bytes if workspace_bytes is not None else workspace.numel() * 4
     if colstats is not None:
-        d.colstats = _p(colstats, "colstats", torch.float32)
+        d.colstats = p(colstats, "colstats", torch.float32)
     if out_t is not None:          # columns [n_split, n) leave transposed per sample in the PERM16 key order (to_q | to_k | to_v in one launch)
-        d.out_t, d.n_split, d.ldo_t, d.rows_per_sample = _p(out_t, "out_t"), n_split, ldo_t, rows_per_sample
+        d.out_t, d.n_split, d.ldo_t, d.rows_per_sample = p(out_t, "out_t"), n_split, ldo_t, rows_per_sample
+    return d
+
+
+def conv_gemm(a0, w, out, **kw):
+    """sd_conv_gemm_f16; keywords as _conv_gemm_desc."""
+    d = _conv_gemm_desc(_p, a0, w, out, **kw)
     _lib.check(_lib.lib().sd_conv_gemm_f16(C.byref(d), _stream(out)), "sd_conv_gemm_f16")
     return out
+
+
+def conv_gemm_describe(a0, w, out, **kw):
+    """sd_conv_gemm_describe: the ConvGemmChoice of the launch conv_gemm(a0, w, out, **kw) would make, or its refusal as ComaHipError.  Host
+    code only: nothing is launched and no pointer is dereferenced, so every tensor argument may also be a plain integer address (with
+    workspace_bytes beside an integer `workspace`) and no GPU is needed."""
+    def address(t, name="tensor", dtype=F16):
+        return t if t is None or isinstance(t, int) else _lib.ptr(t, dtype, name).value
+    d, choice = _conv_gemm_desc(address, a0, w, out, **kw), ConvGemmChoice()
+    rc = _lib.lib().sd_conv_gemm_describe(C.byref(d), C.byref(choice))
+    if rc != 0:
+        raise _lib.ComaHipError(f"sd_conv_gemm_describe failed ({rc}): {_lib.lib().coma_last_error().decode()}")
+    return choice
 
 
 def linear(x, w, out, *, rows, k, n, bias=None, res=None, epi=EPI_NONE, ldo=0):

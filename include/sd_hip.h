@@ -31,9 +31,11 @@ extern "C" {
 #define SD_EPI_PERM16_N 8   /* output column j holds the product with W row kappa(j) = j with bits 2 and 3 swapped, i.e. every group of
                                16 columns is stored in the order (0-3, 8-11, 4-7, 12-15): the V^T layout sd_attention_f16 reads with one
                                16-byte LDS load per MFMA operand (vt_perm16 = 1).  n is rounded up to 16 columns (ldo must cover them);
-                               columns whose source row is >= n hold a clamped finite row */
+                               columns whose source row is >= n hold a clamped finite row.  A `bias` only with SD_EPI_BIAS_ROWS: a column
+                               bias is refused (COMA_E_INVALID) -- it would be added by output position, not by W row */
 #define SD_EPI_PERM32_N 16  /* position p = 8g + e of every group of 32 output columns holds the product with W row 16 (e >> 2) + 4g + (e & 3):
-                               the V^T layout sd_attention_wide_f16 reads (one 16-byte LDS load per 16x16x32 MFMA operand).  n % 32 == 0 */
+                               the V^T layout sd_attention_wide_f16 reads (one 16-byte LDS load per 16x16x32 MFMA operand).  n % 32 == 0.
+                               A `bias` only with SD_EPI_BIAS_ROWS, as for SD_EPI_PERM16_N */
 #define SD_EPI_QUICK_GELU 32 /* out = a * sigmoid(1.702 a), a = acc + bias (CLIP's quick_gelu, fc1 of the text tower); not with GEGLU / SiLU */
 /* every flag above; sd_conv_gemm_f16 refuses (COMA_E_INVALID) an epi with any other bit set.  The kernel, tile and split-K factor
  * of a launch are a function of the descriptor alone. */
@@ -42,7 +44,8 @@ extern "C" {
 /* out[m, n] = sum_k A[m, k] * W[n, k] (+ epilogue) with A gathered from one or two NHWC sources:
  *   m = (b, oy, ox), k = (tap, ci);  taps = 9: 3x3, zero pad 1;  taps = 1: 1x1 / linear;  taps = 4: one sub-pixel phase (see `phase`)
  *   upsample = 1: the 3x3 window slides over the nearest-x2 upsampling of the [in_h, in_w] input
- *   ci runs over the concatenation [a0 (c0 channels) | a1 (c1 channels)]; c0, c1 multiples of 64
+ *   ci runs over the concatenation [a0 (c0 channels) | a1 (c1 channels)]; c0, c1 multiples of 32 (the 64-deep K tiles need multiples of 64)
+ *   stride = 2 is also taken with taps = 1: output (oy, ox) reads pixel (2 oy, 2 ox)
  * replaces: torch.nn.Conv2d / nn.Linear / torch.cat / F.interpolate(nearest) inside diffusers'
  *           UNet2DConditionModel and AutoencoderKL (call sites utils/adaptive_mask_inpainting.py:1001, :1086, :680). */
 typedef struct sd_conv_gemm_desc {
@@ -82,13 +85,23 @@ typedef struct sd_conv_gemm_desc {
    * products per output 2 x 2 block instead of 36, exactly (no transform).  phase = 1 + 2 a + b selects the parity; taps = 4, w fp16
    * [n][4][c0+c1] = the summed weights of that phase (window order (dy, dx) row-major), batch / in_h / in_w = the SOURCE size (out_h = in_h,
    * out_w = in_w, in_w a power of two), `out` = the full [batch, 2 in_h, 2 in_w, ldo] tensor: row m = (b, y, x) of the product is written to
-   * pixel (2y + a, 2x + b).  Four launches (phase 1..4) make the convolution; colstats (optional) must have room for 4 M / 32 slots.
+   * pixel (2y + a, 2x + b).  Four launches (phase 1..4) make the convolution; colstats (optional) must have room for 4 M / 32 slots: phase p of
+   * sample b owns slots [(4 b + p - 1) per, (4 b + p) per), per = in_h * in_w / 32, so colstats needs in_h * in_w % 32 == 0 here (refused otherwise).
    * Plain epilogue only (bias).  0 = off (every other launch; a zero-initialised descriptor). */
   int phase;
 } sd_conv_gemm_desc;
 
 int sd_conv_gemm_f16(const sd_conv_gemm_desc* desc, void* stream);
 size_t sd_conv_gemm_workspace_bytes(void); /* recommended workspace size */
+
+/* Which kernel sd_conv_gemm_f16 runs for a descriptor: the block tile bm x bn x bk, its LDS stages and waves, tm = 32-row MFMA tiles per
+ * wave along M, spread = the next tile's LDS-DMA issued between the K steps (1) or in one burst (0), m16 = 16x16x32 MFMAs in the K loop,
+ * ksplit = split-K factor (1 = none), tap_minor = a 3x3 walks K tap-minor, grid_x / grid_y = the launch grid (grid_x includes the padding
+ * blocks of the XCD-banded order; grid_y = ksplit or nbatch_z).  Host code only: the validation and tile selection of sd_conv_gemm_f16 with
+ * the same return codes and coma_last_error texts; nothing is launched, no data pointer of the descriptor is dereferenced (they must be
+ * non-NULL where the launch needs them), and a plan that is being recorded does not see the call. */
+typedef struct sd_conv_gemm_choice { int bm, bn, bk, stages, waves, tm, spread, m16, ksplit, tap_minor, grid_x, grid_y; } sd_conv_gemm_choice;
+int sd_conv_gemm_describe(const sd_conv_gemm_desc* desc, sd_conv_gemm_choice* choice);
 
 /* GroupNorm (+ optional SiLU) over NHWC fp16, reading the channel concatenation of two sources and writing one
  * tensor [batch, hw, c0+c1].  replaces: nn.GroupNorm(groups, C, eps) + nn.SiLU in diffusers ResnetBlock2D /
