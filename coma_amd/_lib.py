@@ -16,11 +16,12 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # COMA_HIP_LIB=<path>: tuning aid -- load another BUILD of the library (A/B of two builds inside one GPU call: box-to-box spread is larger
 # than most of the effects being measured); the product and the tests use the in-tree library
 LIB_PATH = os.environ.get("COMA_HIP_LIB") or os.path.join(_HERE, "libcoma_hip.so")
-ABI_VERSION = 10                 # = COMA_ABI_VERSION of include/coma_hip.h: bumped with every change of the SIGNATURES table below
+ABI_VERSION = 10                 # = COMA_ABI_VERSION of include/coma_hip.h: bumped when an existing signature changes
 # (not for the text-tower functions: they were only added, no existing signature changed, and a library without them is refused by
 # lib() anyway -- getattr of a missing symbol fails; the same holds for the two coma_sample_eliminate_* functions and for the
 # coma_raster_* / coma_silhouette_iou functions, and for the mesh volume functions of csrc/mesh_volume.hip and the depth-optimisation functions of csrc/depth_opt.hip,
-# and for the two coma_app_objective_* functions of csrc/app_objective.hip and the coma_smplx_* functions of csrc/smplx.hip)
+# and for the two coma_app_objective_* functions of csrc/app_objective.hip and the coma_smplx_* functions of csrc/smplx.hip,
+# and the coma_vposer_* / coma_angle_prior_* functions of csrc/vposer.hip)
 
 _lib = None
 
@@ -76,6 +77,13 @@ SIGNATURES = {
     "coma_smplx_backward_f32": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _i, _vp, _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t,
                                      _vp]),
     "coma_smplx_extra_joints_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "coma_vposer_saved_bytes": (C.c_size_t, [_i, _i, _i]),
+    "coma_vposer_workspace_bytes": (C.c_size_t, [_i, _i, _i]),
+    "coma_vposer_decode_f32": (_i, [_vp] * 7 + [_i, _i, _i, _i, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "coma_vposer_decode_backward_f32": (_i, [_vp] * 4 + [_i, _i, _i, _i, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp]),
+    "coma_vposer_encode_f32": (_i, [_vp] * 9 + [_i, _i, _i, _i, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "coma_angle_prior_f32": (_i, [_vp, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_float), _i, _vp, _vp]),
+    "coma_angle_prior_backward_f32": (_i, [_vp, _vp, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_float), _i, _vp, _vp]),
     # include/sd_hip.h
     "sd_conv_gemm_f16": (_i, [_vp, _vp]),
     "sd_conv_gemm_workspace_bytes": (C.c_size_t, []),

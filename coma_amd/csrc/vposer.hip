@@ -1,0 +1,442 @@
+// VPoser's pose decoder (forward and backward), its encoder (forward) and the SMPLify angle prior, for gfx950.
+// replaces: the `pose_decoder` and `angle_prior` hooks of src/application/optimize.py (the reference's imports/vposer/vposer_smpl.py,
+// imports/vposer/prior.py and the matrix -> quaternion -> axis-angle chain of its utils/transformations.py), called and differentiated
+// in every iteration of the fit, by four launches forward and four backward on the caller's stream.  Rule set: include/coma_hip.h;
+// restated in f64 in tests/vposer_ref.py.
+//
+// In the project's own words.  The decoder is a three-layer perceptron (leaky ReLU, slope 0.2) whose 6 NJ outputs are read, per
+// joint, as two 3-vectors; Gram-Schmidt turns them into an orthonormal frame whose vectors are the COLUMNS of the joint's rotation.
+// The rotation becomes a quaternion by the four-candidate rule (the candidate is chosen from the signs and sizes of the diagonal of
+// the transposed matrix; only the chosen one is evaluated, the others are multiplied by zero in the reference and never reach its
+// square root), and the quaternion becomes an axis-angle vector through 2 atan2(|v|, w) with both arguments negated when w < 0.
+// The backward applies the analytic derivative of that tail for the branch the forward took (the forward stores it), then walks
+// the three layers transposed.  At N = 1 the layers are GEMVs over 1.4 MB of weights: latency- and bandwidth-bound, so the
+// arithmetic is f64 on f32 inputs and the outputs are the f32 rounding of the rule set.
+//
+// Forward layer: one wave per output row; lane l adds the products of columns l, l + 64, ... in ascending order (coalesced reads of
+// the weight row), then the 64 partial sums are folded by v = v + v[lane ^ h], h = 32, 16, 8, 4, 2, 1.  Transposed layer: 64 columns
+// per workgroup, one per lane; wave w of the 16 adds the rows o = w, w + 16, ... of its column in ascending order (a row's 64 columns
+// are consecutive in memory), and the 16 partial sums are added in ascending w through LDS.  No floating-point atomics: two calls
+// give the same bits.
+#include "common.h"
+
+#include <cmath>
+#include <initializer_list>
+
+namespace coma {
+namespace {
+
+constexpr int kMaxN = 64, kMaxD = 256, kMaxH = 2048, kMaxNJ = 64;
+constexpr int kMaxP = 4096, kMaxK = 16;      // angle prior: pose width and number of selected entries
+constexpr int kFwdWaves = 4;                 // output rows per forward workgroup
+constexpr int kBwdWaves = 16;                // row splits per transposed workgroup
+constexpr double kSlope = 0.2;
+constexpr double kNormEps = 1e-12;           // F.normalize's eps
+constexpr double kDiagEps = 1e-6;            // the test on the (2,2) entry
+constexpr double kBnEps = 1e-5;
+
+__device__ __forceinline__ double load(const float* p, int64_t i) { return (double)p[i]; }
+__device__ __forceinline__ double load(const double* p, int64_t i) { return p[i]; }
+
+// y[n, o] = epilogue(b[o] + sum_i W[o, i] x[n, i]); grid (ceil(Out / kFwdWaves), N).
+// act: 0 none, 1 leaky ReLU.  y64 (f64 [N, Out]) or, when y64 is NULL, two f32 outputs of `split` columns each: rows o < split go to
+// lo[n, o], rows o >= split to hi[n, o - split] after softplus (threshold 20) -- the encoder's mean and scale.
+template <typename TX>
+__global__ __launch_bounds__(kFwdWaves * kWave) void vposer_linear_kernel(const TX* __restrict__ x, const float* __restrict__ W,
+                                                                          const float* __restrict__ b, int In, int Out, int act,
+                                                                          double* __restrict__ y64, float* __restrict__ lo,
+                                                                          float* __restrict__ hi, int split) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int o = blockIdx.x * kFwdWaves + (threadIdx.x >> 6);     // wave-uniform
+  const int n = blockIdx.y;
+  if (o >= Out) return;
+  const float* row = W + (int64_t)o * In;
+  double acc = 0.0;
+  for (int i = lane; i < In; i += kWave) acc = acc + (double)row[i] * load(x, (int64_t)n * In + i);
+#pragma unroll
+  for (int h = kWave / 2; h >= 1; h >>= 1) acc = acc + __shfl_xor(acc, h, kWave);
+  if (lane != 0) return;
+  double v = acc + (double)b[o];
+  if (act == 1) v = v > 0.0 ? v : v * kSlope;
+  if (y64) {
+    y64[(int64_t)n * Out + o] = v;
+  } else if (o < split) {
+    lo[(int64_t)n * split + o] = (float)v;
+  } else {
+    hi[(int64_t)n * split + (o - split)] = (float)(v > 20.0 ? v : log1p(exp(v)));
+  }
+}
+
+// gx[n, i] = mask(h[n, i]) * sum_o W[o, i] gy[n, o]; grid (ceil(In / 64), N), kBwdWaves waves.
+// h (f64 [N, In], the layer's activated input) may be NULL: no mask; else the factor is 1 where h > 0 and the slope elsewhere
+// (the leaky ReLU keeps the sign of its argument).  Output f64 gx64 or f32 gx32.
+__global__ __launch_bounds__(kBwdWaves * kWave) void vposer_linear_t_kernel(const double* __restrict__ gy, const float* __restrict__ W,
+                                                                            const double* __restrict__ h, int In, int Out,
+                                                                            double* __restrict__ gx64, float* __restrict__ gx32) {
+  __shared__ double part[kBwdWaves][kWave];
+  const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x >> 6;
+  const int i = blockIdx.x * kWave + lane;
+  const int n = blockIdx.y;
+  double acc = 0.0;
+  if (i < In)
+    for (int o = w; o < Out; o += kBwdWaves) acc = acc + (double)W[(int64_t)o * In + i] * gy[(int64_t)n * Out + o];
+  part[w][lane] = acc;
+  __syncthreads();
+  if (w != 0 || i >= In) return;
+  double s = part[0][lane];
+#pragma unroll
+  for (int k = 1; k < kBwdWaves; ++k) s = s + part[k][lane];
+  if (h) s = h[(int64_t)n * In + i] > 0.0 ? s : s * kSlope;
+  if (gx64) gx64[(int64_t)n * In + i] = s;
+  else gx32[(int64_t)n * In + i] = (float)s;
+}
+
+// eval-mode BatchNorm1d over the columns: y = (x - running_mean) / sqrt(running_var + 1e-5) * weight + bias; bn = [4, C] f32
+template <typename TX>
+__global__ __launch_bounds__(256) void vposer_bn_kernel(const TX* __restrict__ x, const float* __restrict__ bn, int C, int total,
+                                                        double* __restrict__ y) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= total) return;
+  const int c = t % C;
+  const double g = (double)bn[c], beta = (double)bn[C + c], m = (double)bn[2 * C + c], var = (double)bn[3 * C + c];
+  y[t] = (load(x, t) - m) / sqrt(var + kBnEps) * g + beta;
+}
+
+// ---- the tail: 6 numbers -> rotation -> quaternion -> axis-angle ----
+struct Tail {
+  double n0, n1, dot;           // max(|c0|, eps), max(|u|, eps), b1 . c1
+  bool free0, free1;            // the norm, not eps, divided
+  double T[3][3];               // T[i] = b_{i+1}: the TRANSPOSED rotation, the matrix the selection rule reads
+  int branch;
+  double t, q[4];               // the selected t and 0.5 cand / sqrt(t)
+  double s2, s, tt, k;          // sin^2, sin, two_theta, the factor
+};
+
+__device__ __forceinline__ double norm3(const double* v) { return sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]); }
+__device__ __forceinline__ double dot3(const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+__device__ __forceinline__ void cross3(const double* a, const double* b, double* c) {
+  c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+__device__ __forceinline__ void candidate(const double T[3][3], int branch, double* t, double* c) {
+  if (branch == 0) {
+    *t = ((1.0 + T[0][0]) - T[1][1]) - T[2][2];
+    c[0] = T[1][2] - T[2][1]; c[1] = *t; c[2] = T[0][1] + T[1][0]; c[3] = T[2][0] + T[0][2];
+  } else if (branch == 1) {
+    *t = ((1.0 - T[0][0]) + T[1][1]) - T[2][2];
+    c[0] = T[2][0] - T[0][2]; c[1] = T[0][1] + T[1][0]; c[2] = *t; c[3] = T[1][2] + T[2][1];
+  } else if (branch == 2) {
+    *t = ((1.0 - T[0][0]) - T[1][1]) + T[2][2];
+    c[0] = T[0][1] - T[1][0]; c[1] = T[2][0] + T[0][2]; c[2] = T[1][2] + T[2][1]; c[3] = *t;
+  } else {
+    *t = ((1.0 + T[0][0]) + T[1][1]) + T[2][2];
+    c[0] = *t; c[1] = T[1][2] - T[2][1]; c[2] = T[2][0] - T[0][2]; c[3] = T[0][1] - T[1][0];
+  }
+}
+
+// forced >= 0: the branch the forward stored; < 0: select
+__device__ __forceinline__ void tail_forward(const double* o, int forced, Tail& f, double* aa) {
+  const double c0[3] = {o[0], o[2], o[4]}, c1[3] = {o[1], o[3], o[5]};
+  double u[3];
+  const double l0 = norm3(c0);
+  f.free0 = l0 >= kNormEps; f.n0 = f.free0 ? l0 : kNormEps;
+  for (int r = 0; r < 3; ++r) f.T[0][r] = c0[r] / f.n0;
+  f.dot = dot3(f.T[0], c1);
+  for (int r = 0; r < 3; ++r) u[r] = c1[r] - f.dot * f.T[0][r];
+  const double l1 = norm3(u);
+  f.free1 = l1 >= kNormEps; f.n1 = f.free1 ? l1 : kNormEps;
+  for (int r = 0; r < 3; ++r) f.T[1][r] = u[r] / f.n1;
+  cross3(f.T[0], f.T[1], f.T[2]);
+  if (forced >= 0) f.branch = forced;
+  else if (f.T[2][2] < kDiagEps) f.branch = f.T[0][0] > f.T[1][1] ? 0 : 1;
+  else f.branch = f.T[0][0] < -f.T[1][1] ? 2 : 3;
+  double c[4];
+  candidate(f.T, f.branch, &f.t, c);
+  const double root = sqrt(f.t);
+  for (int e = 0; e < 4; ++e) f.q[e] = c[e] / root * 0.5;
+  f.s2 = (f.q[1] * f.q[1] + f.q[2] * f.q[2]) + f.q[3] * f.q[3];
+  f.s = sqrt(f.s2);
+  f.tt = 2.0 * (f.q[0] < 0.0 ? atan2(-f.s, -f.q[0]) : atan2(f.s, f.q[0]));
+  f.k = f.s2 > 0.0 ? f.tt / f.s : 2.0;
+  for (int e = 0; e < 3; ++e) aa[e] = f.q[e + 1] * f.k;
+}
+
+// dL/do [6] from dL/daa [3]
+__device__ __forceinline__ void tail_backward(const double* o, const Tail& f, const double* ga, double* go) {
+  // axis-angle <- quaternion
+  double gq[4];
+  const double gk = (ga[0] * f.q[1] + ga[1] * f.q[2]) + ga[2] * f.q[3];
+  for (int e = 0; e < 3; ++e) gq[e + 1] = ga[e] * f.k;
+  gq[0] = 0.0;
+  if (f.s2 > 0.0) {                       // else k = 2 is a constant: the finite gradient at the identity
+    const double gtt = gk / f.s;
+    const double r2 = f.s2 + f.q[0] * f.q[0];
+    const double gs = -gk * f.tt / f.s2 + 2.0 * gtt * f.q[0] / r2;
+    gq[0] = -2.0 * gtt * f.s / r2;
+    const double gs2 = gs / (2.0 * f.s);
+    for (int e = 1; e < 4; ++e) gq[e] = gq[e] + 2.0 * f.q[e] * gs2;
+  }
+  // quaternion <- the selected candidate: q = 0.5 c / sqrt(t)
+  const double root = sqrt(f.t);
+  double gc[4];
+  for (int e = 0; e < 4; ++e) gc[e] = 0.5 * gq[e] / root;
+  double gt = -0.5 * (((gq[0] * f.q[0] + gq[1] * f.q[1]) + gq[2] * f.q[2]) + gq[3] * f.q[3]) / f.t;
+  double g[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+  if (f.branch == 0) {
+    gt = gt + gc[1];
+    g[0][0] = gt; g[1][1] = -gt; g[2][2] = -gt;
+    g[1][2] = gc[0]; g[2][1] = -gc[0]; g[0][1] = gc[2]; g[1][0] = gc[2]; g[2][0] = gc[3]; g[0][2] = gc[3];
+  } else if (f.branch == 1) {
+    gt = gt + gc[2];
+    g[0][0] = -gt; g[1][1] = gt; g[2][2] = -gt;
+    g[2][0] = gc[0]; g[0][2] = -gc[0]; g[0][1] = gc[1]; g[1][0] = gc[1]; g[1][2] = gc[3]; g[2][1] = gc[3];
+  } else if (f.branch == 2) {
+    gt = gt + gc[3];
+    g[0][0] = -gt; g[1][1] = -gt; g[2][2] = gt;
+    g[0][1] = gc[0]; g[1][0] = -gc[0]; g[2][0] = gc[1]; g[0][2] = gc[1]; g[1][2] = gc[2]; g[2][1] = gc[2];
+  } else {
+    gt = gt + gc[0];
+    g[0][0] = gt; g[1][1] = gt; g[2][2] = gt;
+    g[1][2] = gc[1]; g[2][1] = -gc[1]; g[2][0] = gc[2]; g[0][2] = -gc[2]; g[0][1] = gc[3]; g[1][0] = -gc[3];
+  }
+  // Gram-Schmidt: b3 = b1 x b2, b2 = u / n1, u = c1 - (b1 . c1) b1, b1 = c0 / n0
+  double x[3], gb1[3], gb2[3], gu[3];
+  cross3(f.T[1], g[2], x);
+  for (int r = 0; r < 3; ++r) gb1[r] = g[0][r] + x[r];
+  cross3(g[2], f.T[0], x);
+  for (int r = 0; r < 3; ++r) gb2[r] = g[1][r] + x[r];
+  const double p2 = f.free1 ? dot3(f.T[1], gb2) : 0.0;
+  for (int r = 0; r < 3; ++r) gu[r] = (gb2[r] - f.T[1][r] * p2) / f.n1;
+  const double c1[3] = {o[1], o[3], o[5]};
+  const double pu = dot3(gu, f.T[0]);
+  double gc1[3], gc0[3];
+  for (int r = 0; r < 3; ++r) {
+    gc1[r] = gu[r] - pu * f.T[0][r];
+    gb1[r] = gb1[r] - (f.dot * gu[r] + pu * c1[r]);
+  }
+  const double p1 = f.free0 ? dot3(f.T[0], gb1) : 0.0;
+  for (int r = 0; r < 3; ++r) gc0[r] = (gb1[r] - f.T[0][r] * p1) / f.n0;
+  for (int r = 0; r < 3; ++r) { go[2 * r] = gc0[r]; go[2 * r + 1] = gc1[r]; }
+}
+
+// one thread per (n, joint)
+__global__ __launch_bounds__(256) void vposer_tail_kernel(const double* __restrict__ o, int total, float* __restrict__ aa,
+                                                          float* __restrict__ matrices, int8_t* __restrict__ branch,
+                                                          int8_t* __restrict__ saved_branch) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= total) return;
+  double in[6], out[3];
+  for (int e = 0; e < 6; ++e) in[e] = o[(int64_t)t * 6 + e];
+  Tail f;
+  tail_forward(in, -1, f, out);
+  for (int e = 0; e < 3; ++e) aa[(int64_t)t * 3 + e] = (float)out[e];
+  saved_branch[t] = (int8_t)f.branch;
+  if (branch) branch[t] = (int8_t)f.branch;
+  if (matrices)
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) matrices[(int64_t)t * 9 + 3 * r + c] = (float)f.T[c][r];
+}
+
+__global__ __launch_bounds__(256) void vposer_tail_bwd_kernel(const double* __restrict__ o, const int8_t* __restrict__ saved_branch,
+                                                              const float* __restrict__ grad_aa, int total, double* __restrict__ go) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= total) return;
+  double in[6], out[3], ga[3], g[6];
+  for (int e = 0; e < 6; ++e) in[e] = o[(int64_t)t * 6 + e];
+  for (int e = 0; e < 3; ++e) ga[e] = (double)grad_aa[(int64_t)t * 3 + e];
+  Tail f;
+  tail_forward(in, (int)saved_branch[t] & 3, f, out);
+  tail_backward(in, f, ga, g);
+  for (int e = 0; e < 6; ++e) go[(int64_t)t * 6 + e] = g[e];
+}
+
+// ---- the angle prior ----
+struct PriorArgs { int32_t index[kMaxK]; float sign[kMaxK]; int K; };
+
+__global__ __launch_bounds__(256) void angle_prior_kernel(const float* __restrict__ pose, int N, int P, PriorArgs a, float* __restrict__ out) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= N * a.K) return;
+  const int n = t / a.K, k = t % a.K;
+  const double e = exp((double)a.sign[k] * (double)pose[(int64_t)n * P + a.index[k]]);
+  out[t] = (float)(e * e);
+}
+
+// grad_pose[n, p] = sum over k with index[k] == p, ascending, of grad_out[n, k] 2 sign[k] exp(sign[k] pose[n, p])^2; zero elsewhere
+__global__ __launch_bounds__(256) void angle_prior_bwd_kernel(const float* __restrict__ pose, const float* __restrict__ grad_out, int N, int P,
+                                                              PriorArgs a, float* __restrict__ grad_pose) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= N * P) return;
+  const int n = t / P, p = t % P;
+  double g = 0.0;
+  for (int k = 0; k < a.K; ++k)
+    if (a.index[k] == p) {
+      const double s = (double)a.sign[k];
+      const double e = exp(s * (double)pose[t]);
+      g = g + (double)grad_out[(int64_t)n * a.K + k] * (2.0 * s * (e * e));
+    }
+  grad_pose[t] = (float)g;
+}
+
+// ---- host side ----
+size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+struct Layout {
+  size_t h1, h2, o, branch, saved_total;     // saved: h1, h2 f64 [N,H]; o f64 [N,6NJ]; branch i8 [N,NJ]
+  size_t a, b, c, total;                     // workspace: three f64 [N, max(H, 6 NJ)]
+};
+
+Layout layout(int N, int H, int NJ) {
+  Layout L;
+  const size_t d = sizeof(double);
+  size_t at = 0;
+  L.h1 = at;     at = up16(at + (size_t)N * H * d);
+  L.h2 = at;     at = up16(at + (size_t)N * H * d);
+  L.o = at;      at = up16(at + (size_t)N * 6 * NJ * d);
+  L.branch = at; at = up16(at + (size_t)N * NJ);
+  L.saved_total = at;
+  const size_t wide = (size_t)N * (H > 6 * NJ ? H : 6 * NJ) * d;
+  at = 0;
+  L.a = at; at = up16(at + wide);
+  L.b = at; at = up16(at + wide);
+  L.c = at; at = up16(at + wide);
+  L.total = at;
+  return L;
+}
+
+bool sizes_ok(int N, int H, int NJ) { return N >= 1 && N <= kMaxN && H >= 1 && H <= kMaxH && NJ >= 1 && NJ <= kMaxNJ; }
+
+int check_sizes(const char* who, int N, int D, int H, int NJ) {
+  if (!sizes_ok(N, H, NJ) || D < 1 || D > kMaxD)
+    return fail(COMA_E_INVALID, "%s: N=%d must lie in [1, %d], D=%d in [1, %d], H=%d in [1, %d] and NJ=%d in [1, %d]", who, N, kMaxN, D, kMaxD, H,
+                kMaxH, NJ, kMaxNJ);
+  return COMA_OK;
+}
+
+int check_buffer(const char* who, const char* what, const void* p, size_t have, size_t need) {
+  if (have < need) return fail(COMA_E_INVALID, "%s: %s of %zu bytes, %zu needed", who, what, have, need);
+  if (((uintptr_t)p & 15) != 0) return fail(COMA_E_INVALID, "%s: %s must be 16-byte aligned", who, what);
+  return COMA_OK;
+}
+
+bool f32_aligned(std::initializer_list<const void*> ps) {
+  for (const void* p : ps)
+    if (((uintptr_t)p & 3) != 0) return false;
+  return true;
+}
+
+template <typename TX>
+void linear(hipStream_t s, const TX* x, const float* W, const float* b, int N, int In, int Out, int act, double* y64, float* lo = nullptr,
+            float* hi = nullptr, int split = 0) {
+  hipLaunchKernelGGL(vposer_linear_kernel<TX>, dim3((Out + kFwdWaves - 1) / kFwdWaves, N), dim3(kFwdWaves * kWave), 0, s, x, W, b, In, Out, act, y64,
+                     lo, hi, split);
+}
+
+void linear_t(hipStream_t s, const double* gy, const float* W, const double* h, int N, int In, int Out, double* gx64, float* gx32) {
+  hipLaunchKernelGGL(vposer_linear_t_kernel, dim3((In + kWave - 1) / kWave, N), dim3(kBwdWaves * kWave), 0, s, gy, W, h, In, Out, gx64, gx32);
+}
+
+int prior_args(const char* who, int N, int P, const int32_t* index, const float* sign, int K, PriorArgs& a) {
+  if (N < 1 || N > kMaxN || P < 1 || P > kMaxP || K < 1 || K > kMaxK)
+    return fail(COMA_E_INVALID, "%s: N=%d must lie in [1, %d], P=%d in [1, %d] and K=%d in [1, %d]", who, N, kMaxN, P, kMaxP, K, kMaxK);
+  a = PriorArgs{};
+  a.K = K;
+  for (int k = 0; k < K; ++k) {
+    if (index[k] < 0 || index[k] >= P) return fail(COMA_E_INVALID, "%s: index[%d]=%d outside [0, %d)", who, k, index[k], P);
+    a.index[k] = index[k];
+    a.sign[k] = sign[k];
+  }
+  return COMA_OK;
+}
+
+}  // namespace
+}  // namespace coma
+
+using namespace coma;
+
+extern "C" size_t coma_vposer_saved_bytes(int N, int H, int NJ) { return sizes_ok(N, H, NJ) ? layout(N, H, NJ).saved_total : 0; }
+extern "C" size_t coma_vposer_workspace_bytes(int N, int H, int NJ) { return sizes_ok(N, H, NJ) ? layout(N, H, NJ).total : 0; }
+
+extern "C" int coma_vposer_decode_f32(const float* z, const float* W1, const float* b1, const float* W2, const float* b2, const float* W3,
+                                      const float* b3, int N, int D, int H, int NJ, float* aa, float* matrices, int8_t* branch, void* saved,
+                                      size_t saved_bytes, void* stream) {
+  const char* who = "coma_vposer_decode_f32";
+  if (!z || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !aa || !saved) return fail(COMA_E_INVALID, "%s: null pointer", who);
+  if (int rc = check_sizes(who, N, D, H, NJ)) return rc;
+  if (!f32_aligned({z, W1, b1, W2, b2, W3, b3, aa, matrices})) return fail(COMA_E_INVALID, "%s: an f32 buffer is not 4-byte aligned", who);
+  const Layout L = layout(N, H, NJ);
+  if (int rc = check_buffer(who, "saved state", saved, saved_bytes, L.saved_total)) return rc;
+  char* sv = (char*)saved;
+  hipStream_t s = (hipStream_t)stream;
+  double *h1 = (double*)(sv + L.h1), *h2 = (double*)(sv + L.h2), *o = (double*)(sv + L.o);
+  linear(s, z, W1, b1, N, D, H, 1, h1);
+  linear(s, (const double*)h1, W2, b2, N, H, H, 1, h2);
+  linear(s, (const double*)h2, W3, b3, N, H, 6 * NJ, 0, o);
+  const int total = N * NJ;
+  hipLaunchKernelGGL(vposer_tail_kernel, dim3((total + 255) / 256), dim3(256), 0, s, (const double*)o, total, aa, matrices, branch,
+                     (int8_t*)(sv + L.branch));
+  return check_launch(who);
+}
+
+extern "C" int coma_vposer_decode_backward_f32(const float* grad_aa, const float* W1, const float* W2, const float* W3, int N, int D, int H,
+                                               int NJ, const void* saved, size_t saved_bytes, float* grad_z, void* workspace,
+                                               size_t workspace_bytes, void* stream) {
+  const char* who = "coma_vposer_decode_backward_f32";
+  if (!grad_aa || !W1 || !W2 || !W3 || !saved || !grad_z || !workspace) return fail(COMA_E_INVALID, "%s: null pointer", who);
+  if (int rc = check_sizes(who, N, D, H, NJ)) return rc;
+  if (!f32_aligned({grad_aa, W1, W2, W3, grad_z})) return fail(COMA_E_INVALID, "%s: an f32 buffer is not 4-byte aligned", who);
+  const Layout L = layout(N, H, NJ);
+  if (int rc = check_buffer(who, "saved state", saved, saved_bytes, L.saved_total)) return rc;
+  if (int rc = check_buffer(who, "workspace", workspace, workspace_bytes, L.total)) return rc;
+  const char* sv = (const char*)saved;
+  char* ws = (char*)workspace;
+  hipStream_t s = (hipStream_t)stream;
+  const double *h1 = (const double*)(sv + L.h1), *h2 = (const double*)(sv + L.h2), *o = (const double*)(sv + L.o);
+  double *go = (double*)(ws + L.a), *gh2 = (double*)(ws + L.b), *gh1 = (double*)(ws + L.c);
+  const int total = N * NJ;
+  hipLaunchKernelGGL(vposer_tail_bwd_kernel, dim3((total + 255) / 256), dim3(256), 0, s, o, (const int8_t*)(sv + L.branch), grad_aa, total, go);
+  linear_t(s, go, W3, h2, N, H, 6 * NJ, gh2, nullptr);
+  linear_t(s, gh2, W2, h1, N, H, H, gh1, nullptr);
+  linear_t(s, gh1, W1, nullptr, N, D, H, nullptr, grad_z);
+  return check_launch(who);
+}
+
+extern "C" int coma_vposer_encode_f32(const float* pose, const float* bn1, const float* W1, const float* b1, const float* bn2, const float* W2,
+                                      const float* b2, const float* Wml, const float* bml, int N, int D, int H, int NJ, float* mean,
+                                      float* scale, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* who = "coma_vposer_encode_f32";
+  if (!pose || !bn1 || !W1 || !b1 || !bn2 || !W2 || !b2 || !Wml || !bml || !mean || !scale || !workspace)
+    return fail(COMA_E_INVALID, "%s: null pointer", who);
+  if (int rc = check_sizes(who, N, D, H, NJ)) return rc;
+  if (!f32_aligned({pose, bn1, W1, b1, bn2, W2, b2, Wml, bml, mean, scale})) return fail(COMA_E_INVALID, "%s: an f32 buffer is not 4-byte aligned", who);
+  const Layout L = layout(N, H, NJ);
+  if (int rc = check_buffer(who, "workspace", workspace, workspace_bytes, L.total)) return rc;
+  char* ws = (char*)workspace;
+  hipStream_t s = (hipStream_t)stream;
+  double *a = (double*)(ws + L.a), *b = (double*)(ws + L.b);
+  const int F = 3 * NJ;
+  hipLaunchKernelGGL(vposer_bn_kernel<float>, dim3((N * F + 255) / 256), dim3(256), 0, s, pose, bn1, F, N * F, a);
+  linear(s, (const double*)a, W1, b1, N, F, H, 1, b);
+  hipLaunchKernelGGL(vposer_bn_kernel<double>, dim3((N * H + 255) / 256), dim3(256), 0, s, (const double*)b, bn2, H, N * H, a);
+  linear(s, (const double*)a, W2, b2, N, H, H, 1, b);
+  linear(s, (const double*)b, Wml, bml, N, H, 2 * D, 0, (double*)nullptr, mean, scale, D);
+  return check_launch(who);
+}
+
+extern "C" int coma_angle_prior_f32(const float* pose, int N, int P, const int32_t* index, const float* sign, int K, float* out, void* stream) {
+  const char* who = "coma_angle_prior_f32";
+  if (!pose || !index || !sign || !out) return fail(COMA_E_INVALID, "%s: null pointer", who);
+  PriorArgs a;
+  if (int rc = prior_args(who, N, P, index, sign, K, a)) return rc;
+  hipLaunchKernelGGL(angle_prior_kernel, dim3((N * K + 255) / 256), dim3(256), 0, (hipStream_t)stream, pose, N, P, a, out);
+  return check_launch(who);
+}
+
+extern "C" int coma_angle_prior_backward_f32(const float* pose, const float* grad_out, int N, int P, const int32_t* index, const float* sign,
+                                             int K, float* grad_pose, void* stream) {
+  const char* who = "coma_angle_prior_backward_f32";
+  if (!pose || !grad_out || !index || !sign || !grad_pose) return fail(COMA_E_INVALID, "%s: null pointer", who);
+  PriorArgs a;
+  if (int rc = prior_args(who, N, P, index, sign, K, a)) return rc;
+  hipLaunchKernelGGL(angle_prior_bwd_kernel, dim3((N * P + 255) / 256), dim3(256), 0, (hipStream_t)stream, pose, grad_out, N, P, a, grad_pose);
+  return check_launch(who);
+}

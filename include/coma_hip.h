@@ -26,11 +26,11 @@
 extern "C" {
 #endif
 
-/* bumped whenever ANY exported signature of coma_hip.h / sd_hip.h / seg_hip.h changes; coma_amd/_lib.py refuses a library that
+/* bumped when an existing signature of coma_hip.h / sd_hip.h / seg_hip.h changes; coma_amd/_lib.py refuses a library that
  * reports another value (a stale build loaded through COMA_HIP_LIB would otherwise be called with mismatched argument lists) */
 #define COMA_ABI_VERSION 10  /* 10: sd_conv_gemm_describe added; sd_conv_gemm_f16 refuses a column bias with SD_EPI_PERM16_N / SD_EPI_PERM32_N and colstats in a phase launch with in_h * in_w % 32 != 0 */
 /* The version counts CHANGES of existing signatures, not additions: a function that is only added (the text tower, the sample
- * elimination, the rasteriser, the mesh volume functions) leaves it alone, because a library without it already fails to load
+ * elimination, the rasteriser, the mesh volume functions, the coma_vposer_* and coma_angle_prior_* functions) leaves it alone, because a library without it already fails to load
  * (coma_amd/_lib.py binds every declared name). */
 
 #define COMA_OK 0
@@ -438,6 +438,68 @@ int coma_smplx_backward_f32(const float* grad_vertices, const float* posedirs, c
                             size_t workspace_bytes, void* stream);
 int coma_smplx_extra_joints_f32(const float* vertices, const float* transl, const int32_t* vertex_index, const float* vertex_weight, int V,
                                 int E, float* out, void* stream);
+
+/* VPoser's pose decoder (forward and backward), its encoder (forward), and the SMPLify angle prior.
+ * replaces: the `pose_decoder` and `angle_prior` hooks of src/application/optimize.py, i.e. the reference's vendored VPoser
+ *           (imports/vposer/vposer_smpl.py: decode(output_type="aa") and its autograd in every iteration, encode once per fit),
+ *           rotation_matrix_to_angle_axis of utils/transformations.py:144-280 and SMPLifyAnglePrior of imports/vposer/prior.py:53-85.
+ * PINNED against that code executed on the CPU in f64 with seeded weights (tests/golden/vposer_golden.npz), through the f64
+ * restatement tests/vposer_ref.py.  N = batch, D = latent size, H = neurons, NJ = joints.  Weights in torch's Linear layout
+ * [out, in], f32.  Rule set:
+ *   layers         lrelu(x) = x where x > 0, else 0.2 x.  h1 = lrelu(W1 z + b1) [H], h2 = lrelu(W2 h1 + b2) [H], o = W3 h2 + b3 [6 NJ].
+ *                  Summation order of one output row: lane l of a wave64 adds W[row, i] x[i] for i = l, l + 64, ... ascending; the 64
+ *                  partial sums are folded by v = v + v[lane xor h] for h = 32, 16, 8, 4, 2, 1; the bias is added last.
+ *   Gram-Schmidt   per joint j the six numbers o[6j ..] are a [3,2] matrix with columns c0 = (o0, o2, o4), c1 = (o1, o3, o5):
+ *                  b1 = c0 / max(|c0|, 1e-12), u = c1 - (b1 . c1) b1, b2 = u / max(|u|, 1e-12), b3 = b1 x b2; the rotation R has the
+ *                  COLUMNS b1, b2, b3 (`matrices` [N,NJ,9] is R row-major).  |v| = sqrt((v0^2 + v1^2) + v2^2).
+ *   quaternion     on T = R^T (T[i] = b_{i+1}; the reference transposes first).  Branch id:
+ *                    T22 < 1e-6:  0 when T00 > T11, else 1;        otherwise:  2 when T00 < -T11, else 3.
+ *                    0: t = 1 + T00 - T11 - T22, cand = (T12 - T21, t, T01 + T10, T20 + T02)
+ *                    1: t = 1 - T00 + T11 - T22, cand = (T20 - T02, T01 + T10, t, T12 + T21)
+ *                    2: t = 1 - T00 - T11 + T22, cand = (T01 - T10, T20 + T02, T12 + T21, t)
+ *                    3: t = 1 + T00 + T11 + T22, cand = (t, T12 - T21, T20 - T02, T01 - T10)
+ *                  (t summed left to right), q = cand / sqrt(t) * 0.5.  Only the selected candidate is evaluated: the reference
+ *                  multiplies the other three by zero before its square root.
+ *   axis-angle     s2 = (q1^2 + q2^2) + q3^2, s = sqrt(s2), two_theta = 2 atan2(-s, -q0) when q0 < 0, else 2 atan2(s, q0);
+ *                  k = two_theta / s where s2 > 0, else 2; aa = (q1, q2, q3) k.
+ *   backward       from grad_aa [N, 3 NJ]: the analytic derivative of the three steps above for the branch the forward stored, then
+ *                  g_h2 = lrelu'(h2) (W3^T g_o), g_h1 = lrelu'(h1) (W2^T g_h2), grad_z = W1^T g_h1, with lrelu' = 1 where the activation
+ *                  is > 0 and 0.2 elsewhere.  Summation order of one input column: wave w of 16 adds W[o, i] g[o] for o = w, w + 16,
+ *                  ... ascending; the 16 partial sums are added in ascending w.  NO gradient with respect to the weights.
+ *                  The map is discontinuous where the angle reaches pi, and where s2 == 0 (the exact identity) k is the constant 2.
+ *                  DEVIATION: at the exact identity the reference's autograd gives NaN (torch.where over 0 / 0 in its backward);
+ *                  this backward returns the finite gradient of the k = 2 branch, d aa / d (q1, q2, q3) = 2.
+ *   encoder        eval-mode BatchNorm1d, y = (x - running_mean) / sqrt(running_var + 1e-5) weight + bias (bn = f32 [4, C]: weight, bias,
+ *                  running_mean, running_var): e = lrelu(W2 bn2(lrelu(W1 bn1(pose) + b1)) + b2); Wml f32 [2 D, H] holds the rows of
+ *                  the mu layer, then those of the logvar layer (bml likewise): mean = first D outputs, scale = softplus of the last D,
+ *                  softplus(x) = x where x > 20, else log1p(exp(x)).  Forward only, no dropout (eval mode).
+ *   angle prior    out[n, i] = exp(sign[i] pose[n, index[i]])^2 for i < K; backward: grad_pose f32 [N, P], zero except
+ *                  grad_pose[n, index[i]] = grad_out[n, i] 2 sign[i] out[n, i] (equal indices are added in ascending i).
+ *   precision      inputs and outputs are f32; all arithmetic is f64 (the work is latency- and bandwidth-bound), so the outputs are the
+ *                  f32 rounding of the rule set.  No floating-point atomics: two calls give the same bits.
+ * Out of scope: training and dropout, the GMM and L2 priors, aa2matrot, the tanh decoder, gradients with respect to the weights.
+ * All pointers are device pointers except `index` (i32 [K]) and `sign` (f32 [K]) of the angle prior: HOST, read during the call.
+ * z f32 [N, D]; aa, grad_aa f32 [N, 3 NJ]; matrices f32 [N, NJ, 9] and branch i8 [N, NJ] may be NULL; pose f32 [N, 3 NJ] (encoder) or
+ * [N, P] (prior); mean, scale f32 [N, D].  saved / workspace: coma_vposer_{saved,workspace}_bytes(N, H, NJ) bytes, 16-byte aligned (0
+ * for sizes the calls refuse); `saved` (h1, h2, o in f64 and the branch ids) is written by a decode and read by ITS backward (one per
+ * forward in flight), `workspace` is scratch shared by all calls on one stream.  Refused before any launch: a null pointer, N outside
+ * [1, 64], D outside [1, 256], H outside [1, 2048], NJ outside [1, 64], P outside [1, 4096], K outside [1, 16], an index outside [0, P),
+ * a buffer too small or misaligned.  Decode: 4 launches, its backward: 4, encode: 5, the prior and its backward: 1 each; caller's
+ * stream, no allocation, no host synchronisation. */
+size_t coma_vposer_saved_bytes(int N, int H, int NJ);
+size_t coma_vposer_workspace_bytes(int N, int H, int NJ);
+int coma_vposer_decode_f32(const float* z, const float* W1, const float* b1, const float* W2, const float* b2, const float* W3,
+                           const float* b3, int N, int D, int H, int NJ, float* aa, float* matrices, int8_t* branch, void* saved,
+                           size_t saved_bytes, void* stream);
+int coma_vposer_decode_backward_f32(const float* grad_aa, const float* W1, const float* W2, const float* W3, int N, int D, int H, int NJ,
+                                    const void* saved, size_t saved_bytes, float* grad_z, void* workspace, size_t workspace_bytes,
+                                    void* stream);
+int coma_vposer_encode_f32(const float* pose, const float* bn1, const float* W1, const float* b1, const float* bn2, const float* W2,
+                           const float* b2, const float* Wml, const float* bml, int N, int D, int H, int NJ, float* mean, float* scale,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int coma_angle_prior_f32(const float* pose, int N, int P, const int32_t* index, const float* sign, int K, float* out, void* stream);
+int coma_angle_prior_backward_f32(const float* pose, const float* grad_out, int N, int P, const int32_t* index, const float* sign, int K,
+                                  float* grad_pose, void* stream);
 
 #ifdef __cplusplus
 }

@@ -18,9 +18,13 @@ The hooks own their torch arithmetic; the optimiser stays torch.optim.Adam besid
     (utils.vposer), which this repository does not carry -- a clear error says so;
   * angle_prior(body_pose [1,63]) -> tensor, summed.  Default: likewise.
 --use_collision is REFUSED: COAP (a learned occupancy network with a downloaded checkpoint) is unpinned and not reproduced, as in the
-depth stage.  Two flags are added: --num_iters (the reference's loop count, 2000, is a literal there) and --body_model {smplx,device}
+depth stage.  Three flags are added: --num_iters (the reference's loop count, 2000, is a literal there), --body_model {smplx,device}
 (default smplx, the hook described above; device = coma_amd.body_model.DeviceSMPLX, the same model files read with NumPy and the
-skinning and its backward run by the library's own kernels).
+skinning and its backward run by the library's own kernels) and --pose_prior {vposer,device} (default vposer, the two hooks described
+above; device = coma_amd.pose_prior.DeviceVPoser on the same experiment directory, imports/vposer, read with configparser and
+torch.load, and coma_amd.pose_prior.DeviceAnglePrior: decoder, its backward and the prior run by the library's own kernels).  With
+--body_model device --pose_prior device the loop needs no third-party package; the torch arithmetic left in it is Adam and the
+embedding's pow(2).sum().
 """
 import argparse
 import os
@@ -34,6 +38,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 BODY_MOCAP_PATH = "imports/hand4whole/common/utils_hand4whole/human_model_files/"
+VPOSER_PATH = "imports/vposer"
 DEFAULT_BETAS = [[-0.00982137, 0.03693837, 0.0949352, -0.01299302, 0.00492086, -0.04505398, -0.0008909, -0.00054313, 0.03646483, -0.00803524]]
 COLLISION_REFUSAL = ("--use_collision is not supported: the reference's collision term is COAP's (a learned occupancy network whose "
                      "checkpoint is not available to this project); run without it")
@@ -53,7 +58,7 @@ def default_pose_decoder(device):
     except ImportError as exc:
         raise RuntimeError("optimize: VPoser (utils.vposer of the reference, third party) is needed for the pose embedding "
                            "(pass pose_decoder=... to run without it)") from exc
-    vposer = load_vposer("imports/vposer", vp_model="snapshot").to(device=device)
+    vposer = load_vposer(VPOSER_PATH, vp_model="snapshot").to(device=device)
     vposer.eval()
     return vposer
 
@@ -164,6 +169,9 @@ def build_parser():
     # absent from the namespace unless given (the parsed defaults stay the reference's parameter set); read through body_model_choice()
     p.add_argument("--body_model", choices=("smplx", "device"), default=argparse.SUPPRESS,
                    help="smplx (default): the third-party package (the reference's); device: coma_amd.body_model.DeviceSMPLX on the same model files")
+    p.add_argument("--pose_prior", choices=("vposer", "device"), default=argparse.SUPPRESS,
+                   help="vposer (default): the reference's VPoser loader and angle prior (third party); device: coma_amd.pose_prior on the same "
+                        "experiment directory")
     return p
 
 
@@ -171,9 +179,19 @@ def body_model_choice(args):
     return getattr(args, "body_model", "smplx")
 
 
+def pose_prior_choice(args):
+    return getattr(args, "pose_prior", "vposer")
+
+
 def device_body_model(device="cuda"):
     from coma_amd.body_model import DeviceSMPLX
     return DeviceSMPLX.from_file(BODY_MOCAP_PATH, num_pca_comps=45, device=device)
+
+
+def device_pose_prior(device="cuda"):
+    """(pose decoder, angle prior) on the device, the decoder from the experiment directory the reference's loader reads."""
+    from coma_amd.pose_prior import DeviceAnglePrior, DeviceVPoser
+    return DeviceVPoser.from_dir(VPOSER_PATH, device=device), DeviceAnglePrior(device=device)
 
 
 def main(args, body_model=None, pose_decoder=None, angle_prior=None):
@@ -181,6 +199,10 @@ def main(args, body_model=None, pose_decoder=None, angle_prior=None):
         raise SystemExit(COLLISION_REFUSAL)
     if body_model is None and body_model_choice(args) == "device":
         body_model = device_body_model()
+    if pose_prior_choice(args) == "device" and (pose_decoder is None or angle_prior is None):
+        decoder, prior = device_pose_prior()
+        pose_decoder = pose_decoder if pose_decoder is not None else decoder
+        angle_prior = angle_prior if angle_prior is not None else prior
     return optimize_smpl(supercategory=args.supercategory, category=args.category, coma_path=args.coma_path,
                          asset_downsample_pth=args.asset_downsample_pth, eps=args.eps, principle_vec=[0, 0, 1], sub_principle_vec=[0, 1, 0],
                          reference_object_vertex_index=0, lr=args.lr, body_pose_weight=args.body_pose_weight,
