@@ -26,6 +26,7 @@
 #include <utility>
 
 #include "common.h"
+#include "sd_device.h"
 #include "sd_plan.h"
 #include "../../include/sd_hip.h"
 
@@ -33,10 +34,6 @@ namespace sd {
 
 using coma::check_launch;
 using coma::fail;
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float float16v __attribute__((ext_vector_type(16)));
 
 constexpr int BKV = 64;            // keys per tile
 
@@ -49,8 +46,6 @@ struct AttnArgs {
   int ldq, ldk, ldv, ldo;
   float scale_log2;   // scale * log2(e)
 };
-
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 // 16-byte chunk slot of K-chunk `chunk` in a 128-byte LDS row (same XOR swizzle as the GEMM's BK = 64 tiles): the rows
 // read by one ds_read lane group land on distinct bank slots for both the b128 K reads and the b64 V^T reads
@@ -117,12 +112,6 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(AttnArgs a) {
   // dims, valid bytes end with row d-1.  Anything beyond fails the range check and lands in LDS as zeros.
   const _Float16* kbase = a.k + (long long)b * a.lk * a.ldk + h * d;
   const _Float16* vbase = a.vt + ((long long)b * a.heads + h) * d * (long long)a.ldv;
-  auto make_rsrc = [](const void* p, unsigned bytes) {
-    const unsigned long long u = reinterpret_cast<unsigned long long>(p);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0,
-                                             __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
-  };
   const __amdgpu_buffer_rsrc_t k_rsrc = make_rsrc(kbase, (unsigned)(((long long)(a.lk - 1) * a.ldk + d) * 2));
   const __amdgpu_buffer_rsrc_t v_rsrc = make_rsrc(vbase, (unsigned)((long long)d * a.ldv * 2));
   constexpr unsigned OOB = 0x80000000u;
@@ -199,7 +188,6 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(AttnArgs a) {
     // Scores stay RAW in the accumulators; scale*log2(e) rides in the FMA that forms the exp2 argument.  The
     // running max is only raised when it would grow by more than RESCALE_THR (log2 units): P may then reach
     // 2^THR (fine in fp16/fp32) and the O / l rescale becomes a rare, wave-uniformly skipped branch.
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
     half8 pf[QT][4];
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) {
@@ -370,12 +358,6 @@ __global__ __launch_bounds__(256, 1) void attention_sp_kernel(AttnArgs a) {
   // ---- LDS-DMA set-up (as in attention_kernel): K rows = keys, 5 valid 16-byte chunks per row; V^T rows = head dims
   const _Float16* kbase = a.k + (long long)b * a.lk * a.ldk + h * D;
   const _Float16* vbase = a.vt + ((long long)b * a.heads + h) * D * (long long)a.ldv;
-  auto make_rsrc = [](const void* p, unsigned bytes) {
-    const unsigned long long u = reinterpret_cast<unsigned long long>(p);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0,
-                                             __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
-  };
   const __amdgpu_buffer_rsrc_t k_rsrc = make_rsrc(kbase, (unsigned)(((long long)(a.lk - 1) * a.ldk + D) * 2));
   const __amdgpu_buffer_rsrc_t v_rsrc = make_rsrc(vbase, (unsigned)((long long)D * a.ldv * 2));
   const int l_row = lane >> 3, l_slot = lane & 7;
@@ -663,7 +645,6 @@ __global__ __launch_bounds__(NW * 64, 1) void attention_wide_kernel(AttnArgs a) 
   extern __shared__ __attribute__((aligned(1024))) _Float16 wide_smem[];
   _Float16* Kbuf = wide_smem;                      // [64 keys][D]
   _Float16* Vbuf = wide_smem + BKV * D;            // [D rows][64 keys]
-  typedef float float4v __attribute__((ext_vector_type(4)));
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -696,12 +677,6 @@ __global__ __launch_bounds__(NW * 64, 1) void attention_wide_kernel(AttnArgs a) 
   // V^T: 8 rows of 128 bytes per instruction, swz64 as in the other kernels.
   const _Float16* kbase = a.k + (long long)b * a.lk * a.ldk + h * D;
   const _Float16* vbase = a.vt + ((long long)b * a.heads + h) * D * (long long)a.ldv;
-  auto make_rsrc = [](const void* p, unsigned bytes) {
-    const unsigned long long u = reinterpret_cast<unsigned long long>(p);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0,
-                                             __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
-  };
   const __amdgpu_buffer_rsrc_t k_rsrc = make_rsrc(kbase, (unsigned)(((long long)(a.lk - 1) * a.ldk + D) * 2));
   const __amdgpu_buffer_rsrc_t v_rsrc = make_rsrc(vbase, (unsigned)((long long)D * a.ldv * 2));
   constexpr int KPI = D / 512 > 0 ? D / 512 : 1;   // K instructions per key row (D = 512: 1); smaller D: several rows per instruction

@@ -1,6 +1,6 @@
 // Internal: the GELU of the GEGLU epilogues (sd_gemm.hip, sd_xtail.hip).
 #pragma once
-#include <hip/hip_runtime.h>
+#include "sd_device.h"
 
 namespace sd {
 
@@ -11,7 +11,6 @@ namespace sd {
 // operations per pair against 32 scalar ones + 4 quarter-rate transcendentals for the Abramowitz-Stegun erfc form used before
 // (|error| 4e-7, relative in the negative tail) -- the VALU time of the GEGLU epilogue is not hidden behind anything, it was
 // a third of the kernel (profiles/r02_notes.md section 11).
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x2 gelu_erf2(f32x2 x) {
   const f32x2 xc = {__builtin_amdgcn_fmed3f(x.x, -5.0f, 5.0f), __builtin_amdgcn_fmed3f(x.y, -5.0f, 5.0f)};
   const f32x2 u = __builtin_elementwise_fma(xc * xc, (f32x2){0.08f, 0.08f}, (f32x2){-1.0f, -1.0f});

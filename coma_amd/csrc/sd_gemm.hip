@@ -22,6 +22,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "sd_device.h"
 #include "sd_gelu.h"
 #include "sd_plan.h"
 #include "../../include/sd_hip.h"
@@ -30,11 +31,6 @@ namespace sd {
 
 using coma::check_launch;
 using coma::fail;
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float float16v __attribute__((ext_vector_type(16)));
-typedef float float4v __attribute__((ext_vector_type(4)));
 
 constexpr int BKMIN = 32;   // source channel counts must be multiples of this (and of 64 for the deep-K variant)
 
@@ -113,8 +109,6 @@ __device__ __forceinline__ float epilogue_value(const GemmArgs& g, float v, int 
   return v;
 }
 
-typedef __attribute__((address_space(3))) void* lptr_t;
-
 // LDS tile image: [rows][BK halves], unpadded rows filled by LDS-DMA (global_load_lds, 16 B per lane), so one wave
 // instruction writes 1 KiB lane-linearly (8 rows of 128 B at BK = 64, 16 rows of 64 B at BK = 32).  Bank conflicts of
 // the ds_read_b128 fragment reads are removed by an XOR swizzle applied on the SOURCE side: the 16-byte slot p of row r
@@ -126,9 +120,6 @@ template <int BK>
 __device__ __forceinline__ int swz(int row, int chunk) {
   return BK == 64 ? (chunk ^ ((row >> 1) & 7)) : (chunk ^ ((row >> 2) & 3));
 }
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // Epilogue shared by every kernel of the family: acc[2][TN] (MFMA C layout, see below) -> bias / per-sample bias / SiLU /
 // residual / GEGLU / GroupNorm column statistics -> fp16 output (or fp32 split-K slab), staged through LDS per wave.
@@ -594,11 +585,6 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_gemm_kernel(GemmArgs g) {
   }
   // buffer resources and scalar offsets must live in SGPRs: pin them with readfirstlane (every input is wave-uniform,
   // but the compiler's divergence analysis would otherwise wrap each DMA in a waterfall loop)
-  auto make_rsrc = [](const void* p) {
-    const unsigned long long a = reinterpret_cast<unsigned long long>(p);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0, 0x7fffffff, 0x00020000);
-  };
   const __amdgpu_buffer_rsrc_t w_rsrc = make_rsrc(wp);
   const int lim_h = g.upsample ? 2 * g.in_h : g.in_h;
   const int lim_w = g.upsample ? 2 * g.in_w : g.in_w;

@@ -29,6 +29,7 @@
 #include <hip/hip_fp16.h>
 
 #include "common.h"
+#include "sd_device.h"
 #include "sd_plan.h"
 #include "../../include/sd_hip.h"
 
@@ -38,11 +39,7 @@ namespace hc {
 using coma::check_launch;
 using coma::fail;
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float float4v __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 constexpr int kTile = 16, kHalo = 18, kChunk = 64, kN = 128;
 constexpr int kPatchBytes = kHalo * kHalo * 8 * 16;      // 41 472: 324 pixels x 8 octets of 8 channels
@@ -57,9 +54,6 @@ static_assert(4 * 64 * kStageRow + 4 * 2 * 2 * 64 * 4 <= kAffOff, "epilogue stag
 // groups (18 is even, so pixel parity = column parity; (c >> 1) & 7 takes 8 values over 16 consecutive columns, each at both parities).
 // The swizzle depends on the COLUMN only, so a tap's row shift is a constant byte offset of the fragment address.
 __device__ __forceinline__ int pslot(int r, int c, int v) { return (r * kHalo + c) * 8 + (v ^ ((c >> 1) & 7)); }
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 struct HaloArgs {
   const _Float16* x;          // NHWC [batch][H][W][C]
@@ -110,11 +104,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(HaloArgs a) {
   const int C = a.C, nchunk = C / kChunk, nkt = 9 * nchunk;
   const int nsplit = a.ntot / kN;
 
-  auto make_rsrc = [](const void* p) {
-    const unsigned long long q = reinterpret_cast<unsigned long long>(p);
-    const unsigned lo32 = __builtin_amdgcn_readfirstlane((unsigned)q), hi32 = __builtin_amdgcn_readfirstlane((unsigned)(q >> 32));
-    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi32 << 32) | lo32), 0, 0x7fffffff, 0x00020000);
-  };
   // ---- weight slices by LDS-DMA: instruction j of this wave covers rows (wave * 4 + j) * 8 .. + 7 of the slice; lane -> row + lane / 8,
   // LDS slot lane % 8, which must receive K octet slot ^ ((row >> 1) & 7)
   // (row r + 8 j: the swizzle term (r >> 1) & 7 only flips bit 2 for odd j -> two lane registers serve the four instructions)

@@ -10,6 +10,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "sd_device.h"
 #include "sd_plan.h"
 #include "../../include/sd_hip.h"
 
@@ -19,16 +20,8 @@ using coma::check_launch;
 using coma::fail;
 using coma::kWave;
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-
 constexpr int GN_PIX = 64;       // pixels per partial-sum block
 constexpr int GN_MAX_GROUPS = 32;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  return v;
-}
 
 __device__ __forceinline__ half8 load8(const _Float16* x0, const _Float16* x1, int c0, int c1, long long pix, int c) {
   const _Float16* p = c < c0 ? x0 + pix * c0 + c : x1 + pix * c1 + (c - c0);
@@ -188,7 +181,6 @@ __global__ __launch_bounds__(256) void gn_finalize_colstats_kernel(const float* 
 // hw x (C/G) slice (<= GN_SMALL_ITEMS * 256 four-channel chunks) is read ONCE into registers, reduced through LDS in a
 // fixed order, normalised and written -- three launches and two extra passes over L2 become one.
 constexpr int GN_SMALL_ITEMS = 20;
-typedef _Float16 half4v __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(256) void gn_small_kernel(const _Float16* __restrict__ x0, const _Float16* __restrict__ x1, int c0,
                                                        int c1, int hw, int groups, float eps, const _Float16* __restrict__ gamma,
                                                        const _Float16* __restrict__ beta, int silu, _Float16* __restrict__ out) {
@@ -196,7 +188,7 @@ __global__ __launch_bounds__(256) void gn_small_kernel(const _Float16* __restric
   const int C = c0 + c1, cg = C / groups, q4 = cg / 4;
   const int g = blockIdx.x, b = blockIdx.y;
   const int items = hw * q4;
-  half4v v[GN_SMALL_ITEMS];
+  half4 v[GN_SMALL_ITEMS];
   float s = 0.0f, q = 0.0f;
 #pragma unroll
   for (int k = 0; k < GN_SMALL_ITEMS; ++k) {
@@ -204,7 +196,7 @@ __global__ __launch_bounds__(256) void gn_small_kernel(const _Float16* __restric
     if (it < items) {
       const int p = it / q4, c = g * cg + (it - p * q4) * 4;
       const long long pix = (long long)b * hw + p;
-      v[k] = *reinterpret_cast<const half4v*>(c < c0 ? x0 + pix * c0 + c : x1 + pix * c1 + (c - c0));
+      v[k] = *reinterpret_cast<const half4*>(c < c0 ? x0 + pix * c0 + c : x1 + pix * c1 + (c - c0));
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const float f = (float)v[k][j];
@@ -228,8 +220,8 @@ __global__ __launch_bounds__(256) void gn_small_kernel(const _Float16* __restric
     const int it = threadIdx.x + k * 256;
     if (it < items) {
       const int p = it / q4, c = g * cg + (it - p * q4) * 4;
-      const half4v ga = *reinterpret_cast<const half4v*>(gamma + c), be = *reinterpret_cast<const half4v*>(beta + c);
-      half4v o;
+      const half4 ga = *reinterpret_cast<const half4*>(gamma + c), be = *reinterpret_cast<const half4*>(beta + c);
+      half4 o;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const float sc = rstd * (float)ga[j];
@@ -237,7 +229,7 @@ __global__ __launch_bounds__(256) void gn_small_kernel(const _Float16* __restric
         if (silu) y = y / (1.0f + __expf(-y));
         o[j] = (_Float16)y;
       }
-      *reinterpret_cast<half4v*>(out + ((long long)b * hw + p) * C + c) = o;
+      *reinterpret_cast<half4*>(out + ((long long)b * hw + p) * C + c) = o;
     }
   }
 }

@@ -10,6 +10,7 @@
 #include <hip/hip_fp16.h>
 
 #include "common.h"
+#include "sd_device.h"
 #include "sd_plan.h"
 #include "../../include/sd_hip.h"
 
@@ -18,9 +19,6 @@ namespace sc {
 
 using coma::check_launch;
 using coma::fail;
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float float4v __attribute__((ext_vector_type(4)));
 
 constexpr int kTile = 16, kHalo = 18, kChunk = 64;       // pixels per tile edge, with halo, channels staged per pass
 
@@ -156,7 +154,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_small_n_kernel(const _Float16*
 // utils/adaptive_mask_inpainting.py:677-680).  Through the implicit GEMM it multiplied a 64-channel padded input (K = 576 for 27 real
 // products per output).  Here one elementwise pass packs every pixel's 3 x 3 x 3 neighbourhood into 32 halfs (k = 3 * tap + channel, 5
 // zeros) and the convolution becomes a plain K = 32 product of the existing GEMM.
-typedef _Float16 half4s __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(256) void im2col3x3_c3_kernel(const _Float16* __restrict__ x, int ldx, int batch, int H, int W,
                                                           _Float16* __restrict__ out) {
   const long long m = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -169,8 +166,8 @@ __global__ __launch_bounds__(256) void im2col3x3_c3_kernel(const _Float16* __res
 #pragma unroll
   for (int tap = 0; tap < 9; ++tap) {
     const int yy = y + tap / 3 - 1, xc = xx + tap % 3 - 1;
-    half4s q = {0, 0, 0, 0};
-    if (yy >= 0 && yy < H && xc >= 0 && xc < W) q = *reinterpret_cast<const half4s*>(x + ((b * H + yy) * W + xc) * ldx);
+    half4 q = {0, 0, 0, 0};
+    if (yy >= 0 && yy < H && xc >= 0 && xc < W) q = *reinterpret_cast<const half4*>(x + ((b * H + yy) * W + xc) * ldx);
     v[3 * tap + 0] = q[0]; v[3 * tap + 1] = q[1]; v[3 * tap + 2] = q[2];
   }
   half8* o = reinterpret_cast<half8*>(out + m * 32);
@@ -226,8 +223,8 @@ __global__ __launch_bounds__(256) void conv3x3_c3_kernel(const _Float16* __restr
   for (int p = tid; p < kHalo * kHalo; p += 256) {
     const int r = p / kHalo, c = p - r * kHalo;
     const int yy = ty0 + r - 1, xx = tx0 + c - 1;
-    half4s q = {0, 0, 0, 0};
-    if (yy >= 0 && yy < H && xx >= 0 && xx < W) q = *reinterpret_cast<const half4s*>(x + (((long long)b * H + yy) * W + xx) * ldx);
+    half4 q = {0, 0, 0, 0};
+    if (yy >= 0 && yy < H && xx >= 0 && xx < W) q = *reinterpret_cast<const half4*>(x + (((long long)b * H + yy) * W + xx) * ldx);
     _Float16* d = patch + r * kC3Row + c * 3;
     d[0] = q[0]; d[1] = q[1]; d[2] = q[2];
   }
@@ -256,8 +253,7 @@ __global__ __launch_bounds__(256) void conv3x3_c3_kernel(const _Float16* __restr
 #pragma unroll
     for (int nb = 0; nb < 8; ++nb) {
       const float4v acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[nb], xf, float4v{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-      typedef _Float16 half4v __attribute__((ext_vector_type(4)));
-      half4v o;
+      half4 o;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         o[i] = (_Float16)(acc[i] + bv[nb][i]);
@@ -265,7 +261,7 @@ __global__ __launch_bounds__(256) void conv3x3_c3_kernel(const _Float16* __restr
         cs[nb][i] += f;
         cq[nb][i] += f * f;
       }
-      *reinterpret_cast<half4v*>(stg + px * kC3Stage + nb * 16 + 4 * g) = o;
+      *reinterpret_cast<half4*>(stg + px * kC3Stage + nb * 16 + 4 * g) = o;
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();

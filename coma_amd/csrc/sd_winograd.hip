@@ -16,6 +16,7 @@
 #include <hip/hip_fp16.h>
 
 #include "common.h"
+#include "sd_device.h"
 #include "sd_plan.h"
 #include "../../include/sd_hip.h"
 
@@ -23,8 +24,6 @@ namespace sd {
 
 using coma::check_launch;
 using coma::fail;
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 
 // thread = (tile, chunk of 8 channels); V[p][t][c], p = 4 i + j
 // affine != nullptr: the source is first normalised per (sample, channel) -- y = x * scale + shift, fp32 [batch][c0+c1][2], the table of a
@@ -282,7 +281,6 @@ __global__ void __launch_bounds__(256) winograd_output_cs_kernel(const _Float16*
 // Three launches of the unfused chain (output transform, GroupNorm, input transform) become one; the arithmetic of every stage is the
 // unfused kernels' (same statistics formula, same affine + SiLU expression, transforms in fp32 rounded once).
 constexpr int kGnWinoMaxSlice = 20480;          // halfs: 16 x 16 pixels x 80 channels (C = 2560, 32 groups)
-typedef _Float16 half4w __attribute__((ext_vector_type(4)));
 
 struct GnWinoArgs {
   const _Float16 *x0, *x1;
@@ -298,12 +296,6 @@ struct GnWinoArgs {
   float mscale;               // mode 1: h = mscale * A^T m A + bias (the planes were stored scaled by 1 / mscale)
   _Float16* v;                // fp16 [16][batch * T][C]
 };
-
-__device__ __forceinline__ float wave_sum64(float x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-  return x;
-}
 
 // VEC = channels per lane in the plane-product load, the normalisation and the transform (8 when the group width allows 16-byte
 // accesses, else 4).  The NHWC load keeps 4-channel chunks in sd_groupnorm_f16's own thread order, so that the statistics -- and with
@@ -322,8 +314,8 @@ __global__ __launch_bounds__(256) void gn_winograd_input_kernel(GnWinoArgs a) {
     for (int it = tid; it < hw * q4; it += 256) {
       const int p = it / q4, cc = (it - p * q4) * 4, c = g * cg + cc;
       const long long pix = (long long)b * hw + p;
-      const half4w v4 = *reinterpret_cast<const half4w*>(c < a.c0 ? a.x0 + pix * a.c0 + c : a.x1 + pix * a.c1 + (c - a.c0));
-      *reinterpret_cast<half4w*>(slice + p * cg + cc) = v4;
+      const half4 v4 = *reinterpret_cast<const half4*>(c < a.c0 ? a.x0 + pix * a.c0 + c : a.x1 + pix * a.c1 + (c - a.c0));
+      *reinterpret_cast<half4*>(slice + p * cg + cc) = v4;
 #pragma unroll
       for (int j = 0; j < 4; ++j) { const float f = (float)v4[j]; s += f; q += f * f; }
     }
@@ -373,8 +365,8 @@ __global__ __launch_bounds__(256) void gn_winograd_input_kernel(GnWinoArgs a) {
         }
     }
   }
-  s = wave_sum64(s);
-  q = wave_sum64(q);
+  s = wave_sum(s);
+  q = wave_sum(q);
   if ((tid & 63) == 0) { rs[tid >> 6] = s; rq[tid >> 6] = q; }
   __syncthreads();
   s = (rs[0] + rs[1]) + (rs[2] + rs[3]);

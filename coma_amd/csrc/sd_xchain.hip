@@ -28,31 +28,29 @@
 //   cross attention: wave (wr, wc) handles its 32 rows for heads 4 wc .. 4 wc + 3.  77 keys = 3 key tiles: K and V^T fragments come
 //         straight from global memory into registers (98 KB per sample, L2-resident; no LDS, no barrier), the next head's fragments
 //         are in flight while this head is multiplied; softmax in one pass (all keys at once), denominator from a synthetic ones row.
+// The tile DMA, the weight-slice pipeline, the K = 320 product, the accumulator writer and the row passes are the row-tile toolkit of
+// sd_rowtile.h, shared with xfront_kernel below and xtail_kernel (sd_xtail.hip); this file holds the phase sequences, the cross
+// attention and xfront's GroupNorm affine, re-reading LayerNorm and V^T staging.
 #include <hip/hip_fp16.h>
 
 #include <type_traits>
 
 #include "common.h"
 #include "sd_plan.h"
+#include "sd_rowtile.h"
 #include "../../include/sd_hip.h"
 
 namespace sd {
 
-using coma::check_launch;
 using coma::fail;
 
 namespace xc {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float float16v __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(3))) void* lptr_t;
+using namespace rowtile;
 
-constexpr int C = 320, TM = 64, NW = 4, BK = 32, HEADS = 8, D = 40;   // 64-row tiles: 80 KB of LDS, TWO workgroups per CU
+constexpr int TM = 64, NW = 4, HEADS = 8, D = 40;     // 64-row tiles: 80 KB of LDS, TWO workgroups per CU
 constexpr int T_BYTES = TM * C * 2;                   // 40 KB
-constexpr int WB_STAGE = C * BK;                      // halves per weight slice
 constexpr int LDS_BYTES = T_BYTES + 2 * WB_STAGE * 2; // 40 + 40 KB
-constexpr unsigned OOB = 0x80000000u;
 
 struct Args {
   const _Float16 *a, *h, *wo1, *bo1, *g2, *b2, *wq, *k2, *vt2, *wo2, *bo2, *g3, *b3;
@@ -60,19 +58,6 @@ struct Args {
   int M, rows_per_sample, lk, ldv2, stage;
   float scale_log2, eps;
 };
-
-// 16-byte chunk slot of logical chunk c (0..39) in row `row` of T: the 8 chunks of a 128-byte group are permuted with the row,
-// rows alternate between the two halves of the 256-byte bank window (640 = 512 + 128) -> conflict-free fragment reads
-__device__ __forceinline__ int tswz(int row, int c) { return (c & ~7) | ((c ^ (row >> 1)) & 7); }
-// weight slice rows are 64 bytes (4 chunks)
-__device__ __forceinline__ int wswz(int row, int c) { return c ^ ((row >> 2) & 3); }
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes) {
-  const unsigned long long u = reinterpret_cast<unsigned long long>(p);
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-  return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0,
-                                           __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
-}
 
 __global__ __launch_bounds__(NW * 64, 2) void xchain_kernel(Args g) {
   extern __shared__ __attribute__((aligned(1024))) unsigned char xsmem[];
@@ -86,148 +71,35 @@ __global__ __launch_bounds__(NW * 64, 2) void xchain_kernel(Args g) {
   const int l31 = lane & 31, hh = lane >> 5;
   const int my_row = wr * 32 + l31;                   // the tile row this lane owns in every product
 
-  // ---- tile DMA: 128 rows x 40 chunks = 80 pieces of 1 KiB, 10 per wave; lane -> (row, slot) of the piece, source chunk un-swizzled
-  // (tswz is an involution).  The offsets are recomputed per use (three uses): 10 registers less to carry through the kernel.
-  const unsigned tensor_bytes = (unsigned)((long long)g.M * C * 2);
-  auto load_tile = [&](const _Float16* src) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    const __amdgpu_buffer_rsrc_t rs = make_rsrc(src, tensor_bytes);
-#pragma unroll
-    for (int j = 0; j < 10; ++j) {
-      const int q = (wave * 10 + j) * 64 + lane;
-      const int row = q / 40, slot = q - row * 40;
-      const unsigned off = (m0 + row) < g.M ? (unsigned)(((long long)(m0 + row) * C + tswz(row, slot) * 8) * 2) : OOB;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lptr_t)(T + (wave * 10 + j) * 512), 16, off, 0, 0, 0);
-    }
-#endif
-  };
-  // ---- weight slice DMA: [320 rows][32 k] = 20 pieces, 5 per wave
-  static_assert(TM * 40 / 64 / NW == 10 && 20 % NW == 0, "DMA piece counts");
-  constexpr int WPW = 20 / NW;
-  unsigned w_off[WPW];
-#pragma unroll
-  for (int j = 0; j < WPW; ++j) {
-    const int p = wave + NW * j;
-    const int row = p * 16 + (lane >> 2), slot = lane & 3;
-    w_off[j] = (unsigned)((row * C + wswz(row, slot) * 8) * 2);
-  }
-  auto issue_w = [&](const __amdgpu_buffer_rsrc_t& rs, int buf, int s) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    _Float16* dst = WB + buf * WB_STAGE;
-#pragma unroll
-    for (int j = 0; j < WPW; ++j)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lptr_t)(dst + (wave + NW * j) * 512), 16, w_off[j] + s * (BK * 2), 0, 0, 0);
-#endif
-  };
+  const int rows[1] = {my_row};                       // one 32-row tile per wave
 
-  float16v acc[5];
-  // acc = T[128 x 320] . W[320 x 320]^T for this wave's 32 x 160 patch.  Entry: T complete and visible (a barrier has passed).
-  auto gemm = [&](const _Float16* w) {
-    const __amdgpu_buffer_rsrc_t rs = make_rsrc(w, (unsigned)(C * C * 2));
-#pragma unroll
-    for (int j = 0; j < 5; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[j][r] = 0.0f;
-    issue_w(rs, 0, 0);
-#pragma unroll 1
-    for (int s = 0; s < C / BK; ++s) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();                  // slice s landed everywhere; every wave is done with the other stage
-      if (s + 1 < C / BK) issue_w(rs, (s + 1) & 1, s + 1);
-      const _Float16* Wb = WB + (s & 1) * WB_STAGE;
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        const int ks = 2 * s + kk;
-        const half8 af = *reinterpret_cast<const half8*>(&T[my_row * C + tswz(my_row, 2 * ks + hh) * 8]);
-        half8 wf[5];
-#pragma unroll
-        for (int j = 0; j < 5; ++j) {
-          const int n = wc * 160 + j * 32 + l31;
-          wf[j] = *reinterpret_cast<const half8*>(&Wb[n * BK + wswz(n, 2 * kk + hh) * 8]);
-        }
-#pragma unroll
-        for (int j = 0; j < 5; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[j], af, acc[j], 0, 0, 0);
-      }
-    }
-    __builtin_amdgcn_s_barrier();                    // every wave is done reading T and WB
-  };
-  // register quad (j, rg) of a lane = 4 consecutive columns starting at col(j, rg) of row my_row
-  auto quad_col = [&](int j, int rg) { return wc * 160 + j * 32 + 8 * rg + 4 * hh; };
-  auto quad_ptr = [&](int j, int rg) {
-    const int col = quad_col(j, rg);
-    return &T[my_row * C + tswz(my_row, col >> 3) * 8 + (col & 7)];
-  };
-  // T <- fp16(acc (+ bias + T))
-  auto write_tile = [&](const _Float16* bias, bool add_tile) {
-#pragma unroll
-    for (int j = 0; j < 5; ++j)
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg) {
-        _Float16* p = quad_ptr(j, rg);
-        float v[4] = {acc[j][rg * 4 + 0], acc[j][rg * 4 + 1], acc[j][rg * 4 + 2], acc[j][rg * 4 + 3]};
-        if (bias) {
-          const half4 bv = *reinterpret_cast<const half4*>(bias + quad_col(j, rg));
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] += (float)bv[e];
-        }
-        if (add_tile) {
-          const half4 tv = *reinterpret_cast<const half4*>(p);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] += (float)tv[e];
-        }
-        *reinterpret_cast<half4*>(p) = half4{(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
-      }
-  };
-  // row pass: 4 lanes per row, 10 chunks each.  Stores the row (as it stands in T) to `res_out`, LayerNorms it and either writes the
-  // normalised row back into T (ln_out == nullptr) or stores it to ln_out.
+  // thin wrappers over the row-tile toolkit (sd_rowtile.h).  The tile DMA recomputes its lane offsets per use (three uses): 10
+  // registers less to carry through the kernel; the weight-slice offsets are computed once.
+  const unsigned tensor_bytes = (unsigned)((long long)g.M * C * 2);
+  auto load = [&](const _Float16* src) { load_tile<TM, NW>(T, src, tensor_bytes, m0, g.M, wave, lane); };
+  unsigned w_off[20 / NW];
+  slice_offsets<NW>(w_off, wave, lane);
+  float16v acc[1][5];
+  // acc = T[64 x 320] . W[320 x 320]^T for this wave's 32 x 160 patch.  Entry: T complete and visible (a barrier has passed).
+  auto gemm = [&](const _Float16* w) { product320<NW, false>(acc, T, WB, w, w_off, rows, wave, wc, l31, hh); };
+  // row pass: stores the row (as it stands in T) to `res_out`, LayerNorms it into T (ln_out == nullptr) or to ln_out
   auto row_pass = [&](_Float16* res_out, const _Float16* gamma, const _Float16* beta, _Float16* ln_out) {
-    const int row = tid >> 2, qtr = tid & 3;
-    const bool ok = m0 + row < g.M;
-    half8 x[10];
-    float sum = 0.0f, sq = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-      const int c = qtr * 10 + i;
-      x[i] = *reinterpret_cast<const half8*>(&T[row * C + tswz(row, c) * 8]);
-      if (ok && res_out) *reinterpret_cast<half8*>(res_out + (long long)(m0 + row) * C + c * 8) = x[i];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { const float f = (float)x[i][e]; sum += f; sq += f * f; }
-    }
-    sum += __shfl_xor(sum, 1); sq += __shfl_xor(sq, 1);
-    sum += __shfl_xor(sum, 2); sq += __shfl_xor(sq, 2);
-    const float mean = sum * (1.0f / C);
-    const float var = fmaxf(sq * (1.0f / C) - mean * mean, 0.0f);
-    const float rstd = rsqrtf(var + g.eps);
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-      const int c = qtr * 10 + i;
-      const half8 gm = *reinterpret_cast<const half8*>(gamma + c * 8), bt = *reinterpret_cast<const half8*>(beta + c * 8);
-      half8 y;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) y[e] = (_Float16)(((float)x[i][e] - mean) * rstd * (float)gm[e] + (float)bt[e]);
-      if (ln_out) { if (ok) *reinterpret_cast<half8*>(ln_out + (long long)(m0 + row) * C + c * 8) = y; }
-      else *reinterpret_cast<half8*>(&T[row * C + tswz(row, c) * 8]) = y;
-    }
+    layernorm_rows(T, res_out, gamma, beta, ln_out, g.eps, m0, g.M, tid);
   };
   auto dump = [&]() {                                 // debug: T in logical order -> g.dbg
     __syncthreads();
-    const int row = tid >> 2, qtr = tid & 3;
-    if (g.dbg && m0 + row < g.M)
-      for (int i = 0; i < 10; ++i) {
-        const int c = qtr * 10 + i;
-        *reinterpret_cast<half8*>(g.dbg + (long long)(m0 + row) * C + c * 8) = *reinterpret_cast<const half8*>(&T[row * C + tswz(row, c) * 8]);
-      }
+    if (g.dbg) store_rows<TM, NW>(T, g.dbg, C, 0, m0, g.M, tid);
   };
 
   // ================================================================================================ phase 1: h1, n2
-  load_tile(g.a);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  load(g.a);
+  wait_vmcnt<0>();
   __syncthreads();
   gemm(g.wo1);
-  load_tile(g.h);                                     // T is free: the residual tile comes in coalesced
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  load(g.h);                                          // T is free: the residual tile comes in coalesced
+  wait_vmcnt<0>();
   __syncthreads();
-  write_tile(g.bo1, true);                            // T = h1 (each quad is read and written by the lane that owns it)
+  write_acc<1, true, true>(acc, rows, g.bo1, T, wc, hh);        // T = acc + bo1 + T = h1
   __syncthreads();
   if (g.stage == 1) { dump(); return; }
   row_pass(g.h2, g.g2, g.b2, nullptr);                // h1 -> the h2 buffer (comes back in phase 4, from L2); T = n2
@@ -235,7 +107,7 @@ __global__ __launch_bounds__(NW * 64, 2) void xchain_kernel(Args g) {
   if (g.stage == 2) { dump(); return; }
   // ================================================================================================ phase 2: q2
   gemm(g.wq);
-  write_tile(nullptr, false);                         // T = q2
+  write_acc<1, false, false>(acc, rows, nullptr, T, wc, hh);    // T = q2
   __syncthreads();
   if (g.stage == 3) { dump(); return; }
   // ================================================================================================ phase 3: cross attention
@@ -359,14 +231,13 @@ __global__ __launch_bounds__(NW * 64, 2) void xchain_kernel(Args g) {
   if (g.stage == 4) { dump(); return; }
   // ================================================================================================ phase 4: h2, n3
   gemm(g.wo2);
-  load_tile(g.h2);                                    // h1, written in phase 1 by this workgroup
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  load(g.h2);                                         // h1, written in phase 1 by this workgroup
+  wait_vmcnt<0>();
   __syncthreads();
-  write_tile(g.bo2, true);                            // T = h2
+  write_acc<1, true, true>(acc, rows, g.bo2, T, wc, hh);        // T = h2
   __syncthreads();
   row_pass(g.h2, g.g3, g.b3, g.n3);
 }
-
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // xfront_kernel -- the row-local FRONT of a C = 320 transformer block in one launch:
@@ -400,101 +271,20 @@ __global__ __launch_bounds__(NW * 64, 2) void xfront_kernel(FrontArgs g) {
   const int my_row = wr * 32 + l31;
   const int b = m0 / g.rows_per_sample, tok0 = m0 - b * g.rows_per_sample;
 
+  const int rows[1] = {my_row};
   const unsigned tensor_bytes = (unsigned)((long long)g.M * C * 2);
-  auto load_tile = [&](const _Float16* src) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    const __amdgpu_buffer_rsrc_t rs = make_rsrc(src, tensor_bytes);
-#pragma unroll
-    for (int j = 0; j < 10; ++j) {
-      const int q = (wave * 10 + j) * 64 + lane;
-      const int row = q / 40, slot = q - row * 40;
-      const unsigned off = (m0 + row) < g.M ? (unsigned)(((long long)(m0 + row) * C + tswz(row, slot) * 8) * 2) : OOB;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lptr_t)(T + (wave * 10 + j) * 512), 16, off, 0, 0, 0);
-    }
-#endif
-  };
-  constexpr int WPW = 20 / NW;
-  unsigned w_off[WPW];
-#pragma unroll
-  for (int j = 0; j < WPW; ++j) {
-    const int p = wave + NW * j;
-    const int row = p * 16 + (lane >> 2), slot = lane & 3;
-    w_off[j] = (unsigned)((row * C + wswz(row, slot) * 8) * 2);
-  }
-  auto issue_w = [&](const __amdgpu_buffer_rsrc_t& rs, int buf, int s) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    _Float16* dst = WB + buf * WB_STAGE;
-#pragma unroll
-    for (int j = 0; j < WPW; ++j)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lptr_t)(dst + (wave + NW * j) * 512), 16, w_off[j] + s * (BK * 2), 0, 0, 0);
-#endif
-  };
-  float16v acc[5];
-  // swapped = false: acc[j][.] = rows my_row x columns (wc, j) of T W^T (a lane owns a token row);
+  unsigned w_off[20 / NW];
+  slice_offsets<NW>(w_off, wave, lane);
+  float16v acc[1][5];
+  // swapped = false: acc[0][j][.] = rows my_row x columns (wc, j) of T W^T (a lane owns a token row);
   // swapped = true : the operand roles exchanged -- a lane owns weight row wc * 160 + 32 j + l31 and 4 consecutive tokens of tile wr
   auto gemm = [&](const _Float16* w, auto swapc) {
-    constexpr bool SWAPPED = decltype(swapc)::value;
-    const __amdgpu_buffer_rsrc_t rs = make_rsrc(w, (unsigned)(C * C * 2));
-#pragma unroll
-    for (int j = 0; j < 5; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[j][r] = 0.0f;
-    issue_w(rs, 0, 0);
-#pragma unroll 1
-    for (int s = 0; s < C / BK; ++s) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      if (s + 1 < C / BK) issue_w(rs, (s + 1) & 1, s + 1);
-      const _Float16* Wb = WB + (s & 1) * WB_STAGE;
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        const int ks = 2 * s + kk;
-        const half8 af = *reinterpret_cast<const half8*>(&T[my_row * C + tswz(my_row, 2 * ks + hh) * 8]);
-        half8 wf[5];
-#pragma unroll
-        for (int j = 0; j < 5; ++j) {
-          const int n = wc * 160 + j * 32 + l31;
-          wf[j] = *reinterpret_cast<const half8*>(&Wb[n * BK + wswz(n, 2 * kk + hh) * 8]);
-        }
-#pragma unroll
-        for (int j = 0; j < 5; ++j)
-          acc[j] = SWAPPED ? __builtin_amdgcn_mfma_f32_32x32x16_f16(af, wf[j], acc[j], 0, 0, 0)
-                           : __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[j], af, acc[j], 0, 0, 0);
-      }
-    }
-    __builtin_amdgcn_s_barrier();
-  };
-  // token-major result -> fp16 into a swizzled [64][320] tile at `dst` (T itself or the idle weight stages)
-  auto write_rows = [&](_Float16* dst, const _Float16* bias) {
-#pragma unroll
-    for (int j = 0; j < 5; ++j)
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg) {
-        const int col = wc * 160 + j * 32 + 8 * rg + 4 * hh;
-        float v[4] = {acc[j][rg * 4 + 0], acc[j][rg * 4 + 1], acc[j][rg * 4 + 2], acc[j][rg * 4 + 3]};
-        if (bias) {
-          const half4 bv = *reinterpret_cast<const half4*>(bias + col);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] += (float)bv[e];
-        }
-        *reinterpret_cast<half4*>(&dst[my_row * C + tswz(my_row, col >> 3) * 8 + (col & 7)]) =
-            half4{(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
-      }
-  };
-  // rows of a swizzled [64][320] tile -> global [M, ld] at column offset col0: 4 lanes per row, coalesced 16-byte stores
-  auto store_rows = [&](const _Float16* src, _Float16* out, int ld, int col0) {
-    const int row = tid >> 2, qtr = tid & 3;
-    if (m0 + row < g.M)
-#pragma unroll
-      for (int i = 0; i < 10; ++i) {
-        const int c = qtr * 10 + i;
-        *reinterpret_cast<half8*>(out + (long long)(m0 + row) * ld + col0 + c * 8) = *reinterpret_cast<const half8*>(&src[row * C + tswz(row, c) * 8]);
-      }
+    product320<NW, decltype(swapc)::value>(acc, T, WB, w, w_off, rows, wave, wc, l31, hh);
   };
 
   // ---- x -> T, GroupNorm affine in place
-  load_tile(g.x);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  load_tile<TM, NW>(T, g.x, tensor_bytes, m0, g.M, wave, lane);
+  wait_vmcnt<0>();
   __syncthreads();
   {
     const int row = tid >> 2, qtr = tid & 3;
@@ -517,7 +307,7 @@ __global__ __launch_bounds__(NW * 64, 2) void xfront_kernel(FrontArgs g) {
   __syncthreads();
   // ---- h = n Wpi^T + bpi -> T; h to memory (the residual of the block), n1 = LayerNorm1(h) -> T
   gemm(g.wpi, std::false_type{});
-  write_rows(T, g.bpi);
+  write_acc<1, true, false>(acc, rows, g.bpi, T, wc, hh);
   __syncthreads();
   {
     const int row = tid >> 2, qtr = tid & 3;
@@ -553,9 +343,9 @@ __global__ __launch_bounds__(NW * 64, 2) void xfront_kernel(FrontArgs g) {
 #pragma unroll 1
   for (int part = 0; part < 2; ++part) {
     gemm(g.wqk + (long long)part * C * C, std::false_type{});
-    write_rows(WB, nullptr);
+    write_acc<1, false, false>(acc, rows, nullptr, WB, wc, hh);      // staged in the idle weight stages
     __syncthreads();
-    store_rows(WB, g.qk, 2 * C, part * C);
+    store_rows<TM, NW>(WB, g.qk, 2 * C, part * C, m0, g.M, tid);
     __syncthreads();
   }
   // ---- V^T: lane owns head-dim row dd = 160 wc + 32 j + l31 and tokens 32 wr + 8 rg + 4 hh .. + 3; staged as [320][64 tokens] (rows of
@@ -569,7 +359,7 @@ __global__ __launch_bounds__(NW * 64, 2) void xfront_kernel(FrontArgs g) {
       const int t = wr * 32 + 8 * rg + 4 * hh;                        // first of 4 consecutive tokens, t % 4 == 0
       const int tq = (t & ~12) | ((t & 4) << 1) | ((t & 8) >> 1);     // its position in the permuted order
       *reinterpret_cast<half4*>(&WB[dd * 64 + (((tq >> 3) ^ (dd >> 1)) & 7) * 8 + (tq & 7)]) =
-          half4{(_Float16)acc[j][rg * 4 + 0], (_Float16)acc[j][rg * 4 + 1], (_Float16)acc[j][rg * 4 + 2], (_Float16)acc[j][rg * 4 + 3]};
+          half4{(_Float16)acc[0][j][rg * 4 + 0], (_Float16)acc[0][j][rg * 4 + 1], (_Float16)acc[0][j][rg * 4 + 2], (_Float16)acc[0][j][rg * 4 + 3]};
     }
   __syncthreads();
   {
@@ -606,10 +396,7 @@ extern "C" int sd_xattn_chain_f16(const void* attn1_out, const void* h, const vo
   g.M = (int)rows; g.rows_per_sample = rows_per_sample; g.lk = lk; g.ldv2 = ldv2; g.stage = debug_out ? debug_stage : 0;
   g.scale_log2 = 0.15811388300841897f * 1.4426950408889634f;      // 40^-0.5 * log2(e)
   g.eps = eps;
-  static coma::LdsOptIn lds_opt;
-  if (int rc = coma::opt_in_lds(lds_opt, reinterpret_cast<const void*>(xc::xchain_kernel), xc::LDS_BYTES, "sd_xattn_chain_f16")) return rc;
-  hipLaunchKernelGGL(xc::xchain_kernel, dim3((unsigned)(rows / xc::TM)), dim3(xc::NW * 64), xc::LDS_BYTES, (hipStream_t)stream, g);
-  return check_launch("xchain_kernel");
+  return rowtile::launch<xc::xchain_kernel>(g, rows, xc::TM, xc::NW, xc::LDS_BYTES, "sd_xattn_chain_f16", "xchain_kernel", stream);
 }
 
 extern "C" int sd_xfront_f16(const void* x, const float* gn_affine, const void* wpi, const void* bpi, const void* gamma1, const void* beta1,
@@ -625,8 +412,5 @@ extern "C" int sd_xfront_f16(const void* x, const float* gn_affine, const void* 
   g.x = (const _Float16*)x; g.gn_affine = gn_affine; g.wpi = (const _Float16*)wpi; g.bpi = (const _Float16*)bpi; g.g1 = (const _Float16*)gamma1;
   g.b1 = (const _Float16*)beta1; g.wqk = (const _Float16*)wqk; g.wv = (const _Float16*)wv; g.h = (_Float16*)h; g.qk = (_Float16*)qk;
   g.vt = (_Float16*)vt; g.M = (int)rows; g.rows_per_sample = rows_per_sample; g.ldv = ldv; g.eps = eps;
-  static coma::LdsOptIn lds_opt;
-  if (int rc = coma::opt_in_lds(lds_opt, reinterpret_cast<const void*>(xc::xfront_kernel), xc::LDS_BYTES, "sd_xfront_f16")) return rc;
-  hipLaunchKernelGGL(xc::xfront_kernel, dim3((unsigned)(rows / xc::TM)), dim3(xc::NW * 64), xc::LDS_BYTES, (hipStream_t)stream, g);
-  return check_launch("xfront_kernel");
+  return rowtile::launch<xc::xfront_kernel>(g, rows, xc::TM, xc::NW, xc::LDS_BYTES, "sd_xfront_f16", "xfront_kernel", stream);
 }

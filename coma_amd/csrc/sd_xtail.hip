@@ -23,6 +23,8 @@
 // across the per-slice barrier), GEGLU 3.9 k (VALU), 1.6 k wait, second product 4.6 k; third product 16.6 k, final residual + store 16 k.
 // One workgroup per CU (160 KB of LDS, 8 waves); a 4-wave form with 64 x 128 / 64 x 160 wave tiles (0.7 reads per MFMA, accumulators in
 // AGPRs) measured 25 % slower.
+// Tile DMA, swizzles, the MFMAs of one weight slice, the accumulator writer and the final store are the row-tile toolkit of
+// sd_rowtile.h; the three weight pipelines (their stage rotation is specific to this kernel), the GEGLU and the column statistics are here.
 #include <hip/hip_fp16.h>
 
 #include <type_traits>
@@ -30,21 +32,18 @@
 #include "common.h"
 #include "sd_gelu.h"
 #include "sd_plan.h"
+#include "sd_rowtile.h"
 #include "../../include/sd_hip.h"
 
 namespace sd {
 
-using coma::check_launch;
 using coma::fail;
 
 namespace xt {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float float16v __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(3))) void* lptr_t;
+using namespace rowtile;
 
-constexpr int C = 320, HID = 1280, TM = 128, NW = 8, BK = 32, CH = 128;     // CH hidden columns per chunk
+constexpr int HID = 1280, TM = 128, NW = 8, CH = 128;  // CH hidden columns per chunk
 constexpr int RT = TM / 32 / (NW / 2);                 // 32-row MFMA tiles per wave (waves: NW / 2 row groups x 2 column groups)
 constexpr int W1_DMA = 16 / NW, W2_DMA = 24 / NW;      // DMA instructions per wave for a W1 / a (padded) W2 or Wpo slice
 constexpr int T_BYTES = TM * C * 2;                    // 80 KB
@@ -53,7 +52,6 @@ constexpr int W2_STAGE = 12288;                        // halves: two stages (at
 constexpr int WB_BYTES = 3 * W1_STAGE * 2;             // 48 KB
 constexpr int H_BYTES = TM * CH * 2;                   // 32 KB
 constexpr int LDS_BYTES = T_BYTES + WB_BYTES + H_BYTES;
-constexpr unsigned OOB = 0x80000000u;
 
 struct Args {
   const _Float16 *n3, *h2, *x, *w1, *b1, *w2, *b2, *wpo, *bpo;
@@ -62,16 +60,7 @@ struct Args {
   int M;
 };
 
-__device__ __forceinline__ int tswz(int row, int c) { return (c & ~7) | ((c ^ (row >> 1)) & 7); }   // 640-byte rows
-__device__ __forceinline__ int hswz(int row, int c) { return c ^ (row & 15); }                      // 256-byte rows (16 chunks)
-__device__ __forceinline__ int wswz(int row, int c) { return c ^ ((row >> 2) & 3); }                // 64-byte rows
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes) {
-  const unsigned long long u = reinterpret_cast<unsigned long long>(p);
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-  return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0,
-                                           __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
-}
+__device__ __forceinline__ int hswz(int row, int c) { return c ^ (row & 15); }      // H: 256-byte rows (16 chunks)
 
 __global__ __launch_bounds__(NW * 64, NW / 4) void xtail_kernel(Args g) {
   extern __shared__ __attribute__((aligned(1024))) unsigned char xsmem[];
@@ -96,23 +85,11 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void xtail_kernel(Args g) {
   for (int i = 0; i < RT1; ++i) row1[i] = (wr1 * RT1 + i) * 32 + l31;
 
   const unsigned tensor_bytes = (unsigned)((long long)g.M * C * 2);
-  // [128 rows][40 chunks] = 80 pieces of 1 KiB, 80 / NW per wave
-  auto load_tile = [&](const _Float16* src) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    const __amdgpu_buffer_rsrc_t rs = make_rsrc(src, tensor_bytes);
-#pragma unroll
-    for (int j = 0; j < 80 / NW; ++j) {
-      const int q = (wave * (80 / NW) + j) * 64 + lane;
-      const int row = q / 40, slot = q - row * 40;
-      const unsigned off = (m0 + row) < g.M ? (unsigned)(((long long)(m0 + row) * C + tswz(row, slot) * 8) * 2) : OOB;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lptr_t)(T + (wave * (80 / NW) + j) * 512), 16, off, 0, 0, 0);
-    }
-#endif
-  };
+  auto load = [&](const _Float16* src) { load_tile<TM, NW>(T, src, tensor_bytes, m0, g.M, wave, lane); };
   // weight slice [rows][32 k] of a row-major [n][ld] matrix starting at row r0, column k0: `pieces` pieces of 16 rows; wave w takes
-  // pieces w, w + NW, ...
+  // pieces w, w + NW, ...  (the strided, padded form of rowtile::issue_w: W1 and W2 are not [320][320], and the stages rotate by three)
   const int p_row = lane >> 2, p_slot = lane & 3;
-  auto issue_w = [&](const __amdgpu_buffer_rsrc_t& rs, _Float16* dst, int r0, int ld, int k0, int pieces, int nrows) {
+  auto issue_slice = [&](const __amdgpu_buffer_rsrc_t& rs, _Float16* dst, int r0, int ld, int k0, int pieces, int nrows) {
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
     for (int j = 0; j < 24 / NW; ++j) {
@@ -142,12 +119,12 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void xtail_kernel(Args g) {
   // third products.  The stages overlap; the schedule below only ever requests a slice into bytes no wave can still be reading:
   //   chunk parity 0: W1 slice s -> stage s % 3,       W2 slice k -> stage (k + 1) & 1, next chunk's W1 slice 0 -> stage 2
   //   chunk parity 1: W1 slice s -> stage (s + 2) % 3, W2 slice k -> stage k & 1,       next chunk's W1 slice 0 -> stage 0
-  auto issue_w1 = [&](int c, int sl, int stage) { issue_w(w1_rs, WB + stage * W1_STAGE, 256 * c, C, sl * BK, 16, 256); };     // 16 / NW DMAs per wave
+  auto issue_w1 = [&](int c, int sl, int stage) { issue_slice(w1_rs, WB + stage * W1_STAGE, 256 * c, C, sl * BK, 16, 256); };     // 16 / NW DMAs per wave
   // [320][32] slices are padded to 24 pieces (rows >= 320 out of bounds: zeros into the 4 KB behind the slice) so that every wave
   // issues the same number of DMAs (W2_DMA) and one s_waitcnt immediate serves all of them
-  auto issue_w2 = [&](const __amdgpu_buffer_rsrc_t& rs, int stage, int ld, int k0) { issue_w(rs, WB + stage * W2_STAGE, 0, ld, k0, 24, C); };
+  auto issue_w2 = [&](const __amdgpu_buffer_rsrc_t& rs, int stage, int ld, int k0) { issue_slice(rs, WB + stage * W2_STAGE, 0, ld, k0, 24, C); };
 
-  load_tile(g.n3);
+  load(g.n3);
   issue_w1(0, 0, 0);
   issue_w1(0, 1, 1);
 
@@ -163,33 +140,18 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void xtail_kernel(Args g) {
     int st = PHI ? 2 : 0;
 #pragma unroll 1
     for (int s = 0; s < C / BK; ++s) {
-      if (s + 1 < C / BK) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(W1_DMA) : "memory");     // slice s landed (slice s + 1 may still be in flight)
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (s + 1 < C / BK) wait_vmcnt<W1_DMA>();     // slice s landed (slice s + 1 may still be in flight)
+      else wait_vmcnt<0>();
       __builtin_amdgcn_s_barrier();
       const int st2 = st == 0 ? 2 : st - 1;            // (st + 2) % 3: the stage slice s - 1 has just left
       if (s + 2 < C / BK) issue_w1(c, s + 2, st2);
       else if (s + 1 == C / BK) issue_w2(w2_rs, PHI ? 0 : 1, HID, c * CH);      // first slice of the second product
       const _Float16* Wb = WB + st * W1_STAGE;
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        const int ks = 2 * s + kk;
-        half8 af[RT1], wf[2];
-#pragma unroll
-        for (int i = 0; i < RT1; ++i) af[i] = *reinterpret_cast<const half8*>(&T[row1[i] * C + tswz(row1[i], 2 * ks + hh) * 8]);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const int n = wc1 * 64 + j * 32 + l31;
-          wf[j] = *reinterpret_cast<const half8*>(&Wb[n * BK + wswz(n, 2 * kk + hh) * 8]);
-        }
-#pragma unroll
-        for (int i = 0; i < RT1; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) acc1[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[j], af[i], acc1[i][j], 0, 0, 0);
-      }
+      slice_mfma<C, tswz, false>(acc1, T, row1, Wb, wc1 * 64, s, l31, hh);
       st = st == 2 ? 0 : st + 1;
     }
     __builtin_amdgcn_s_barrier();                    // every wave is done with the W1 stages, with T (last chunk) and with H of the previous chunk
-    if (last) load_tile(g.h2);                       // n3 is no longer needed: the residual of the second product lands under the GEGLU
+    if (last) load(g.h2);                            // n3 is no longer needed: the residual of the second product lands under the GEGLU
     issue_w2(w2_rs, PHI ? 1 : 0, HID, c * CH + BK);  // second slice; both land while the GEGLU arithmetic runs
     // ---- GEGLU: tiles (i, 0) and (i, 1) of this wave are (value, gate) of the same 32 hidden columns -> H
 #pragma unroll
@@ -210,35 +172,20 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void xtail_kernel(Args g) {
         }
         *reinterpret_cast<half4*>(&H[row1[i] * CH + hswz(row1[i], col >> 3) * 8 + (col & 7)]) = o4;
       }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __syncthreads();                                 // H complete and visible, W2 slices 0 and 1 (and h2) landed
     // ---- second product: acc2 += H . W2[:, 128 c .. 128 c + 127]^T, K = 128 in 4 slices
 #pragma unroll 1
     for (int s = 0; s < CH / BK; ++s) {
       if (s >= 1) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();                // slice s landed, every wave is done with slice s - 1
         if (s + 1 < CH / BK) issue_w2(w2_rs, PHI ? ((s + 1) & 1) : (s & 1), HID, c * CH + (s + 1) * BK);
         else if (!last) issue_w1(c + 1, 0, PHI ? 0 : 2);           // first W1 slice of the next chunk
         else issue_w2(wpo_rs, 0, C, 0);                            // (last chunk has parity 1: stage 0 is free) first slice of proj_out
       }
       const _Float16* Wb = WB + (PHI ? (s & 1) : ((s + 1) & 1)) * W2_STAGE;
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        const int ks = 2 * s + kk;
-        half8 af[RT], wf[5];
-#pragma unroll
-        for (int i = 0; i < RT; ++i) af[i] = *reinterpret_cast<const half8*>(&H[my_row[i] * CH + hswz(my_row[i], 2 * ks + hh) * 8]);
-#pragma unroll
-        for (int j = 0; j < 5; ++j) {
-          const int n = wc * 160 + j * 32 + l31;
-          wf[j] = *reinterpret_cast<const half8*>(&Wb[n * BK + wswz(n, 2 * kk + hh) * 8]);
-        }
-#pragma unroll
-        for (int i = 0; i < RT; ++i)
-#pragma unroll
-          for (int j = 0; j < 5; ++j) acc2[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[j], af[i], acc2[i][j], 0, 0, 0);
-      }
+      slice_mfma<CH, hswz, false>(acc2, H, my_row, Wb, wc * 160, s, l31, hh);
     }
     __builtin_amdgcn_s_barrier();                    // weight stages and H free again
     if (!last) issue_w1(c + 1, 1, PHI ? 1 : 0);      // second W1 slice of the next chunk
@@ -250,30 +197,8 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void xtail_kernel(Args g) {
     chunk(2 * c2 + 1, std::integral_constant<int, 1>{}, c2 + 1 == HID / CH / 2);
   }
 
-  // quad (j, rg) of acc2 = 4 consecutive columns col(j, rg) of row my_row
-  auto quad_col = [&](int j, int rg) { return wc * 160 + j * 32 + 8 * rg + 4 * hh; };
-  auto quad_ptr = [&](int i, int j, int rg) {
-    const int col = quad_col(j, rg);
-    return &T[my_row[i] * C + tswz(my_row[i], col >> 3) * 8 + (col & 7)];
-  };
-  auto write_tile = [&](const _Float16* bias) {       // T <- fp16(acc2 + bias + T)
-#pragma unroll
-    for (int i = 0; i < RT; ++i)
-#pragma unroll
-      for (int j = 0; j < 5; ++j)
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg) {
-          _Float16* p = quad_ptr(i, j, rg);
-          const half4 bv = *reinterpret_cast<const half4*>(bias + quad_col(j, rg));
-          const half4 tv = *reinterpret_cast<const half4*>(p);
-          half4 o4;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) o4[e] = (_Float16)(acc2[i][j][rg * 4 + e] + (float)bv[e] + (float)tv[e]);
-          *reinterpret_cast<half4*>(p) = o4;
-        }
-  };
   // ---- h3 = acc2 + b2 + h2 -> T (h2 arrived under the last chunk)
-  write_tile(g.b2);
+  write_acc<RT, true, true>(acc2, my_row, g.b2, T, wc, hh);
   __syncthreads();
   // ---- third product: acc2 = h3 (T) . Wpo^T, three stages (0, 24 KB, 48 KB = the idle H tile); slices 0 and 1 were requested during
   // the last chunk
@@ -286,46 +211,23 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void xtail_kernel(Args g) {
   int st3 = 0;
 #pragma unroll 1
   for (int s = 0; s < C / BK; ++s) {
-    if (s + 1 < C / BK) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(W2_DMA) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (s + 1 < C / BK) wait_vmcnt<W2_DMA>();
+    else wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     if (s + 2 < C / BK) issue_w2(wpo_rs, st3 == 0 ? 2 : st3 - 1, C, (s + 2) * BK);
     const _Float16* Wb = WB + st3 * W2_STAGE;
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      const int ks = 2 * s + kk;
-      half8 af[RT], wf[5];
-#pragma unroll
-      for (int i = 0; i < RT; ++i) af[i] = *reinterpret_cast<const half8*>(&T[my_row[i] * C + tswz(my_row[i], 2 * ks + hh) * 8]);
-#pragma unroll
-      for (int j = 0; j < 5; ++j) {
-        const int n = wc * 160 + j * 32 + l31;
-        wf[j] = *reinterpret_cast<const half8*>(&Wb[n * BK + wswz(n, 2 * kk + hh) * 8]);
-      }
-#pragma unroll
-      for (int i = 0; i < RT; ++i)
-#pragma unroll
-        for (int j = 0; j < 5; ++j) acc2[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[j], af[i], acc2[i][j], 0, 0, 0);
-    }
+    slice_mfma<C, tswz, false>(acc2, T, my_row, Wb, wc * 160, s, l31, hh);
     st3 = st3 == 2 ? 0 : st3 + 1;
   }
   __builtin_amdgcn_s_barrier();
   // ---- out = acc2 + bpo + x -> T, then coalesced stores and the GroupNorm column statistics of the next block
-  load_tile(g.x);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  load(g.x);
+  wait_vmcnt<0>();
   __syncthreads();
-  write_tile(g.bpo);
+  write_acc<RT, true, true>(acc2, my_row, g.bpo, T, wc, hh);
   __syncthreads();
   {
-    const int qtr = tid & 3;
-#pragma unroll
-    for (int row = tid >> 2; row < TM; row += NW * 16)
-      if (m0 + row < g.M)
-#pragma unroll
-        for (int i = 0; i < 10; ++i) {
-          const int c = qtr * 10 + i;
-          *reinterpret_cast<half8*>(g.out + (long long)(m0 + row) * C + c * 8) = *reinterpret_cast<const half8*>(&T[row * C + tswz(row, c) * 8]);
-        }
+    store_rows<TM, NW>(T, g.out, C, 0, m0, g.M, tid);
     if (g.colstats && tid < 160) {                    // (32-row block rb, 8-column chunk c): sums of the STORED fp16 values, rows in order
       const int rb = tid / 40, c = tid - rb * 40;
       float s1[8], s2[8];
@@ -358,8 +260,5 @@ extern "C" int sd_xtail_f16(const void* n3, const void* h2, const void* x, const
   g.n3 = (const _Float16*)n3; g.h2 = (const _Float16*)h2; g.x = (const _Float16*)x; g.w1 = (const _Float16*)w1; g.b1 = (const _Float16*)b1;
   g.w2 = (const _Float16*)w2; g.b2 = (const _Float16*)b2; g.wpo = (const _Float16*)wpo; g.bpo = (const _Float16*)bpo; g.out = (_Float16*)out;
   g.colstats = colstats; g.M = (int)rows;
-  static coma::LdsOptIn lds_opt;
-  if (int rc = coma::opt_in_lds(lds_opt, reinterpret_cast<const void*>(xt::xtail_kernel), xt::LDS_BYTES, "sd_xtail_f16")) return rc;
-  hipLaunchKernelGGL(xt::xtail_kernel, dim3((unsigned)(rows / xt::TM)), dim3(xt::NW * 64), xt::LDS_BYTES, (hipStream_t)stream, g);
-  return check_launch("xtail_kernel");
+  return rowtile::launch<xt::xtail_kernel>(g, rows, xt::TM, xt::NW, xt::LDS_BYTES, "sd_xtail_f16", "xtail_kernel", stream);
 }
