@@ -16,12 +16,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # COMA_HIP_LIB=<path>: tuning aid -- load another BUILD of the library (A/B of two builds inside one GPU call: box-to-box spread is larger
 # than most of the effects being measured); the product and the tests use the in-tree library
 LIB_PATH = os.environ.get("COMA_HIP_LIB") or os.path.join(_HERE, "libcoma_hip.so")
-ABI_VERSION = 10                 # = COMA_ABI_VERSION of include/coma_hip.h: bumped when an existing signature changes
-# (not for the text-tower functions: they were only added, no existing signature changed, and a library without them is refused by
-# lib() anyway -- getattr of a missing symbol fails; the same holds for the two coma_sample_eliminate_* functions and for the
-# coma_raster_* / coma_silhouette_iou functions, and for the mesh volume functions of csrc/mesh_volume.hip and the depth-optimisation functions of csrc/depth_opt.hip,
-# and for the two coma_app_objective_* functions of csrc/app_objective.hip and the coma_smplx_* functions of csrc/smplx.hip,
-# and the coma_vposer_* / coma_angle_prior_* functions of csrc/vposer.hip)
+# = COMA_ABI_VERSION of include/coma_hip.h.  Bumped only when an EXISTING signature changes: a library that merely lacks an added
+# function is refused by lib() anyway, through the getattr of the missing symbol.
+ABI_VERSION = 10
 
 _lib = None
 
@@ -247,6 +244,18 @@ def on_device(device):
     finally:
         if prev is not None:
             torch.cuda.set_device(prev)
+
+
+def need_device(device, who, resolve=True):
+    """`device` as a torch.device of a HIP device, or ComaHipError: there is no CPU path.  With resolve (the default) a bare "cuda"
+    becomes cuda:N of the current device, as tensors report it -- that asks the runtime, so an object that must not touch the device
+    before its first call checks with resolve=False when it is built and resolves from its first upload."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise ComaHipError(f"{who} needs a HIP device (got {dev}); there is no CPU path")
+    if resolve and dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    return dev
 
 
 def vec3(v):

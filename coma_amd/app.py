@@ -82,9 +82,7 @@ class ComaObjective:
         tgt = _host_f32(target_points, (-1, 3), "target_points")
         if tgt.shape[0] != k:
             raise ValueError(f"target_points: {tgt.shape[0]} rows for {k} selected vertices")
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise _lib.ComaHipError(f"ComaObjective needs a HIP device (got {dev}); there is no CPU path")
+        dev = _lib.need_device(device, "ComaObjective")
         off, vf = vertex_face_csr(faces, V)
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
         self.V, self.F, self.k, self.eps = V, F, k, float(eps)
@@ -98,7 +96,7 @@ class ComaObjective:
         nbytes = int(_lib.lib().coma_app_objective_workspace_bytes(V, F, k))
         self._ws = torch.empty([max(16, nbytes)], dtype=torch.uint8, device=dev)
         self._ws_bytes = nbytes
-        self.device = self.faces.device
+        self.device = dev
 
     @classmethod
     def from_state(cls, affordance_info, asset_downsample, faces, reference_object_vertex_index, contact_threshold,

@@ -60,9 +60,7 @@ class DeviceSMPLX:
                  extra_joint_vertex_ids=None):
         """model: a dict of arrays with the keys of an SMPL-X model file (v_template, shapedirs, posedirs, J_regressor, kintree_table,
         weights, f, hands_components{l,r}, hands_mean{l,r}, lmk_faces_idx, lmk_bary_coords)."""
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise _lib.ComaHipError(f"DeviceSMPLX needs a HIP device (got {dev}); there is no CPU path")
+        dev = _lib.need_device(device, "DeviceSMPLX", resolve=False)
         need = ("v_template", "shapedirs", "posedirs", "J_regressor", "kintree_table", "weights", "f", "hands_componentsl", "hands_componentsr",
                 "hands_meanl", "hands_meanr", "lmk_faces_idx", "lmk_bary_coords")
         missing = [k for k in need if k not in model]
@@ -165,8 +163,7 @@ class DeviceSMPLX:
     def _upload(self):
         if self._uploaded:
             return
-        if self.device.index is None:                                    # "cuda" means the current device; tensors report cuda:N
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _lib.need_device(self.device, "DeviceSMPLX")      # "cuda" means the current device; tensors report cuda:N
         h, dev = self.host, self.device
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
         self._v_template, self._shapedirs, self._posedirs = up(h["v_template"]), up(h["shapedirs"]), up(h["posedirs"])

@@ -11,6 +11,7 @@
 // gradient returns to the vertices by a gather over the vertex->face CSR table, the contact term's second direction by a scan in
 // ascending j, and the two term sums by per-workgroup trees whose partials a single workgroup adds in block order.
 #include "common.h"
+#include "coma_device.h"
 
 #include <cmath>
 
@@ -20,27 +21,6 @@ namespace {
 constexpr int kRowTile = 64;      // rows per workgroup (one wave) and points per LDS stage of the double minimum
 constexpr int kBlock = 256;       // every other kernel
 constexpr int kMinGrid = 1024;    // workgroups the double minimum aims for (256 CUs x 4 SIMDs, one wave each)
-
-struct D3 { double x, y, z; };
-__device__ __forceinline__ D3 operator+(D3 a, D3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ D3 operator-(D3 a, D3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ D3 operator*(D3 a, double s) { return {a.x * s, a.y * s, a.z * s}; }
-__device__ __forceinline__ double dot(D3 a, D3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ D3 cross(D3 a, D3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ D3 load3(const float* p, int64_t i) { return {(double)p[3 * i], (double)p[3 * i + 1], (double)p[3 * i + 2]}; }
-__device__ __forceinline__ D3 load3(const double* p, int64_t i) { return {p[3 * i], p[3 * i + 1], p[3 * i + 2]}; }
-
-// sum over the workgroup in a fixed shape: lds[t] + lds[t + h] for h = 128 ... 1; the result is valid in thread 0
-__device__ __forceinline__ double block_sum(double v, double* lds) {
-  const int t = threadIdx.x;
-  lds[t] = v;
-  __syncthreads();
-  for (int h = kBlock / 2; h >= 1; h >>= 1) {
-    if (t < h) lds[t] = lds[t] + lds[t + h];
-    __syncthreads();
-  }
-  return lds[0];
-}
 
 struct AppArgs {
   const float* verts;
@@ -78,20 +58,20 @@ __global__ __launch_bounds__(kBlock) void app_vertex_kernel(AppArgs A) {
       const D3 v0 = load3(A.verts, i0);
       N = N + cross(load3(A.verts, i1) - v0, load3(A.verts, i2) - v0);
     }
-    const double n0 = sqrt(dot(N, N));
+    const double n0 = norm(N);
     if (!ok) {
       t = NAN;                                         // a table that leaves the mesh poisons the term, it is not followed
     } else if (n0 > 0.0) {
       const double m = fmax(n0, 1e-6);                 // F.normalize(eps=1e-6)
       const D3 n1 = N * (1.0 / m);
-      const double r1 = sqrt(dot(n1, n1)), s1 = r1 + A.eps;
-      const D3 n2 = {n1.x / s1, n1.y / s1, n1.z / s1};
-      const double r2 = sqrt(dot(n2, n2)), s2 = r2 + A.eps;
-      const D3 a = {n2.x / s2, n2.y / s2, n2.z / s2};
+      const double r1 = norm(n1), s1 = r1 + A.eps;
+      const D3 n2 = n1 / s1;
+      const double r2 = norm(n2), s2 = r2 + A.eps;
+      const D3 a = n2 / s2;
       const D3 f = {(A.M[0] * a.x + A.M[1] * a.y) + A.M[2] * a.z, (A.M[3] * a.x + A.M[4] * a.y) + A.M[5] * a.z,
                     (A.M[6] * a.x + A.M[7] * a.y) + A.M[8] * a.z};
-      const double rf = sqrt(dot(f, f));
-      const D3 fh = {f.x / rf, f.y / rf, f.z / rf};
+      const double rf = norm(f);
+      const D3 fh = f / rf;
       const D3 gt = load3(A.gt, h);
       t = 1.0 - (dot(gt, fh) + 1.0) / 2.0;
       if (t != t) {
@@ -113,7 +93,7 @@ __global__ __launch_bounds__(kBlock) void app_vertex_kernel(AppArgs A) {
     }
     A.gN[3 * (int64_t)h] = g.x; A.gN[3 * (int64_t)h + 1] = g.y; A.gN[3 * (int64_t)h + 2] = g.z;
   }
-  const double s = block_sum(t, lds);
+  const double s = block_sum<kBlock>(t, lds);
   if (threadIdx.x == 0) A.part_o[blockIdx.x] = s;
 }
 
@@ -215,7 +195,7 @@ __global__ __launch_bounds__(kBlock) void app_contact_merge_kernel(ContactArgs C
       if (arg >= 0) {
         const D3 a = point_a(C, dir == 0 ? t : arg), b = load3(C.targets, dir == 0 ? arg : t);
         const D3 df = a - b;
-        dd = sqrt(dot(df, df));
+        dd = norm(df);
       }
       d[dir] = dd;
       C.dist[(int64_t)dir * C.k + t] = dd;
@@ -223,9 +203,8 @@ __global__ __launch_bounds__(kBlock) void app_contact_merge_kernel(ContactArgs C
     }
   }
   const int nb = gridDim.x;
-  const double s0 = block_sum(d[0], lds);
-  __syncthreads();
-  const double s1 = block_sum(d[1], lds);
+  const double s0 = block_sum<kBlock>(d[0], lds);
+  const double s1 = block_sum<kBlock>(d[1], lds);
   if (threadIdx.x == 0) { C.part_c[blockIdx.x] = s0; C.part_c[nb + blockIdx.x] = s1; }
 }
 
@@ -270,10 +249,7 @@ __global__ __launch_bounds__(kBlock) void app_finalize_kernel(const double* __re
   for (int b = threadIdx.x; b < nb_o; b += kBlock) s[0] = s[0] + part_o[b];
   for (int b = threadIdx.x; b < nb_c; b += kBlock) { s[1] = s[1] + part_c[b]; s[2] = s[2] + part_c[nb_c + b]; }
   double r[3];
-  for (int q = 0; q < 3; ++q) {
-    r[q] = block_sum(s[q], lds);
-    __syncthreads();
-  }
+  for (int q = 0; q < 3; ++q) r[q] = block_sum<kBlock>(s[q], lds);
   if (threadIdx.x == 0) {
     terms[0] = (float)(r[0] / (double)V);
     terms[1] = k > 0 ? (float)(r[1] / (double)k + r[2] / (double)k) : 0.0f;
@@ -284,8 +260,6 @@ struct Layout {
   size_t gN, part_o, part_c, dist, arg, pmin, parg, total;
   int nb_v, nb_k, row_blocks, chunk, nsplit;
 };
-
-size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 Layout layout(int V, int k) {
   Layout L = {};
@@ -299,15 +273,15 @@ Layout layout(int V, int k) {
     L.chunk = (L.row_blocks + want - 1) / want;         // column tiles per split
     L.nsplit = (L.row_blocks + L.chunk - 1) / L.chunk;  // no split is empty
   }
-  size_t at = 0;
-  L.gN = at;     at = up16(at + (size_t)V * 3 * sizeof(double));
-  L.part_o = at; at = up16(at + (size_t)L.nb_v * sizeof(double));
-  L.part_c = at; at = up16(at + (size_t)2 * L.nb_k * sizeof(double));
-  L.dist = at;   at = up16(at + (size_t)2 * k * sizeof(double));
-  L.arg = at;    at = up16(at + (size_t)2 * k * sizeof(int32_t));
-  L.pmin = at;   at = up16(at + (size_t)2 * L.nsplit * k * sizeof(float));
-  L.parg = at;   at = up16(at + (size_t)2 * L.nsplit * k * sizeof(int32_t));
-  L.total = at;
+  Carve ws;
+  L.gN = ws.take((size_t)V * 3 * sizeof(double));
+  L.part_o = ws.take((size_t)L.nb_v * sizeof(double));
+  L.part_c = ws.take((size_t)2 * L.nb_k * sizeof(double));
+  L.dist = ws.take((size_t)2 * k * sizeof(double));
+  L.arg = ws.take((size_t)2 * k * sizeof(int32_t));
+  L.pmin = ws.take((size_t)2 * L.nsplit * k * sizeof(float));
+  L.parg = ws.take((size_t)2 * L.nsplit * k * sizeof(int32_t));
+  L.total = ws.at;
   return L;
 }
 
@@ -341,8 +315,7 @@ extern "C" int coma_app_objective_f32(const float* verts, const int32_t* faces, 
   if (k > 0 && (!selected || !targets)) return fail(COMA_E_INVALID, "%s: null pointer (selected / targets with k > 0)", who);
   if (!(eps >= 0.0) || !std::isfinite(eps)) return fail(COMA_E_INVALID, "%s: eps must be finite and >= 0", who);
   const Layout L = layout(V, k);
-  if (workspace_bytes < L.total) return fail(COMA_E_INVALID, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, L.total);
-  if (((uintptr_t)workspace & 15) != 0) return fail(COMA_E_INVALID, "%s: workspace must be 16-byte aligned", who);
+  if (int rc = check_buffer(who, "workspace", workspace, workspace_bytes, L.total)) return rc;
 
   // the canonicalisation of one column b is linear in the normalised vertex normal: f = M a
   double b[3], p[3], s[3];

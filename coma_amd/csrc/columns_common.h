@@ -3,6 +3,7 @@
 // column: the intersection volume) and depth_opt.hip (the lists sorted once and kept: the shift profile of the depth optimisation),
 // so that the two cannot drift apart.  The kernels themselves live in mesh_volume.hip.
 #pragma once
+#include "coma_device.h"
 #include "raster_common.h"
 
 namespace coma {
@@ -21,11 +22,6 @@ enum { kHdrNeeded = 2, kHdrSums = 3 };             // in units of int64
 // a crossing as stored: Z << 2 | mesh << 1 | (sigma > 0)
 __device__ __forceinline__ long long pack_crossing(long long Z, int mesh, bool flipped) {
   return Z * 4 + (mesh << 1) + (flipped ? 0 : 1);
-}
-
-__device__ __forceinline__ long long wave_sum(long long v) {
-  for (int d = kWave / 2; d > 0; d >>= 1) v += __shfl_down(v, d, kWave);
-  return v;
 }
 
 struct ColumnsLayout {

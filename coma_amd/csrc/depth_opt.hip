@@ -14,6 +14,7 @@
 // coma_depth_optimize_f64: init (traj[0] = d0, Adam state, Ltraj = 0) -> per epoch: profile (K = 1, d read from traj) -> step (one
 //   workgroup: multiview loss and gradient, collision ratio and slope from Ltraj, Adam, traj[e + 1]).
 #include "columns_common.h"
+#include "coma_device.h"
 
 namespace coma {
 
@@ -209,19 +210,6 @@ __global__ __launch_bounds__(256) void depth_init_kernel(const char* __restrict_
   }
 }
 
-// sum of v over the 256 threads in a fixed shape: an LDS tree, lds[t] + lds[t + d] for d = 128, 64, ..., 1
-__device__ __forceinline__ double block_tree_sum(double v, double* __restrict__ lds) {
-  const int tid = threadIdx.x;
-  __syncthreads();
-  lds[tid] = v;
-  __syncthreads();
-  for (int d = 128; d > 0; d >>= 1) {
-    if (tid < d) lds[tid] = lds[tid] + lds[tid + d];
-    __syncthreads();
-  }
-  return lds[0];
-}
-
 // One workgroup.  Thread t adds up the views t, t + 256, ... in ascending order, each view its joints in ascending order; the
 // tree follows.  joints = J0 + d f; per view q = joints (R C) - t (R C), xy = q / scale max(res) + res / 2 (view_record layout).
 __global__ __launch_bounds__(256) void depth_step_kernel(const char* __restrict__ ws, const double* __restrict__ views,
@@ -262,8 +250,8 @@ __global__ __launch_bounds__(256) void depth_step_kernel(const char* __restrict_
     loss = loss + 0.5 * sq;   // the sum over the joints, the mean over the two coordinates
     grad = grad + gr;
   }
-  loss = block_tree_sum(loss, lds);
-  grad = block_tree_sum(grad, lds);
+  loss = block_sum<256>(loss, lds);
+  grad = block_sum<256>(grad, lds);
   if (threadIdx.x != 0) return;
   if (N > 0) loss = loss / (double)N, grad = grad / (double)N;
   double ratio = 0.0, slope = 0.0;
@@ -289,9 +277,7 @@ __global__ __launch_bounds__(256) void depth_step_kernel(const char* __restrict_
 
 static int read_status(const void* hdr, void* stream, int64_t* needed, const char* who) {
   long long head[3] = {0, 0, 0};   // status word + list length, list length + depth flag, crossings counted
-  hipStream_t st = (hipStream_t)stream;
-  if (hipMemcpyAsync(head, hdr, sizeof(head), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-    return fail(COMA_E_DEVICE, "%s: %s", who, hipGetErrorString(hipGetLastError()));
+  if (int rc = read_back(head, hdr, sizeof(head), stream, who)) return rc;
   const int word = (int)(head[0] & 0xffffffffll);
   if (needed) *needed = head[kHdrNeeded];
   const char* of = "coma_shift_columns_prepare";   // the call whose refusal the workspace holds
@@ -402,10 +388,7 @@ extern "C" int coma_depth_optimize_f64(const void* workspace, const double* view
 extern "C" int coma_depth_optimize_status(const void* state, void* stream, int* epoch) {
   if (!state) return fail(COMA_E_INVALID, "coma_depth_optimize_status: null pointer");
   long long tail[2] = {0, 0};
-  hipStream_t st = (hipStream_t)stream;
-  if (hipMemcpyAsync(tail, (const long long*)state + kStStatus, sizeof(tail), hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess)
-    return fail(COMA_E_DEVICE, "coma_depth_optimize_status: %s", hipGetErrorString(hipGetLastError()));
+  if (int rc = read_back(tail, (const long long*)state + kStStatus, sizeof(tail), stream, "coma_depth_optimize_status")) return rc;
   if (epoch) *epoch = (int)tail[1];
   if (tail[0] == 3) return fail(COMA_E_INVALID, "coma_depth_optimize_f64: cand_view holds an index outside [0, n_views) (met in epoch %d; later epochs not run)", (int)tail[1]);
   if (tail[0] == 2) return fail(COMA_E_INVALID, "coma_depth_optimize_f64: the columns workspace holds a refused call (nothing written)");

@@ -261,17 +261,6 @@ __global__ void columns_finish_kernel(const int* __restrict__ hdr, long long* __
 }
 
 // ---- signed volume ----
-__device__ __forceinline__ double block_sum_f64(double v, double* __restrict__ lds) {
-  const int tid = threadIdx.x;
-  lds[tid] = v;
-  __syncthreads();
-  for (int d = 128; d > 0; d >>= 1) {
-    if (tid < d) lds[tid] = lds[tid] + lds[tid + d];
-    __syncthreads();
-  }
-  return lds[0];
-}
-
 __global__ __launch_bounds__(256) void volume_partial_kernel(const double* __restrict__ verts, int V, const int* __restrict__ faces, int F,
                                                              double* __restrict__ partial) {
   __shared__ double lds[256];
@@ -282,19 +271,18 @@ __global__ __launch_bounds__(256) void volume_partial_kernel(const double* __res
       acc = __builtin_nan("");   // nothing is read through a bad index; the result says so
       continue;
     }
-    const double ax = verts[3 * (int64_t)ia], ay = verts[3 * (int64_t)ia + 1], az = verts[3 * (int64_t)ia + 2];
-    const double bx = verts[3 * (int64_t)ib], by = verts[3 * (int64_t)ib + 1], bz = verts[3 * (int64_t)ib + 2];
-    const double cx = verts[3 * (int64_t)ic], cy = verts[3 * (int64_t)ic + 1], cz = verts[3 * (int64_t)ic + 2];
-    const double det = (ax * (by * cz - bz * cy) - ay * (bx * cz - bz * cx)) + az * (bx * cy - by * cx);
+    const D3 a = load3(verts, ia), b = load3(verts, ib), c = load3(verts, ic);
+    // the cofactor expansion as written, not dot(a, cross(b, c)): the middle term is subtracted
+    const double det = (a.x * (b.y * c.z - b.z * c.y) - a.y * (b.x * c.z - b.z * c.x)) + a.z * (b.x * c.y - b.y * c.x);
     acc = acc + det;
   }
-  const double s = block_sum_f64(acc, lds);
+  const double s = block_sum<256>(acc, lds);
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
 __global__ __launch_bounds__(256) void volume_final_kernel(const double* __restrict__ partial, int nb, double* __restrict__ out) {
   __shared__ double lds[256];
-  const double s = block_sum_f64((int)threadIdx.x < nb ? partial[threadIdx.x] : 0.0, lds);
+  const double s = block_sum<256>((int)threadIdx.x < nb ? partial[threadIdx.x] : 0.0, lds);
   if (threadIdx.x == 0) out[0] = s / 6.0;
 }
 
@@ -403,9 +391,7 @@ extern "C" int coma_intersection_columns(const double* vertsA, int VA, const int
 extern "C" int coma_intersection_status(const void* workspace, void* stream, int64_t* needed) {
   if (!workspace) return fail(COMA_E_INVALID, "coma_intersection_status: null pointer");
   long long head[3] = {0, 0, 0};   // status word + list length, list length + depth flag, crossings counted
-  hipStream_t st = (hipStream_t)stream;
-  if (hipMemcpyAsync(head, workspace, sizeof(head), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-    return fail(COMA_E_DEVICE, "coma_intersection_status: %s", hipGetErrorString(hipGetLastError()));
+  if (int rc = read_back(head, workspace, sizeof(head), stream, "coma_intersection_status")) return rc;
   const int word = (int)(head[0] & 0xffffffffll);
   if (needed) *needed = head[kHdrNeeded];
   if (word & kBadNonFinite) return fail(COMA_E_INVALID, "coma_intersection_columns: non-finite vertex (sums untouched)");

@@ -236,9 +236,7 @@ extern "C" int coma_raster_depth_f64(const double* verts, int V, const int32_t* 
 extern "C" int coma_raster_status(const void* workspace, void* stream) {
   if (!workspace) return fail(COMA_E_INVALID, "coma_raster_status: null pointer");
   int word = 0;
-  hipStream_t st = (hipStream_t)stream;
-  if (hipMemcpyAsync(&word, workspace, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-    return fail(COMA_E_DEVICE, "coma_raster_status: %s", hipGetErrorString(hipGetLastError()));
+  if (int rc = read_back(&word, workspace, sizeof(int), stream, "coma_raster_status")) return rc;
   if (word & kBadNonFinite) return fail(COMA_E_INVALID, "coma_raster_depth_f64: non-finite vertex (depth map untouched)");
   if (word & kBadRange)
     return fail(COMA_E_INVALID, "coma_raster_depth_f64: a snapped coordinate exceeds +-2^25 (1/256-pixel units; depth map untouched)");

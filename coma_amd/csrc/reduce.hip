@@ -6,17 +6,12 @@
 //           :402-427 (masked max), :455-475 (entropy score).
 #include <cstdint>
 
+#include "coma_device.h"
 #include "common.h"
 
 namespace coma {
 
 constexpr int kRowWaves = 4;   // rows (waves) per block
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  return v;
-}
 
 // prob[m,:] /= (sum + eps);  contact[m] = (sum_k prob*(1 - p.n_k)/2) * nom/den
 __global__ __launch_bounds__(kRowWaves* kWave) void contact_map_kernel(

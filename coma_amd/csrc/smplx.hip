@@ -20,6 +20,7 @@
 // P dot products, one workgroup each.  No transposed copy.  No floating-point atomics: every sum over vertices is per-workgroup
 // (fixed order inside), then one fixed-order pass over the workgroups, so two calls give the same bits.
 #include "common.h"
+#include "coma_device.h"
 
 #include <cmath>
 
@@ -34,17 +35,6 @@ constexpr int kMaxRows = (9 * (kMaxJ - 1) + kPSplit - 1) / kPSplit;
 constexpr int kMaxPca = 64;
 
 struct Tree { int32_t parent[kMaxJ]; };
-
-__device__ __forceinline__ double block_sum(double v, double* lds) {   // lds[t] + lds[t + h], h = 128 ... 1
-  const int t = threadIdx.x;
-  lds[t] = v;
-  __syncthreads();
-  for (int h = kBlock / 2; h >= 1; h >>= 1) {
-    if (t < h) lds[t] = lds[t] + lds[t + h];
-    __syncthreads();
-  }
-  return lds[0];
-}
 
 // ---- shape stage ----
 __global__ __launch_bounds__(kBlock) void smplx_shape_kernel(const float* __restrict__ v_template, const float* __restrict__ shapedirs,
@@ -69,9 +59,8 @@ __global__ __launch_bounds__(kBlock) void smplx_jrest_kernel(const float* __rest
     s[2] = s[2] + w * v_shaped[3 * (int64_t)v + 2];
   }
   for (int c = 0; c < 3; ++c) {
-    const double r = block_sum(s[c], lds);
+    const double r = block_sum<kBlock>(s[c], lds);
     if (threadIdx.x == 0) j_rest[3 * j + c] = r;
-    __syncthreads();
   }
 }
 
@@ -329,7 +318,7 @@ __global__ __launch_bounds__(kBlock) void smplx_feature_bwd_kernel(const float* 
   double acc = 0.0;
 #pragma unroll 4
   for (int i = threadIdx.x; i < n3; i += kBlock) acc = acc + (double)row[i] * gvp[i];
-  const double s = block_sum(acc, lds);
+  const double s = block_sum<kBlock>(acc, lds);
   if (threadIdx.x == 0) dfeat[blockIdx.x] = s;
 }
 
@@ -423,8 +412,6 @@ __global__ __launch_bounds__(kBlock) void smplx_gather_kernel(const float* __res
   out[q] = (float)(acc + tr);
 }
 
-size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
-
 struct Layout {
   size_t feat, part, gvp, dA_part, dfeat, total;      // workspace
   size_t v_shaped, j_rest, shape_total;               // shape state
@@ -439,22 +426,20 @@ Layout layout(int V, int J) {
   L.rows = (L.P + kPSplit - 1) / kPSplit;
   L.nblk = (V + kTile - 1) / kTile;
   L.nb3 = (int)((n3 + kBlock - 1) / kBlock);
-  size_t at = 0;
-  L.feat = at;    at = up16(at + (size_t)(L.P > 0 ? L.P : 1) * d);
-  L.part = at;    at = up16(at + (size_t)kPSplit * n3 * d);
-  L.gvp = at;     at = up16(at + n3 * d);
-  L.dA_part = at; at = up16(at + (size_t)L.nblk * (12 * J + 3) * d);
-  L.dfeat = at;   at = up16(at + (size_t)(L.P > 0 ? L.P : 1) * d);
-  L.total = at;
-  at = 0;
-  L.v_shaped = at; at = up16(at + n3 * d);
-  L.j_rest = at;   at = up16(at + (size_t)3 * J * d);
-  L.shape_total = at;
-  at = 0;
-  L.s_pose = at;   at = up16(at + (size_t)3 * J * d);
-  L.s_A = at;      at = up16(at + (size_t)12 * J * d);
-  L.s_vposed = at; at = up16(at + n3 * d);
-  L.saved_total = at;
+  Carve ws, shape, saved;
+  L.feat = ws.take((size_t)(L.P > 0 ? L.P : 1) * d);
+  L.part = ws.take((size_t)kPSplit * n3 * d);
+  L.gvp = ws.take(n3 * d);
+  L.dA_part = ws.take((size_t)L.nblk * (12 * J + 3) * d);
+  L.dfeat = ws.take((size_t)(L.P > 0 ? L.P : 1) * d);
+  L.total = ws.at;
+  L.v_shaped = shape.take(n3 * d);
+  L.j_rest = shape.take((size_t)3 * J * d);
+  L.shape_total = shape.at;
+  L.s_pose = saved.take((size_t)3 * J * d);
+  L.s_A = saved.take((size_t)12 * J * d);
+  L.s_vposed = saved.take(n3 * d);
+  L.saved_total = saved.at;
   return L;
 }
 
@@ -473,12 +458,6 @@ int check_common(const char* who, int V, int J, int hand_dim, int n_pca, const i
     if (parents[i] < 0 || parents[i] >= i) return fail(COMA_E_INVALID, "%s: parent %d of joint %d outside [0, %d)", who, parents[i], i, i);
     tree.parent[i] = parents[i];
   }
-  return COMA_OK;
-}
-
-int check_buffer(const char* who, const char* what, const void* p, size_t have, size_t need) {
-  if (have < need) return fail(COMA_E_INVALID, "%s: %s of %zu bytes, %zu needed", who, what, have, need);
-  if (((uintptr_t)p & 15) != 0) return fail(COMA_E_INVALID, "%s: %s must be 16-byte aligned", who, what);
   return COMA_OK;
 }
 

@@ -39,6 +39,7 @@ __device__ __forceinline__ void render(const View& w, double x, double y, double
   py = cy / w.scale * w.maxres + w.hy;
 }
 
+// not coma_device.h's block_sum<128>: that is an LDS tree, this is a wave butterfly and then the two partials -- other bits
 __device__ __forceinline__ double block_sum_128(double v, double* sh) {
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);

@@ -19,9 +19,9 @@
 // are consecutive in memory), and the 16 partial sums are added in ascending w through LDS.  No floating-point atomics: two calls
 // give the same bits.
 #include "common.h"
+#include "coma_device.h"
 
 #include <cmath>
-#include <initializer_list>
 
 namespace coma {
 namespace {
@@ -34,9 +34,6 @@ constexpr double kSlope = 0.2;
 constexpr double kNormEps = 1e-12;           // F.normalize's eps
 constexpr double kDiagEps = 1e-6;            // the test on the (2,2) entry
 constexpr double kBnEps = 1e-5;
-
-__device__ __forceinline__ double load(const float* p, int64_t i) { return (double)p[i]; }
-__device__ __forceinline__ double load(const double* p, int64_t i) { return p[i]; }
 
 // y[n, o] = epilogue(b[o] + sum_i W[o, i] x[n, i]); grid (ceil(Out / kFwdWaves), N).
 // act: 0 none, 1 leaky ReLU.  y64 (f64 [N, Out]) or, when y64 is NULL, two f32 outputs of `split` columns each: rows o < split go to
@@ -106,50 +103,43 @@ __global__ __launch_bounds__(256) void vposer_bn_kernel(const TX* __restrict__ x
 struct Tail {
   double n0, n1, dot;           // max(|c0|, eps), max(|u|, eps), b1 . c1
   bool free0, free1;            // the norm, not eps, divided
-  double T[3][3];               // T[i] = b_{i+1}: the TRANSPOSED rotation, the matrix the selection rule reads
+  D3 T[3];                      // T[i] = b_{i+1}: the TRANSPOSED rotation, the matrix the selection rule reads
   int branch;
   double t, q[4];               // the selected t and 0.5 cand / sqrt(t)
   double s2, s, tt, k;          // sin^2, sin, two_theta, the factor
 };
 
-__device__ __forceinline__ double norm3(const double* v) { return sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]); }
-__device__ __forceinline__ double dot3(const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
-__device__ __forceinline__ void cross3(const double* a, const double* b, double* c) {
-  c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0];
-}
-
-__device__ __forceinline__ void candidate(const double T[3][3], int branch, double* t, double* c) {
+__device__ __forceinline__ void candidate(const D3* T, int branch, double* t, double* c) {
   if (branch == 0) {
-    *t = ((1.0 + T[0][0]) - T[1][1]) - T[2][2];
-    c[0] = T[1][2] - T[2][1]; c[1] = *t; c[2] = T[0][1] + T[1][0]; c[3] = T[2][0] + T[0][2];
+    *t = ((1.0 + T[0].x) - T[1].y) - T[2].z;
+    c[0] = T[1].z - T[2].y; c[1] = *t; c[2] = T[0].y + T[1].x; c[3] = T[2].x + T[0].z;
   } else if (branch == 1) {
-    *t = ((1.0 - T[0][0]) + T[1][1]) - T[2][2];
-    c[0] = T[2][0] - T[0][2]; c[1] = T[0][1] + T[1][0]; c[2] = *t; c[3] = T[1][2] + T[2][1];
+    *t = ((1.0 - T[0].x) + T[1].y) - T[2].z;
+    c[0] = T[2].x - T[0].z; c[1] = T[0].y + T[1].x; c[2] = *t; c[3] = T[1].z + T[2].y;
   } else if (branch == 2) {
-    *t = ((1.0 - T[0][0]) - T[1][1]) + T[2][2];
-    c[0] = T[0][1] - T[1][0]; c[1] = T[2][0] + T[0][2]; c[2] = T[1][2] + T[2][1]; c[3] = *t;
+    *t = ((1.0 - T[0].x) - T[1].y) + T[2].z;
+    c[0] = T[0].y - T[1].x; c[1] = T[2].x + T[0].z; c[2] = T[1].z + T[2].y; c[3] = *t;
   } else {
-    *t = ((1.0 + T[0][0]) + T[1][1]) + T[2][2];
-    c[0] = *t; c[1] = T[1][2] - T[2][1]; c[2] = T[2][0] - T[0][2]; c[3] = T[0][1] - T[1][0];
+    *t = ((1.0 + T[0].x) + T[1].y) + T[2].z;
+    c[0] = *t; c[1] = T[1].z - T[2].y; c[2] = T[2].x - T[0].z; c[3] = T[0].y - T[1].x;
   }
 }
 
 // forced >= 0: the branch the forward stored; < 0: select
 __device__ __forceinline__ void tail_forward(const double* o, int forced, Tail& f, double* aa) {
-  const double c0[3] = {o[0], o[2], o[4]}, c1[3] = {o[1], o[3], o[5]};
-  double u[3];
-  const double l0 = norm3(c0);
+  const D3 c0 = {o[0], o[2], o[4]}, c1 = {o[1], o[3], o[5]};
+  const double l0 = norm(c0);
   f.free0 = l0 >= kNormEps; f.n0 = f.free0 ? l0 : kNormEps;
-  for (int r = 0; r < 3; ++r) f.T[0][r] = c0[r] / f.n0;
-  f.dot = dot3(f.T[0], c1);
-  for (int r = 0; r < 3; ++r) u[r] = c1[r] - f.dot * f.T[0][r];
-  const double l1 = norm3(u);
+  f.T[0] = c0 / f.n0;
+  f.dot = dot(f.T[0], c1);
+  const D3 u = c1 - f.T[0] * f.dot;
+  const double l1 = norm(u);
   f.free1 = l1 >= kNormEps; f.n1 = f.free1 ? l1 : kNormEps;
-  for (int r = 0; r < 3; ++r) f.T[1][r] = u[r] / f.n1;
-  cross3(f.T[0], f.T[1], f.T[2]);
+  f.T[1] = u / f.n1;
+  f.T[2] = cross(f.T[0], f.T[1]);
   if (forced >= 0) f.branch = forced;
-  else if (f.T[2][2] < kDiagEps) f.branch = f.T[0][0] > f.T[1][1] ? 0 : 1;
-  else f.branch = f.T[0][0] < -f.T[1][1] ? 2 : 3;
+  else if (f.T[2].z < kDiagEps) f.branch = f.T[0].x > f.T[1].y ? 0 : 1;
+  else f.branch = f.T[0].x < -f.T[1].y ? 2 : 3;
   double c[4];
   candidate(f.T, f.branch, &f.t, c);
   const double root = sqrt(f.t);
@@ -181,42 +171,36 @@ __device__ __forceinline__ void tail_backward(const double* o, const Tail& f, co
   double gc[4];
   for (int e = 0; e < 4; ++e) gc[e] = 0.5 * gq[e] / root;
   double gt = -0.5 * (((gq[0] * f.q[0] + gq[1] * f.q[1]) + gq[2] * f.q[2]) + gq[3] * f.q[3]) / f.t;
-  double g[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+  D3 g[3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};       // dL/dT, row by row
   if (f.branch == 0) {
     gt = gt + gc[1];
-    g[0][0] = gt; g[1][1] = -gt; g[2][2] = -gt;
-    g[1][2] = gc[0]; g[2][1] = -gc[0]; g[0][1] = gc[2]; g[1][0] = gc[2]; g[2][0] = gc[3]; g[0][2] = gc[3];
+    g[0].x = gt; g[1].y = -gt; g[2].z = -gt;
+    g[1].z = gc[0]; g[2].y = -gc[0]; g[0].y = gc[2]; g[1].x = gc[2]; g[2].x = gc[3]; g[0].z = gc[3];
   } else if (f.branch == 1) {
     gt = gt + gc[2];
-    g[0][0] = -gt; g[1][1] = gt; g[2][2] = -gt;
-    g[2][0] = gc[0]; g[0][2] = -gc[0]; g[0][1] = gc[1]; g[1][0] = gc[1]; g[1][2] = gc[3]; g[2][1] = gc[3];
+    g[0].x = -gt; g[1].y = gt; g[2].z = -gt;
+    g[2].x = gc[0]; g[0].z = -gc[0]; g[0].y = gc[1]; g[1].x = gc[1]; g[1].z = gc[3]; g[2].y = gc[3];
   } else if (f.branch == 2) {
     gt = gt + gc[3];
-    g[0][0] = -gt; g[1][1] = -gt; g[2][2] = gt;
-    g[0][1] = gc[0]; g[1][0] = -gc[0]; g[2][0] = gc[1]; g[0][2] = gc[1]; g[1][2] = gc[2]; g[2][1] = gc[2];
+    g[0].x = -gt; g[1].y = -gt; g[2].z = gt;
+    g[0].y = gc[0]; g[1].x = -gc[0]; g[2].x = gc[1]; g[0].z = gc[1]; g[1].z = gc[2]; g[2].y = gc[2];
   } else {
     gt = gt + gc[0];
-    g[0][0] = gt; g[1][1] = gt; g[2][2] = gt;
-    g[1][2] = gc[1]; g[2][1] = -gc[1]; g[2][0] = gc[2]; g[0][2] = -gc[2]; g[0][1] = gc[3]; g[1][0] = -gc[3];
+    g[0].x = gt; g[1].y = gt; g[2].z = gt;
+    g[1].z = gc[1]; g[2].y = -gc[1]; g[2].x = gc[2]; g[0].z = -gc[2]; g[0].y = gc[3]; g[1].x = -gc[3];
   }
   // Gram-Schmidt: b3 = b1 x b2, b2 = u / n1, u = c1 - (b1 . c1) b1, b1 = c0 / n0
-  double x[3], gb1[3], gb2[3], gu[3];
-  cross3(f.T[1], g[2], x);
-  for (int r = 0; r < 3; ++r) gb1[r] = g[0][r] + x[r];
-  cross3(g[2], f.T[0], x);
-  for (int r = 0; r < 3; ++r) gb2[r] = g[1][r] + x[r];
-  const double p2 = f.free1 ? dot3(f.T[1], gb2) : 0.0;
-  for (int r = 0; r < 3; ++r) gu[r] = (gb2[r] - f.T[1][r] * p2) / f.n1;
-  const double c1[3] = {o[1], o[3], o[5]};
-  const double pu = dot3(gu, f.T[0]);
-  double gc1[3], gc0[3];
-  for (int r = 0; r < 3; ++r) {
-    gc1[r] = gu[r] - pu * f.T[0][r];
-    gb1[r] = gb1[r] - (f.dot * gu[r] + pu * c1[r]);
-  }
-  const double p1 = f.free0 ? dot3(f.T[0], gb1) : 0.0;
-  for (int r = 0; r < 3; ++r) gc0[r] = (gb1[r] - f.T[0][r] * p1) / f.n0;
-  for (int r = 0; r < 3; ++r) { go[2 * r] = gc0[r]; go[2 * r + 1] = gc1[r]; }
+  D3 gb1 = g[0] + cross(f.T[1], g[2]);
+  const D3 gb2 = g[1] + cross(g[2], f.T[0]);
+  const double p2 = f.free1 ? dot(f.T[1], gb2) : 0.0;
+  const D3 gu = (gb2 - f.T[1] * p2) / f.n1;
+  const D3 c1 = {o[1], o[3], o[5]};
+  const double pu = dot(gu, f.T[0]);
+  const D3 gc1 = gu - f.T[0] * pu;
+  gb1 = gb1 - (gu * f.dot + c1 * pu);
+  const double p1 = f.free0 ? dot(f.T[0], gb1) : 0.0;
+  const D3 gc0 = (gb1 - f.T[0] * p1) / f.n0;
+  go[0] = gc0.x; go[1] = gc1.x; go[2] = gc0.y; go[3] = gc1.y; go[4] = gc0.z; go[5] = gc1.z;
 }
 
 // one thread per (n, joint)
@@ -233,8 +217,10 @@ __global__ __launch_bounds__(256) void vposer_tail_kernel(const double* __restri
   saved_branch[t] = (int8_t)f.branch;
   if (branch) branch[t] = (int8_t)f.branch;
   if (matrices)
-    for (int r = 0; r < 3; ++r)
-      for (int c = 0; c < 3; ++c) matrices[(int64_t)t * 9 + 3 * r + c] = (float)f.T[c][r];
+    for (int c = 0; c < 3; ++c) {                       // the rotation's column c is T[c]
+      float* m = matrices + (int64_t)t * 9 + c;
+      m[0] = (float)f.T[c].x; m[3] = (float)f.T[c].y; m[6] = (float)f.T[c].z;
+    }
 }
 
 __global__ __launch_bounds__(256) void vposer_tail_bwd_kernel(const double* __restrict__ o, const int8_t* __restrict__ saved_branch,
@@ -278,8 +264,6 @@ __global__ __launch_bounds__(256) void angle_prior_bwd_kernel(const float* __res
 }
 
 // ---- host side ----
-size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
-
 struct Layout {
   size_t h1, h2, o, branch, saved_total;     // saved: h1, h2 f64 [N,H]; o f64 [N,6NJ]; branch i8 [N,NJ]
   size_t a, b, c, total;                     // workspace: three f64 [N, max(H, 6 NJ)]
@@ -288,18 +272,17 @@ struct Layout {
 Layout layout(int N, int H, int NJ) {
   Layout L;
   const size_t d = sizeof(double);
-  size_t at = 0;
-  L.h1 = at;     at = up16(at + (size_t)N * H * d);
-  L.h2 = at;     at = up16(at + (size_t)N * H * d);
-  L.o = at;      at = up16(at + (size_t)N * 6 * NJ * d);
-  L.branch = at; at = up16(at + (size_t)N * NJ);
-  L.saved_total = at;
+  Carve saved, ws;
+  L.h1 = saved.take((size_t)N * H * d);
+  L.h2 = saved.take((size_t)N * H * d);
+  L.o = saved.take((size_t)N * 6 * NJ * d);
+  L.branch = saved.take((size_t)N * NJ);
+  L.saved_total = saved.at;
   const size_t wide = (size_t)N * (H > 6 * NJ ? H : 6 * NJ) * d;
-  at = 0;
-  L.a = at; at = up16(at + wide);
-  L.b = at; at = up16(at + wide);
-  L.c = at; at = up16(at + wide);
-  L.total = at;
+  L.a = ws.take(wide);
+  L.b = ws.take(wide);
+  L.c = ws.take(wide);
+  L.total = ws.at;
   return L;
 }
 
@@ -310,18 +293,6 @@ int check_sizes(const char* who, int N, int D, int H, int NJ) {
     return fail(COMA_E_INVALID, "%s: N=%d must lie in [1, %d], D=%d in [1, %d], H=%d in [1, %d] and NJ=%d in [1, %d]", who, N, kMaxN, D, kMaxD, H,
                 kMaxH, NJ, kMaxNJ);
   return COMA_OK;
-}
-
-int check_buffer(const char* who, const char* what, const void* p, size_t have, size_t need) {
-  if (have < need) return fail(COMA_E_INVALID, "%s: %s of %zu bytes, %zu needed", who, what, have, need);
-  if (((uintptr_t)p & 15) != 0) return fail(COMA_E_INVALID, "%s: %s must be 16-byte aligned", who, what);
-  return COMA_OK;
-}
-
-bool f32_aligned(std::initializer_list<const void*> ps) {
-  for (const void* p : ps)
-    if (((uintptr_t)p & 3) != 0) return false;
-  return true;
 }
 
 template <typename TX>

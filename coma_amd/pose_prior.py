@@ -34,17 +34,10 @@ _LAYERS = {"bodyprior_enc_fc1": ("H", "F"), "bodyprior_enc_fc2": ("H", "H"), "bo
 _NORMS = {"bodyprior_enc_bn1": "F", "bodyprior_enc_bn2": "H"}
 
 
-def _need_device(device, who):
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise _lib.ComaHipError(f"{who} needs a HIP device (got {dev}); there is no CPU path")
-    return dev
-
-
 class DeviceVPoser:
     def __init__(self, state_dict, num_neurons, latentD, data_shape, device="cuda"):
         """state_dict: a VPoser snapshot (tensors or arrays under the names of its layers); data_shape: [1, NJ, 3]."""
-        dev = _need_device(device, "DeviceVPoser")
+        dev = _lib.need_device(device, "DeviceVPoser", resolve=False)
         shape = [int(x) for x in data_shape]
         if len(shape) != 3 or shape[0] != 1 or shape[2] != 3:
             raise ValueError(f"DeviceVPoser: data_shape must be [1, NJ, 3], got {list(data_shape)}")
@@ -106,8 +99,7 @@ class DeviceVPoser:
     def _upload(self):
         if self._uploaded:
             return
-        if self.device.index is None:                                    # "cuda" means the current device; tensors report cuda:N
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _lib.need_device(self.device, "DeviceVPoser")      # "cuda" means the current device; tensors report cuda:N
         self._w = {k: torch.from_numpy(v).to(self.device) for k, v in self.host.items()}
         self._uploaded = True
 
@@ -215,7 +207,7 @@ class DeviceAnglePrior:
     INDEX, SIGN = (55, 58, 12, 15), (1.0, -1.0, -1.0, -1.0)
 
     def __init__(self, device="cuda"):
-        self.device = _need_device(device, "DeviceAnglePrior")
+        self.device = _lib.need_device(device, "DeviceAnglePrior", resolve=False)
 
     def vectors(self, with_global_pose=False):
         index = [i - (0 if with_global_pose else 3) for i in self.INDEX]
