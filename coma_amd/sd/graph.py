@@ -1,63 +1,29 @@
-"""Static launch graphs: a network is compiled ONCE into a flat list of kernel launches over pre-allocated NHWC fp16 buffers (no
-allocation, no host sync inside).  The list is RECORDED into a library-owned model (coma_amd/csrc/sd_plan.hip, sd/model.py): the
-launch list and the hipGraph captured from it live in libcoma_hip.so, a denoising step is one sd_model_replay, and the model can
-be saved to a file a caller without Python loads and runs (sd_model_load / sd_unet_forward).  The Python closures are kept for
-per-launch profiling (`run`, `profile`).  This replaces the per-op Python dispatch of the reference's diffusers modules -- the
-MI355X-first equivalent of a tracing compiler is "hipGraph over hand-written kernels", not op-by-op eager execution.
+"""The diffusion operator vocabulary over the launch recorder (sd/recorder.py): a network is compiled ONCE into a flat list of kernel
+launches over pre-allocated NHWC fp16 buffers.  This replaces the per-op Python dispatch of the reference's diffusers modules -- the
+MI355X-first equivalent of a tracing compiler is "hipGraph over hand-written kernels", not op-by-op eager execution.  Which producer
+leaves GroupNorm statistics and which consumer may read them is decided in one place, sd/gn_stats.py.
 """
 from __future__ import annotations
 
 import torch
 
 from . import ops
-from .model import BUF_ZEROED, SdModel
-
-F16 = torch.float16
-# GroupNorm statistics ride on the producer's epilogue from this many output rows on (below, the GEMMs are split-K launches whose reduce pass
-# owns the epilogue, and a one-launch GroupNorm is as cheap as the finalize + apply pair)
-GN_STATS_MIN_M = 16384
+from .gn_stats import GnStats
+from .recorder import F16, LaunchRecorder  # noqa: F401  (F16 is re-exported: the network builders import it from here)
 
 
-class LaunchGraph:
+class LaunchGraph(LaunchRecorder):
     def __init__(self, device, model=None, plan="step"):
-        self.device = torch.device(device)
-        self.model = model if model is not None else SdModel(device)     # several graphs may share one model (UNet: step + context)
-        self.plan = plan
-        self._recorded = False
-        self.launches = []          # zero-argument closures
-        self.tags = []              # (description, flops) per launch, for profiling
-        self.alg_bytes = []         # algorithmic HBM bytes per launch (inputs read once + output written once)
-        self.flops = 0              # ALGORITHMIC flops per run: 2*M*N*K of every GEMM-shaped operator (a Winograd convolution counts as the
-                                    # 3x3 convolution it computes, 2 * 9 * M * N * C_in)
-        self.exec_flops = 0         # MFMA flops actually issued (a Winograd convolution: 16 plane products = 4/9 of the above)
-        self.exec_tags = []         # executed flops per launch, parallel to `tags`
-        self._gn_stats = None
+        super().__init__(device, model, plan)
+        self._gn_scratch = None
         self._ws = None             # split-K workspace shared by every GEMM of the graph (launches are serial)
-        self._colstats = {}         # data_ptr of a GEMM output -> its [M/32][2][N] column-sum buffer (GroupNorm statistics)
-        self._colstats_tile = {}    # data_ptr of a halo-convolution output -> its [M/256][2][N] per-tile column sums (table consumers only)
-        self.fuse_gn_stats = True
-
-    # ---- memory
-    def buf(self, *shape, dtype=F16, zero=False):
-        t = (torch.zeros if zero else torch.empty)(*shape, dtype=dtype, device=self.device)
-        self.model.register(t, BUF_ZEROED if zero else 0)                # scratch: not part of a saved model's contents
-        return t
+        self.gn_stats = GnStats(self.buf)
 
     def gn_scratch(self, batch, hw):
         n = ops.gn_scratch_floats(batch, hw)
-        if self._gn_stats is None or self._gn_stats.numel() < n:
-            self._gn_stats = self.buf(max(n, 1 << 16), dtype=torch.float32)
-        return self._gn_stats
-
-    # ---- recording
-    def add(self, fn, flops=0, tag="", nbytes=0, alg_flops=None):
-        alg = flops if alg_flops is None else alg_flops
-        self.launches.append(fn)
-        self.tags.append((tag, alg))
-        self.exec_tags.append(flops)
-        self.alg_bytes.append(nbytes)
-        self.flops += alg
-        self.exec_flops += flops
+        if self._gn_scratch is None or self._gn_scratch.numel() < n:
+            self._gn_scratch = self.buf(max(n, 1 << 16), dtype=torch.float32)
+        return self._gn_scratch
 
     def conv(self, a0, w, out, *, batch, in_h, in_w, c0, n, out_h=None, out_w=None, a1=None, c1=0, taps=1, **kw):
         oh = out_h if out_h is not None else in_h
@@ -66,14 +32,13 @@ class LaunchGraph:
         if self._ws is None:
             self._ws = self.buf(16 << 20, dtype=torch.float32)   # 64 MiB
         kw.setdefault("workspace", self._ws)
-        # GroupNorm statistics of the consumer come for free from the epilogue of large, never-split GEMMs
         M = batch * oh * ow
         alg_flops = kw.pop("alg_flops", None)
         tag_note = kw.pop("tag_note", "")
-        if kw.pop("stats", False) and self.fuse_gn_stats and z == 1 and M >= GN_STATS_MIN_M and M % 32 == 0:
-            cs = self.buf(M // 32, 2, n, dtype=torch.float32, zero=True)
+        # GroupNorm statistics of the consumer come for free from the epilogue of large, never-split GEMMs
+        cs = self.gn_stats.produce(out, "gemm", rows=M, n=n, hw=oh * ow, asked=kw.pop("stats", False), z=z)
+        if cs is not None:
             kw["colstats"] = cs
-            self._colstats[out.data_ptr()] = cs
         self.add(lambda: ops.conv_gemm(a0, w, out, batch=batch, in_h=in_h, in_w=in_w, out_h=oh, out_w=ow, c0=c0, n=n, a1=a1,
                                        c1=c1, taps=taps, **kw),
                  flops=2 * batch * oh * ow * n * taps * (c0 + c1) * z, alg_flops=alg_flops,
@@ -92,10 +57,7 @@ class LaunchGraph:
         assert in_w & (in_w - 1) == 0, "phase launches need a power-of-two source width"
         M = batch * in_h * in_w
         ws = upsample_phase_weights(w_raw)
-        cs = None
-        if stats and self.fuse_gn_stats and 4 * M >= GN_STATS_MIN_M and (in_h * in_w) % 32 == 0:
-            cs = self.buf(4 * M // 32, 2, n, dtype=torch.float32, zero=True)          # 4 M / 32 slots: phase p of sample b owns a quarter of b's range
-            self._colstats[out.data_ptr()] = cs
+        cs = self.gn_stats.produce(out, "phase", rows=4 * M, n=n, hw=4 * in_h * in_w, asked=stats)      # ONE buffer for the four launches
         for ph in range(4):
             self.conv(a0, ws[ph], out, batch=batch, in_h=in_h, in_w=in_w, c0=c0, n=n, taps=4, phase=ph + 1, bias=bias, colstats=cs,
                       alg_flops=2 * M * n * 9 * c0, tag_note=f" (upsample phase {ph})")
@@ -147,10 +109,7 @@ class LaunchGraph:
         """stats: also leave the column sums of `out` for the consumer's GroupNorm (w = 32 only: one image row = one 32-row slot).
         vscale: the scale the producer of V applied (the planes are WINO_USCALE * vscale times the true products)."""
         mscale = 1.0 / (self.WINO_USCALE * vscale)
-        cs, M = None, batch * h * w
-        if stats and self.fuse_gn_stats and w == 32 and n % 128 == 0 and M >= GN_STATS_MIN_M:
-            cs = self.buf(M // 32, 2, n, dtype=torch.float32, zero=True)
-            self._colstats[out.data_ptr()] = cs
+        cs = self.gn_stats.produce(out, "winograd", rows=batch * h * w, n=n, hw=h * w, asked=stats, w=w)
         self.add(lambda: ops.winograd_output(P, out, batch=batch, h=h, w=w, n=n, bias=bias, bias_bn=bias_bn, ldbb=ldbb, res=res, colstats=cs, mscale=mscale),
                  tag=f"winograd output{' (+ colstats)' if cs is not None else ''} B={batch} {h}x{w} N={n}",
                  nbytes=2 * (5 + (1 if res is not None else 0)) * batch * h * w * n)
@@ -160,15 +119,10 @@ class LaunchGraph:
         """GroupNorm (+ SiLU) folded into the input transform through the per-(sample, channel) affine table, for slices too large for
         gn_winograd_input: needs the column sums of every source (left by its producer); returns None when one is missing.  Two launches
         (table, transform), and the normalised tensor is never written."""
-        hw = h * w
-        cs0 = self._colstats.get(x0.data_ptr()) if hw % 32 == 0 else None
-        cs1 = self._colstats.get(x1.data_ptr()) if (x1 is not None and hw % 32 == 0) else None
-        if cs0 is None or (x1 is not None and cs1 is None):
+        table = self._table(x0, gamma, beta, batch=batch, hw=h * w, c=c0, eps=eps, x1=x1, c1=c1, accepts=(32,), from_stats_only=True)
+        if table is None:
             return None
-        table = self.gn_scratch(batch, hw)
         C, T = c0 + c1, batch * (h // 2) * (w // 2)
-        self.add(lambda: ops.groupnorm_table_cat(gamma, beta, table, cs0, cs1, batch=batch, hw=hw, c0=c0, c1=c1, eps=eps),
-                 tag=f"groupnorm(table) B={batch} hw={hw} C={C}")
         V = self.buf(16, T, C)
         self.add(lambda: ops.winograd_input(x0, V, batch=batch, h=h, w=w, c0=c0, x1=x1, c1=c1, gn_affine=table, silu=silu),
                  tag=f"groupnorm apply + winograd input B={batch} {h}x{w} C={C}", nbytes=2 * 5 * batch * h * w * C)
@@ -188,11 +142,9 @@ class LaunchGraph:
         """dst = [src | src] along the batch axis (two identical CFG halves); the GroupNorm column sums of src follow."""
         assert dst.numel() == 2 * src.numel()
         self._dup(src, dst, tag=f"dup {src.numel() * 2 >> 20} MiB")
-        cs = self._colstats.get(src.data_ptr())
+        cs = self.gn_stats.follow(src, dst)
         if cs is not None:
-            cs2 = self.buf(2 * cs.shape[0], *cs.shape[1:], dtype=cs.dtype, zero=True)
-            self._dup(cs, cs2, tag="dup colstats")
-            self._colstats[dst.data_ptr()] = cs2
+            self._dup(*cs, tag="dup colstats")
         return dst
 
     def _dup(self, src, dst, tag):
@@ -202,9 +154,8 @@ class LaunchGraph:
 
     def groupnorm(self, x0, gamma, beta, out, *, batch, hw, c0, x1=None, c1=0, eps, silu):
         stats = self.gn_scratch(batch, hw)
-        cs0 = self._colstats.get(x0.data_ptr())
-        cs1 = self._colstats.get(x1.data_ptr()) if x1 is not None else None
-        if cs0 is not None and (x1 is None or cs1 is not None) and hw % 32 == 0:
+        cs0, cs1, _ = self.gn_stats.consume(x0, x1, hw=hw)
+        if cs0 is not None:
             self.add(lambda: ops.groupnorm_colstats(x0, gamma, beta, out, stats, cs0, batch=batch, hw=hw, c0=c0, x1=x1, c1=c1,
                                                     colstats1=cs1, eps=eps, silu=silu),
                      tag=f"groupnorm(colstats) B={batch} hw={hw} C={c0 + c1}")
@@ -233,10 +184,7 @@ class LaunchGraph:
     def xfront(self, x, gamma, beta, wpi, bpi, g1, b1, wqk, wv, h, qk, vt, *, batch, hw, gn_eps):
         """GroupNorm table (from the producer's column sums when it left them) + the fused front of a C = 320 transformer block."""
         c = 320
-        stats = self.gn_scratch(batch, hw)
-        cs0 = self._colstats.get(x.data_ptr()) if hw % 32 == 0 else None
-        self.add(lambda: ops.groupnorm_table(x, gamma, beta, stats, batch=batch, hw=hw, c0=c, eps=gn_eps, colstats0=cs0),
-                 tag=f"groupnorm(table) B={batch} hw={hw} C={c}")
+        stats = self._table(x, gamma, beta, batch=batch, hw=hw, c=c, eps=gn_eps, accepts=(32,))
         rows = batch * hw
         self.add(lambda: ops.xfront(x, stats, wpi, bpi, g1, b1, wqk, wv, h, qk, vt, rows=rows, rows_per_sample=hw, ldv=vt.shape[-1]),
                  flops=4 * 2 * rows * c * c, tag=f"xfront rows={rows} C={c}", nbytes=2 * (5 * rows * c + 4 * c * c))
@@ -244,10 +192,7 @@ class LaunchGraph:
 
     def xtail(self, n3, h2, x, w1, b1, w2, b2, wpo, bpo, out, *, rows):
         c = 320
-        cs = None
-        if self.fuse_gn_stats and rows >= GN_STATS_MIN_M:        # the next GroupNorm takes its statistics from these column sums
-            cs = self.buf(rows // 32, 2, c, dtype=torch.float32, zero=True)
-            self._colstats[out.data_ptr()] = cs
+        cs = self.gn_stats.produce(out, "xtail", rows=rows, n=c)         # the next GroupNorm takes its statistics from these column sums
         self.add(lambda: ops.xtail(n3, h2, x, w1, b1, w2, b2, wpo, bpo, out, cs, rows=rows),
                  flops=2 * rows * c * (8 * c + 4 * c + c), tag=f"xtail rows={rows} C={c}", nbytes=2 * (4 * rows * c + 13 * c * c))
         return out
@@ -262,15 +207,19 @@ class LaunchGraph:
                  flops=2 * batch * hw * n * 9 * c, tag=f"conv3x3(small n) B={batch} {h}x{w_} C={c} n={n}", nbytes=2 * batch * hw * (c + 8))
         return out
 
-    def _table(self, x, gamma, beta, *, batch, hw, c, eps):
-        """The (scale, shift) table of a GroupNorm over x, from whatever column sums its producer left (32-row slots of a GEMM epilogue,
-        per-tile slots of a halo convolution) or from a statistics pass."""
+    def _table(self, x0, gamma, beta, *, batch, hw, c, eps, x1=None, c1=0, accepts=(256, 32), from_stats_only=False):
+        """The (scale, shift) table of a GroupNorm over x0 (| x1), from whatever column sums the producers left that the consumer accepts
+        (32-row slots of a GEMM epilogue, per-tile slots of a halo convolution), else from a statistics pass over x0 -- or, for a consumer
+        whose table launch reads column sums only (from_stats_only: sd_groupnorm_table_cat_f16), None and no launch."""
+        cs0, cs1, rps = self.gn_stats.consume(x0, x1, hw=hw, accepts=accepts)
+        if from_stats_only and cs0 is None:
+            return None
         table = self.gn_scratch(batch, hw)
-        cs0, rps = self._colstats_tile.get(x.data_ptr()), 256
-        if cs0 is None:
-            cs0, rps = (self._colstats.get(x.data_ptr()) if hw % 32 == 0 else None), 32
-        self.add(lambda: ops.groupnorm_table(x, gamma, beta, table, batch=batch, hw=hw, c0=c, eps=eps, colstats0=cs0, rows_per_slot=rps),
-                 tag=f"groupnorm(table) B={batch} hw={hw} C={c}")
+        if from_stats_only:
+            fn = lambda: ops.groupnorm_table_cat(gamma, beta, table, cs0, cs1, batch=batch, hw=hw, c0=c, c1=c1, eps=eps)
+        else:
+            fn = lambda: ops.groupnorm_table(x0, gamma, beta, table, batch=batch, hw=hw, c0=c, eps=eps, colstats0=cs0, rows_per_slot=rps)
+        self.add(fn, tag=f"groupnorm(table) B={batch} hw={hw} C={c + c1}")
         return table
 
     def gn_silu_conv3x3_halo(self, x, gamma, beta, w, bias, out, *, batch, h, w_, c, n, eps, silu=True, res=None, stats=False):
@@ -279,14 +228,20 @@ class LaunchGraph:
         tensor is never written; stats: leave the per-tile column sums of `out` for the next GroupNorm table."""
         hw = h * w_
         table = self._table(x, gamma, beta, batch=batch, hw=hw, c=c, eps=eps)
-        cs = None
-        if stats and self.fuse_gn_stats:
-            cs = self.buf(batch * hw // 256, 2, n, dtype=torch.float32, zero=True)
-            self._colstats_tile[out.data_ptr()] = cs
+        cs = self.gn_stats.produce(out, "tile", rows=batch * hw, n=n, hw=hw, asked=stats)
         self.add(lambda: ops.conv3x3_halo(x, w, out, batch=batch, h=h, w_=w_, c=c, n=n, bias=bias, res=res, gn_affine=table, silu=silu,
                                           colstats=cs, ldo=out.shape[-1]),
                  flops=2 * batch * hw * n * 9 * c, tag=f"conv3x3(halo) B={batch} {h}x{w_} C={c} n={n}",
                  nbytes=2 * batch * hw * (c + n * (2 if res is not None else 1)) + 2 * n * 9 * c)
+        return out
+
+    def conv3x3_c3(self, x, w27, bias, out, *, batch, h, w, n, ldx=64):
+        """3 -> n channels in one launch (sd_conv3x3_c3_f16): the halo patch of a 16 x 16 tile in LDS, K = 32 operands built there
+        (w27: [n][ky][kx][c] padded to 32 halfs), per-tile column sums of `out` for the next GroupNorm table."""
+        cs = self.gn_stats.produce(out, "tile", rows=batch * h * w, n=n, hw=h * w)
+        self.add(lambda: ops.conv3x3_c3(x, w27, out, batch=batch, h=h, w=w, ldx=ldx, n=n, bias=bias, colstats=cs),
+                 flops=2 * batch * h * w * n * 32, alg_flops=2 * batch * h * w * n * 27, tag=f"conv3x3(c3) B={batch} {h}x{w} n={n}",
+                 nbytes=2 * batch * h * w * (4 + n))
         return out
 
     def attention_causal(self, q, k, v, out, *, seqs, heads, len_, d, ldq, ldk, ldv, ldo):
@@ -306,55 +261,3 @@ class LaunchGraph:
                                             scale=d ** -0.5),
                  flops=4 * batch * heads * lq * lk * d, tag=f"attention(wide) B={batch} h={heads} lq={lq} lk={lk} d={d}")
         return out
-
-    # ---- execution
-    def run(self):
-        for fn in self.launches:
-            fn()
-
-    def profile(self, reps=3):
-        """Eager per-launch timing with HIP events -> list of (tag, flops, ms); for tuning only."""
-        dev = self.device
-        self.run()
-        torch.cuda.synchronize(dev)
-        out = []
-        for fn, (tag, fl) in zip(self.launches, self.tags):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(reps):
-                fn()
-            b.record()
-            torch.cuda.synchronize(dev)
-            out.append((tag, fl, a.elapsed_time(b) / reps))
-        return out
-
-    def capture(self):
-        """Record the launch list into the library-owned plan (once), run it eagerly once (module loading and argument checks happen
-        outside any capture); the library captures its hipGraph on the first replay."""
-        if not self._recorded:
-            def record_checked():
-                # every closure must end up in the plan: one that calls no sd_* entry point (a stray torch op) would execute now,
-                # during recording, and be missing from every replay and from a saved model
-                for fn, (tag, _) in zip(self.launches, self.tags):
-                    n0 = self.model.num_launches(self.plan)
-                    fn()
-                    if self.model.num_launches(self.plan) <= n0:
-                        raise RuntimeError(f"launch '{tag}' of plan '{self.plan}' recorded nothing: only sd_* entry points may be added to a LaunchGraph")
-            assert len(self.tags) == len(self.launches)
-            self.model.record(self.plan, record_checked)
-            self._recorded = True
-            self.model.run(self.plan)
-            torch.cuda.synchronize(self.device)
-        return self.model
-
-    def run_recorded(self):
-        """The recorded list launched natively one by one (no Python per launch, no graph)."""
-        self.capture()
-        self.model.run(self.plan)
-
-    def replay(self):
-        if not self._recorded:
-            self.capture()            # recorded, then run eagerly once: that run IS this call's execution (no second pass over the step)
-            self.model.prepare(self.plan)      # the hipGraph is captured and instantiated now (nothing executes), so the next call only launches
-            return
-        self.model.replay(self.plan)

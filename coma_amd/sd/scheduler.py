@@ -11,10 +11,7 @@ import numpy as np
 import torch
 
 from . import ops
-
-
-class _Cfg(dict):
-    __getattr__ = dict.__getitem__
+from .weights import Cfg
 
 
 class DDIMScheduler:
@@ -34,9 +31,9 @@ class DDIMScheduler:
         self.betas = betas
         self.alphas_cumprod = torch.cumprod(1.0 - betas, dim=0)
         self.final_alpha_cumprod = torch.tensor(1.0) if set_alpha_to_one else self.alphas_cumprod[0]
-        self.config = _Cfg(num_train_timesteps=num_train_timesteps, steps_offset=steps_offset, beta_start=beta_start,
-                           beta_end=beta_end, beta_schedule=beta_schedule, clip_sample=clip_sample,
-                           set_alpha_to_one=set_alpha_to_one)
+        self.config = Cfg(num_train_timesteps=num_train_timesteps, steps_offset=steps_offset, beta_start=beta_start,
+                          beta_end=beta_end, beta_schedule=beta_schedule, clip_sample=clip_sample,
+                          set_alpha_to_one=set_alpha_to_one)
         self.num_inference_steps = None
         self.timesteps = torch.from_numpy(np.arange(0, num_train_timesteps)[::-1].copy().astype(np.int64))
 
@@ -71,7 +68,7 @@ class DDIMScheduler:
         x0 = torch.empty_like(lat)
         ops.cfg_ddim_step(eps16, 8, lat, x0, None, None, None, batch=B, hw=h * w, guidance=1.0, alpha_t=a_t, alpha_prev=a_p)
         back = lambda z: z.reshape(B, h, w, C).permute(0, 3, 1, 2).contiguous()
-        out = _Cfg(prev_sample=back(lat), pred_original_sample=back(x0))
+        out = Cfg(prev_sample=back(lat), pred_original_sample=back(x0))
         return out if return_dict else (out.prev_sample,)
 
     def add_noise(self, original_samples, noise, timesteps):

@@ -23,11 +23,7 @@ import torch
 
 from . import ops
 from .graph import F16, LaunchGraph
-from .weights import UNET_CFG, conv_weight, geglu_interleave, pad_vec
-
-
-class _Cfg(dict):
-    __getattr__ = dict.__getitem__
+from .weights import UNET_CFG, Cfg, conv_weight, geglu_interleave, pad_vec
 
 
 GN_WINOGRAD_MIN_CG = 40     # GroupNorm folded into the Winograd input transform only for groups of >= 40 channels: a workgroup owns one (sample, group)
@@ -50,7 +46,7 @@ class HipUNet2DConditionModel:
         Everything before the first cross-attention (conv_in, the first ResNet block, the first self-attention) then
         sees identical inputs in both halves; it is computed once on batch/2 and duplicated -- bit-identical outputs."""
         self.cfgd = cfg
-        self.config = _Cfg(in_channels=cfg["in_channels"], out_channels=cfg["out_channels"], sample_size=height)
+        self.config = Cfg(in_channels=cfg["in_channels"], out_channels=cfg["out_channels"], sample_size=height)
         self.device = torch.device(device)
         self.batch, self.H, self.W, self.ctx_len = batch, height, width, ctx_len
         self.heads = cfg["heads"]
@@ -331,17 +327,11 @@ class HipUNet2DConditionModel:
     def set_context(self, encoder_hidden_states):
         """[batch, ctx_len, 768]; recomputes the cross-attention K / V^T of every transformer block."""
         self.ctx.copy_(encoder_hidden_states.to(self.device, F16).reshape(self.ctx.shape))
-        if self.use_graph:
-            self.gc.replay()
-        else:
-            self.gc.run()
+        self.gc.execute(self.use_graph)
 
     def forward_static(self):
         """x_in / timesteps already written into the static buffers; result lands in self.eps ([B*HW, 64])."""
-        if self.use_graph:
-            self.g.replay()                  # sd_model_replay: the library's hipGraph of the recorded launch list
-        else:
-            self.g.run()
+        self.g.execute(self.use_graph)       # use_graph: sd_model_replay, the library's hipGraph of the recorded launch list
         return self.eps
 
     def save(self, path):
@@ -365,5 +355,5 @@ class HipUNet2DConditionModel:
         ops.nhwc_to_nchw(self.eps, out, batch=B, c=self.config.out_channels, hw=HW, ld=64)
         out = out.to(sample.dtype) if sample.dtype in (torch.float16, torch.float32) else out
         if return_dict:
-            return _Cfg(sample=out)
+            return Cfg(sample=out)
         return (out,)

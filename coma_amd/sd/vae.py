@@ -12,11 +12,7 @@ import torch
 
 from . import ops
 from .graph import F16, LaunchGraph
-from .weights import VAE_CFG, conv_weight, pad_vec
-
-
-class _Cfg(dict):
-    __getattr__ = dict.__getitem__
+from .weights import VAE_CFG, Cfg, conv_weight, pad_vec
 
 
 class _VaeBase:
@@ -101,11 +97,6 @@ class _VaeBase:
         g.conv(a, s[p + ".to_out.0.weight"], out, batch=M, in_h=1, in_w=1, c0=C, n=C, bias=s[p + ".to_out.0.bias"], res=x)   # (M tokens as batch: no stats)
         return out
 
-    def _replay(self):
-        if not self.use_graph:
-            return self.g.run()
-        self.g.replay()
-
     def save(self, path):
         """The model file sd_model_load + sd_vae_decode / sd_vae_encode run without Python."""
         self.g.capture()
@@ -115,8 +106,8 @@ class _VaeBase:
 class HipVaeDecoder(_VaeBase):
     """z (fp16 NHWC [B, h*w, 64], 4 valid channels, ALREADY divided by scaling_factor) -> image NHWC [B, 64*h*w, 64]."""
 
-    def __init__(self, state, batch, latent_h=64, latent_w=64, device="cuda", cfg=VAE_CFG):
-        super().__init__(state, batch, device, cfg, plan="decode")
+    def __init__(self, state, batch, latent_h=64, latent_w=64, device="cuda", cfg=VAE_CFG, use_graph=True):
+        super().__init__(state, batch, device, cfg, use_graph, plan="decode")
         g, s, B = self.g, self.s, batch
         ch = cfg["block_out_channels"]
         H, W = latent_h, latent_w
@@ -166,15 +157,15 @@ class HipVaeDecoder(_VaeBase):
         g.model.bind("image", self.image)
 
     def decode_static(self):
-        self._replay()
+        self.g.execute(self.use_graph)
         return self.image
 
 
 class HipVaeEncoder(_VaeBase):
     """image (fp16 NHWC [B, H*W, 64], 3 valid channels in [-1,1]) -> moments NHWC [B, H/8*W/8, 64] (mean 4 | logvar 4)."""
 
-    def __init__(self, state, batch, height=512, width=512, device="cuda", cfg=VAE_CFG):
-        super().__init__(state, batch, device, cfg, plan="encode")
+    def __init__(self, state, batch, height=512, width=512, device="cuda", cfg=VAE_CFG, use_graph=True):
+        super().__init__(state, batch, device, cfg, use_graph, plan="encode")
         g, s, B = self.g, self.s, batch
         ch = cfg["block_out_channels"]
         H, W = height, width
@@ -184,11 +175,7 @@ class HipVaeEncoder(_VaeBase):
             # 3 -> 128 channels in one launch: the halo patch of a 16 x 16 tile in LDS, K = 32 operands built there, per-tile column sums for the
             # first ResNet's GroupNorm table (sd_conv3x3_c3_f16)
             w27 = torch.nn.functional.pad(conv_weight(s["encoder.conv_in.weight"]), (0, 5)).contiguous()       # [n][ky][kx][c] -> [n][32]
-            cs = g.buf(B * H * W // 256, 2, ch[0], dtype=torch.float32, zero=True)
-            g._colstats_tile[x.data_ptr()] = cs
-            g.add(lambda h0=H, w0=W, xo=x: ops.conv3x3_c3(self.x, w27, xo, batch=B, h=h0, w=w0, ldx=64, n=ch[0], bias=s["encoder.conv_in.bias"], colstats=cs),     # (x, H, W are rebound below)
-                  flops=2 * B * H * W * ch[0] * 32, alg_flops=2 * B * H * W * ch[0] * 27, tag=f"conv3x3(c3) B={B} {H}x{W} n={ch[0]}",
-                  nbytes=2 * B * H * W * (4 + ch[0]))
+            g.conv3x3_c3(self.x, w27, s["encoder.conv_in.bias"], x, batch=B, h=H, w=W, n=ch[0])
         elif self.packed_conv_in and s["encoder.conv_in.weight"].shape[1] == 3:
             # 3 input channels: one elementwise pass packs every pixel's 3x3x3 neighbourhood into 32 halfs and conv_in is a plain K = 32 product
             # (the implicit GEMM multiplied a 64-channel padded input: K = 576 for 27 real products)
@@ -230,7 +217,7 @@ class HipVaeEncoder(_VaeBase):
         g.model.bind("moments", self.moments)
 
     def encode_static(self):
-        self._replay()
+        self.g.execute(self.use_graph)
         return self.moments
 
 
@@ -259,14 +246,11 @@ class HipAutoencoderKL:
     """diffusers-shaped facade over the two graphs (NCHW tensors at the boundary, as the reference pipeline passes)."""
 
     def __init__(self, state, batch, height=512, width=512, device="cuda", cfg=VAE_CFG, with_encoder=True, use_graph=True):
-        self.config = _Cfg(scaling_factor=cfg["scaling_factor"], latent_channels=cfg["latent_channels"],
-                           block_out_channels=list(cfg["block_out_channels"]))
+        self.config = Cfg(scaling_factor=cfg["scaling_factor"], latent_channels=cfg["latent_channels"],
+                          block_out_channels=list(cfg["block_out_channels"]))
         self.device, self.batch, self.dtype = torch.device(device), batch, F16
-        self.dec = HipVaeDecoder(state, batch, height // 8, width // 8, device, cfg)
-        self.enc = HipVaeEncoder(state, batch, height, width, device, cfg) if with_encoder else None
-        self.dec.use_graph = use_graph
-        if self.enc is not None:
-            self.enc.use_graph = use_graph
+        self.dec = HipVaeDecoder(state, batch, height // 8, width // 8, device, cfg, use_graph)
+        self.enc = HipVaeEncoder(state, batch, height, width, device, cfg, use_graph) if with_encoder else None
 
     def decode(self, z, return_dict=False, **kw):
         B, hw = self.batch, self.dec.h * self.dec.w
@@ -274,10 +258,10 @@ class HipAutoencoderKL:
         img = self.dec.decode_static()
         out = torch.empty(B, 3, self.dec.out_h, self.dec.out_w, dtype=torch.float32, device=self.device)
         ops.nhwc_to_nchw(img, out, batch=B, c=3, hw=self.dec.out_h * self.dec.out_w, ld=64)
-        return _Cfg(sample=out) if return_dict else (out,)
+        return Cfg(sample=out) if return_dict else (out,)
 
     def encode(self, image):
         B, H, W = self.batch, image.shape[-2], image.shape[-1]
         ops.nchw_to_nhwc(image.to(self.device, torch.float32).contiguous(), self.enc.x, batch=B, c=3, hw=H * W, cpad=64)
         mom = self.enc.encode_static()
-        return _Cfg(latent_dist=_LatentDist(self, mom, B * self.enc.lat_h * self.enc.lat_w))
+        return Cfg(latent_dist=_LatentDist(self, mom, B * self.enc.lat_h * self.enc.lat_w))

@@ -11,6 +11,11 @@ import math
 
 import torch
 
+class Cfg(dict):
+    """A diffusers-shaped `.config` / return record: keys read as attributes."""
+    __getattr__ = dict.__getitem__
+
+
 UNET_CFG = dict(in_channels=9, out_channels=4, block_out_channels=(320, 640, 1280, 1280), layers_per_block=2,
                 heads=8, cross_attention_dim=768, groups=32,
                 down_has_attn=(True, True, True, False), up_has_attn=(False, True, True, True))

@@ -16,7 +16,7 @@ import math
 import numpy as np
 import torch
 
-from ..sd.graph import LaunchGraph
+from ..sd.recorder import LaunchRecorder
 from . import ops
 from . import weights as W
 
@@ -91,7 +91,7 @@ class HipPointRend:
         self.nh, self.nw = shortest_edge_size(height, width)
         self.hp, self.wp = -(-self.nh // DIVIS) * DIVIS, -(-self.nw // DIVIS) * DIVIS
         self.P = {k: (w.to(self.device).contiguous(), b.to(self.device).contiguous()) for k, (w, b) in W.prepare(state).items()}
-        self.g = LaunchGraph(self.device, plan="segment")
+        self.g = LaunchRecorder(self.device, plan="segment")
         self.t = {}                      # named intermediates (tests, debugging)
         self._build()
 
@@ -298,10 +298,7 @@ class HipPointRend:
                 fn()
                 torch.cuda.synchronize(self.device)
             return self.out
-        if self.use_graph:
-            self.g.replay()
-        else:
-            self.g.run()
+        self.g.execute(self.use_graph)
         return self.out
 
     def instances(self, b=0):
