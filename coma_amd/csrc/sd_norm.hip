@@ -445,6 +445,7 @@ extern "C" int sd_groupnorm_f16(const void* x0, const void* x1, int c0, int c1, 
                                 const void* gamma, const void* beta, int silu, void* out, float* stats, void* stream) {
   if (sd::plan_recording()) return sd::record<sd::PK_GN>(x0, x1, c0, c1, batch, hw, groups, eps, gamma, beta, silu, out, stats);
   if (!x0 || !gamma || !beta || !out || !stats) return fail(COMA_E_INVALID, "sd_groupnorm_f16: null pointer");
+  if (c0 <= 0 || c1 < 0) return fail(COMA_E_INVALID, "sd_groupnorm_f16: c0 must be positive and c1 non-negative (c0=%d c1=%d)", c0, c1);
   if (c1 > 0 && !x1) return fail(COMA_E_INVALID, "sd_groupnorm_f16: x1 missing");
   const int C = c0 + c1;
   if (batch <= 0 || hw <= 0 || groups <= 0 || groups > GN_MAX_GROUPS || C % groups || c0 % 8 || c1 % 8 || C > GN_MAX_C)
@@ -497,6 +498,7 @@ extern "C" int sd_softmax_f16(void* x, int64_t rows, int n, int ld, float scale,
   if (sd::plan_recording()) return sd::record<sd::PK_SOFTMAX>(x, rows, n, ld, scale);
   if (!x) return fail(COMA_E_INVALID, "sd_softmax_f16: null pointer");
   if (rows <= 0 || n <= 0 || ld < n) return fail(COMA_E_INVALID, "sd_softmax_f16: bad shape");
+  if (rows > 2147483647LL) return fail(COMA_E_INVALID, "sd_softmax_f16: rows = %lld exceeds the grid limit 2147483647", (long long)rows);
   hipLaunchKernelGGL(softmax_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, (_Float16*)x, n, ld, scale);
   return check_launch("softmax_kernel");
 }
@@ -507,6 +509,7 @@ extern "C" int sd_groupnorm_colstats_f16(const void* x0, const void* x1, int c0,
   if (sd::plan_recording()) return sd::record<sd::PK_GN_COLSTATS>(x0, x1, c0, c1, batch, hw, groups, eps, gamma, beta, silu, out, stats, colstats0,
                                                                   colstats1);
   if (!x0 || !gamma || !beta || !out || !stats || !colstats0) return fail(COMA_E_INVALID, "sd_groupnorm_colstats_f16: null pointer");
+  if (c0 <= 0 || c1 < 0) return fail(COMA_E_INVALID, "sd_groupnorm_colstats_f16: c0 must be positive and c1 non-negative (c0=%d c1=%d)", c0, c1);
   if (c1 > 0 && (!x1 || !colstats1)) return fail(COMA_E_INVALID, "sd_groupnorm_colstats_f16: second source incomplete");
   const int C = c0 + c1;
   if (batch <= 0 || hw <= 0 || hw % 32 || groups <= 0 || groups > GN_MAX_GROUPS || C % groups || c0 % 8 || c1 % 8)
@@ -530,6 +533,7 @@ extern "C" int sd_groupnorm_table_f16(const void* x0, int c0, int batch, int hw,
   if (!x0 || !gamma || !beta || !stats) return fail(COMA_E_INVALID, "sd_groupnorm_table_f16: null pointer");
   if (rows_per_slot == 0) rows_per_slot = 32;
   const int C = c0;
+  if (c0 <= 0) return fail(COMA_E_INVALID, "sd_groupnorm_table_f16: c0 must be positive (c0=%d)", c0);
   if (batch <= 0 || hw <= 0 || groups <= 0 || groups > GN_MAX_GROUPS || C % groups || c0 % 8 || C > GN_MAX_C || C / groups > 256)
     return fail(COMA_E_INVALID, "sd_groupnorm_table_f16: bad shape C=%d groups=%d", C, groups);
   hipStream_t s = (hipStream_t)stream;

@@ -442,6 +442,7 @@ int sd_winograd_input_f16(const void* x0, const void* x1, int c0, int c1, int ba
   if (!(vscale > 0.0f)) return fail(COMA_E_INVALID, "sd_winograd_input_f16: vscale must be positive");
   if (c0 <= 0 || c0 % 8 || c1 < 0 || c1 % 8 || (c1 > 0 && !x1)) return fail(COMA_E_INVALID, "sd_winograd_input_f16: channel counts must be multiples of 8");
   if (batch <= 0 || h <= 0 || w <= 0 || (h & 1) || (w & 1)) return fail(COMA_E_INVALID, "sd_winograd_input_f16: even h, w required");
+  if (silu && !gn_affine) return fail(COMA_E_INVALID, "sd_winograd_input_f16: silu needs gn_affine");
   const long long total = (long long)batch * (h / 2) * (w / 2) * ((c0 + c1) / 8);
   hipLaunchKernelGGL(winograd_input_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      (const _Float16*)x0, (const _Float16*)x1, c0, c1, batch, h, w, upsample, gn_affine, silu, vscale, (_Float16*)v);
@@ -464,9 +465,14 @@ int sd_winograd_output_f16(const void* m, int ldm, int batch, int h, int w, int 
   if (!m || !out) return fail(COMA_E_INVALID, "sd_winograd_output_f16: null pointer");
   if (!(mscale > 0.0f)) return fail(COMA_E_INVALID, "sd_winograd_output_f16: mscale must be positive");
   if (n <= 0 || n % 8 || ldm % 8 || batch <= 0 || (h & 1) || (w & 1)) return fail(COMA_E_INVALID, "sd_winograd_output_f16: bad shape");
+  if (h <= 0 || w <= 0) return fail(COMA_E_INVALID, "sd_winograd_output_f16: h and w must be positive (h=%d w=%d)", h, w);
+  if (ldm < n) return fail(COMA_E_INVALID, "sd_winograd_output_f16: ldm = %d is below n = %d", ldm, n);
   if (ldo == 0) ldo = n;
   if (ldr == 0) ldr = n;
   if (ldbb == 0) ldbb = n;
+  if (ldo < n || ldo % 8) return fail(COMA_E_INVALID, "sd_winograd_output_f16: ldo = %d must be a multiple of 8, at least n = %d", ldo, n);
+  if (res && (ldr < n || ldr % 8)) return fail(COMA_E_INVALID, "sd_winograd_output_f16: ldr = %d must be a multiple of 8, at least n = %d", ldr, n);
+  if (bias_bn && (ldbb < n || ldbb % 8)) return fail(COMA_E_INVALID, "sd_winograd_output_f16: ldbb = %d must be a multiple of 8, at least n = %d", ldbb, n);
   if (colstats) {
     if (w != 32 || n % 128) return fail(COMA_E_INVALID, "sd_winograd_output_f16: column sums need w = 32 and n %% 128 == 0 (w=%d n=%d)", w, n);
     hipLaunchKernelGGL(winograd_output_cs_kernel, dim3((unsigned)(batch * (h / 2)), (unsigned)(n / 128)), dim3(256), 0, (hipStream_t)stream,
@@ -497,6 +503,8 @@ int sd_gn_winograd_input_f16(const void* x0, const void* x1, int c0, int c1, con
   if ((long long)h * w * (C / groups) > kGnWinoMaxSlice)
     return fail(COMA_E_INVALID, "sd_gn_winograd_input_f16: a group's slice (%d x %d pixels x %d channels) exceeds %d elements", h, w, C / groups, kGnWinoMaxSlice);
   if (m && (ldm % 4 || ldm < C)) return fail(COMA_E_INVALID, "sd_gn_winograd_input_f16: ldm = %d", ldm);
+  if (bias_bn && ldbb > 0 && (ldbb < C || ldbb % 4))
+    return fail(COMA_E_INVALID, "sd_gn_winograd_input_f16: ldbb = %d must be 0 or a multiple of 4, at least C = %d", ldbb, C);
   GnWinoArgs a;
   a.x0 = (const _Float16*)x0; a.x1 = (const _Float16*)x1; a.c0 = c0; a.c1 = c1; a.m = (const _Float16*)m; a.ldm = ldm;
   a.bias = (const _Float16*)bias; a.bias_bn = (const _Float16*)bias_bn; a.ldbb = ldbb > 0 ? ldbb : C; a.h = h; a.w = w; a.groups = groups;

@@ -106,16 +106,24 @@ int sd_conv_gemm_describe(const sd_conv_gemm_desc* desc, sd_conv_gemm_choice* ch
 /* GroupNorm (+ optional SiLU) over NHWC fp16, reading the channel concatenation of two sources and writing one
  * tensor [batch, hw, c0+c1].  replaces: nn.GroupNorm(groups, C, eps) + nn.SiLU in diffusers ResnetBlock2D /
  * Transformer2DModel / VAE (and the torch.cat feeding the UNet up blocks).
- * stats: fp32 scratch of batch*(c0+c1)*2 + batch*ceil(hw/64)*groups*2 floats (affine table + partial sums). */
+ * stats: fp32 scratch of batch*(c0+c1)*2 + batch*ceil(hw/64)*groups*2 floats (affine table + partial sums); nothing behind it is touched.
+ * Its contents are UNSPECIFIED after the call: feature maps with (c0+c1)/groups a multiple of 4 and hw*(c0+c1)/groups <= 20480 elements
+ * per group run as one launch that never writes it (use sd_groupnorm_table_f16 for the table).
+ * Accepted: c0 > 0 and c1 >= 0, both multiples of 8, c0 + c1 <= 2560; 1 <= groups <= 32 dividing c0 + c1; batch, hw > 0; x1 != NULL when
+ * c1 > 0.  Anything else returns COMA_E_INVALID and launches nothing (as for every entry point below).  Statistics are summed in a fixed
+ * order: the same call gives the same bits.  Tested over this domain by tests/test_sd_norm_domain_gpu.py. */
 int sd_groupnorm_f16(const void* x0, const void* x1, int c0, int c1, int batch, int hw, int groups, float eps,
                      const void* gamma, const void* beta, int silu, void* out, float* stats, void* stream);
 /* Same, but the statistics come from the column sums the producing GEMMs left behind (sd_conv_gemm_desc.colstats of x0
- * and, with two sources, of x1): no statistics pass over the tensor.  hw % 32 == 0. */
+ * and, with two sources, of x1): no statistics pass over the tensor.  colstats0 / colstats1: fp32 [batch*hw/32][2][c0] / [..][2][c1].
+ * hw % 32 == 0, at most 256 channels per group, c0 > 0, c1 >= 0 (multiples of 8), 1 <= groups <= 32; x1 AND colstats1 when c1 > 0.
+ * Here the affine table [batch][c0+c1][2] at the start of `stats` is written. */
 int sd_groupnorm_colstats_f16(const void* x0, const void* x1, int c0, int c1, int batch, int hw, int groups, float eps,
                               const void* gamma, const void* beta, int silu, void* out, float* stats, const float* colstats0,
                               const float* colstats1, void* stream);
 
-/* LayerNorm over the last dim of fp16 [rows, c].  replaces: nn.LayerNorm(C) in BasicTransformerBlock. */
+/* LayerNorm over the last dim of fp16 [rows, c] (two-pass variance in fp32).  rows > 0; c a multiple of 8, at most 2048.
+ * replaces: nn.LayerNorm(C) in BasicTransformerBlock. */
 int sd_layernorm_f16(const void* x, int64_t rows, int c, float eps, const void* gamma, const void* beta, void* out,
                      void* stream);
 
@@ -169,10 +177,13 @@ int sd_attention_causal_f16(const void* q, const void* k, const void* v, void* o
 /* Only the per-(sample, channel) affine table of a GroupNorm: fp32 [batch][c0][2] = (scale, shift) at the start of `stats` (same
  * scratch size as sd_groupnorm_f16), from the producer's column sums (colstats0 != NULL: fp32 [batch * hw / rows_per_slot][2][c0], rows_per_slot
  * = 32 for sd_conv_gemm_desc.colstats -- 0 means 32 -- and 256 for sd_conv3x3_halo_f16) or from a statistics pass over x0; nothing is
- * applied.  For consumers that apply the affine themselves (sd_xfront_f16, sd_conv3x3_halo_f16, sd_conv3x3_small_n_f16). */
+ * applied.  For consumers that apply the affine themselves (sd_xfront_f16, sd_conv3x3_halo_f16, sd_conv3x3_small_n_f16).
+ * Accepted: c0 > 0, a multiple of 8, <= 2560; 1 <= groups <= 32 dividing c0, at most 256 channels per group; with colstats0:
+ * rows_per_slot >= 32 and hw % rows_per_slot == 0.  x0 must be non-NULL in both forms (it is only read without colstats0). */
 int sd_groupnorm_table_f16(const void* x0, int c0, int batch, int hw, int groups, float eps, const void* gamma, const void* beta,
                            float* stats, const float* colstats0, int rows_per_slot, void* stream);
-/* The same table for a GroupNorm over the channel concatenation of two tensors, from both producers' column sums only (hw % 32 == 0). */
+/* The same table for a GroupNorm over the channel concatenation of two tensors, from both producers' column sums only (32-row slots,
+ * hw % 32 == 0; c0 > 0, c1 >= 0, multiples of 8, c0 + c1 <= 2560, at most 256 channels per group; colstats1 != NULL when c1 > 0). */
 int sd_groupnorm_table_cat_f16(int c0, int c1, int batch, int hw, int groups, float eps, const void* gamma, const void* beta, float* stats,
                                const float* colstats0, const float* colstats1, void* stream);
 
@@ -223,7 +234,11 @@ int sd_xattn_chain_f16(const void* attn1_out, const void* h, const void* wo1, co
  *   sd_winograd_output_f16  out fp16 [batch*h*w, ldo] = A^T m A of m fp16 [16][T][ldm] + bias + per-sample bias, SiLU, + residual;
  *                           colstats != NULL (w = 32, n % 128 == 0): also fp32 [batch*h*w/32][2][n], the column sums / sums of squares of
  *                           `out` per 32 rows (sd_conv_gemm_desc.colstats layout: the consumer's GroupNorm statistics)
- * h, w even; channel counts multiples of 8.  sd_winograd_input_f16 / _output_f16 are recordable (sd_winograd_weight_f16 runs at prep time).
+ * h, w even and positive; channel counts multiples of 8 (sd_winograd_weight_f16: any n, c > 0); c0 > 0, c1 >= 0; the scales positive.
+ * sd_winograd_input_f16: silu without gn_affine is refused (as sd_conv3x3_halo_f16 refuses it): there is nothing to activate.
+ * sd_winograd_output_f16: ldm >= n; ldo, ldr, ldbb: 0 means n, otherwise >= n; ldm, ldo, ldr and ldbb multiples of 8 (every access is
+ * 16 bytes wide; ldr / ldbb only matter with res / bias_bn); SiLU is applied BEFORE the residual is added; gap columns are left alone.
+ * sd_winograd_input_f16 / _output_f16 are recordable (sd_winograd_weight_f16 runs at prep time).
  * fp16 range: V and the plane products are STORED as fp16 (the direct path keeps that sum in fp32 registers), so the transforms take
  * power-of-two scales -- v = vscale * B^T d B, u = uscale * G g G^T, out = mscale * A^T m A + bias ... with mscale = 1 / (uscale * vscale):
  * exact in the normal range; the product uses uscale = 1/4 (and vscale = 1/4 where the input is an un-normalised residual stream, V alone
@@ -241,7 +256,13 @@ int sd_winograd_output_f16(const void* m, int ldm, int batch, int h, int w, int 
  *            convolution (x0 == x1 == NULL, c0 = its output channels, c1 = 0), rounded to fp16 and never written;
  *   v fp16 [16][batch*h/2*w/2][c0+c1] = B^T act(GroupNorm(source)) B.
  * Replaces sd_winograd_output_f16 -> sd_groupnorm_f16 -> sd_winograd_input_f16 (conv1 -> norm2 -> SiLU -> conv2 of a ResnetBlock2D)
- * or sd_groupnorm_f16 -> sd_winograd_input_f16 (norm1 -> SiLU -> conv1) with one launch.  Recordable. */
+ * or sd_groupnorm_f16 -> sd_winograd_input_f16 (norm1 -> SiLU -> conv1) with one launch.  Recordable.
+ * With NHWC sources every output bit equals sd_groupnorm_f16 -> sd_winograd_input_f16 (same statistics order; asserted by
+ * tests/test_sd_norm_domain_gpu.py); from plane products the statistics are summed in another order than the unfused chain's.
+ * Accepted: c0 > 0, c1 >= 0 and (c0 + c1) / groups multiples of 4; batch <= 65535; h, w even; with m: mscale > 0, ldm >= c0 a multiple
+ * of 4, x0 == x1 == NULL, c1 = 0; ldbb: 0 means c0, otherwise >= c0 and a multiple of 4.  Accesses are 16 bytes wide when the group
+ * width, ldm and ldbb are multiples of 8 and m, bias, bias_bn, gamma, beta and v are 16-byte aligned, else 8 bytes wide (those
+ * pointers must then be 8-byte aligned). */
 int sd_gn_winograd_input_f16(const void* x0, const void* x1, int c0, int c1, const void* m, int ldm, const void* bias, const void* bias_bn,
                              int ldbb, int batch, int h, int w, int groups, float eps, const void* gamma, const void* beta, int silu, float mscale,
                              void* v, void* stream);
@@ -291,7 +312,8 @@ int sd_im2col3x3_c3_f16(const void* x, int ldx, int batch, int h, int w_, void* 
 int sd_conv3x3_c3_f16(const void* x, int ldx, const void* w32, const void* bias, int batch, int h, int w_, int n, void* out, int ldo,
                       float* colstats, void* stream);
 
-/* Row softmax in place over fp16 [rows, n] with scale (VAE mid-block attention, un-fused). */
+/* Row softmax in place over fp16 [rows, n] with scale (VAE mid-block attention, un-fused): x[r * ld + i], i < n, becomes
+ * softmax_i(scale * x[r, i]); ld >= n, columns n .. ld-1 are neither read nor written; 0 < rows <= 2^31 - 1 (one workgroup per row). */
 int sd_softmax_f16(void* x, int64_t rows, int n, int ld, float scale, void* stream);
 
 /* Classifier-free guidance + DDIM step (eta = 0) + assembly of the next UNet input, one elementwise pass.
