@@ -307,6 +307,10 @@ extern "C" int sd_conv3x3_small_n_f16(const void* x, const float* gn_affine, int
   if (c != 128 && c != 320) return fail(COMA_E_INVALID, "sd_conv3x3_small_n_f16: c = %d (built for 128 and 320 input channels)", c);
   if (n < 1 || n > 4 || batch <= 0 || h <= 0 || w_ <= 0 || ldo < 8 || ldo % 8)
     return fail(COMA_E_INVALID, "sd_conv3x3_small_n_f16: bad shape n=%d batch=%d h=%d w=%d ldo=%d", n, batch, h, w_, ldo);
+  if (silu && !gn_affine) return fail(COMA_E_INVALID, "sd_conv3x3_small_n_f16: silu is applied with the GroupNorm affine (gn_affine is NULL)");
+  // batch and the tile rows are grid.z / grid.y: 65535 each
+  if (batch > 65535) return fail(COMA_E_INVALID, "sd_conv3x3_small_n_f16: batch = %d exceeds the grid limit 65535", batch);
+  if ((h + kTile - 1) / kTile > 65535) return fail(COMA_E_INVALID, "sd_conv3x3_small_n_f16: h = %d exceeds the grid limit of 65535 tile rows", h);
   if ((size_t)batch * h * w_ * c >= (1ull << 40)) return fail(COMA_E_INVALID, "sd_conv3x3_small_n_f16: tensor too large");
   const dim3 grid((unsigned)((w_ + kTile - 1) / kTile), (unsigned)((h + kTile - 1) / kTile), (unsigned)batch);
   if (c == 128)
@@ -338,6 +342,7 @@ extern "C" int sd_conv3x3_c3_f16(const void* x, int ldx, const void* w32, const 
   if (n != 128) return fail(COMA_E_INVALID, "sd_conv3x3_c3_f16: n = %d (built for 128 output channels)", n);
   if (ldx < 4 || ldx % 4 || batch <= 0 || batch > 65535 || h <= 0 || w_ <= 0 || h % kTile || w_ % kTile || ldo < n || ldo % 8)
     return fail(COMA_E_INVALID, "sd_conv3x3_c3_f16: bad shape ldx=%d batch=%d h=%d w=%d ldo=%d (h, w multiples of 16; ldx %% 4 == 0; ldo %% 8 == 0)", ldx, batch, h, w_, ldo);
+  if (h / kTile > 65535) return fail(COMA_E_INVALID, "sd_conv3x3_c3_f16: h = %d exceeds the grid limit of 65535 tile rows", h);
   dim3 grid((unsigned)(w_ / kTile), (unsigned)(h / kTile), (unsigned)batch);
   hipLaunchKernelGGL(conv3x3_c3_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const _Float16*)x, ldx, (const _Float16*)w32, (const _Float16*)bias, h, w_,
                      (_Float16*)out, ldo, colstats);

@@ -277,6 +277,13 @@ int sd_gn_winograd_input_f16(const void* x0, const void* x1, int c0, int c1, con
  *   colstats != NULL: fp32 [batch*h*w/256][2][n], sums / sums of squares of the stored output per 16 x 16 pixel tile (one slot per
  *   workgroup: sd_groupnorm_table_f16 with rows_per_slot = 256; 8 x fewer slots than the GEMM epilogue's 32-row slots -- at 512 x 512 the
  *   consumer's table launch read 67 MB of them, 84-120 us).  Recordable.
+ * Accepted (anything else is COMA_E_INVALID before a launch): n in {128, 256, 384, 512}; c in {64, 128, ..., 512}; batch > 0; h, w > 0 and
+ *   multiples of 16; one input sample (h * w * c * 2 bytes) below 2 GiB; batch * (h / 16) * (w / 16) * (n / 128) <= 2^31 - 1 workgroups;
+ *   silu requires gn_affine (there is nothing else to activate).  w fp16 [n][9][c] (tap = 3 ky + kx), bias fp16 [n] or NULL,
+ *   res fp16 [batch*h*w][ldr] or NULL, out fp16 [batch*h*w][ldo].  ldo = 0 means n, ldr = 0 means n; otherwise ldo >= n, ldo % 8 == 0 and,
+ *   with res, ldr >= n, ldr % 8 == 0 (ldr is ignored without res).  Columns n .. ldo - 1 of out are neither read nor written, columns
+ *   n .. ldr - 1 of res are not read.  Every access is 16 bytes wide: x, w, bias, res and out must be 16-byte aligned; gn_affine 8-byte,
+ *   colstats 4-byte aligned.
  * replaces: GroupNorm -> SiLU -> Conv2d(3x3) of ResnetBlock2D inside self.vae.decode / self.vae.encode,
  * utils/adaptive_mask_inpainting.py:1086, :1112, :677-680. */
 int sd_conv3x3_halo_f16(const void* x, int c, const float* gn_affine, int silu, const void* w, const void* bias, const void* res, int ldr,
@@ -289,6 +296,10 @@ int sd_conv3x3_halo_f16(const void* x, int c, const float* gn_affine, int silu, 
  * (ldo >= 8, multiple of 8): channels 0..7 of every pixel are written (n results + zeros), channels >= 8 are left alone.
  * The normalised tensor is never written: the halo patch of a 16 x 16 pixel tile is activated on its way into LDS and rounded to
  * fp16 there, i.e. the result equals GroupNorm kernel -> convolution up to fp32 summation order.  Recordable.
+ * Accepted (anything else is COMA_E_INVALID before a launch): c = 128 or 320; 1 <= n <= 4; 0 < batch <= 65535; h, w > 0, any size
+ *   (tiles of 16 x 16, ragged at the right and bottom edge), at most 65535 tile rows (h <= 1048560); batch * h * w * c < 2^40;
+ *   ldo >= 8 and ldo % 8 == 0; silu requires gn_affine (there is nothing else to activate).  Rows of w and entries of bias at and
+ *   beyond n are not read.  x, w and out must be 16-byte aligned (16-byte accesses), gn_affine 8-byte, bias 2-byte aligned.
  * replaces: decoder.conv_norm_out + SiLU + decoder.conv_out of AutoencoderKL (self.vae.decode, utils/adaptive_mask_inpainting.py:1086, :1112)
  *           and conv_norm_out + SiLU + conv_out of UNet2DConditionModel (self.unet(...), :1001-1007). */
 int sd_conv3x3_small_n_f16(const void* x, const float* gn_affine, int silu, const void* w, const void* bias, int batch, int h, int w_,
@@ -298,6 +309,8 @@ int sd_conv3x3_small_n_f16(const void* x, const float* gn_affine, int silu, cons
  * (tap = 3 * ky + kx, zero padding, columns 27..31 zero), so that a convolution with 3 input channels is a plain K = 32 product
  * (sd_conv_gemm_f16 with weights [n][32] = [n][ky][kx][c] padded).  x fp16 NHWC [batch, h, w, ldx] (channels 0..2 read, ldx % 4 == 0),
  * out fp16 [batch*h*w][32].  Recordable.
+ * Accepted (anything else is COMA_E_INVALID before a launch): ldx >= 4 and ldx % 4 == 0; batch, h, w > 0, any size; batch * h * w <= 2^31 - 1.
+ *   Channels 3 .. ldx - 1 of x are not used (a pixel is read as one 8-byte access: x must be 8-byte aligned, out 16-byte aligned).
  * replaces: the im2col half of encoder.conv_in of AutoencoderKL (self.vae.encode, utils/adaptive_mask_inpainting.py:677-680). */
 int sd_im2col3x3_c3_f16(const void* x, int ldx, int batch, int h, int w_, void* out, void* stream);
 
@@ -307,6 +320,10 @@ int sd_im2col3x3_c3_f16(const void* x, int ldx, int batch, int h, int w_, void* 
  * colstats (or NULL): fp32 [batch*h*w/256][2][128], the column sums / sums of squares of the stored output per 16 x 16 pixel tile -- the slot layout
  * of sd_conv3x3_halo_f16, read by sd_groupnorm_table_f16 with rows_per_slot = 256.  Same products as im2col + K = 32 GEMM (fp32 accumulation in the
  * MFMA, another summation order); the packed [batch*h*w][32] matrix is never written.  Recordable.
+ * Accepted (anything else is COMA_E_INVALID before a launch): n = 128; ldx >= 4 and ldx % 4 == 0; 0 < batch <= 65535; h, w > 0 and multiples of 16,
+ *   at most 65535 tile rows (h <= 1048560); ldo >= n and ldo % 8 == 0 (columns n .. ldo - 1 of out are left alone).  Channels 3 .. ldx - 1 of x are
+ *   not used (a pixel is read as one 8-byte access: x must be 8-byte aligned); w32 and out must be 16-byte aligned, bias 2-byte, colstats 4-byte;
+ *   columns 27 .. 31 of w32 must be zero.
  * replaces: encoder.conv_in of AutoencoderKL (self.vae.encode, utils/adaptive_mask_inpainting.py:677-680) + the statistics pass of the first
  *           ResNet block's GroupNorm. */
 int sd_conv3x3_c3_f16(const void* x, int ldx, const void* w32, const void* bias, int batch, int h, int w_, int n, void* out, int ldo,
