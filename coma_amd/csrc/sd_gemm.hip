@@ -75,7 +75,7 @@ struct GemmArgs {
   // is (y - pad, x - pad_x), and row m = (b, y, x) of the product is output pixel (2 y + a, 2 x + b): row 2 m + 2 W floor(m / W) + a 2 W + b
   // of `out` (W = in_w, a power of two).  kw = taps per window row (3, or 2 in phase mode).
   int kw, pad_x;
-  int phase;                  // 0: off; 1 + 2 a + b otherwise
+  int phase;                  // 0: off; 1 + 2 a + b otherwise; 5: all four, grid y = phase - 1 (resolved per block at kernel entry)
   int ph_wshift, ph_rowoff;   // log2(in_w); a * 2 W + b
 };
 
@@ -489,7 +489,14 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, AccQ accq, _Flo
 //        MFMA) -- drops to 0.225 DMA per MFMA.
 //   <WM=2, WN=1/2, ...> 64-wide fallbacks for small N.
 template <int WM, int WN, int TN, int BK, int STAGES, bool SPREAD = false, int TM = 2, bool M16 = false>
-__global__ __launch_bounds__(WM* WN * 64, 2) void conv_gemm_kernel(GemmArgs g) {
+__global__ __launch_bounds__(WM* WN * 64, 2) void conv_gemm_kernel(GemmArgs g_in) {
+  // The four sub-pixel phases as ONE launch (phase = 5, grid y = phase - 1): everything the phase decides -- the window origin, the row
+  // offset in `out`, the statistics slots -- comes from the block's own phase; the weights of phase p sit (p - 1) * sw further on
+  GemmArgs g = g_in;
+  if (g_in.phase == 5) {
+    const int pa = blockIdx.y >> 1, pb = blockIdx.y & 1;
+    g.phase = (int)blockIdx.y + 1; g.pad = 1 - pa; g.pad_x = 1 - pb; g.ph_rowoff = pa * 2 * g_in.in_w + pb;
+  }
   constexpr int NW = WM * WN;                       // waves per block
   constexpr int BM_ = WM * TM * 32, BN = WN * TN * 32;
   constexpr int CPR = BK / 8;                       // 16-byte chunks per tile row
@@ -900,11 +907,15 @@ static int conv_gemm_configure(const sd_conv_gemm_desc* d_in, GemmArgs& g, int& 
   const sd_conv_gemm_desc* d = &d_copy;
   if (!d->a0 || !d->w || !d->out) return fail(COMA_E_INVALID, "sd_conv_gemm_f16: null pointer");
   const int phase = d->phase;
-  if (phase < 0 || phase > 4) return fail(COMA_E_INVALID, "sd_conv_gemm_f16: phase must be 0..4");
+  // phase = 5: the four phases as the z dimension of ONE launch (nbatch_z = 4, the weights of phase p at w + (p - 1) * stride_w)
+  const bool zphase = phase == 5 && d->nbatch_z == 4;
+  if (phase < 0 || (phase > 4 && !zphase)) return fail(COMA_E_INVALID, "sd_conv_gemm_f16: phase must be 0..4, or 5 with nbatch_z = 4 (all four phases in one launch)");
+  if (zphase && (d->stride_a || d->stride_out || d->stride_w < (int64_t)d->n * 4 * (d->c0 + d->c1)))
+    return fail(COMA_E_INVALID, "sd_conv_gemm_f16: phase = 5 shares the source and `out` between the phases (stride_a = stride_out = 0) and needs stride_w >= n * 4 * (c0 + c1)");
   if (phase) {
     // sub-pixel phase of conv3x3(nearest-upsample-x2(x)): a 2 x 2 window over the source, rows scattered to the output pixels of that parity
     if (d->taps != 4 || d->stride != 1 || d->upsample || d->out_h != d->in_h || d->out_w != d->in_w || (d->in_w & (d->in_w - 1)) ||
-        (d->nbatch_z > 1) || d->res || d->bias_bn || d->out_t || d->epi || d->n % 8 ||
+        (d->nbatch_z > 1 && !zphase) || d->res || d->bias_bn || d->out_t || d->epi || d->n % 8 ||
         (d->ldo > 0 && d->ldo % 8))
       return fail(COMA_E_INVALID, "sd_conv_gemm_f16: a phase launch needs taps = 4, stride 1, out = in size, in_w a power of two, n %% 8 == 0 and "
                                   "a plain epilogue (bias, optional colstats)");
@@ -927,7 +938,7 @@ static int conv_gemm_configure(const sd_conv_gemm_desc* d_in, GemmArgs& g, int& 
   g.taps = d->taps; g.stride = d->stride; g.upsample = d->upsample; g.pad = d->taps == 9 ? d->pad : 0;
   g.kw = 3; g.pad_x = g.pad; g.phase = phase; g.ph_wshift = 0; g.ph_rowoff = 0;
   if (phase) {
-    const int pa = (phase - 1) >> 1, pb = (phase - 1) & 1;
+    const int pa = zphase ? 0 : (phase - 1) >> 1, pb = zphase ? 0 : (phase - 1) & 1;       // phase = 5: the kernel sets these three per block
     g.kw = 2; g.pad = 1 - pa; g.pad_x = 1 - pb;                  // window rows y - 1 + a, y + a; columns x - 1 + b, x + b
     while ((1 << g.ph_wshift) < d->in_w) ++g.ph_wshift;
     g.ph_rowoff = pa * 2 * d->in_w + pb;
@@ -941,7 +952,7 @@ static int conv_gemm_configure(const sd_conv_gemm_desc* d_in, GemmArgs& g, int& 
   if (d->taps != 1 && d->batch > 65535) return fail(COMA_E_INVALID, "sd_conv_gemm_f16: a 3x3 convolution takes at most 65535 samples per launch");
   // the LDS-DMA addresses rows with 32-bit byte offsets from the tensor base (bit 31 marks zero padding)
   const long long a_bytes = (long long)d->batch * d->in_h * d->in_w * (d->c0 > d->c1 ? d->c0 : d->c1) * 2;
-  const long long w_bytes = (long long)d->n * d->taps * (d->c0 + d->c1) * 2;
+  const long long w_bytes = (long long)d->n * d->taps * (d->c0 + d->c1) * 2;       // per z: every block's resource starts at its own weights
   if (a_bytes >= 0x80000000LL || w_bytes >= 0x80000000LL)
     return fail(COMA_E_INVALID, "sd_conv_gemm_f16: a source tensor (%lld B) or the weights (%lld B) exceed 2 GiB per launch; split the batch",
                 a_bytes, w_bytes);
@@ -978,7 +989,9 @@ static int conv_gemm_configure(const sd_conv_gemm_desc* d_in, GemmArgs& g, int& 
   // ... or z-batched plain products whose tiles fill it together (the 16 plane products of a Winograd convolution at the 16 x 16 level:
   // 4 x 4 tiles x 16 planes = one block per CU, where the generic 128 x 128 tile needs 2.5 rounds)
   const bool zplain = nz > 1 && d->taps == 1 && !d->colstats && !d->out_t && !d->epi;
-  const bool big = !geglu && (nz == 1 || zplain) && k64 && g.N % 320 == 0 && (long long)((g.M + 255) / 256) * (g.N / 320) * nz >= 192;
+  // ... or the four phases of one launch (the 640-channel Upsample2D convolution of the UNet: 64 x 2 tiles x 4 phases, two per CU, where a
+  // single phase is one 128 x 320 tile per CU in one round)
+  const bool big = !geglu && (nz == 1 || zplain || zphase) && k64 && g.N % 320 == 0 && (long long)((g.M + 255) / 256) * (g.N / 320) * nz >= 192;
   // GEGLU (needs an even number of MFMA column tiles per wave): 256 x 256, 8 waves, wave tile 64 x 128
   const bool big_geglu = geglu && nz == 1 && k64 && g.N % 256 == 0 && g.M >= 256 * 16;
   // VAE widths (128 / 256 / 512 channels at up to 512 x 512 pixels): 256 x 256 and 256 x 128 tiles, 8 waves
@@ -1019,7 +1032,7 @@ static int conv_gemm_configure(const sd_conv_gemm_desc* d_in, GemmArgs& g, int& 
                                   "n - n_split multiples of 640, M and rows_per_sample multiples of 32, ldo >= n_split, ldo_t >= rows_per_sample, both % 8 == 0");
     if (d->n_split % bn) return fail(COMA_E_INVALID, "sd_conv_gemm_f16: out_t: the %d-column tile of this shape does not divide n_split = %d", bn, d->n_split);
   }
-  if (g.colstats && (geglu || nz != 1 || g.M % 32 || g.N % 8 || (d->epi & SD_EPI_BIAS_ROWS) || g.ldo % 8 || (g.res && g.ldr % 8) ||
+  if (g.colstats && (geglu || (nz != 1 && !zphase) || g.M % 32 || g.N % 8 || (d->epi & SD_EPI_BIAS_ROWS) || g.ldo % 8 || (g.res && g.ldr % 8) ||
                      (g.bias_bn && (g.res || g.rows_per_batch % 32 || g.ldbb % 8)) || (long long)(g.M + 512) * g.ldo * 2 >= 0x7fffffffLL ||
                      (g.res && (long long)(g.M + 512) * g.ldr * 2 >= 0x7fffffffLL)))
     return fail(COMA_E_INVALID, "sd_conv_gemm_f16: colstats needs M %% 32 == 0, N %% 8 == 0, 16-byte aligned rows, < 2 GiB tensors, no GEGLU / batching");

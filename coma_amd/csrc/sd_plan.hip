@@ -82,7 +82,7 @@ int record_conv(const sd_conv_gemm_desc* d_in) {
   for (int k = 0; k < 22; ++k) r.i[k] = is[k];
   if (d.out_t && (d.n_split < 0 || d.n_split >= (1 << 20) || d.ldo_t < 0 || d.ldo_t >= (1 << 20) || d.rows_per_sample < 0 || d.rows_per_sample >= (1 << 20)))
     return fail(COMA_E_INVALID, "sd_conv_gemm_f16: out_t sizes out of range");
-  if (d.phase < 0 || d.phase > 4) return fail(COMA_E_INVALID, "sd_conv_gemm_f16: phase must be 0..4");
+  if (d.phase < 0 || d.phase > 5 || (d.phase == 5 && d.nbatch_z != 4)) return fail(COMA_E_INVALID, "sd_conv_gemm_f16: phase must be 0..4, or 5 with nbatch_z = 4 (all four phases in one launch)");
   if (d.epi & ~SD_EPI_ALL) return fail(COMA_E_INVALID, "sd_conv_gemm_f16: epi 0x%x holds bits outside SD_EPI_ALL", d.epi);
   r.i[22] = (int64_t)d.n_split | ((int64_t)d.ldo_t << 20) | ((int64_t)d.rows_per_sample << 40) | ((int64_t)d.phase << 60);
   return plan_record(r);

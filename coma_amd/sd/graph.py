@@ -49,15 +49,21 @@ class LaunchGraph(LaunchRecorder):
                  tag=f"gemm M={batch * oh * ow} N={n} K={taps * (c0 + c1)} taps={taps} z={z}" + tag_note)
         return out
 
-    def conv3x3_upsampled(self, a0, w_raw, out, *, batch, in_h, in_w, c0, n, bias=None, stats=False):
+    def conv3x3_upsampled(self, a0, w_raw, out, *, batch, in_h, in_w, c0, n, bias=None, stats=False, one_launch=False):
         """diffusers Upsample2D: conv3x3(nearest-upsample-x2(a0)) as FOUR sub-pixel phase products over the source (sd_conv_gemm_desc.phase):
         16 multiplies per output 2 x 2 block instead of 36, exact (the folded weights are sums of the 3x3 taps), no transformed tensors.
-        w_raw: the torch-layout weight [n, c0, 3, 3]; out: [batch * 2 in_h * 2 in_w, n]."""
+        w_raw: the torch-layout weight [n, c0, 3, 3]; out: [batch * 2 in_h * 2 in_w, n].
+        one_launch: the four products as the z dimension of ONE launch (phase = 5) -- their tiles fill the chip together where a single
+        phase is a round of one tile per CU (the 640-channel upsampler of the UNet)."""
         from .weights import upsample_phase_weights
         assert in_w & (in_w - 1) == 0, "phase launches need a power-of-two source width"
         M = batch * in_h * in_w
         ws = upsample_phase_weights(w_raw)
-        cs = self.gn_stats.produce(out, "phase", rows=4 * M, n=n, hw=4 * in_h * in_w, asked=stats)      # ONE buffer for the four launches
+        cs = self.gn_stats.produce(out, "phase", rows=4 * M, n=n, hw=4 * in_h * in_w, asked=stats)      # ONE buffer for the four phases
+        if one_launch:
+            self.conv(a0, torch.stack(ws).contiguous(), out, batch=batch, in_h=in_h, in_w=in_w, c0=c0, n=n, taps=4, phase=5, nbatch_z=4,
+                      stride_w=n * 4 * c0, bias=bias, colstats=cs, alg_flops=2 * 4 * M * n * 9 * c0, tag_note=" (upsample, four phases)")
+            return out
         for ph in range(4):
             self.conv(a0, ws[ph], out, batch=batch, in_h=in_h, in_w=in_w, c0=c0, n=n, taps=4, phase=ph + 1, bias=bias, colstats=cs,
                       alg_flops=2 * M * n * 9 * c0, tag_note=f" (upsample phase {ph})")

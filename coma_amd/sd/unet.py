@@ -14,8 +14,8 @@ concatenation -> GroupNorm/SiLU -> conv_out.  Fusions done here, none of which c
   * nearest-x2 upsampling and stride-2 downsampling are index arithmetic inside the conv's operand gather;
   * cross-attention K/V of the text context are computed once per prompt, not once per step.
 Measured and removed (A/B history in profiles/r02_notes.md 6, r04_notes.md 4-7, r05_notes.md): the LayerNorms folded algebraically into
-their consumer GEMMs (0.2-0.7 ms SLOWER per forward in three rounds of A/B), Upsample2D as four sub-pixel phase products inside the UNet
-(slower; the VAE decoder uses them), and the run-time switches of the Winograd sub-features, whose winning settings are now code.
+their consumer GEMMs (0.2-0.7 ms SLOWER per forward in three rounds of A/B), Upsample2D as four SEPARATE sub-pixel phase launches inside the
+UNet (slower: each launch is one partial round of tiles; as ONE launch they win, see PHASE_UPSAMPLE_MIN_HW), and the run-time switches of the Winograd sub-features, whose winning settings are now code.
 """
 from __future__ import annotations
 
@@ -29,6 +29,10 @@ from .weights import UNET_CFG, Cfg, conv_weight, geglu_interleave, pad_vec
 GN_WINOGRAD_MIN_CG = 40     # GroupNorm folded into the Winograd input transform only for groups of >= 40 channels: a workgroup owns one (sample, group)
                             # slice, and with 20-channel groups (C = 640) its 40-byte pieces of every (plane, tile) row waste most of each memory
                             # transaction (48-114 us per launch at the 32 x 32 level against 18 us at C = 1280, profiles/r04_notes.md 4)
+PHASE_UPSAMPLE_MIN_BATCH = 8    # Upsample2D convolutions as ONE launch of the four sub-pixel phase products (sd_conv_gemm_desc.phase = 5) from this UNet
+PHASE_UPSAMPLE_MIN_HW = 16      # batch and source size on.  Per forward at batch 16, A B A B inside the captured graph (profiles/r07_notes.md):
+                                # 32 x 32 source, 640 channels (was the direct 3x3 over the upsampled tensor) -0.17 ms; 16 x 16, 1280 channels (was
+                                # Winograd) -0.13 ms; 8 x 8, 1280 channels: a tie (17.120 vs 17.119 ms), Winograd stays
 XTAIL_MIN_ROWS = 32768      # the fused feed-forward tail (sd_xtail_f16, 128-row tiles) from one workgroup per CU on: at UNet batch 2 (8192 rows, 64
                             # workgroups) the three separate GEMMs are 2.1 % of a forward faster (7.13 -> 6.97 ms, profiles/r06_notes.md 6), at batch 16 the
                             # fused launch wins (r5)
@@ -141,9 +145,14 @@ class HipUNet2DConditionModel:
             if i < len(ch) - 1:
                 p = f"up_blocks.{i}.upsamplers.0.conv"
                 o = g.buf(B * 4 * H * W, cout)
-                if self.winograd_max_h and 2 * max(H, W) <= self.winograd_max_h and cout >= 1280 and B >= self.winograd_min_batch:
-                    # Upsample2D + conv at the deep levels: the input transform reads the nearest-x2 upsampling in place.  (The four sub-pixel
-                    # phase products the VAE decoder uses lose here: 17.55 -> 17.67 ms per forward at M = 1024 ... 16384 source rows.)
+                if (B >= PHASE_UPSAMPLE_MIN_BATCH and min(H, W) >= PHASE_UPSAMPLE_MIN_HW and W & (W - 1) == 0 and (H * W) % 32 == 0
+                        and 4 * B * H * W * cout * 2 < (1 << 31) - (1 << 22)):
+                    # Upsample2D + conv as the four sub-pixel phase products over the source in ONE launch: 2.25 x fewer multiplies than the 3x3
+                    # over the upsampled tensor, no transformed tensors, and the tiles of the four products fill the chip together (256 x 320)
+                    g.conv3x3_upsampled(h, s[p + ".weight"], o, batch=B, in_h=H, in_w=W, c0=cout, n=cout, bias=s[p + ".bias"], stats=True,
+                                        one_launch=True)
+                elif self.winograd_max_h and 2 * max(H, W) <= self.winograd_max_h and cout >= 1280 and B >= self.winograd_min_batch:
+                    # Upsample2D + conv at the deepest level (8 x 8 source): the Winograd input transform reads the nearest-x2 upsampling in place
                     g.conv3x3_winograd(h, conv_weight(s[p + ".weight"]), o, batch=B, in_h=2 * H, in_w=2 * W, c0=cout, n=cout, bias=s[p + ".bias"],
                                        upsample=True, stats=True)
                 else:

@@ -87,7 +87,12 @@ typedef struct sd_conv_gemm_desc {
    * out_w = in_w, in_w a power of two), `out` = the full [batch, 2 in_h, 2 in_w, ldo] tensor: row m = (b, y, x) of the product is written to
    * pixel (2y + a, 2x + b).  Four launches (phase 1..4) make the convolution; colstats (optional) must have room for 4 M / 32 slots: phase p of
    * sample b owns slots [(4 b + p - 1) per, (4 b + p) per), per = in_h * in_w / 32, so colstats needs in_h * in_w % 32 == 0 here (refused otherwise).
-   * Plain epilogue only (bias).  0 = off (every other launch; a zero-initialised descriptor). */
+   * Plain epilogue only (bias).  0 = off (every other launch; a zero-initialised descriptor).
+   * phase = 5 with nbatch_z = 4: the four phases as ONE launch, grid z = phase - 1.  w holds the four summed-weight matrices stride_w
+   * elements apart (stride_w >= n * 4 * (c0+c1)); the source, `out`, bias and colstats are shared (stride_a = stride_out = 0), every phase
+   * writing its own pixels and its own colstats slots as above.  The tile is chosen for the four products together, so a launch whose
+   * single phases would each be one partial round of tiles fills the chip (the UNet's 640-channel Upsample2D convolution).  Everything a
+   * single phase launch refuses is refused here too; phase = 5 with any other nbatch_z is refused. */
   int phase;
 } sd_conv_gemm_desc;
 
