@@ -63,6 +63,17 @@ SIGNATURES = {
     "coma_depth_optimize_state_bytes": (C.c_size_t, []),
     "coma_depth_optimize_f64": (_i, [_vp, _vp, _i, _vp, C.POINTER(_d), _vp, _vp, _i, _i, _d, _d, _d, _d, _i, _vp, _vp, _vp, _vp, _vp]),
     "coma_depth_optimize_status": (_i, [_vp, _vp, C.POINTER(_i)]),
+    "coma_coap_weights_floats": (C.c_size_t, [_i]),
+    "coma_coap_code_bytes": (C.c_size_t, [_i]),
+    "coma_coap_encode_workspace_bytes": (C.c_size_t, [_i, _i]),
+    "coma_coap_query_workspace_bytes": (C.c_size_t, [_i, _i]),
+    "coma_coap_encode_f32": (_i, [_vp, C.c_size_t, _vp, _vp, _vp, _i, C.POINTER(C.c_int32), C.POINTER(C.c_uint8), _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp,
+                                  C.c_size_t, _vp]),
+    "coma_coap_status": (_i, [_vp, _vp]),
+    "coma_coap_query_f32": (_i, [_vp, C.c_size_t, _vp, _i, _vp, _i, _vp, _fp3, _i, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "coma_coap_collision_f32": (_i, [_vp, C.c_size_t, _vp, _i, _vp, _i, _vp, _fp3, _d, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "coma_depth_optimize_coap_f64": (_i, [_vp, C.c_size_t, _vp, _i, _vp, _i, _d, _vp, C.c_size_t, _vp, _i, _vp, C.POINTER(_d), _vp, _vp, _i, _i,
+                                          _d, _d, _d, _d, _i, _vp, _vp, _vp, _vp, _vp]),
     "coma_app_objective_workspace_bytes": (C.c_size_t, [_i, _i, _i]),
     "coma_app_objective_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _fp3, _fp3, _fp3, _d, _vp, _vp, _i, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "coma_smplx_workspace_bytes": (C.c_size_t, [_i, _i]),

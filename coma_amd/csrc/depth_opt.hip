@@ -13,6 +13,7 @@
 //   64 neighbouring columns, whose lists are adjacent in memory; wave reduction, one integer atomic per wave and non-zero sum.
 // coma_depth_optimize_f64: init (traj[0] = d0, Adam state, Ltraj = 0) -> per epoch: profile (K = 1, d read from traj) -> step (one
 //   workgroup: multiview loss and gradient, collision ratio and slope from Ltraj, Adam, traj[e + 1]).
+#include "coap_internal.h"
 #include "columns_common.h"
 #include "coma_device.h"
 
@@ -210,19 +211,12 @@ __global__ __launch_bounds__(256) void depth_init_kernel(const char* __restrict_
   }
 }
 
-// One workgroup.  Thread t adds up the views t, t + 256, ... in ascending order, each view its joints in ascending order; the
-// tree follows.  joints = J0 + d f; per view q = joints (R C) - t (R C), xy = q / scale max(res) + res / 2 (view_record layout).
-__global__ __launch_bounds__(256) void depth_step_kernel(const char* __restrict__ ws, const double* __restrict__ views,
-                                                         const double* __restrict__ joints0, double f0, double f1, double f2,
-                                                         const int* __restrict__ cand_view, int n_views, const double* __restrict__ cand_xy,
-                                                         int N, int J, double lr, double w_multiview, double w_collision, int e, double* __restrict__ traj,
-                                                         const long long* __restrict__ Ltraj, double* __restrict__ losses,
-                                                         double* __restrict__ state) {
-  __shared__ double lds[256];
-  const long long stopped = ((const long long*)state)[kStStatus];
-  __syncthreads();   // every thread has read the word before any thread may set it below: the branch is uniform
-  if (stopped) return;
-  const double d = traj[e];
+// The multiview term of one epoch, by one workgroup: thread t adds up the views t, t + 256, ... in ascending order, each view its
+// joints in ascending order; the tree follows.  joints = J0 + d f; per view q = joints (R C) - t (R C), xy = q / scale max(res) +
+// res / 2 (view_record layout).  Every thread returns the mean loss and its derivative.
+__device__ __forceinline__ void multiview_term(const double* __restrict__ views, const double* __restrict__ joints0, double f0, double f1, double f2,
+                                               const int* __restrict__ cand_view, int n_views, const double* __restrict__ cand_xy, int N, int J, int e,
+                                               double d, double* __restrict__ state, double* lds, double* loss_out, double* grad_out) {
   const double ox = d * f0, oy = d * f1, oz = d * f2;
   double loss = 0.0, grad = 0.0;
   for (int n = threadIdx.x; n < N; n += 256) {
@@ -252,8 +246,36 @@ __global__ __launch_bounds__(256) void depth_step_kernel(const char* __restrict_
   }
   loss = block_sum<256>(loss, lds);
   grad = block_sum<256>(grad, lds);
-  if (threadIdx.x != 0) return;
   if (N > 0) loss = loss / (double)N, grad = grad / (double)N;
+  *loss_out = loss, *grad_out = grad;
+}
+
+// Adam on the one parameter (thread 0): g = the objective's derivative at traj[e]; writes traj[e + 1] and the state block
+__device__ __forceinline__ void adam_step(double g, double d, double lr, int e, double* __restrict__ traj, double* __restrict__ state) {
+  const double b1 = 0.9, b2 = 0.999;
+  const double m = b1 * state[kStM] + (1.0 - b1) * g;
+  const double v = b2 * state[kStV] + (1.0 - b2) * g * g;
+  const double p1 = state[kStP1] * b1, p2 = state[kStP2] * b2;
+  const double next = d - (lr / (1.0 - p1)) * m / (sqrt(v) / sqrt(1.0 - p2) + 1e-8);
+  state[kStM] = m, state[kStV] = v, state[kStP1] = p1, state[kStP2] = p2;
+  traj[e + 1] = next;
+  if (!__builtin_isfinite(next) && !((long long*)state)[kStStatus]) ((long long*)state)[kStStatus] = 1, ((long long*)state)[kStEpoch] = e + 1;
+}
+
+__global__ __launch_bounds__(256) void depth_step_kernel(const char* __restrict__ ws, const double* __restrict__ views,
+                                                         const double* __restrict__ joints0, double f0, double f1, double f2,
+                                                         const int* __restrict__ cand_view, int n_views, const double* __restrict__ cand_xy,
+                                                         int N, int J, double lr, double w_multiview, double w_collision, int e, double* __restrict__ traj,
+                                                         const long long* __restrict__ Ltraj, double* __restrict__ losses,
+                                                         double* __restrict__ state) {
+  __shared__ double lds[256];
+  const long long stopped = ((const long long*)state)[kStStatus];
+  __syncthreads();   // every thread has read the word before any thread may set it below: the branch is uniform
+  if (stopped) return;
+  const double d = traj[e];
+  double loss, grad;
+  multiview_term(views, joints0, f0, f1, f2, cand_view, n_views, cand_xy, N, J, e, d, state, lds, &loss, &grad);
+  if (threadIdx.x != 0) return;
   double ratio = 0.0, slope = 0.0;
   if (ws && w_collision != 0.0) {
     const long long la = ((const long long*)(ws + kParamBytes))[kHdrSums + 1];
@@ -264,15 +286,26 @@ __global__ __launch_bounds__(256) void depth_step_kernel(const char* __restrict_
     }
   }
   losses[2 * e] = loss, losses[2 * e + 1] = ratio;
-  const double b1 = 0.9, b2 = 0.999;
-  const double g = w_multiview * grad + w_collision * slope;
-  const double m = b1 * state[kStM] + (1.0 - b1) * g;
-  const double v = b2 * state[kStV] + (1.0 - b2) * g * g;
-  const double p1 = state[kStP1] * b1, p2 = state[kStP2] * b2;
-  const double next = d - (lr / (1.0 - p1)) * m / (sqrt(v) / sqrt(1.0 - p2) + 1e-8);
-  state[kStM] = m, state[kStV] = v, state[kStP1] = p1, state[kStP2] = p2;
-  traj[e + 1] = next;
-  if (!__builtin_isfinite(next) && !((long long*)state)[kStStatus]) ((long long*)state)[kStStatus] = 1, ((long long*)state)[kStEpoch] = e + 1;
+  adam_step(w_multiview * grad + w_collision * slope, d, lr, e, traj, state);
+}
+
+// The same step with COAP's collision term: Ctraj[e] = {loss, d loss / d d} of this epoch, written by the collision launches
+__global__ __launch_bounds__(256) void depth_step_coap_kernel(const double* __restrict__ views, const double* __restrict__ joints0, double f0, double f1,
+                                                              double f2, const int* __restrict__ cand_view, int n_views,
+                                                              const double* __restrict__ cand_xy, int N, int J, double lr, double w_multiview,
+                                                              double w_collision, int e, double* __restrict__ traj, const double* __restrict__ Ctraj,
+                                                              double* __restrict__ losses, double* __restrict__ state) {
+  __shared__ double lds[256];
+  const long long stopped = ((const long long*)state)[kStStatus];
+  __syncthreads();
+  if (stopped) return;
+  const double d = traj[e];
+  double loss, grad;
+  multiview_term(views, joints0, f0, f1, f2, cand_view, n_views, cand_xy, N, J, e, d, state, lds, &loss, &grad);
+  if (threadIdx.x != 0) return;
+  const double term = w_collision != 0.0 ? Ctraj[2 * e] : 0.0, slope = w_collision != 0.0 ? Ctraj[2 * e + 1] : 0.0;
+  losses[2 * e] = loss, losses[2 * e + 1] = term;
+  adam_step(w_multiview * grad + w_collision * slope, d, lr, e, traj, state);
 }
 
 static int read_status(const void* hdr, void* stream, int64_t* needed, const char* who) {
@@ -381,6 +414,44 @@ extern "C" int coma_depth_optimize_f64(const void* workspace, const double* view
     hipLaunchKernelGGL(depth_step_kernel, dim3(1), dim3(256), 0, st, ws, views, joints0, front[0], front[1], front[2], cand_view, n_views, cand_xy, N, J, lr,
                        w_multiview, w_collision, e, traj, (const long long*)Ltraj, losses, (double*)state);
     if (int rc = check_launch("depth_step_kernel")) return rc;
+  }
+  return COMA_OK;
+}
+
+extern "C" int coma_depth_optimize_coap_f64(const float* weights, size_t weights_floats, const void* code, int K, const float* points, int T,
+                                            double filter_threshold, void* coap_workspace, size_t coap_workspace_bytes, const double* views, int n_views,
+                                            const double* joints0, const double* front, const int32_t* cand_view, const double* cand_xy, int N, int J,
+                                            double d0, double lr, double w_multiview, double w_collision, int E, double* traj, double* Ctraj,
+                                            double* losses, void* state, void* stream) {
+  const char* who = "coma_depth_optimize_coap_f64";
+  if (!front || !traj || !losses || !state) return fail(COMA_E_INVALID, "%s: null pointer", who);
+  if (E < 1 || E > kMaxEpochs) return fail(COMA_E_INVALID, "%s: E=%d outside [1, %d]", who, E, kMaxEpochs);
+  if (N < 0 || N > kMaxInliers || J < 1 || J > kMaxJoints || n_views < 0)
+    return fail(COMA_E_INVALID, "%s: N=%d outside [0, %d], J=%d outside [1, %d] or n_views=%d < 0", who, N, kMaxInliers, J, kMaxJoints, n_views);
+  if (N > 0 && (!views || !joints0 || !cand_view || !cand_xy || n_views < 1))
+    return fail(COMA_E_INVALID, "%s: null pointer (views, joints0, cand_view, cand_xy are read when N > 0)", who);
+  if (!__builtin_isfinite(d0) || !__builtin_isfinite(lr) || !__builtin_isfinite(w_multiview) || !__builtin_isfinite(w_collision) ||
+      !__builtin_isfinite(front[0]) || !__builtin_isfinite(front[1]) || !__builtin_isfinite(front[2]))
+    return fail(COMA_E_INVALID, "%s: d0, lr, the weights and front must be finite", who);
+  const bool collide = w_collision != 0.0;
+  if (collide) {
+    if (!Ctraj) return fail(COMA_E_INVALID, "%s: Ctraj is written when the collision term is on", who);
+    if (int rc = coap_collision_check(who, weights, code, K, points, T, front, filter_threshold, coap_workspace, coap_workspace_bytes)) return rc;
+    if (weights_floats < coap_weights_floats(K)) return fail(COMA_E_INVALID, "%s: weights of %zu floats, %zu needed", who, weights_floats, coap_weights_floats(K));
+    if (((uintptr_t)weights & 15) || ((uintptr_t)Ctraj & 7)) return fail(COMA_E_INVALID, "%s: Ctraj 8-byte, the weights 16-byte aligned", who);
+  }
+  if ((uintptr_t)state % 8) return fail(COMA_E_INVALID, "%s: state must be 8-byte aligned", who);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(depth_init_kernel, dim3(1), dim3(256), 0, st, (const char*)nullptr, d0, traj, (long long*)nullptr, E, (double*)state);
+  if (int rc = check_launch("depth_init_kernel")) return rc;
+  for (int e = 0; e < E; ++e) {
+    if (collide)
+      if (int rc = coap_collision_launch(weights, code, K, points, T, traj + e, front, filter_threshold, Ctraj + 2 * (int64_t)e, nullptr, coap_workspace,
+                                         (const long long*)state, st))
+        return rc;
+    hipLaunchKernelGGL(depth_step_coap_kernel, dim3(1), dim3(256), 0, st, views, joints0, front[0], front[1], front[2], cand_view, n_views, cand_xy, N, J, lr,
+                       w_multiview, w_collision, e, traj, (const double*)Ctraj, losses, (double*)state);
+    if (int rc = check_launch("depth_step_coap_kernel")) return rc;
   }
   return COMA_OK;
 }

@@ -1,16 +1,18 @@
 """Depth optimisation on MI355X: the stage of the reference's src/generation/optimize_depth.py between the depth initialisation and
-the sample metrics, without COAP and without a body model in the loop.
+the sample metrics, without a body model in the loop; COAP's collision loss is opt-in (optimize_displacement_coap).
 
 The reference's optimiser holds one parameter, the displacement d along the camera's front vector f (optimize_depth.py:690-695): the
 pose, shape and orientation residuals it creates never reach the optimiser, so the SMPL-X forward gives the same vertices V0 and
 joints J0 in every epoch and the human of epoch t is V0 + d f, J0 + d f.  Its loss is w_multiview * multiview_joint_loss +
 w_collision * collision (:757).
 
-COAP's collision loss is UNPINNED and NOT reproduced (a learned occupancy network whose checkpoint is downloaded).  The collision
-term here is geometric: with both meshes rotated into the camera-aligned frame (front vector = +z) the human's column crossings only
-shift by a constant, so the intersection length L_AB is an exact integer, piecewise-linear function of the shift, and the term is the
-intersection ratio L_AB / L_A in [0, 1] -- the quantity compute_metrics.py reports and filter.py thresholds.  `w_collision`
-therefore weights a ratio, not COAP's loss.  Rule set: include/coma_hip.h; restated in tests/shift_ref.py.
+COAP's collision loss (a learned occupancy network) runs through coma_amd.coap and optimize_displacement_coap; its architecture is
+pinned against the code the reference vendors with seeded weights, its downloaded checkpoint has never been executed here.  The
+default collision term (optimize_displacement) is geometric: with both meshes rotated into the camera-aligned frame (front vector =
++z) the human's column crossings only shift by a constant, so the intersection length L_AB is an exact integer, piecewise-linear
+function of the shift, and the term is the intersection ratio L_AB / L_A in [0, 1] -- the quantity compute_metrics.py reports and
+filter.py thresholds.  `w_collision` there weights a ratio, not COAP's loss.  Rule set: include/coma_hip.h; restated in
+tests/shift_ref.py.
 
 Everything per epoch runs on the device (coma_amd/csrc/depth_opt.hip); no CPU fallback.
 """
@@ -160,6 +162,49 @@ def optimize_displacement(columns, views, joints0, front, cand_view, cand_xy, d0
     _lib.check(rc, "coma_depth_optimize_f64")
     traj_h = traj.cpu().numpy()
     return dict(d=float(traj_h[-1]), traj=traj_h, Ltraj=Ltraj.cpu().numpy(), losses=losses.cpu().numpy())
+
+
+def optimize_displacement_coap(coap, points, views, joints0, front, cand_view, cand_xy, d0=0.0, lr=0.01, w_multiview=1e-3, w_collision=0.4,
+                               num_epoch=200, filter_threshold=0.01):
+    """coma_depth_optimize_coap_f64: optimize_displacement with COAP's collision term (coma_amd.coap.DeviceCOAP, a body already
+    encoded at d = 0) over the scene points [T,3] in place of the column profile -> dict(d, traj f64 [E+1], Ctraj f64 [E,2] = {COAP
+    loss, d loss / d d} at traj[e], losses f64 [E,2] = {multiview loss, COAP loss}) as NumPy.  points None or empty: no collision
+    term.  Every epoch filters the points as the reference's sample_scene_points does (the posed vertices' box, occupancy above
+    filter_threshold); where it keeps a random 10 000 of more survivors, here all count."""
+    L = _lib.lib()
+    f64 = torch.float64
+    if coap is not None and coap.code is None:
+        raise _lib.ComaHipError("optimize_displacement_coap: the DeviceCOAP holds no encoded body")
+    dev = coap.code.device if coap is not None else torch.device("cuda", torch.cuda.current_device())
+
+    def dev_f64(x):
+        return torch.as_tensor(np.ascontiguousarray(np.asarray(x, dtype=np.float64)), device=dev)
+    v, j0, cxy = dev_f64(views).reshape(-1, 28), dev_f64(joints0).reshape(-1, 3), dev_f64(cand_xy)
+    cv = torch.as_tensor(np.ascontiguousarray(np.asarray(cand_view, dtype=np.int32)), device=dev)
+    N, J, E = int(cv.numel()), int(j0.shape[0]), int(num_epoch)
+    assert cxy.numel() == N * J * 2 and (N == 0 or (int(cv.min()) >= 0 and int(cv.max()) < v.shape[0]))
+    p = None if points is None or coap is None else coap._f32(points, [-1, 3])
+    T = 0 if p is None else int(p.shape[0])
+    w_collision = float(w_collision) if T else 0.0
+    traj = torch.full([max(E, 0) + 1], float("nan"), dtype=f64, device=dev)
+    Ctraj = torch.zeros([max(E, 1), 2], dtype=f64, device=dev)
+    losses = torch.zeros([max(E, 1), 2], dtype=f64, device=dev)
+    state = torch.zeros([max(1, int(L.coma_depth_optimize_state_bytes()) // 8)], dtype=torch.int64, device=dev)
+    fr = (C.c_double * 3)(*(float(x) for x in np.asarray(front, dtype=np.float64).reshape(3)))
+    ws = coap._scratch("query", L.coma_coap_query_workspace_bytes(coap.K, T)) if T else None
+    epoch = C.c_int(0)
+    with _lib.on_device(dev) as stream:
+        rc = L.coma_depth_optimize_coap_f64(_lib.ptr(coap.weights) if T else None, coap.weights.numel() if T else 0, _lib.ptr(coap.code) if T else None,
+                                            coap.K if T else 0, _lib.ptr(p) if T else None, T, float(filter_threshold), _lib.ptr(ws) if T else None,
+                                            ws.numel() if T else 0, _lib.ptr(v, f64, "views") if N else None, int(v.shape[0]),
+                                            _lib.ptr(j0, f64, "joints0") if N else None, fr, _lib.ptr(cv, torch.int32) if N else None,
+                                            _lib.ptr(cxy, f64, "cand_xy") if N else None, N, J, float(d0), float(lr), float(w_multiview), w_collision, E,
+                                            _lib.ptr(traj), _lib.ptr(Ctraj), _lib.ptr(losses), _lib.ptr(state), stream)
+        if rc == 0:
+            rc = L.coma_depth_optimize_status(_lib.ptr(state), stream, C.byref(epoch))
+    _lib.check(rc, "coma_depth_optimize_coap_f64")
+    traj_h = traj.cpu().numpy()
+    return dict(d=float(traj_h[-1]), traj=traj_h, Ctraj=Ctraj.cpu().numpy(), losses=losses.cpu().numpy())
 
 
 def collision_columns(human_verts, human_faces, asset_verts, asset_faces, R, resolution=512, device="cuda"):

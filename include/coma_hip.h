@@ -285,10 +285,11 @@ int coma_intersection_status(const void* workspace, void* stream, int64_t* neede
  * joint term and a collision term.
  * replaces: the optimisation loop of src/generation/optimize_depth.py:689-780.  Its optimiser holds the displacement alone (:695), so
  *           the body model's output is the same in every epoch: vertices V0 + d f, joints J0 + d f.
- * COAP's collision loss (a learned occupancy network, :752-753) is UNPINNED and NOT reproduced (its checkpoint is not available to
- * this project).  The collision term here is geometric: the intersection ratio L_AB / L_A of the column rule set above, in [0, 1],
- * as a function of d; that is what --w_collision weights.  What is pinned, bit for bit against the NumPy restatement
- * tests/shift_ref.py, is this rule set:
+ * COAP's collision loss (a learned occupancy network, :752-753) is available through coma_depth_optimize_coap_f64 (the section
+ * "COAP" below): its ARCHITECTURE is pinned against the code the reference vendors with seeded weights; its checkpoint is a download
+ * that is not available to this project and has never been executed here.  The default collision term is geometric: the intersection
+ * ratio L_AB / L_A of the column rule set above, in [0, 1], as a function of d; that is what --w_collision weights with
+ * --collision columns.  What is pinned, bit for bit against the NumPy restatement tests/shift_ref.py, is this rule set:
  *   frame          the host rotates both meshes into the camera-aligned frame p' = p R (f64; R the camera's rotation, so the front
  *                  vector R[:, 2] becomes +z) and lays the grid over the xy overlap of the two bounding boxes; the z extent does not
  *                  enter, because the human slides along it and its footprint never changes.
@@ -336,6 +337,90 @@ int coma_depth_optimize_f64(const void* workspace, const double* views, int n_vi
                             const int32_t* cand_view, const double* cand_xy, int N, int J, double d0, double lr, double w_multiview,
                             double w_collision, int E, double* traj, int64_t* Ltraj, double* losses, void* state, void* stream);
 int coma_depth_optimize_status(const void* state, void* stream, int* epoch);
+
+/* COAP: the learned occupancy body model behind the reference's collision loss -- encode a posed body once, query points against it.
+ * replaces: imports/coap/coap.py (Partitioner :162-594 on the host, COAPBodyModel.encode_body / query / collision_loss :639-742) and
+ *           imports/coap/modules.py (ResnetPointnet, ImplicitNet) as src/generation/optimize_depth.py:104-132, 671, 752-753 uses them.
+ * PINNED against the reference's own COAPBodyModel executed on the CPU in f64 with a SEEDED state dict on a seeded SMPL-X-layout model
+ * (tests/golden/coap_golden.npz), through the f64 restatement tests/coap_ref.py.  Only the architecture is pinned: the trained
+ * checkpoint is a download and has never been executed here.  Rule set:
+ *   partition      on the host (coma_amd/coap.py partition): a vertex's part is the arg-max of its skinning weights after the merges of
+ *                  MERGE_BODY_PARTS, a face's the most frequent of its three vertices; K parts, joint_mapper picks their joints.
+ *   transforms     R_k: the Rodrigues chain over the first mK joints (angle = |r + 1e-8|, axis r / angle), origin j_k: the posed joint.
+ *                  Local coordinates are R_k^T (p - j_k), the analytic inverse of the rigid transform, in f64 on the f32 data (the
+ *                  reference inverts the 4 x 4 numerically; its R is orthogonal to about 1e-8, far below the f32 bound).
+ *   boxes          min and max of the part's own vertices (tight_vert_selector) in its frame; centre = (min + max) / 2, size =
+ *                  |max - min| 1.125; inside: |q - centre| < size / 2 in every coordinate, strictly.
+ *   samples        an INPUT: per part n_samples entries (the first n_samples / 2 on the tight faces, the rest on the extended ones)
+ *                  of three vertex ids and three barycentric weights; the point is v0 + b1 (v1 - v0) + b2 (v2 - v0) -- the first
+ *                  weight is implied, so that the weights sum to one exactly and the samples move rigidly with the body.  pytorch3d's
+ *                  own sampler (which the reference calls every epoch) is not reproduced: its point set is unpinned.
+ *   encoder        ResnetPointnet(out 128, hidden 128) without block_2 on the local samples: fc_pos 3 -> 256; four ResnetBlockFC
+ *                  (256 -> 128, fc_1(relu(fc_0(relu(x)))) plus a bias-free shortcut), after each of the first three the output beside
+ *                  its maximum over the part's samples; max-pool, relu, fc_c.  The pooled half of a block's input is constant per part
+ *                  and enters as a per-part bias.
+ *   query          input [q (3), inside (1), one-hot (K), latent (128)]; query_encoder = ImplicitNet(d_in 132 + K, 256 x 3, out 128,
+ *                  skip_in [2]): lin1 has 124 - K outputs and lin2 reads cat(x, input) / sqrt 2; decoder = ImplicitNet(d_in 131 =
+ *                  [q, z], 256 x 6, out 1, skip_in [3]); Softplus(beta 100, threshold 20); occ_k = sigmoid(-x) inside; occ = max over
+ *                  the parts.  Pairs (part, point) outside the part's box contribute exactly zero and are not evaluated; for the
+ *                  others inside = 1, so the one-hot, inside and latent inputs of lin0 and lin2 are per-part biases.
+ *   shift          with d (a device scalar) and front f the body is taken as moved by d f: the query is x - d f, everything else is
+ *                  unchanged (R_k^T (p - j_k) does not see a translation of the whole body).
+ *   derivative     d occ / d d = the tangent pass of the winning part along -R_k^T f: y' = W x' at every layer, y' softplus'(y) at
+ *                  every activation, -s (1 - s) x' at the sigmoid; 0 where no part holds the point.  Ties between parts of equal occ
+ *                  go to the larger bit pattern of the derivative (the reference: to the first part).
+ *   collision      a point counts if it lies in the closed box of the posed vertices (moved by d f) and occ > filter_threshold
+ *                  (optimize_depth.py:104-120); loss = sum relu(occ - 0.5), d loss / d d = sum [occ > 0.5] d occ / d d, in f64: 256
+ *                  points per partial in point order, the tree of block_sum; then partial t, t + 256, ... and the tree again.
+ *                  DEVIATION: where more than 10 000 points survive the reference keeps a random 10 000 (:129-130); here all count.
+ * Arithmetic: transforms, boxes, sample points and local coordinates in f64 on the f32 data; the networks in f32 on
+ * v_mfma_f32_32x32x2_f32, every sum in a fixed k order; maxima by integer-keyed atomics; no floating-point atomics: two calls give
+ * identical bits.
+ * weights: coma_coap_weights_floats(K) floats (device, 16-byte aligned), packed by coma_amd/coap.py pack_weights, in this order (a
+ *   "fragment" matrix [in, out] is stored [out / 32][in / 8][64 lanes][4]: lane l of step g holds W[k = 8 g + 4 (l / 32) + e][n = 32 nb
+ *   + l % 32], zero beyond the matrix; a "plain" one row-major [in][out]): encoder fc_pos (fragment 8 x 256, bias); per block: fc_0,
+ *   shortcut, fc_1 (fragments; of fc_0 and shortcut only the first 128 inputs in blocks 1 - 3), their two biases, and in blocks 1 - 3
+ *   the pooled halves of fc_0 and shortcut (plain); fc_c (plain, bias); for lin0 and lin2 of the query encoder: the inside column, the
+ *   one-hot columns [K][256], the latent columns (plain), the bias (lin2's columns divided by sqrt 2); then the ten layers as
+ *   fragments, each followed by its bias padded to whole column blocks: lin0 (q only), lin1, lin2 (rows [x, q] / sqrt 2), lin3,
+ *   decoder lin0 (rows [q, z]), lin1, lin2, lin3 (rows [x, q, z] / sqrt 2), lin4, lin5; decoder lin6 [256] and its bias.
+ * coma_coap_encode_f32: full_pose f32 [>= 3 mK], joints f32 [>= mK,3], vertices f32 [V,3] (device); parents i32 [mK], joint_mapper
+ *   u8 [mK] (HOST, read during the call; parents[i] in [0, i), joint_mapper selects K joints); selector i32 [K,S]; sample_ids i32
+ *   [K,n_samples,3], sample_bary f32 [K,n_samples,3] (device).  K in [1, 32], mK in [K, 64], n_samples in [2, 4096] (no multiple of
+ *   anything), S in [1, V].  code: coma_coap_code_bytes(K) bytes, 16-byte aligned: a 16-byte header {magic, K, status, 0}, then per
+ *   part 24 doubles {R row-major (9), origin (3), centre (3), size / 2 (3), min (3), max (3)}, the posed vertices' box {min, max}
+ *   (6 doubles), then f32: latent [K,128], the per-part biases of lin0 and lin2 [K,256] each (every field at a multiple of 16 bytes).
+ *   workspace: coma_coap_encode_workspace_bytes(K, n_samples).  An id outside [0, V) or a non-finite input is recorded in the header
+ *   (the id reads vertex 0); coma_coap_status(code, stream) -- which waits -- then returns COMA_E_INVALID, and queries against such
+ *   a code block return zeros.
+ * coma_coap_query_f32: points f32 [T,3], T in [1, 2^22]; d f64 (device, may be NULL: 0); front f32 [3] (HOST; read with d or the
+ *   derivative); occ f32 [T]; docc f32 [T] (written with derivative != 0).  workspace: coma_coap_query_workspace_bytes(K, T); its first
+ *   i32 is the length of the (part, point) list of the last call.  One fused launch runs all layers over the list.
+ * coma_coap_collision_f32: the epoch's term; result f64 [2] = {loss, d loss / d d}, kept i64 (may be NULL) the number of points past
+ *   the filter (device); filter_threshold in [0, 1).
+ * coma_depth_optimize_coap_f64: coma_depth_optimize_f64 with the term above in place of the column profile: per epoch the collision
+ *   launches (d read from traj) and one step kernel; multiview term, Adam, state block, stop rule and coma_depth_optimize_status are
+ *   the same.  Ctraj f64 [E,2] = {loss, d loss / d d} at traj[e] (written when w_collision != 0); losses f64 [E,2] = {multiview loss,
+ *   COAP loss}, unweighted.  With w_collision == 0 nothing of COAP is read. */
+size_t coma_coap_weights_floats(int K);
+size_t coma_coap_code_bytes(int K);
+size_t coma_coap_encode_workspace_bytes(int K, int n_samples);
+size_t coma_coap_query_workspace_bytes(int K, int T);
+int coma_coap_encode_f32(const float* weights, size_t weights_floats, const float* full_pose, const float* joints, const float* vertices, int V,
+                         const int32_t* parents, const uint8_t* joint_mapper, int mK, int K, const int32_t* selector, int S,
+                         const int32_t* sample_ids, const float* sample_bary, int n_samples, void* code, void* workspace,
+                         size_t workspace_bytes, void* stream);
+int coma_coap_status(const void* code, void* stream);
+int coma_coap_query_f32(const float* weights, size_t weights_floats, const void* code, int K, const float* points, int T, const double* d,
+                        const float* front, int derivative, float* occ, float* docc, void* workspace, size_t workspace_bytes, void* stream);
+int coma_coap_collision_f32(const float* weights, size_t weights_floats, const void* code, int K, const float* points, int T, const double* d,
+                            const float* front, double filter_threshold, double* result, int64_t* kept, void* workspace,
+                            size_t workspace_bytes, void* stream);
+int coma_depth_optimize_coap_f64(const float* weights, size_t weights_floats, const void* code, int K, const float* points, int T,
+                                 double filter_threshold, void* coap_workspace, size_t coap_workspace_bytes, const double* views, int n_views,
+                                 const double* joints0, const double* front, const int32_t* cand_view, const double* cand_xy, int N, int J,
+                                 double d0, double lr, double w_multiview, double w_collision, int E, double* traj, double* Ctraj,
+                                 double* losses, void* state, void* stream);
 
 /* The optimisation app's ComA objective: the orientation term and the contact term of one posed mesh, unweighted, and their
  * gradients with respect to the vertices, in one pass (the app never needs a loss without its gradient).

@@ -1,6 +1,6 @@
 """Depth optimisation: slide the depth-initialised human along the viewing axis until its joints agree with the
 other views' predictions and it stops intersecting the asset -- the stage between src/generation/initialize_depth.py and
-src/generation/compute_metrics.py -- with the whole Adam loop on the device (coma_amd.depth_opt) and WITHOUT COAP.
+src/generation/compute_metrics.py -- with the whole Adam loop on the device (coma_amd.depth_opt); COAP's collision loss is opt-in.
 
 CLI surface, work list, slice rule, string sentinels and output pickle of the reference's ``src/generation/optimize_depth.py``:
   * inputs  {inpaint_dir}/{SC}/{C}/{asset}/{view}/{mask}/{prompt}/{id}.png of registered assets, {human_initial_dir}/.../{id:06}.pickle
@@ -15,8 +15,15 @@ CLI surface, work list, slice rule, string sentinels and output pickle of the re
 The optimiser holds the displacement alone (:695), so the body model runs ONCE: `body_model(smplx_data, smplx_path)` gives the
 vertices and the 137 joints in the pose estimator's camera space, and everything after that is this project's.  The default hook
 imports `smplx` when it is first called.
-The collision term is NOT COAP's (unpinned, a downloaded checkpoint): --w_collision weights the intersection ratio in [0, 1] of
-include/coma_hip.h's column rule set (see coma_amd/depth_opt.py).  --w_refview is accepted and, as in the reference (:757), not part
+The collision term is chosen by --collision.  `columns` (the default): --w_collision weights the intersection ratio in [0, 1] of
+include/coma_hip.h's column rule set (see coma_amd/depth_opt.py), not COAP's loss.  `coap`: --w_collision weights COAP's sum of
+relu(occupancy - 0.5) over the asset's vertices, as in the reference (:752-753), through coma_amd.coap.DeviceCOAP with the checkpoint
+--coap_ckpt FILE (a {"state_dict": ...} file in the reference's key layout; a missing file is an error).  COAP's ARCHITECTURE is
+pinned against the code the reference vendors with seeded weights; the real checkpoint is a download that has never been executed
+here.  Deviations with `coap`: the body is encoded ONCE per item from --coap_samples surface samples drawn with pytorch3d's method
+from the seed --coap_seed (the reference re-draws them with pytorch3d every epoch), and where more than 10 000 asset vertices survive
+the epoch's filter all of them count (the reference keeps a random 10 000).  The body model hook is then called with full_pose=True
+and returns (verts, joints, full_pose [165]).  --w_refview is accepted and, as in the reference (:757), not part
 of the loss.  --asset_seg_dir is accepted and unused, as in the reference.
 Three flags are added: --asset_obj_root (as in initialize_depth.py; OBJ assets only), --volume_resolution (cells along the longer
 side of the collision grid) and --perturb_view_num (the reference restricts the inlier search to the reference view's group of
@@ -46,8 +53,9 @@ NOT_ALLOWED, TOO_FEW = "NOT ALLOWED VIEWPOINT PROMPTS", "TOO LITTLE INLIERS"
 DEFAULT_INITIAL_DIR, DEFAULT_SAVE_DIR = "results/generation/human_before_opt", "results/generation/human_after_opt"
 
 
-def default_body_model(smplx_data, smplx_path):
-    """(verts [V,3], joints [137,3]) of the SMPL-X model for one prediction, before its translation (optimize_depth.py:670-684)."""
+def default_body_model(smplx_data, smplx_path, full_pose=False):
+    """(verts [V,3], joints [137,3]) of the SMPL-X model for one prediction, before its translation (optimize_depth.py:670-684); with
+    full_pose also the 165 axis-angle entries COAP reads."""
     try:
         import smplx
     except ImportError as exc:
@@ -57,6 +65,8 @@ def default_body_model(smplx_data, smplx_path):
     params = {k: torch.as_tensor(np.asarray(v)).float() for k, v in smplx_data.items() if k != "transl"}
     with torch.no_grad():
         out = human(**params, return_verts=True, return_full_pose=True)
+    if full_pose:
+        return out.vertices[0].cpu().numpy(), out.joints[0].cpu().numpy(), out.full_pose[0].cpu().numpy()
     return out.vertices[0].cpu().numpy(), out.joints[0].cpu().numpy()
 
 
@@ -76,7 +86,7 @@ def load_vertex_ids(pth):
     return ids
 
 
-def device_body_model(smplx_data, smplx_path, device="cuda", extra_joint_vertex_ids=None):
+def device_body_model(smplx_data, smplx_path, device="cuda", extra_joint_vertex_ids=None, full_pose=False):
     """default_body_model's contract through coma_amd.body_model.DeviceSMPLX (--body_model device): no third-party package.  Refused
     when the vertex picks among the joints cannot be had: the stage would read face landmarks in their place."""
     import torch
@@ -91,7 +101,38 @@ def device_body_model(smplx_data, smplx_path, device="cuda", extra_joint_vertex_
     params = {k: torch.as_tensor(np.asarray(v)).float().to(device) for k, v in smplx_data.items() if k != "transl"}
     with torch.no_grad():
         out = human(**params, return_verts=True, return_full_pose=True)
+    if full_pose:
+        return out.vertices[0].cpu().numpy(), out.joints[0].cpu().numpy(), out.full_pose[0].cpu().numpy()
     return out.vertices[0].cpu().numpy(), out.joints[0].cpu().numpy()
+
+
+_COAP_MODELS = {}          # (smplx_path, checkpoint, samples, seed, device) -> DeviceCOAP: partition and packing happen once, not per item
+
+
+def coap_model(smplx_path, coap, device="cuda"):
+    """The DeviceCOAP of --collision coap: the partition from the SMPL-X model file at smplx_path (read with NumPy), the weights from
+    coap["ckpt"]."""
+    from coma_amd.body_model import DeviceSMPLX
+    from coma_amd.coap import DeviceCOAP
+    key = (os.path.abspath(smplx_path), os.path.abspath(coap["ckpt"]), coap["samples"], coap["seed"], str(device))
+    if key not in _COAP_MODELS:
+        if not os.path.exists(coap["ckpt"]):
+            raise FileNotFoundError(f"optimize_depth: --coap_ckpt {coap['ckpt']} does not exist (COAP's checkpoint is a download; see the reference's "
+                                    "imports/coap)")
+        body = DeviceSMPLX.from_file(smplx_path, num_pca_comps=45, device=device, extra_joint_vertex_ids=[])
+        _COAP_MODELS[key] = DeviceCOAP(body, coap["ckpt"], n_samples=coap["samples"], seed=coap["seed"], device=device)
+    return _COAP_MODELS[key]
+
+
+def solve_displacement_coap(model, full_pose, human_verts, joints, asset_verts, cam_R, inliers, lr, w_multiview, w_collision, num_epoch):
+    """solve_displacement with COAP's term: the body encoded once at d = 0, the asset's vertices as the scene points."""
+    from coma_amd import depth_opt as D
+    model.detach_cache()
+    model.encode_body(dict(full_pose=full_pose, joints=joints, vertices=human_verts))
+    views, cand_view, cand_xy = D.inlier_views(inliers)
+    joints0 = np.asarray(joints, dtype=np.float64)[D.BODY_INDICES]
+    return D.optimize_displacement_coap(model, asset_verts, views, joints0, np.asarray(cam_R, dtype=np.float64)[:, 2], cand_view, cand_xy, 0.0, lr,
+                                        w_multiview, w_collision, num_epoch)["d"]
 
 
 def _dump(payload, pth):
@@ -161,8 +202,8 @@ def solve_displacement(human_verts, human_faces, asset_verts, asset_faces, cam_R
 
 def optimize_item(item, human_preds_dir, camera_dir, smplx_path, maximum_candidates, ransac_threshold, triangulation_threshold, num_epoch,
                   minimum_inliers, lr, w_collision, w_multiview, enable_aggregate_total_prompts, allowed_viewpoint_prompts,
-                  disable_lowres_switch_for_behave, asset_obj_root, volume_resolution, perturb_view_num, body_model, device):
-    """One work item -> what the reference pickles for it (:598-780)."""
+                  disable_lowres_switch_for_behave, asset_obj_root, volume_resolution, perturb_view_num, body_model, device, coap=None):
+    """One work item -> what the reference pickles for it (:598-780).  coap: None (the column term), or dict(ckpt, samples, seed)."""
     from coma_amd import depth_opt as D
     from coma_amd.downsample import load_obj
     with open(item["human_initial_pth"], "rb") as fh:
@@ -181,7 +222,11 @@ def optimize_item(item, human_preds_dir, camera_dir, smplx_path, maximum_candida
     if len(inliers) < minimum_inliers:
         return TOO_FEW
     smplx_data = preds["smplx_data"]
-    verts_cam, joints_cam = body_model(smplx_data, smplx_path)
+    use_coap = coap is not None and w_collision != 0.0
+    if use_coap:
+        verts_cam, joints_cam, full_pose = body_model(smplx_data, smplx_path, full_pose=True)
+    else:
+        verts_cam, joints_cam = body_model(smplx_data, smplx_path)
     placed = initial.get("displacement")                       # where the depth initialisation put the human (None with --no_initialize)
     placed = np.zeros((1, 3)) if placed is None else np.asarray(placed, dtype=np.float64).reshape((1, 3))
     to_real = [D.convert_cam2real(x, smplx_data["transl"], cam_resolution, camera_data, preds["convert_data"]).astype(np.float64) + placed
@@ -193,8 +238,12 @@ def optimize_item(item, human_preds_dir, camera_dir, smplx_path, maximum_candida
         obj_verts, asset_faces = load_obj(asset_obj_path(asset_obj_root, item["supercategory"], item["category"], item["asset_id"],
                                                          disable_lowres_switch_for_behave))
         asset_verts = asset_world(obj_verts, camera_data, CATEGORY2DATASET_TYPE[(item["supercategory"], item["category"])])
-    d = solve_displacement(human_verts, human_faces, asset_verts, asset_faces, camera_data["R"], joints, inliers, lr, w_multiview, w_collision,
-                           num_epoch, volume_resolution, device)
+    if use_coap:
+        d = solve_displacement_coap(coap_model(smplx_path, coap, device), full_pose, human_verts, joints, asset_verts, camera_data["R"], inliers, lr,
+                                    w_multiview, w_collision, num_epoch)
+    else:
+        d = solve_displacement(human_verts, human_faces, asset_verts, asset_faces, camera_data["R"], joints, inliers, lr, w_multiview, w_collision,
+                               num_epoch, volume_resolution, device)
     front = np.asarray(camera_data["R"], dtype=np.float64)[:, 2].reshape((1, 3))
     return dict(verts=(human_verts + d * front).astype(np.float32), faces=human_faces.astype(np.uint32), num_inliers=len(inliers))
 
@@ -203,7 +252,7 @@ def run_depth_optimization(supercategories, categories, prompts, inpaint_dir, as
                            save_dir, smplx_path, maximum_candidates, ransac_threshold, triangulation_threshold, num_epoch, minimum_inliers, lr,
                            w_collision, w_multiview, w_refview, enable_aggregate_total_prompts, allowed_viewpoint_prompts,
                            disable_lowres_switch_for_behave, skip_done, verbose, parallel_num, parallel_idx, asset_obj_root="data",
-                           volume_resolution=512, perturb_view_num=None, body_model=None, device="cuda"):
+                           volume_resolution=512, perturb_view_num=None, body_model=None, device="cuda", coap=None):
     """This process's share of the work list -> optimised humans; returns the paths written by the loop (sentinels answered while the
     list is built are not among them)."""
     body_model = body_model or default_body_model
@@ -218,7 +267,7 @@ def run_depth_optimization(supercategories, categories, prompts, inpaint_dir, as
         result = optimize_item(item, human_preds_dir, camera_dir, smplx_path, maximum_candidates, ransac_threshold, triangulation_threshold,
                                num_epoch, minimum_inliers, lr, w_collision, w_multiview, enable_aggregate_total_prompts,
                                allowed_viewpoint_prompts, disable_lowres_switch_for_behave, asset_obj_root, volume_resolution, perturb_view_num,
-                               body_model, device)
+                               body_model, device, coap)
         _dump(result, item["save_path"])
         done.append(item["save_path"])
     return done
@@ -242,7 +291,13 @@ def build_parser():
     p.add_argument("--num_epoch", type=int, default=200)
     p.add_argument("--minimum_inliers", type=int, default=1)
     p.add_argument("--lr", type=float, default=0.01)
-    p.add_argument("--w_collision", type=float, default=0.4, help="weight of the intersection ratio in [0, 1] (not COAP's loss)")
+    p.add_argument("--w_collision", type=float, default=0.4,
+                   help="weight of the collision term: the intersection ratio in [0, 1] (--collision columns) or COAP's loss (--collision coap)")
+    p.add_argument("--collision", choices=("columns", "coap"), default="columns",
+                   help="columns: the geometric intersection ratio; coap: COAP's learned occupancy loss, as in the reference (needs --coap_ckpt)")
+    p.add_argument("--coap_ckpt", type=str, default=None, help="with --collision coap: COAP's checkpoint, a {'state_dict': ...} file")
+    p.add_argument("--coap_samples", type=int, default=1000, help="surface samples per body part for COAP's encoder")
+    p.add_argument("--coap_seed", type=int, default=0, help="seed of the surface sample table")
     p.add_argument("--w_multiview", type=float, default=1e-3)
     p.add_argument("--w_refview", type=float, default=0.0)
     p.add_argument("--disable_lowres_switch_for_behave", action="store_true")
@@ -268,7 +323,14 @@ def build_parser():
 def main(args, body_model=None):
     if body_model is None and getattr(args, "body_model", "smplx") == "device":
         ids = load_vertex_ids(args.extra_joint_vertex_ids) if getattr(args, "extra_joint_vertex_ids", None) else None
-        body_model = lambda smplx_data, smplx_path: device_body_model(smplx_data, smplx_path, extra_joint_vertex_ids=ids)
+        body_model = lambda smplx_data, smplx_path, **kw: device_body_model(smplx_data, smplx_path, extra_joint_vertex_ids=ids, **kw)
+    coap = None
+    if getattr(args, "collision", "columns") == "coap" and not args.no_collision and args.w_collision != 0.0:
+        if not getattr(args, "coap_ckpt", None):
+            raise SystemExit("optimize_depth: --collision coap needs --coap_ckpt FILE (COAP's checkpoint is a download that this repository does not hold)")
+        if not os.path.exists(args.coap_ckpt):
+            raise SystemExit(f"optimize_depth: --coap_ckpt {args.coap_ckpt} does not exist")
+        coap = dict(ckpt=args.coap_ckpt, samples=int(getattr(args, "coap_samples", 1000)), seed=int(getattr(args, "coap_seed", 0)))
     for name in ("supercategories", "categories", "prompts", "allowed_viewpoint_prompts"):
         if getattr(args, name) is not None:
             setattr(args, name, [x.lower() for x in getattr(args, name)])
@@ -294,7 +356,7 @@ def main(args, body_model=None):
                                   disable_lowres_switch_for_behave=args.disable_lowres_switch_for_behave, skip_done=args.skip_done,
                                   verbose=args.verbose, parallel_num=args.parallel_num, parallel_idx=args.parallel_idx,
                                   asset_obj_root=args.asset_obj_root, volume_resolution=args.volume_resolution,
-                                  perturb_view_num=args.perturb_view_num, body_model=body_model)
+                                  perturb_view_num=args.perturb_view_num, body_model=body_model, coap=coap)
 
 
 if __name__ == "__main__":
