@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("COMA_HIP_LIB") or os.path.join(_HERE, "libcoma_hip.so")
 # = COMA_ABI_VERSION of include/coma_hip.h.  Bumped only when an EXISTING signature changes: a library that merely lacks an added
 # function is refused by lib() anyway, through the getattr of the missing symbol.
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 _lib = None
 
@@ -147,6 +147,7 @@ SIGNATURES = {
     "sd_mask_adapt_batched": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _d, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     # include/seg_hip.h
     "seg_conv_gemm_f32": (_i, [_vp, _vp]),
+    "seg_conv_gemm_describe": (_i, [_vp, _vp]),
     "seg_resize_normalize_u8": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _f, _f, _f, _vp, _vp, _vp, _vp]),
     "seg_maxpool3x3s2_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "seg_subsample2_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),

@@ -417,79 +417,10 @@ __global__ __launch_bounds__(256) void seg_splitk_reduce_kernel(const GemmArgs a
 }
 
 
-template <int WM, int WN, int TM, int TN, bool UNI>
-static int launch_gemm(GemmArgs& a, hipStream_t st, int force_split, size_t ws_bytes) {
-  constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
-  constexpr size_t lds_ops = (size_t)2 * (BM + BN) * kLd * sizeof(float), lds_epi = (size_t)BM * (BN + 8) * sizeof(float);
-  constexpr size_t lds = lds_ops > lds_epi ? lds_ops : lds_epi;      // the epilogue stages the output tile over the operand stages (128 x 128: 68 KB)
-  static coma::LdsOptIn opt;
-  static coma::LdsOptIn opt_pre;
-  if (lds > 65536) {
-    if (int rc = coma::opt_in_lds(opt, (const void*)conv_gemm_f32_kernel<WM, WN, TM, TN, UNI, false>, lds, "seg_conv_gemm_f32")) return rc;
-    if (int rc = coma::opt_in_lds(opt_pre, (const void*)conv_gemm_f32_kernel<WM, WN, TM, TN, UNI, true>, lds, "seg_conv_gemm_f32")) return rc;
-  }
-  const long long gx = (a.M + BM - 1) / BM;
-  const int gy = (a.N + BN - 1) / BN;
-  if (a.M >= 0x7fffffffLL - BM || gx * gy >= 0x7fffffffLL) return fail(COMA_E_INVALID, "seg_conv_gemm_f32: M=%lld rows / %d column tiles exceed the kernel's 32-bit row arithmetic", a.M, gy);
-  // split-K: only where the tiles leave more than half of the chip idle and every slice keeps >= 4 chunks (128 k values)
-  const int nk = a.Kpad / kBK;
-  const long long tiles = gx * gy;
-  int S = 1;
-  constexpr int slots = 512;
-  if (force_split > 0) S = force_split;
-  else if (force_split == 0 && a.ws && tiles < 2 * slots && nk >= 8) {
-    // per-CU cost model, unit = one K chunk of a workgroup that shares its CU's matrix pipe with another one (~3.5 us on a 128 x 128 tile):
-    // a launch of W = tiles * S workgroups of nk / S chunks (+ 3 for prologue and epilogue) gives every CU n = ceil(W / 256) of them, and from two
-    // workgroups on the pipe is the bottleneck -- the CU needs n x (nk / S + 3) / 2 units however many of them are resident at a time; a CU with
-    // ONE workgroup cannot fill the pipe: 0.6 per chunk.  A split launch also pays the reduce pass: a second launch (~3 us behind the GEMM
-    // inside a graph) that reads S slabs at ~4 TB/s.  Measured against forced factors on the plan's shapes (profiles/r06_notes.md 5):
-    // res5.x.conv2 picks 3 (220 us; 2: 315, 4: 250), the M = 20 000 3 x 3 layers on 128 x 64 tiles pick 2 (230 us; unsplit 244-252), the point
-    // head (392 tiles x 11 chunks) stays unsplit (56 us; split in two 78).  Every slice >= 4 chunks.
-    auto cu_cost = [](double w, double chunks) {
-      const double n = (double)(long long)((w + 255.0) / 256.0);
-      return n * (chunks + 3.0) * (n <= 1.0 ? 0.6 : 0.5);
-    };
-    double best = cu_cost((double)tiles, (double)nk);
-    const double unit_us = 3.5 * ((double)BM * BN / (128.0 * 128.0));
-    const double slab_units = 4.0 * (double)a.M * a.N / 4.0e6 / unit_us;      // one slab read back (the GEMM's slab writes overlap with its own work)
-    for (int c = 2; c <= 16 && nk / c >= 4; ++c) {
-      const double cost = cu_cost((double)tiles * c, (double)nk / c) + 3.0 / unit_us + c * slab_units;
-      if (cost < best * 0.95) { best = cost; S = c; }
-    }
-  }
-  a.ws_ld = gy * BN;
-  const long long slab = gx * BM * (long long)a.ws_ld;
-  if (S > 1 && a.ws) S = (int)std::min<long long>(S, (long long)(ws_bytes / sizeof(float)) / slab);
-  if (S > nk) S = nk;
-  if (S <= 1 || !a.ws) {
-    a.splits = 1; a.nk_per = nk;
-    if (force_split > 1) return fail(COMA_E_INVALID, "seg_conv_gemm_f32: split_k=%d needs a workspace of %lld bytes", force_split, slab * 4 * force_split);
-  } else {
-    a.nk_per = (nk + S - 1) / S;
-    a.splits = (nk + a.nk_per - 1) / a.nk_per;            // every slice non-empty
-  }
-  a.gx = (int)gx; a.gy = gy;
-  // the residual is requested before the epilogue only for K <= 128: from K = 256 on the K loop hides the epilogue of the co-resident
-  // workgroup anyway, and the 254-register kernel is the slower one (res5.x.conv3, K = 512: 124 us without, 146 us with)
-  if (a.res_mode != 0 && a.splits == 1 && nk <= 4)
-    hipLaunchKernelGGL((conv_gemm_f32_kernel<WM, WN, TM, TN, UNI, true>), dim3((unsigned)(gx * gy), 1, 1), dim3(256), lds, st, a);
-  else
-    hipLaunchKernelGGL((conv_gemm_f32_kernel<WM, WN, TM, TN, UNI, false>), dim3((unsigned)(gx * gy), 1, (unsigned)a.splits), dim3(256), lds, st, a);
-  if (int rc = check_launch("seg::conv_gemm_f32_kernel")) return rc;
-  if (a.splits > 1) {
-    const long long n = a.M * ((a.N + 3) / 4);
-    hipLaunchKernelGGL(seg_splitk_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, slab);
-    return check_launch("seg::seg_splitk_reduce_kernel");
-  }
-  return COMA_OK;
-}
-
-}  // namespace seg
-
-extern "C" int seg_conv_gemm_f32(const seg_conv_desc* d, void* stream) {
-  using namespace seg;
+// ---- the choice of a launch: tile, uniform-tap addressing, residual prefetch, split-K.  ONE function for the launcher and for
+// seg_conv_gemm_describe, host code only: nothing is launched and no pointer is dereferenced.
+static int choose_gemm(const seg_conv_desc* d, seg_conv_choice* ch) {
   if (!d) return fail(COMA_E_INVALID, "seg_conv_gemm_f32: null descriptor");
-  if (sd::plan_recording()) return sd::record_seg_conv(d);
   if (!d->x || !d->w || !d->out) return fail(COMA_E_INVALID, "seg_conv_gemm_f32: null pointer");
   if (d->batch <= 0 || d->in_h <= 0 || d->in_w <= 0 || d->out_h <= 0 || d->out_w <= 0 || d->n <= 0)
     return fail(COMA_E_INVALID, "seg_conv_gemm_f32: batch=%d in=%dx%d out=%dx%d n=%d", d->batch, d->in_h, d->in_w, d->out_h, d->out_w, d->n);
@@ -504,22 +435,10 @@ extern "C" int seg_conv_gemm_f32(const seg_conv_desc* d, void* stream) {
   if (d->res_mode == 2 && ((d->out_h | d->out_w) & 1)) return fail(COMA_E_INVALID, "seg_conv_gemm_f32: up-sampled residual needs even out_h, out_w");
   if (d->m_dev && (d->rows_per_item <= 0 || d->unit_rows <= 0))
     return fail(COMA_E_INVALID, "seg_conv_gemm_f32: rows_per_item=%d unit_rows=%d", d->rows_per_item, d->unit_rows);
-  GemmArgs a;
-  a.x = (const float*)d->x; a.w = (const float*)d->w; a.bias = (const float*)d->bias; a.res = (const float*)d->res; a.out = (float*)d->out;
-  a.m_dev = (const int*)d->m_dev;
-  a.B = d->batch; a.H = d->in_h; a.W = d->in_w; a.C = d->c; a.ldx = ldx; a.N = d->n; a.Kpad = d->kpad; a.kh = d->kh; a.kw = d->kw;
-  a.stride = d->stride; a.pad = d->pad; a.OH = d->out_h; a.OW = d->out_w; a.ldr = d->ldr ? d->ldr : d->n; a.res_mode = d->res_mode;
-  a.ldo = d->ldo ? d->ldo : d->n; a.relu = d->relu; a.rows_per_item = d->rows_per_item; a.unit_rows = d->unit_rows;
-  a.M = (long long)d->batch * d->out_h * d->out_w;
-  if (a.ldo < d->n) return fail(COMA_E_INVALID, "seg_conv_gemm_f32: ldo=%d < n=%d", a.ldo, d->n);
+  const int ldo = d->ldo ? d->ldo : d->n;
+  const long long M = (long long)d->batch * d->out_h * d->out_w;
+  if (ldo < d->n) return fail(COMA_E_INVALID, "seg_conv_gemm_f32: ldo=%d < n=%d", ldo, d->n);
   if (d->split_k < -1 || (d->workspace && d->workspace_bytes < 16)) return fail(COMA_E_INVALID, "seg_conv_gemm_f32: split_k=%d workspace_bytes=%zu", d->split_k, d->workspace_bytes);
-  a.ws = (float*)d->workspace; a.splits = 1; a.nk_per = 0; a.ws_ld = 0;
-  static const float* zeros = [] { void* p = nullptr; return hipGetSymbolAddress(&p, HIP_SYMBOL(kZerosDev)) == hipSuccess ? (const float*)p : nullptr; }();
-  if (!zeros) return fail(COMA_E_DEVICE, "seg_conv_gemm_f32: hipGetSymbolAddress(kZerosDev) failed");
-  a.zeros = zeros;
-  const int fs = d->split_k;                     // 0 = by the rule above, -1 = never, S > 1 = exactly S slices (tests)
-  const size_t wb = d->workspace_bytes;
-  hipStream_t st = (hipStream_t)stream;
   // tile: 0 = by width (n <= 32: 128 x 32, n <= 64: 128 x 64, else 128 x 128); 1 / 2 / 3 force 128 x 128 / 128 x 64 / 128 x 32 (tests)
   int tile = d->tile;
   if (tile == 0) {
@@ -530,21 +449,130 @@ extern "C" int seg_conv_gemm_f32(const seg_conv_desc* d, void* stream) {
       // re-reads its A rows from LDS for half the columns) of a 128 x 128 one.  Measured on the plan's shapes (profiles/r06_notes.md 5):
       // res3.x.conv2 241 -> 204 us, res3.x.conv1 116 -> 97, res4.x.conv1 141 -> 111, res5.x.conv3 124 -> 102, res2.x.conv3 201 -> 188,
       // res4.x.conv3 119 -> 109; the long-K large layers (fpn_output2 / 3, rpn_conv, box_fc1) stay on 128 x 128.
-      const long long t1 = ((a.M + 127) / 128) * ((d->n + 127) / 128), t2 = ((a.M + 127) / 128) * ((d->n + 63) / 64);
+      const long long t1 = ((M + 127) / 128) * ((d->n + 127) / 128), t2 = ((M + 127) / 128) * ((d->n + 63) / 64);
       const double nk = d->kpad / 32.0;
       const double r = 0.45 + 0.13 * (nk < 64.0 ? nk / 64.0 : 1.0);      // (three narrow-tile workgroups per CU since the unpadded LDS rows)
       if ((double)((t2 + 255) / 256) * r < 0.95 * (double)((t1 + 255) / 256)) tile = 2;
     }
   }
-  // uniform-tap addressing wherever a 32-wide K chunk lies inside one tap (every layer but the stem, C = 4, and the point head, C = 336)
-  if (d->c % kBK == 0) {
-    if (tile == 1) return launch_gemm<2, 2, 2, 2, true>(a, st, fs, wb);
-    if (tile == 2) return launch_gemm<4, 1, 1, 2, true>(a, st, fs, wb);
-    if (tile == 3) return launch_gemm<4, 1, 1, 1, true>(a, st, fs, wb);
-  } else {
-    if (tile == 1) return launch_gemm<2, 2, 2, 2, false>(a, st, fs, wb);
-    if (tile == 2) return launch_gemm<4, 1, 1, 2, false>(a, st, fs, wb);
-    if (tile == 3) return launch_gemm<4, 1, 1, 1, false>(a, st, fs, wb);
+  if (tile < 1 || tile > 3) return fail(COMA_E_INVALID, "seg_conv_gemm_f32: tile=%d", d->tile);
+  const int BM = 128, BN = tile == 1 ? 128 : (tile == 2 ? 64 : 32);
+  const long long gx = (M + BM - 1) / BM;
+  const int gy = (d->n + BN - 1) / BN;
+  if (M >= 0x7fffffffLL - BM || gx * gy >= 0x7fffffffLL) return fail(COMA_E_INVALID, "seg_conv_gemm_f32: M=%lld rows / %d column tiles exceed the kernel's 32-bit row arithmetic", M, gy);
+  // split-K: only where the tiles leave more than half of the chip idle and every slice keeps >= 4 chunks (128 k values)
+  const int force_split = d->split_k;            // 0 = by the rule below, -1 = never, S > 1 = exactly S slices (tests)
+  const int nk = d->kpad / kBK;
+  const long long tiles = gx * gy;
+  int S = 1;
+  constexpr int slots = 512;
+  if (force_split > 0) S = force_split;
+  else if (force_split == 0 && d->workspace && tiles < 2 * slots && nk >= 8) {
+    // per-CU cost model, unit = one K chunk of a workgroup that shares its CU's matrix pipe with another one (~3.5 us on a 128 x 128 tile):
+    // a launch of W = tiles * S workgroups of nk / S chunks (+ 3 for prologue and epilogue) gives every CU n = ceil(W / 256) of them, and from two
+    // workgroups on the pipe is the bottleneck -- the CU needs n x (nk / S + 3) / 2 units however many of them are resident at a time; a CU with
+    // ONE workgroup cannot fill the pipe: 0.6 per chunk.  A split launch also pays the reduce pass: a second launch (~3 us behind the GEMM
+    // inside a graph) that reads S slabs at ~4 TB/s.  Measured against forced factors on the plan's shapes (profiles/r06_notes.md 5):
+    // res5.x.conv2 picks 3 (220 us; 2: 315, 4: 250), the M = 20 000 3 x 3 layers on 128 x 64 tiles pick 2 (230 us; unsplit 244-252), the point
+    // head (392 tiles x 11 chunks) stays unsplit (56 us; split in two 78).  Every slice >= 4 chunks.
+    auto cu_cost = [](double w, double chunks) {
+      const double n = (double)(long long)((w + 255.0) / 256.0);
+      return n * (chunks + 3.0) * (n <= 1.0 ? 0.6 : 0.5);
+    };
+    double best = cu_cost((double)tiles, (double)nk);
+    const double unit_us = 3.5 * ((double)BM * BN / (128.0 * 128.0));
+    const double slab_units = 4.0 * (double)M * d->n / 4.0e6 / unit_us;      // one slab read back (the GEMM's slab writes overlap with its own work)
+    for (int c = 2; c <= 16 && nk / c >= 4; ++c) {
+      const double cost = cu_cost((double)tiles * c, (double)nk / c) + 3.0 / unit_us + c * slab_units;
+      if (cost < best * 0.95) { best = cost; S = c; }
+    }
   }
-  return fail(COMA_E_INVALID, "seg_conv_gemm_f32: tile=%d", d->tile);
+  const int ws_ld = gy * BN;
+  const long long slab = gx * BM * (long long)ws_ld;
+  if (S > nk) S = nk;                            // a factor above the chunk count: one chunk per slice
+  if (S > 1 && d->workspace) {
+    const long long fit = (long long)(d->workspace_bytes / sizeof(float)) / slab;
+    // the rule takes as many slices as the workspace holds; a FORCED factor means exactly that many slices (seg_hip.h), so one that does not fit
+    // is refused instead of silently running with fewer
+    if (force_split > 1 && fit < S) return fail(COMA_E_INVALID, "seg_conv_gemm_f32: split_k=%d needs a workspace of %lld bytes", force_split, slab * 4 * S);
+    S = (int)std::min<long long>(S, fit);
+  }
+  int splits, nk_per;
+  if (S <= 1 || !d->workspace) {
+    splits = 1; nk_per = nk;
+    if (force_split > 1) return fail(COMA_E_INVALID, "seg_conv_gemm_f32: split_k=%d needs a workspace of %lld bytes", force_split, slab * 4 * force_split);
+  } else {
+    nk_per = (nk + S - 1) / S;
+    splits = (nk + nk_per - 1) / nk_per;                   // every slice non-empty
+  }
+  ch->tile = tile; ch->bm = BM; ch->bn = BN;
+  // uniform-tap addressing wherever a 32-wide K chunk lies inside one tap (every layer but the stem, C = 4, and the point head, C = 336)
+  ch->uni = d->c % kBK == 0;
+  // the residual is requested before the epilogue only for K <= 128: from K = 256 on the K loop hides the epilogue of the co-resident
+  // workgroup anyway, and the 254-register kernel is the slower one (res5.x.conv3, K = 512: 124 us without, 146 us with)
+  ch->pre = d->res_mode != 0 && splits == 1 && nk <= 4;
+  ch->splits = splits; ch->nk = nk; ch->nk_per = nk_per; ch->grid_x = (int)gx; ch->grid_y = gy; ch->ws_ld = ws_ld; ch->slab_elems = slab;
+  return COMA_OK;
+}
+
+template <int WM, int WN, int TM, int TN, bool UNI>
+static int launch_gemm(GemmArgs& a, hipStream_t st, const seg_conv_choice& ch) {
+  constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
+  constexpr size_t lds_ops = (size_t)2 * (BM + BN) * kLd * sizeof(float), lds_epi = (size_t)BM * (BN + 8) * sizeof(float);
+  constexpr size_t lds = lds_ops > lds_epi ? lds_ops : lds_epi;      // the epilogue stages the output tile over the operand stages (128 x 128: 68 KB)
+  static coma::LdsOptIn opt;
+  static coma::LdsOptIn opt_pre;
+  if (lds > 65536) {
+    if (int rc = coma::opt_in_lds(opt, (const void*)conv_gemm_f32_kernel<WM, WN, TM, TN, UNI, false>, lds, "seg_conv_gemm_f32")) return rc;
+    if (int rc = coma::opt_in_lds(opt_pre, (const void*)conv_gemm_f32_kernel<WM, WN, TM, TN, UNI, true>, lds, "seg_conv_gemm_f32")) return rc;
+  }
+  if (ch.bm != BM || ch.bn != BN) return fail(COMA_E_INVALID, "seg_conv_gemm_f32: tile %d x %d chosen, %d x %d instantiated", ch.bm, ch.bn, BM, BN);
+  a.splits = ch.splits; a.nk_per = ch.nk_per; a.ws_ld = ch.ws_ld; a.gx = ch.grid_x; a.gy = ch.grid_y;
+  const unsigned tiles = (unsigned)((long long)ch.grid_x * ch.grid_y);
+  if (ch.pre)
+    hipLaunchKernelGGL((conv_gemm_f32_kernel<WM, WN, TM, TN, UNI, true>), dim3(tiles, 1, 1), dim3(256), lds, st, a);
+  else
+    hipLaunchKernelGGL((conv_gemm_f32_kernel<WM, WN, TM, TN, UNI, false>), dim3(tiles, 1, (unsigned)a.splits), dim3(256), lds, st, a);
+  if (int rc = check_launch("seg::conv_gemm_f32_kernel")) return rc;
+  if (a.splits > 1) {
+    const long long n = a.M * ((a.N + 3) / 4);
+    hipLaunchKernelGGL(seg_splitk_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, (long long)ch.slab_elems);
+    return check_launch("seg::seg_splitk_reduce_kernel");
+  }
+  return COMA_OK;
+}
+
+}  // namespace seg
+
+extern "C" int seg_conv_gemm_describe(const seg_conv_desc* d, seg_conv_choice* choice) {
+  if (!choice) return seg::fail(COMA_E_INVALID, "seg_conv_gemm_describe: null choice");
+  return seg::choose_gemm(d, choice);
+}
+
+extern "C" int seg_conv_gemm_f32(const seg_conv_desc* d, void* stream) {
+  using namespace seg;
+  if (!d) return fail(COMA_E_INVALID, "seg_conv_gemm_f32: null descriptor");
+  if (sd::plan_recording()) return sd::record_seg_conv(d);
+  seg_conv_choice ch;
+  if (int rc = choose_gemm(d, &ch)) return rc;
+  GemmArgs a;
+  a.x = (const float*)d->x; a.w = (const float*)d->w; a.bias = (const float*)d->bias; a.res = (const float*)d->res; a.out = (float*)d->out;
+  a.m_dev = (const int*)d->m_dev;
+  a.B = d->batch; a.H = d->in_h; a.W = d->in_w; a.C = d->c; a.ldx = d->ldx ? d->ldx : d->c; a.N = d->n; a.Kpad = d->kpad; a.kh = d->kh; a.kw = d->kw;
+  a.stride = d->stride; a.pad = d->pad; a.OH = d->out_h; a.OW = d->out_w; a.ldr = d->ldr ? d->ldr : d->n; a.res_mode = d->res_mode;
+  a.ldo = d->ldo ? d->ldo : d->n; a.relu = d->relu; a.rows_per_item = d->rows_per_item; a.unit_rows = d->unit_rows;
+  a.M = (long long)d->batch * d->out_h * d->out_w;
+  a.ws = (float*)d->workspace; a.splits = 1; a.nk_per = 0; a.ws_ld = 0;
+  static const float* zeros = [] { void* p = nullptr; return hipGetSymbolAddress(&p, HIP_SYMBOL(kZerosDev)) == hipSuccess ? (const float*)p : nullptr; }();
+  if (!zeros) return fail(COMA_E_DEVICE, "seg_conv_gemm_f32: hipGetSymbolAddress(kZerosDev) failed");
+  a.zeros = zeros;
+  hipStream_t st = (hipStream_t)stream;
+  if (ch.uni) {
+    if (ch.tile == 1) return launch_gemm<2, 2, 2, 2, true>(a, st, ch);
+    if (ch.tile == 2) return launch_gemm<4, 1, 1, 2, true>(a, st, ch);
+    return launch_gemm<4, 1, 1, 1, true>(a, st, ch);
+  }
+  if (ch.tile == 1) return launch_gemm<2, 2, 2, 2, false>(a, st, ch);
+  if (ch.tile == 2) return launch_gemm<4, 1, 1, 2, false>(a, st, ch);
+  return launch_gemm<4, 1, 1, 1, false>(a, st, ch);
 }

@@ -225,7 +225,10 @@ __device__ __forceinline__ void decode_box(const float* anchor, float d0, float 
   const float w = anchor[2] - anchor[0], h = anchor[3] - anchor[1];
   const float cx = anchor[0] + 0.5f * w, cy = anchor[1] + 0.5f * h;
   const float dx = d0 / wx, dy = d1 / wy;
-  const float dw = fminf(d2 / ww, kScaleClamp), dh = fminf(d3 / wh, kScaleClamp);
+  // torch.clamp(x, max=SCALE_CLAMP) keeps a NaN delta, and the box it decodes to is then dropped as non-finite; fminf returned the clamp value
+  // for it, a finite box as wide as the image that took part in the NMS (tests/seg_ref.RPN_CASES: the NaN delta of a selected anchor)
+  const float qw = d2 / ww, qh = d3 / wh;
+  const float dw = qw > kScaleClamp ? kScaleClamp : qw, dh = qh > kScaleClamp ? kScaleClamp : qh;
   const float pcx = dx * w + cx, pcy = dy * h + cy;
   const float pw = expf(dw) * w, ph = expf(dh) * h;
   o[0] = pcx - 0.5f * pw; o[1] = pcy - 0.5f * ph; o[2] = pcx + 0.5f * pw; o[3] = pcy + 0.5f * ph;
@@ -533,7 +536,13 @@ __global__ __launch_bounds__(1024) void roi_align_kernel(const RoiArgs a) {
   const float* bx = a.boxes + 4ll * roi;
   const float area = (bx[2] - bx[0]) * (bx[3] - bx[1]);
   const float v = sqrtf(area) / 224.f + 1e-8f;
-  const int lv = (v >= 0.5f) + (v >= 1.f) + (v >= 2.f);             // = clamp(floor(4 + log2(v)), 2, 5) - 2
+  // = clamp(floor(4 + log2(v)), 2, 5) - 2 AS THE ORACLE'S fp32 EXPRESSION ROUNDS IT (oracle/seg_oracle.py assign_levels): for v one to three
+  // floats below a power of two log2(v) is about -1e-7 and 4 + log2(v) rounds up to the integer, so the higher level begins below 0.5, 1 and 2.
+  // Each cut is the smallest float for which that expression reaches the level, found by walking the floats around the power of two on the
+  // CPU (2, 1 and 3 floats below); tests/test_seg_ref_host.py pins the three against assign_levels.  Constants, not log2f here: the device's
+  // last bit need not be the CPU's.  A NaN v (negative area) compares false three times: level 0.
+  constexpr float kCut3 = 0x1.fffffcp-2f, kCut4 = 0x1.fffffep-1f, kCut5 = 0x1.fffffap+0f;
+  const int lv = (v >= kCut3) + (v >= kCut4) + (v >= kCut5);
   if (threadIdx.x == 0 && a.level) a.level[roi] = lv;
   const float scale = 1.f / (float)(4 << lv);
   const int H = a.fh[lv], W = a.fw[lv];
@@ -541,7 +550,9 @@ __global__ __launch_bounds__(1024) void roi_align_kernel(const RoiArgs a) {
   const float x1 = bx[0] * scale - 0.5f, y1 = bx[1] * scale - 0.5f, x2 = bx[2] * scale - 0.5f, y2 = bx[3] * scale - 0.5f;
   const float rw = x2 - x1, rh = y2 - y1;
   const float bw = rw / (float)a.out_size, bh = rh / (float)a.out_size;
-  const int gh = (int)ceilf(rh / (float)a.out_size), gw = (int)ceilf(rw / (float)a.out_size);
+  // an inverted box has a negative sample count on that axis: no samples, as torchvision's loops run (`for iy < grid_h`).  Unclamped, a box
+  // inverted on BOTH axes had gh * gw > 0 samples and indexed the tables below with negative sample numbers.
+  const int gh = max((int)ceilf(rh / (float)a.out_size), 0), gw = max((int)ceilf(rw / (float)a.out_size), 0);
   const int c4 = a.c / 4;
   // ---- per-axis sample tables in LDS (r6): the geometry of a sample is wave-uniform work that every lane was redoing per sample (2.6e8 wave
   // instructions per launch, VALU-bound).  Sample ix of bin column pw depends on (pw, ix) only, sample iy of bin row ph on (ph, iy) only: wave w

@@ -20,20 +20,53 @@ class SegConvDesc(C.Structure):
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("split_k", C.c_int)]
 
 
-def conv_gemm(x, w, out, *, batch, in_h, in_w, c, n, kh=1, kw=1, stride=1, pad=0, out_h=None, out_w=None, bias=None, res=None, res_mode=0,
-              ldr=0, ldo=0, ldx=0, relu=False, m_dev=None, rows_per_item=1, unit_rows=0, tile=0, workspace=None, split_k=0):
+class SegConvChoice(C.Structure):
+    """seg_conv_choice of include/seg_hip.h: the launch seg_conv_gemm_f32 makes for a descriptor."""
+    _fields_ = [(k, C.c_int) for k in ("tile", "bm", "bn", "uni", "pre", "splits", "nk", "nk_per", "grid_x", "grid_y", "ws_ld")] + \
+               [("slab_elems", C.c_longlong)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def _conv_desc(p, x, w, out, *, batch, in_h, in_w, c, n, kpad=None, kh=1, kw=1, stride=1, pad=0, out_h=None, out_w=None, bias=None, res=None,
+               res_mode=0, ldr=0, ldo=0, ldx=0, relu=False, m_dev=None, rows_per_item=1, unit_rows=0, tile=0, workspace=None, workspace_bytes=None,
+               split_k=0):
+    """The descriptor of a launch; p(tensor, name, dtype) -> address.  kpad: the row length of w (default: w.shape[-1])."""
     d = SegConvDesc()
-    d.x, d.batch, d.in_h, d.in_w, d.c, d.ldx = _p(x, "x", F32), batch, in_h, in_w, c, ldx
-    d.w, d.n, d.kpad = _p(w, "w", F32), n, w.shape[-1]
+    d.x, d.batch, d.in_h, d.in_w, d.c, d.ldx = p(x, "x", F32), batch, in_h, in_w, c, ldx
+    d.w, d.n, d.kpad = p(w, "w", F32), n, kpad if kpad is not None else w.shape[-1]
     d.kh, d.kw, d.stride, d.pad = kh, kw, stride, pad
     d.out_h = out_h if out_h is not None else (in_h + 2 * pad - kh) // stride + 1
     d.out_w = out_w if out_w is not None else (in_w + 2 * pad - kw) // stride + 1
-    d.bias, d.res, d.ldr, d.res_mode = _p(bias, "bias", F32), _p(res, "res", F32), ldr, res_mode
-    d.out, d.ldo, d.relu = _p(out, "out", F32), ldo, 1 if relu else 0
-    d.m_dev, d.rows_per_item, d.unit_rows, d.tile = _p(m_dev, "m_dev", I32), rows_per_item, unit_rows, tile
-    d.workspace, d.workspace_bytes, d.split_k = _p(workspace, "workspace", F32), (workspace.numel() * 4 if workspace is not None else 0), split_k
+    d.bias, d.res, d.ldr, d.res_mode = p(bias, "bias", F32), p(res, "res", F32), ldr, res_mode
+    d.out, d.ldo, d.relu = p(out, "out", F32), ldo, 1 if relu else 0
+    d.m_dev, d.rows_per_item, d.unit_rows, d.tile = p(m_dev, "m_dev", I32), rows_per_item, unit_rows, tile
+    d.workspace = p(workspace, "workspace", F32)
+    if workspace_bytes is None:
+        workspace_bytes = workspace.numel() * 4 if isinstance(workspace, torch.Tensor) else 0
+    d.workspace_bytes, d.split_k = workspace_bytes, split_k
+    return d
+
+
+def conv_gemm(x, w, out, **kw):
+    """seg_conv_gemm_f32; keywords as _conv_desc."""
+    d = _conv_desc(_p, x, w, out, **kw)
     _lib.check(_lib.lib().seg_conv_gemm_f32(C.byref(d), _stream(out)), "seg_conv_gemm_f32")
     return out
+
+
+def conv_gemm_describe(x, w, out, **kw):
+    """seg_conv_gemm_describe: the SegConvChoice of the launch conv_gemm(x, w, out, **kw) would make, or its refusal as ComaHipError.  Host
+    code only: nothing is launched and no pointer is dereferenced, so every tensor argument may also be a plain integer address (with kpad
+    beside an integer `w` and workspace_bytes beside an integer `workspace`) and no GPU is needed."""
+    def address(t, name="tensor", dtype=F32):
+        return t if t is None or isinstance(t, int) else _lib.ptr(t, dtype, name).value
+    d, choice = _conv_desc(address, x, w, out, **kw), SegConvChoice()
+    rc = _lib.lib().seg_conv_gemm_describe(C.byref(d), C.byref(choice))
+    if rc != 0:
+        raise _lib.ComaHipError(f"seg_conv_gemm_describe failed ({rc}): {_lib.lib().coma_last_error().decode()}")
+    return choice
 
 
 def resize_normalize(src, tmp, out, *, batch, h, w, new_h, new_w, pad_h, pad_w, bounds_x, kk_x, bounds_y, kk_y, mean, resized=None):

@@ -28,7 +28,7 @@ extern "C" {
 
 /* bumped when an existing signature of coma_hip.h / sd_hip.h / seg_hip.h changes; coma_amd/_lib.py refuses a library that
  * reports another value (a stale build loaded through COMA_HIP_LIB would otherwise be called with mismatched argument lists) */
-#define COMA_ABI_VERSION 10  /* 10: sd_conv_gemm_describe added; sd_conv_gemm_f16 refuses a column bias with SD_EPI_PERM16_N / SD_EPI_PERM32_N and colstats in a phase launch with in_h * in_w % 32 != 0 */
+#define COMA_ABI_VERSION 11  /* 11: seg_conv_gemm_describe added; seg_conv_gemm_f32 refuses a forced split_k whose slabs the workspace does not hold (it ran with fewer slices); 10: sd_conv_gemm_describe added; sd_conv_gemm_f16 refuses a column bias with SD_EPI_PERM16_N / SD_EPI_PERM32_N and colstats in a phase launch with in_h * in_w % 32 != 0 */
 /* The version counts CHANGES of existing signatures, not additions: a function that is only added (the text tower, the sample
  * elimination, the rasteriser, the mesh volume functions, the coma_vposer_* and coma_angle_prior_* functions) leaves it alone, because a library without it already fails to load
  * (coma_amd/_lib.py binds every declared name). */

@@ -53,10 +53,25 @@ typedef struct seg_conv_desc {
   void* workspace;      /* f32 scratch for split-K partial tiles or NULL (then K is never split) */
   size_t workspace_bytes;
   int split_k;          /* 0 = by rule (fewer than 1024 tiles and K >= 256: the slice count a per-CU cost model picks, slices of >= 128 k values,
-                           as many as the workspace holds), -1 = never, S > 1 = exactly S slices (tests); the slices are summed in order:
-                           deterministic */
+                           as many as the workspace holds), -1 = never, S > 1 = exactly min(S, K chunks) slices (tests; refused when the
+                           workspace holds fewer slabs); the slices are summed in order: deterministic */
 } seg_conv_desc;
 int seg_conv_gemm_f32(const seg_conv_desc* d, void* stream);
+
+/* The launch seg_conv_gemm_f32 makes for a descriptor, or its refusal (same return code and coma_last_error text): host code only, nothing is
+ * launched and no pointer of the descriptor is dereferenced, so it needs no device.  The launcher takes its choice from the same function. */
+typedef struct seg_conv_choice {
+  int tile;             /* 1 / 2 / 3 = 128x128 / 128x64 / 128x32 */
+  int bm, bn;           /* rows, columns of a tile */
+  int uni;              /* 1: c % 32 == 0, a K chunk lies inside one tap (wave-uniform addressing) */
+  int pre;              /* 1: residual and bias are requested in front of the last K chunk (residual, unsplit, at most 4 chunks) */
+  int splits;           /* K slices (1: no split-K, no reduce pass) */
+  int nk, nk_per;       /* K chunks of 32 in all, per slice (the last slice may hold fewer) */
+  int grid_x, grid_y;   /* row tiles, column tiles */
+  int ws_ld;            /* columns of a workspace slab = grid_y * bn */
+  long long slab_elems; /* floats of a workspace slab = grid_x * bm * ws_ld; a split launch writes splits * slab_elems floats */
+} seg_conv_choice;
+int seg_conv_gemm_describe(const seg_conv_desc* d, seg_conv_choice* choice);
 
 /* DefaultPredictor's ResizeShortestEdge (PIL bilinear on uint8: horizontal pass, uint8 in between, vertical pass; 22-bit fixed-point
  * weights computed by the host exactly as Pillow does) + GeneralizedRCNN.preprocess_image (- pixel_mean, zero pad to [pad_h, pad_w]).

@@ -27,12 +27,13 @@ def test_every_declared_symbol_is_exported_and_bound(hip_lib):
     assert sorted(_lib.SIGNATURES) == decl, "ctypes signature table out of sync with the header"
 
 
-def test_abi_version_10_and_error_text(hip_lib):
+def test_abi_version_11_and_error_text(hip_lib):
+    # 11: seg_conv_gemm_describe joined the ABI; seg_conv_gemm_f32 refuses a forced split_k whose slabs the workspace does not hold
     # 10: sd_conv_gemm_describe joined the ABI; sd_conv_gemm_f16 refuses a column bias with SD_EPI_PERM16_N / SD_EPI_PERM32_N and colstats in
     # a phase launch with in_h * in_w % 32 != 0
-    assert hip_lib.coma_abi_version() == 10 == _lib.ABI_VERSION
+    assert hip_lib.coma_abi_version() == 11 == _lib.ABI_VERSION
     hdr = open(os.path.join(ROOT, "include", "coma_hip.h")).read()
-    assert re.search(r"#define COMA_ABI_VERSION (\d+)", hdr).group(1) == "10"
+    assert re.search(r"#define COMA_ABI_VERSION (\d+)", hdr).group(1) == "11"
     rc = hip_lib.coma_nearest_vertex_i64(None, None, 1, 1, None, None)
     assert rc == -1 and b"null pointer" in hip_lib.coma_last_error()
     one = C.c_void_p(8)   # never dereferenced: size validation fails first

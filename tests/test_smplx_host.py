@@ -208,7 +208,7 @@ def test_new_names_are_in_the_header_and_the_ctypes_table():
     for name in names:
         assert re.search(rf"\b{name}\(", header), name
         assert name in _lib.SIGNATURES, name
-    assert "COMA_ABI_VERSION 10" in header.replace("  ", " ") or _lib.ABI_VERSION == 10
+    assert "COMA_ABI_VERSION 11" in header.replace("  ", " ") or _lib.ABI_VERSION == 11
 
 
 def test_argument_validation_happens_before_any_launch(hip_lib):
