@@ -84,6 +84,9 @@ SIGNATURES = {
                                     _vp, C.c_size_t, _vp]),
     "coma_smplx_backward_f32": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _i, _vp, _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t,
                                      _vp]),
+    "coma_smplx_grad_workspace_bytes": (C.c_size_t, [_i, _i, _i]),
+    "coma_smplx_backward_full_f32": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp,
+                                          C.c_size_t, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "coma_smplx_extra_joints_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "coma_vposer_saved_bytes": (C.c_size_t, [_i, _i, _i]),
     "coma_vposer_workspace_bytes": (C.c_size_t, [_i, _i, _i]),

@@ -6,8 +6,17 @@ src/application/optimize.py and src/generation/optimize_depth.py call: keyword t
 .joints, .full_pose and .faces out.  `.vertices` is the output of a torch.autograd.Function whose backward is the device backward, so
 a pose decoder or a prior on the other side of the hook keeps differentiating through torch.
 
+By default `.joints` and `.full_pose` carry no gradient and betas / expression must not require grad.  `differentiable=` opts in, any
+subset of {"joints", "full_pose", "shape"}: with "joints" / "full_pose" those outputs take part in autograd too, with "shape" betas
+and expression may require grad and receive gradients from whichever outputs are differentiable (coma_smplx_backward_full_f32; the
+backward is once_differentiable: no double backward).  With any of them, every forward keeps the shape state it ran on, so a
+backward after the coefficients have changed still differentiates ITS forward; with "shape" the shape stage reads the coefficients
+from the device tensors (nothing is copied to the host) and re-runs whenever a tensor or its version counter differs.
+
 Deviations from the package, all refused or stated rather than silently different:
-  * NO gradient with respect to betas or expression (the call raises if either requires grad) and none through `.joints`;
+  * by default NO gradient with respect to betas or expression (the call raises if either requires grad) and none through `.joints`
+    or `.full_pose`; each needs its entry in `differentiable=`;
+  * no gradient with respect to the model's own tensors (shapedirs, posedirs, weights), no double backward;
   * batch size 1 only;
   * the package's table of vertex ids for the extra joints (nose, eyes, ears, toes, heels, finger tips) is not shipped: it is taken
     from `smplx.vertex_ids` when that package imports, may be passed in, and otherwise `.joints` is [J posed joints | landmarks] and
@@ -28,6 +37,8 @@ from . import _lib
 
 SHAPE_SPACE_DIM, EXPRESSION_SPACE_DIM = 300, 100
 MAX_JOINTS = 64
+MAX_GRAD_EXTRA_JOINTS = 4096                                             # the full backward's bound on E
+DIFFERENTIABLE = ("joints", "full_pose", "shape")
 # the package's order of the extra joints (vertex_joint_selector.py): face and feet, then the finger tips of both hands
 _FACE_FEET = ("nose", "reye", "leye", "rear", "lear", "LBigToe", "LSmallToe", "LHeel", "RBigToe", "RSmallToe", "RHeel")
 _TIPS = ("thumb", "index", "middle", "ring", "pinky")
@@ -57,10 +68,14 @@ def _row(x, n, name):
 
 class DeviceSMPLX:
     def __init__(self, model, n_pca=45, flat_hand_mean=False, use_pca=True, device="cuda", num_betas=10, num_expression_coeffs=10,
-                 extra_joint_vertex_ids=None):
+                 extra_joint_vertex_ids=None, differentiable=()):
         """model: a dict of arrays with the keys of an SMPL-X model file (v_template, shapedirs, posedirs, J_regressor, kintree_table,
-        weights, f, hands_components{l,r}, hands_mean{l,r}, lmk_faces_idx, lmk_bary_coords)."""
+        weights, f, hands_components{l,r}, hands_mean{l,r}, lmk_faces_idx, lmk_bary_coords).  differentiable: a subset of
+        DIFFERENTIABLE, what besides .vertices -> pose / transl takes part in autograd (module docstring); empty = none."""
         dev = _lib.need_device(device, "DeviceSMPLX", resolve=False)
+        if isinstance(differentiable, str) or not set(differentiable) <= set(DIFFERENTIABLE):
+            raise ValueError(f"DeviceSMPLX: differentiable={differentiable!r} must be a collection of names out of {DIFFERENTIABLE}")
+        self.differentiable = frozenset(differentiable)
         need = ("v_template", "shapedirs", "posedirs", "J_regressor", "kintree_table", "weights", "f", "hands_componentsl", "hands_componentsr",
                 "hands_meanl", "hands_meanr", "lmk_faces_idx", "lmk_bary_coords")
         missing = [k for k in need if k not in model]
@@ -135,6 +150,8 @@ class DeviceSMPLX:
         self.hand_size = self.num_pca_comps if use_pca else hd          # entries of one hand's argument
         self.num_theta = self.num_lead + 2 * self.hand_size
         self.num_extra = int(idx.shape[0])
+        if "joints" in self.differentiable and self.num_extra > MAX_GRAD_EXTRA_JOINTS:
+            raise ValueError(f"DeviceSMPLX: {self.num_extra} extra joints; the gradient through .joints handles at most {MAX_GRAD_EXTRA_JOINTS}")
         # host copies (read by the tests) and their device uploads
         self.host = dict(v_template=v_template, shapedirs=shapedirs, posedirs=posedirs, J_regressor=J_regressor, weights=weights,
                          parents=parents, hand_components=comps, pose_mean=mean, extra_index=idx, extra_weight=w)
@@ -145,7 +162,7 @@ class DeviceSMPLX:
 
     @classmethod
     def from_file(cls, model_path, gender="neutral", num_pca_comps=45, flat_hand_mean=False, use_pca=True, device="cuda", num_betas=10,
-                  num_expression_coeffs=10, extra_joint_vertex_ids=None):
+                  num_expression_coeffs=10, extra_joint_vertex_ids=None, differentiable=()):
         """model_path: the model file itself, or -- the path rule of the package's `create(model_path, model_type="smplx")` -- a
         directory whose `smplx/` sub-directory holds SMPLX_{GENDER}.npz; read with NumPy alone."""
         pth = model_path
@@ -158,7 +175,7 @@ class DeviceSMPLX:
         with np.load(pth, allow_pickle=True) as data:
             model = {k: data[k] for k in data.files}
         return cls(model, n_pca=num_pca_comps, flat_hand_mean=flat_hand_mean, use_pca=use_pca, device=device, num_betas=num_betas,
-                   num_expression_coeffs=num_expression_coeffs, extra_joint_vertex_ids=extra_joint_vertex_ids)
+                   num_expression_coeffs=num_expression_coeffs, extra_joint_vertex_ids=extra_joint_vertex_ids, differentiable=differentiable)
 
     def _upload(self):
         if self._uploaded:
@@ -175,6 +192,9 @@ class DeviceSMPLX:
             L.coma_smplx_workspace_bytes, L.coma_smplx_shape_state_bytes, L.coma_smplx_saved_bytes))
         self._ws = torch.empty([self._ws_bytes], dtype=torch.uint8, device=dev)
         self._shape_state = torch.empty([self._shape_bytes], dtype=torch.uint8, device=dev)
+        if self.differentiable:
+            self._grad_ws_bytes = int(L.coma_smplx_grad_workspace_bytes(self.V, self.J, self.num_betas + self.num_expression_coeffs))
+            self._grad_ws = torch.empty([self._grad_ws_bytes], dtype=torch.uint8, device=dev)
         self._uploaded = True
 
     # ---- the three device calls ----
@@ -184,9 +204,12 @@ class DeviceSMPLX:
         anything else is compared on the host copy made here (one device-to-host copy when the coefficients live on the device).
         LIMITATION: a write that does not move the version counter -- through `.data`, or from outside torch -- is not seen on the
         same-tensor path; pass a new tensor, or write in place through torch."""
+        if "shape" in self.differentiable:
+            return self._shape_stage_on_device(betas, expression)
         for x, name in ((betas, "betas"), (expression, "expression")):     # looked at on every call, whichever path follows
             if torch.is_tensor(x) and x.requires_grad:
-                raise _lib.ComaHipError(f"DeviceSMPLX: {name} requires grad, and the device body model has no gradient with respect to {name}")
+                raise _lib.ComaHipError(f"DeviceSMPLX: {name} requires grad, and the device body model has no gradient with respect to {name} "
+                                        f"unless it is built with \"shape\" in differentiable=")
         source = (betas, expression)
         version = tuple(x._version if torch.is_tensor(x) else None for x in source)
         if self._shape_source is not None and version == self._shape_version and all(
@@ -205,15 +228,41 @@ class DeviceSMPLX:
         self._shape_source, self._shape_version = source, version
         if key == self._shape_key:
             return
-        d_coef = torch.from_numpy(coef).to(self.device)
+        self._run_shape(torch.from_numpy(coef).to(self.device))
+        self._shape_key = key
+
+    def _run_shape(self, d_coef):
+        """The shape stage from device coefficients f32 [NB].  With anything in `differentiable`, into a NEW shape state: forwards that
+        ran on the previous one hold on to it for their backward."""
         f32 = torch.float32
+        if self.differentiable:
+            self._shape_state = torch.empty([self._shape_bytes], dtype=torch.uint8, device=self.device)
         with _lib.on_device(self.device) as stream:
             rc = _lib.lib().coma_smplx_shape_f32(_lib.ptr(self._v_template, f32), _lib.ptr(self._shapedirs, f32), _lib.ptr(d_coef, f32),
-                                                 _lib.ptr(self._J_regressor, f32), self.V, self.J, int(coef.size), _lib.ptr(self._shape_state),
+                                                 _lib.ptr(self._J_regressor, f32), self.V, self.J, int(d_coef.numel()), _lib.ptr(self._shape_state),
                                                  self._shape_bytes, stream)
         _lib.check(rc, "coma_smplx_shape_f32")
-        self._shape_key = key
         self.shape_stage_runs += 1
+
+    def _shape_stage_on_device(self, betas, expression):
+        """differentiable "shape": the coefficients as ONE device tensor f32 [NB] that is part of the autograd graph (its gradient
+        splits back into betas and expression through torch), built without copying anything to the host.  The shape stage is
+        skipped for the same tensor objects at the same version counters and re-run otherwise: values are never compared, that
+        would take a read-back.  The LIMITATION of `_shape_stage` about writes that do not move the version counter holds here too."""
+        self._upload()
+        parts = []
+        for x, n, name in ((betas, self.num_betas, "betas"), (expression, self.num_expression_coeffs, "expression")):
+            x = _row(x, n, name)
+            parts.append(torch.zeros([n], dtype=torch.float32, device=self.device) if x is None
+                         else x.reshape(-1).to(device=self.device, dtype=torch.float32))
+        coef = torch.cat(parts)
+        source = (betas, expression)
+        version = tuple(x._version if torch.is_tensor(x) else None for x in source)
+        if not (self._shape_source is not None and version == self._shape_version and all(
+                (x is None and y is None) or (torch.is_tensor(x) and x is y) for x, y in zip(source, self._shape_source))):
+            self._run_shape(coef.detach().contiguous())
+            self._shape_source, self._shape_version, self._shape_key = source, version, None
+        return coef
 
     def _forward(self, theta, transl):
         """theta f32 [num_theta], transl f32 [3] or None (device) -> vertices [V,3], joints [J + extra, 3], full_pose [3J], saved."""
@@ -249,15 +298,35 @@ class DeviceSMPLX:
         _lib.check(rc, "coma_smplx_backward_f32")
         return g_theta, g_transl
 
+    def _backward_full(self, grad_vertices, grad_joints, grad_full_pose, saved, shape_state, want_coefficients):
+        """The full backward of ONE forward (its saved state and the shape state it ran on); each gradient f32 on the device or None
+        = absent -> (g_theta, g_transl, g_coefficients or None)."""
+        f32, dev = torch.float32, self.device
+        NB = self.num_betas + self.num_expression_coeffs
+        g_theta = torch.empty([self.num_theta], dtype=f32, device=dev)
+        g_transl = torch.empty([3], dtype=f32, device=dev)
+        g_coef = torch.empty([NB], dtype=f32, device=dev) if want_coefficients else None
+        with _lib.on_device(dev) as stream:
+            rc = _lib.lib().coma_smplx_backward_full_f32(
+                _lib.ptr(grad_vertices, f32, "grad_vertices"), _lib.ptr(grad_joints, f32, "grad_joints"), _lib.ptr(grad_full_pose, f32, "grad_full_pose"),
+                _lib.ptr(self._posedirs, f32), _lib.ptr(self._weights, f32), self._parents, _lib.ptr(self._comps, f32),
+                _lib.ptr(self._extra_index, torch.int32), _lib.ptr(self._extra_weight, f32), self.num_extra, _lib.ptr(self._shapedirs, f32),
+                _lib.ptr(self._J_regressor, f32), NB, self.V, self.J, self.hand_dim, self.num_pca_comps, _lib.ptr(shape_state), _lib.ptr(saved),
+                self._saved_bytes, _lib.ptr(g_theta), _lib.ptr(g_transl), _lib.ptr(g_coef, f32), _lib.ptr(self._grad_ws), self._grad_ws_bytes,
+                stream)
+        _lib.check(rc, "coma_smplx_backward_full_f32")
+        return g_theta, g_transl, g_coef
+
     def __call__(self, betas=None, global_orient=None, body_pose=None, left_hand_pose=None, right_hand_pose=None, transl=None, expression=None,
                  jaw_pose=None, leye_pose=None, reye_pose=None, return_verts=True, return_full_pose=False, **unused):
         """The package's call: every argument [1, n] (None = zeros).  Gradients flow from .vertices to the seven pose arguments and
-        transl; betas and expression must not require grad."""
+        transl; betas and expression must not require grad.  `differentiable=` (constructor) adds .joints, .full_pose (ask for it with
+        return_full_pose=True) and the gradient to betas / expression."""
         sizes = (("global_orient", global_orient, 3), ("body_pose", body_pose, self.num_body), ("jaw_pose", jaw_pose, 3),
                  ("leye_pose", leye_pose, 3), ("reye_pose", reye_pose, 3), ("left_hand_pose", left_hand_pose, self.hand_size),
                  ("right_hand_pose", right_hand_pose, self.hand_size), ("transl", transl, 3))
         rows = [(name, _row(x, n, name), n) for name, x, n in sizes]          # shapes first: nothing has touched the device yet
-        self._shape_stage(betas, expression)
+        coefficients = self._shape_stage(betas, expression)                 # a device tensor with differentiable "shape", else None
         parts = []
         for name, x, n in rows:
             if x is None:
@@ -267,7 +336,10 @@ class DeviceSMPLX:
             parts.append(x if x is None else x.reshape(-1).to(torch.float32))
         transl = parts.pop()
         theta = torch.cat(parts)
-        vertices, joints, full_pose = _SkinFunction.apply(self, theta, transl)
+        if self.differentiable:
+            vertices, joints, full_pose = _FullFunction.apply(self, theta, transl, coefficients)
+        else:
+            vertices, joints, full_pose = _SkinFunction.apply(self, theta, transl)
         return SimpleNamespace(vertices=vertices[None] if return_verts else None, joints=joints[None],
                                full_pose=full_pose[None] if return_full_pose else None, faces=self.faces, betas=betas, expression=expression,
                                global_orient=global_orient, body_pose=body_pose, jaw_pose=jaw_pose, transl=transl)
@@ -285,3 +357,32 @@ class _SkinFunction(torch.autograd.Function):
     def backward(ctx, grad_vertices, _grad_joints, _grad_full_pose):
         g_theta, g_transl = ctx.model._backward(grad_vertices.to(torch.float32).contiguous(), ctx.saved)
         return None, g_theta, (g_transl if ctx.has_transl else None)
+
+
+class _FullFunction(torch.autograd.Function):
+    """The forward of _SkinFunction with the outputs named in `differentiable` left differentiable and the full device backward.  It
+    keeps the shape state its forward ran on: a later call with other coefficients writes a new one."""
+
+    @staticmethod
+    def forward(ctx, model, theta, transl, coefficients):
+        vertices, joints, full_pose, saved = model._forward(theta.detach().contiguous(), None if transl is None else transl.detach().contiguous())
+        ctx.model, ctx.saved, ctx.shape_state, ctx.has_transl = model, saved, model._shape_state, transl is not None
+        dead = [t for name, t in (("joints", joints), ("full_pose", full_pose)) if name not in model.differentiable]
+        if dead:
+            ctx.mark_non_differentiable(*dead)
+        ctx.set_materialize_grads(False)                      # an output the loss does not read arrives as None and is passed as absent
+        return vertices, joints, full_pose
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_vertices, grad_joints, grad_full_pose):
+        model = ctx.model
+        if "joints" not in model.differentiable:
+            grad_joints = None
+        if "full_pose" not in model.differentiable:
+            grad_full_pose = None
+        f32 = lambda g: None if g is None else g.to(torch.float32).contiguous()
+        want_coefficients = len(ctx.needs_input_grad) > 3 and ctx.needs_input_grad[3]
+        g_theta, g_transl, g_coef = model._backward_full(f32(grad_vertices), f32(grad_joints), f32(grad_full_pose), ctx.saved, ctx.shape_state,
+                                                         want_coefficients)
+        return None, g_theta, (g_transl if ctx.has_transl else None), g_coef

@@ -12,6 +12,11 @@
 // A_i = [G_i.R | G_i.t - G_i.R J_i].  The skinning stage adds the pose-dependent offsets (the entries of R_i - I for i >= 1 times
 // `posedirs`) to the shaped template, blends the A_i with the vertex's weights and applies the blend.  The backward walks all of
 // that in reverse from dL/dvertices to dL/dtheta and dL/dtransl; betas, expression and the joint outputs get NO gradient.
+// The FULL backward (coma_smplx_backward_full_f32) is the same three launches with additions: dL/djoints of the extra joints is
+// gathered into an effective vertex gradient first; dL/djoints of the posed joints and dL/dfull_pose are injected into the chain
+// kernel, which also collects the gradient of the rest joints; J_regressor^T and shapedirs^T carry that and the skinning's dL/dv_posed
+// back to the coefficients.  Up to three launches more; with none of its inputs given it is the backward, bit for bit.  COAP's own
+// backward is not built on it yet: src/application/optimize.py --use_collision stays refused.
 //
 // Everything is evaluated in f64 on f32 inputs (as the rest of the per-vertex code of this library: V = 10 475 and a 55-joint
 // chain are latency- and bandwidth-bound, the f64 rate does not show), so the outputs are the f32 rounding of the rule set.  The
@@ -265,17 +270,19 @@ __global__ __launch_bounds__(kTile) void smplx_skin_kernel(SkinArgs a) {
 }
 
 // ---- backward ----
+template <typename TG>
 struct SkinBwdArgs {
   const float* weights;
   const double* A;
   const double* v_posed;
-  const float* grad;        // dL/dvertices [V,3]
+  const TG* grad;           // dL/dvertices [V,3]: the caller's f32, or the f64 effective gradient of the full backward
   int V, J;
   double* gvp;              // workspace [V,3]: T[:3,:3]^T g
   double* dA_part;          // workspace [blocks][12 J + 3]: the block's share of dL/dA, then of dL/dtransl
 };
 
-__global__ __launch_bounds__(kTile) void smplx_skin_bwd_kernel(SkinBwdArgs a) {
+template <typename TG>
+__global__ __launch_bounds__(kTile) void smplx_skin_bwd_kernel(SkinBwdArgs<TG> a) {
   __shared__ float Wt[kTile * kMaxJ];
   __shared__ double Al[12 * kMaxJ];
   __shared__ double gl[3 * kTile], vl[4 * kTile];
@@ -283,7 +290,7 @@ __global__ __launch_bounds__(kTile) void smplx_skin_bwd_kernel(SkinBwdArgs a) {
   const int t = threadIdx.x;
   if (t < n) {
     const int64_t v = (int64_t)blockIdx.x * kTile + t;
-    const double g[3] = {(double)a.grad[3 * v], (double)a.grad[3 * v + 1], (double)a.grad[3 * v + 2]};
+    const double g[3] = {load(a.grad, 3 * v), load(a.grad, 3 * v + 1), load(a.grad, 3 * v + 2)};
     double T[12];
     blend(Wt + t * a.J, Al, a.J, T);
 #pragma unroll
@@ -332,10 +339,16 @@ struct PoseBwdArgs {
   Tree tree;
   float* grad_theta;
   float* grad_transl;
+  // the full backward's additions; each pointer may be null and then changes nothing
+  const float* gJ;          // dL/djoints [J + E, 3]
+  const float* gP;          // dL/dfull_pose [3J]
+  const float* extra_w;     // [E,3]: the extra joints' weights, for the direct transl term (read only with gJ)
+  int E;
+  double* dJ_out;           // dL/dJ_rest [J,3]
 };
 
 __global__ __launch_bounds__(kBlock) void smplx_pose_bwd_kernel(PoseBwdArgs a) {
-  __shared__ double pose[3 * kMaxJ], R[9 * kMaxJ], G[12 * kMaxJ], dG[12 * kMaxJ], dR[9 * kMaxJ];
+  __shared__ double pose[3 * kMaxJ], R[9 * kMaxJ], G[12 * kMaxJ], dG[12 * kMaxJ], dR[9 * kMaxJ], dJ[3 * kMaxJ];
   const int t = threadIdx.x, J = a.J;
   for (int k = t; k < 3 * J; k += kBlock) pose[k] = a.s_pose[k];
   __syncthreads();
@@ -346,8 +359,21 @@ __global__ __launch_bounds__(kBlock) void smplx_pose_bwd_kernel(PoseBwdArgs a) {
   for (int q = t; q < nq; q += kBlock) {
     double acc = 0.0;
     for (int b = 0; b < a.nblk; ++b) acc = acc + a.dA_part[(int64_t)b * nq + q];
-    if (q < 12 * J) dA[q] = acc;
-    else a.grad_transl[q - 12 * J] = (float)acc;
+    if (q < 12 * J) {
+      dA[q] = acc;
+    } else {
+      const int r = q - 12 * J;
+      if (a.gJ) {                                           // joints_i = G_i.t + transl, and the extra joints' direct term
+        double posed = 0.0, direct = 0.0;
+        for (int i = 0; i < J; ++i) posed = posed + (double)a.gJ[3 * i + r];
+        for (int e = 0; e < a.E; ++e) {
+          const double w = ((double)a.extra_w[3 * e] + (double)a.extra_w[3 * e + 1]) + (double)a.extra_w[3 * e + 2];
+          direct = direct + (1.0 - w) * (double)a.gJ[3 * (J + e) + r];
+        }
+        acc = (acc + posed) + direct;
+      }
+      a.grad_transl[r] = (float)acc;
+    }
   }
   __syncthreads();
   // A = [G.R | G.t - G.R J]: dG.t = dA.t, dG.R = dA.R - dA.t J^T   (each entry reads its own row's dA.t, which is not rewritten)
@@ -355,7 +381,16 @@ __global__ __launch_bounds__(kBlock) void smplx_pose_bwd_kernel(PoseBwdArgs a) {
     const int i = q / 12, r = (q % 12) / 4, c = q % 4;
     if (c < 3) dG[q] = dA[q] - dA[12 * i + 4 * r + 3] * a.j_rest[3 * i + c];
   }
+  if (a.dJ_out)                                           // ... and dJ_i = -G_i.R^T dA_i.t
+    for (int q = t; q < 3 * J; q += kBlock) {
+      const int i = q / 3, c = q % 3;
+      dJ[q] = -((G[12 * i + c] * dA[12 * i + 3] + G[12 * i + 4 + c] * dA[12 * i + 7]) + G[12 * i + 8 + c] * dA[12 * i + 11]);
+    }
   __syncthreads();
+  if (a.gJ) {                                             // dG_i.t += dL/djoints_i, once dA.t has been read
+    for (int q = t; q < 3 * J; q += kBlock) dG[12 * (q / 3) + 4 * (q % 3) + 3] = dG[12 * (q / 3) + 4 * (q % 3) + 3] + (double)a.gJ[q];
+    __syncthreads();
+  }
   for (int i = J - 1; i >= 1; --i) {
     const int p = a.tree.parent[i];
     if (t < 9) {                                          // dR_i = G_p.R^T dG_i.R + dL/dfeature
@@ -373,8 +408,18 @@ __global__ __launch_bounds__(kBlock) void smplx_pose_bwd_kernel(PoseBwdArgs a) {
         add = di[3];
       }
       dG[12 * p + e] = dG[12 * p + e] + add;
+    } else if (t >= 32 && t < 35 && a.dJ_out) {            // G_i.t = G_p.R (J_i - J_p) + G_p.t: u = G_p.R^T dG_i.t to J_i, -u to J_p
+      const int c = t - 32;
+      const double u = (G[12 * p + c] * dG[12 * i + 3] + G[12 * p + 4 + c] * dG[12 * i + 7]) + G[12 * p + 8 + c] * dG[12 * i + 11];
+      dJ[3 * i + c] = dJ[3 * i + c] + u;
+      dJ[3 * p + c] = dJ[3 * p + c] - u;
     }
     __syncthreads();
+  }
+  if (a.dJ_out) {                                         // the root: G_0.t = J_0
+    if (t >= 32 && t < 35) dJ[t - 32] = dJ[t - 32] + dG[4 * (t - 32) + 3];
+    __syncthreads();
+    for (int q = t; q < 3 * J; q += kBlock) a.dJ_out[q] = dJ[q];
   }
   if (t < 9) dR[t] = dG[4 * (t / 3) + t % 3];
   __syncthreads();
@@ -382,6 +427,9 @@ __global__ __launch_bounds__(kBlock) void smplx_pose_bwd_kernel(PoseBwdArgs a) {
   if (t < J) {
     double dr[3];
     rodrigues_backward(pose + 3 * t, dR + 9 * t, dr);
+    if (a.gP) {                                           // full_pose = assembled theta + pose_mean
+      dr[0] = dr[0] + (double)a.gP[3 * t]; dr[1] = dr[1] + (double)a.gP[3 * t + 1]; dr[2] = dr[2] + (double)a.gP[3 * t + 2];
+    }
     dpose[3 * t] = dr[0]; dpose[3 * t + 1] = dr[1]; dpose[3 * t + 2] = dr[2];
   }
   __syncthreads();
@@ -410,6 +458,78 @@ __global__ __launch_bounds__(kBlock) void smplx_gather_kernel(const float* __res
     acc = acc + (double)w[3 * e + i] * x;
   }
   out[q] = (float)(acc + tr);
+}
+
+// ---- the full backward's own passes ----
+constexpr int kMaxE = 4096;       // extra joints whose gradient is scattered back
+constexpr int kEffChunk = 768;    // table entries in LDS per pass
+
+// The effective vertex gradient: g_eff[v] = g[v] (zeros without g) + the sum over the table entries (e, i) with index v, in ascending
+// (e, i), of w[e,i] gJ_extra[e].  Written as a gather -- every vertex scans the whole table from LDS -- so repeated indices (a vertex
+// pick is (i, i, i), landmark faces share vertices) add in the table's order without atomics; an index outside [0, V) matches nothing.
+__global__ __launch_bounds__(kBlock) void smplx_effective_grad_kernel(const float* __restrict__ g, const float* __restrict__ gJ_extra,
+                                                                     const int32_t* __restrict__ idx, const float* __restrict__ w, int V, int E,
+                                                                     double* __restrict__ g_eff) {
+  __shared__ int32_t li[kEffChunk];
+  __shared__ double lw[3 * kEffChunk];
+  const int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  D3 acc = {0.0, 0.0, 0.0};
+  if (g && v < V) acc = load3(g, v);
+  for (int n0 = 0; n0 < 3 * E; n0 += kEffChunk) {
+    const int m = min(kEffChunk, 3 * E - n0);
+    __syncthreads();
+    for (int q = threadIdx.x; q < m; q += kBlock) {
+      const int k = n0 + q;
+      const D3 c = load3(gJ_extra, k / 3) * (double)w[k];
+      li[q] = idx[k];
+      lw[3 * q] = c.x; lw[3 * q + 1] = c.y; lw[3 * q + 2] = c.z;
+    }
+    __syncthreads();
+    if (v < V)
+      for (int q = 0; q < m; ++q)
+        if (li[q] == (int32_t)v) acc = acc + D3{lw[3 * q], lw[3 * q + 1], lw[3 * q + 2]};
+  }
+  if (v < V) { g_eff[3 * v] = acc.x; g_eff[3 * v + 1] = acc.y; g_eff[3 * v + 2] = acc.z; }
+}
+
+// kBlock rows i = 3 v + c of the [3V] axis per workgroup.  dL/dv_shaped[i] = gvp[i] + sum_j J_regressor[j, v] dJ[j][c] (j ascending)
+// stays in LDS; then one thread per coefficient l sums shapedirs[i, l] dv_shaped[i] over the workgroup's rows in ascending order
+// (threads along l read the [3V, NB] table contiguously) into part[workgroup][l].
+__global__ __launch_bounds__(kBlock) void smplx_shape_bwd_kernel(const float* __restrict__ shapedirs, const float* __restrict__ J_regressor,
+                                                                const double* __restrict__ gvp, const double* __restrict__ dJ, int V, int J, int NB,
+                                                                double* __restrict__ part) {
+  __shared__ double dJl[3 * kMaxJ], dv[kBlock];
+  const int t = threadIdx.x;
+  const int64_t n3 = 3 * (int64_t)V, i0 = (int64_t)blockIdx.x * kBlock, i = i0 + t;
+  for (int q = t; q < 3 * J; q += kBlock) dJl[q] = dJ[q];
+  __syncthreads();
+  double x = 0.0;
+  if (i < n3) {
+    const int64_t v = i / 3;
+    const int c = (int)(i % 3);
+    double reg = 0.0;
+    for (int j = 0; j < J; ++j) reg = reg + (double)J_regressor[(int64_t)j * V + v] * dJl[3 * j + c];
+    x = gvp[i] + reg;
+  }
+  dv[t] = x;
+  __syncthreads();
+  const int rows = (int)min((int64_t)kBlock, n3 - i0);
+  for (int l = t; l < NB; l += kBlock) {
+    const float* col = shapedirs + i0 * NB + l;
+    double acc = 0.0;
+#pragma unroll 8
+    for (int r = 0; r < rows; ++r) acc = acc + (double)col[(int64_t)r * NB] * dv[r];
+    part[(int64_t)blockIdx.x * NB + l] = acc;
+  }
+}
+
+// dL/dcoefficient_l: the workgroups' shares in ascending order
+__global__ __launch_bounds__(kBlock) void smplx_coef_sum_kernel(const double* __restrict__ part, int nblk, int NB, float* __restrict__ out) {
+  const int l = blockIdx.x * kBlock + threadIdx.x;
+  if (l >= NB) return;
+  double acc = 0.0;
+  for (int b = 0; b < nblk; ++b) acc = acc + part[(int64_t)b * NB + l];
+  out[l] = (float)acc;
 }
 
 struct Layout {
@@ -447,6 +567,26 @@ constexpr int kMaxV = 1 << 24;
 constexpr int kMaxNB = 1024;
 
 bool sizes_ok(int V, int J) { return V >= 1 && V <= kMaxV && J >= 1 && J <= kMaxJ; }
+
+// the full backward's workspace: what the backward needs of the one above (at offsets of its own), then its additions
+struct GradLayout {
+  size_t gvp, dA_part, dfeat, g_eff, dJ, coef_part, total;
+};
+
+GradLayout grad_layout(int V, int J, int NB) {
+  const Layout L = layout(V, J);
+  GradLayout G = {};
+  const size_t n3 = (size_t)3 * V, d = sizeof(double);
+  Carve ws;
+  G.gvp = ws.take(n3 * d);
+  G.dA_part = ws.take((size_t)L.nblk * (12 * J + 3) * d);
+  G.dfeat = ws.take((size_t)(L.P > 0 ? L.P : 1) * d);
+  G.g_eff = ws.take(n3 * d);
+  G.dJ = ws.take((size_t)3 * J * d);
+  G.coef_part = ws.take((size_t)L.nb3 * (NB > 0 ? NB : 1) * d);
+  G.total = ws.at;
+  return G;
+}
 
 int check_common(const char* who, int V, int J, int hand_dim, int n_pca, const int32_t* parents, Tree& tree) {
   if (!sizes_ok(V, J)) return fail(COMA_E_INVALID, "%s: V=%d must lie in [1, %d] and J=%d in [1, %d]", who, V, kMaxV, J, kMaxJ);
@@ -519,35 +659,117 @@ extern "C" int coma_smplx_forward_f32(const float* theta, const float* transl, c
   return check_launch(who);
 }
 
-extern "C" int coma_smplx_backward_f32(const float* grad_vertices, const float* posedirs, const float* weights, const int32_t* parents,
-                                       const float* hand_components, int V, int J, int hand_dim, int n_pca, const void* shape_state,
-                                       const void* saved, size_t saved_bytes, float* grad_theta, float* grad_transl, void* workspace,
-                                       size_t workspace_bytes, void* stream) {
-  const char* who = "coma_smplx_backward_f32";
-  if (!grad_vertices || !posedirs || !weights || !parents || !shape_state || !saved || !grad_theta || !grad_transl || !workspace)
+namespace coma {
+namespace {
+
+// what coma_smplx_backward_full_f32 adds to coma_smplx_backward_f32; every pointer may be null
+struct FullBwd {
+  const float* grad_joints;
+  const float* grad_full_pose;
+  const int32_t* extra_index;
+  const float* extra_weight;
+  int E;
+  const float* shapedirs;
+  const float* J_regressor;
+  int NB;
+  float* grad_coefficients;
+};
+
+// Both backward entry points: `full` null is the vertices-only backward on the forward's workspace layout (its launches and bits are
+// those of the first release); otherwise the full backward on its own layout.
+int backward_impl(const char* who, const float* grad_vertices, const float* posedirs, const float* weights, const int32_t* parents,
+                  const float* hand_components, int V, int J, int hand_dim, int n_pca, const void* shape_state, const void* saved,
+                  size_t saved_bytes, float* grad_theta, float* grad_transl, void* workspace, size_t workspace_bytes, void* stream,
+                  const FullBwd* full) {
+  if ((!full && !grad_vertices) || !posedirs || !weights || !parents || !shape_state || !saved || !grad_theta || !grad_transl || !workspace)
     return fail(COMA_E_INVALID, "%s: null pointer", who);
   if (n_pca > 0 && hand_dim > 0 && !hand_components) return fail(COMA_E_INVALID, "%s: null pointer (hand_components with n_pca > 0)", who);
   PoseBwdArgs pb = {};
   if (int rc = check_common(who, V, J, hand_dim, n_pca, parents, pb.tree)) return rc;
   const Layout L = layout(V, J);
+  size_t o_gvp = L.gvp, o_dA = L.dA_part, o_dfeat = L.dfeat, need = L.total;
+  GradLayout GL = {};
+  bool scatter = false, want_coef = false;
+  if (full) {
+    if (full->E < 0 || full->E > kMaxE) return fail(COMA_E_INVALID, "%s: E=%d outside [0, %d]", who, full->E, kMaxE);
+    scatter = full->grad_joints && full->E > 0;
+    if (scatter && (!full->extra_index || !full->extra_weight))
+      return fail(COMA_E_INVALID, "%s: null pointer (the extra-joint tables with grad_joints and E > 0)", who);
+    want_coef = full->grad_coefficients != nullptr;
+    if (full->NB < (want_coef ? 1 : 0) || full->NB > kMaxNB) return fail(COMA_E_INVALID, "%s: NB=%d outside [%d, %d]", who, full->NB, want_coef ? 1 : 0, kMaxNB);
+    if (want_coef && !full->shapedirs) return fail(COMA_E_INVALID, "%s: null pointer (shapedirs with grad_coefficients)", who);
+    if (want_coef && !full->J_regressor) return fail(COMA_E_INVALID, "%s: null pointer (J_regressor with grad_coefficients)", who);
+    GL = grad_layout(V, J, full->NB);
+    o_gvp = GL.gvp; o_dA = GL.dA_part; o_dfeat = GL.dfeat; need = GL.total;
+  }
   if (int rc = check_buffer(who, "saved state", saved, saved_bytes, L.saved_total)) return rc;
-  if (int rc = check_buffer(who, "workspace", workspace, workspace_bytes, L.total)) return rc;
+  if (int rc = check_buffer(who, "workspace", workspace, workspace_bytes, need)) return rc;
   if (((uintptr_t)shape_state & 15) != 0) return fail(COMA_E_INVALID, "%s: shape state must be 16-byte aligned", who);
   const char* st = (const char*)shape_state;
   const char* sv = (const char*)saved;
   char* ws = (char*)workspace;
   hipStream_t s = (hipStream_t)stream;
-  SkinBwdArgs sb = {};
-  sb.weights = weights; sb.A = (const double*)(sv + L.s_A); sb.v_posed = (const double*)(sv + L.s_vposed); sb.grad = grad_vertices;
-  sb.V = V; sb.J = J; sb.gvp = (double*)(ws + L.gvp); sb.dA_part = (double*)(ws + L.dA_part);
-  hipLaunchKernelGGL(smplx_skin_bwd_kernel, dim3(L.nblk), dim3(kTile), 0, s, sb);
+  double* gvp = (double*)(ws + o_gvp);
+  double* dA_part = (double*)(ws + o_dA);
+  if (scatter || !grad_vertices) {                          // only then does the gradient at the vertices differ from the caller's
+    double* g_eff = (double*)(ws + GL.g_eff);
+    const int E = scatter ? full->E : 0;
+    hipLaunchKernelGGL(smplx_effective_grad_kernel, dim3((V + kBlock - 1) / kBlock), dim3(kBlock), 0, s, grad_vertices,
+                       scatter ? full->grad_joints + 3 * (size_t)J : nullptr, full->extra_index, full->extra_weight, V, E, g_eff);
+    SkinBwdArgs<double> sb = {};
+    sb.weights = weights; sb.A = (const double*)(sv + L.s_A); sb.v_posed = (const double*)(sv + L.s_vposed); sb.grad = g_eff;
+    sb.V = V; sb.J = J; sb.gvp = gvp; sb.dA_part = dA_part;
+    hipLaunchKernelGGL(smplx_skin_bwd_kernel<double>, dim3(L.nblk), dim3(kTile), 0, s, sb);
+  } else {
+    SkinBwdArgs<float> sb = {};
+    sb.weights = weights; sb.A = (const double*)(sv + L.s_A); sb.v_posed = (const double*)(sv + L.s_vposed); sb.grad = grad_vertices;
+    sb.V = V; sb.J = J; sb.gvp = gvp; sb.dA_part = dA_part;
+    hipLaunchKernelGGL(smplx_skin_bwd_kernel<float>, dim3(L.nblk), dim3(kTile), 0, s, sb);
+  }
   if (L.P > 0)
-    hipLaunchKernelGGL(smplx_feature_bwd_kernel, dim3(L.P), dim3(kBlock), 0, s, posedirs, (const double*)(ws + L.gvp), 3 * V, (double*)(ws + L.dfeat));
+    hipLaunchKernelGGL(smplx_feature_bwd_kernel, dim3(L.P), dim3(kBlock), 0, s, posedirs, (const double*)gvp, 3 * V, (double*)(ws + o_dfeat));
   pb.s_pose = (const double*)(sv + L.s_pose); pb.j_rest = (const double*)(st + L.j_rest); pb.comps = hand_components;
-  pb.dA_part = sb.dA_part; pb.dfeat = (const double*)(ws + L.dfeat); pb.J = J; pb.hd = hand_dim; pb.n_pca = n_pca; pb.nblk = L.nblk;
+  pb.dA_part = dA_part; pb.dfeat = (const double*)(ws + o_dfeat); pb.J = J; pb.hd = hand_dim; pb.n_pca = n_pca; pb.nblk = L.nblk;
   pb.grad_theta = grad_theta; pb.grad_transl = grad_transl;
+  if (full) {
+    pb.gJ = full->grad_joints; pb.gP = full->grad_full_pose; pb.extra_w = full->extra_weight; pb.E = scatter ? full->E : 0;
+    pb.dJ_out = want_coef ? (double*)(ws + GL.dJ) : nullptr;
+  }
   hipLaunchKernelGGL(smplx_pose_bwd_kernel, dim3(1), dim3(kBlock), 0, s, pb);
+  if (want_coef) {
+    double* part = (double*)(ws + GL.coef_part);
+    hipLaunchKernelGGL(smplx_shape_bwd_kernel, dim3(L.nb3), dim3(kBlock), 0, s, full->shapedirs, full->J_regressor, (const double*)gvp,
+                       (const double*)(ws + GL.dJ), V, J, full->NB, part);
+    hipLaunchKernelGGL(smplx_coef_sum_kernel, dim3((full->NB + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (const double*)part, L.nb3, full->NB,
+                       full->grad_coefficients);
+  }
   return check_launch(who);
+}
+
+}  // namespace
+}  // namespace coma
+
+extern "C" int coma_smplx_backward_f32(const float* grad_vertices, const float* posedirs, const float* weights, const int32_t* parents,
+                                       const float* hand_components, int V, int J, int hand_dim, int n_pca, const void* shape_state,
+                                       const void* saved, size_t saved_bytes, float* grad_theta, float* grad_transl, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+  return backward_impl("coma_smplx_backward_f32", grad_vertices, posedirs, weights, parents, hand_components, V, J, hand_dim, n_pca, shape_state,
+                       saved, saved_bytes, grad_theta, grad_transl, workspace, workspace_bytes, stream, nullptr);
+}
+
+extern "C" size_t coma_smplx_grad_workspace_bytes(int V, int J, int NB) {
+  return sizes_ok(V, J) && NB >= 0 && NB <= kMaxNB ? grad_layout(V, J, NB).total : 0;
+}
+
+extern "C" int coma_smplx_backward_full_f32(const float* grad_vertices, const float* grad_joints, const float* grad_full_pose,
+                                            const float* posedirs, const float* weights, const int32_t* parents, const float* hand_components,
+                                            const int32_t* extra_index, const float* extra_weight, int E, const float* shapedirs,
+                                            const float* J_regressor, int NB, int V, int J, int hand_dim, int n_pca, const void* shape_state,
+                                            const void* saved, size_t saved_bytes, float* grad_theta, float* grad_transl,
+                                            float* grad_coefficients, void* workspace, size_t workspace_bytes, void* stream) {
+  const FullBwd full = {grad_joints, grad_full_pose, extra_index, extra_weight, E, shapedirs, J_regressor, NB, grad_coefficients};
+  return backward_impl("coma_smplx_backward_full_f32", grad_vertices, posedirs, weights, parents, hand_components, V, J, hand_dim, n_pca,
+                       shape_state, saved, saved_bytes, grad_theta, grad_transl, workspace, workspace_bytes, stream, &full);
 }
 
 extern "C" int coma_smplx_extra_joints_f32(const float* vertices, const float* transl, const int32_t* vertex_index, const float* vertex_weight,

@@ -491,14 +491,37 @@ int coma_app_objective_f32(const float* verts, const int32_t* faces, const int32
  *                  f32 [V,J], j ascending), vertex = T [v_posed, 1] (+ transl).
  *   backward       from g = dL/dvertices f32 [V,3]: dL/dtransl = sum_v g_v; dL/dA_j = sum_v weights[v,j] g_v (x) [v_posed, 1];
  *                  g_vposed = T.R^T g_v; dL/dfeature_p = <posedirs[p, :], g_vposed>; the chain in descending i; the derivative of
- *                  the Rodrigues formula with the 1e-8 inside the norm; the hand components transposed.  NO gradient with respect
- *                  to betas, expression, or through the joints output.  Sums over vertices: per workgroup of 128 vertices in
+ *                  the Rodrigues formula with the 1e-8 inside the norm; the hand components transposed.  coma_smplx_backward_f32 gives
+ *                  NO gradient with respect to betas, expression, or through the joints output (coma_smplx_backward_full_f32
+ *                  does: `full backward` below).  Sums over vertices: per workgroup of 128 vertices in
  *                  ascending order, then over the workgroups in ascending order; the P dot products as 256 strided partial sums and
  *                  a tree lds[t] + lds[t + h], h = 128 ... 1.  No floating-point atomics: two calls give the same bits.
  *   extra joints   out_e = sum_{i<3} vertex_weight[e,i] (vertex[vertex_index[e,i]] - transl) + transl: a vertex pick is index
  *                  (i, i, i) with weights (1, 0, 0), a static landmark a face's three vertices with its barycentric weights.  The
- *                  caller lays the result behind the J posed joints: [J | vertex picks | landmarks].  No gradient.
- *   precision      inputs and outputs are f32; every stage is evaluated in f64 (the work is bandwidth- and latency-bound), so the
+ *                  caller lays the result behind the J posed joints: [J | vertex picks | landmarks].  No gradient of its own: the
+ *                  full backward takes the table and scatters.
+ *   full backward  coma_smplx_backward_full_f32: from g = dL/dvertices [V,3], gJ = dL/djoints [J + E, 3] (posed joints first, then
+ *                  the extra joints as the forward lays them out) and gP = dL/dfull_pose [3J], each of which may be NULL = zeros, to
+ *                  dL/dtheta, dL/dtransl and dL/dcoefficients f32 [NB] (betas followed by expression).
+ *                  extra joints: the effective vertex gradient g_eff[v] = g[v] + sum of w[e,i] gJ[J + e] over the table entries with
+ *                    vertex_index[e,i] = v, added in ascending (e, i) (a gather per vertex over the whole table: repeated indices --
+ *                    a vertex pick, landmark faces sharing a vertex -- need no atomics; an index outside [0, V) matches nothing);
+ *                    g_eff takes g's place in every rule of `backward`; dL/dtransl += (1 - ((w[e,0] + w[e,1]) + w[e,2])) gJ[J + e],
+ *                    e ascending.
+ *                  posed joints: joints_i = G_i.t + transl, so dG_i.t += gJ[i] before the descending chain walk and dL/dtransl +=
+ *                    sum_i gJ[i], i ascending; dL/dtransl = (vertex share + posed-joint share) + extra-joint share.
+ *                  full pose: full_pose = assembled theta + pose_mean, so dpose += gP after the Rodrigues derivative and before the
+ *                    transposed hand components.
+ *                  rest joints: from A_i.t = G_i.t - G_i.R J_i, dJ_i = -G_i.R^T dA_i.t; in the chain walk, from G_i.t = G_p.R (J_i -
+ *                    J_p) + G_p.t with u = G_p.R^T dG_i.t (dG_i.t complete: every child has a larger index), dJ_i += u and dJ_p -= u;
+ *                    at the root dJ_0 += dG_0.t.
+ *                  shape: dL/dv_shaped[v] = g_vposed[v] (of g_eff) + sum_j J_regressor[j,v] dJ_j, j ascending; dL/dcoefficient_l =
+ *                    sum_{i < 3V} shapedirs[i,l] dL/dv_shaped[i]: per workgroup of 256 rows i in ascending order, then over the
+ *                    workgroups in ascending order.
+ *                  With grad_joints, grad_full_pose and grad_coefficients all NULL, grad_theta and grad_transl are the bits of
+ *                  coma_smplx_backward_f32.  All in f64 on the f32 data; two calls give the same bits.  The 3 launches of the
+ *                  backward, plus 1 when gJ reaches extra joints or g is NULL (the effective gradient), plus 2 for the coefficients.
+ *   precision     inputs and outputs are f32; every stage is evaluated in f64 (the work is bandwidth- and latency-bound), so the
  *                  outputs are the f32 rounding of the rule set.
  * All pointers are device pointers except `parents` (HOST, i32 [J], read during the call; parents[0] is ignored, parents[i] must lie
  * in [0, i) for i > 0).  shape_state / saved / workspace: coma_smplx_{shape_state,saved,workspace}_bytes(V, J) bytes, 16-byte aligned
@@ -507,7 +530,15 @@ int coma_app_objective_f32(const float* verts, const int32_t* faces, const int32
  * f32 [NT], grad_transl f32 [3], transl f32 [3] (may be NULL).  Refused before any launch: a null pointer, V outside [1, 2^24], J
  * outside [1, 64], NB outside [1, 1024], n_pca outside [0, 64], hand_dim not a multiple of 3 or 2 hand_dim > 3 (J - 1), a bad parent, a
  * buffer too small or misaligned.  A vertex_index outside [0, V) is not followed and gives NaN.  Forward: 3 launches, backward: 3,
- * shape: 2, extra joints: 1; caller's stream, no allocation, no host synchronisation. */
+ * shape: 2, extra joints: 1; caller's stream, no allocation, no host synchronisation.
+ * coma_smplx_backward_full_f32 takes what the backward takes plus grad_joints f32 [J + E, 3], grad_full_pose f32 [3J], the extra-joint
+ * table (vertex_index i32 [E,3], vertex_weight f32 [E,3]; read only with grad_joints and E > 0), shapedirs, J_regressor, NB and
+ * grad_coefficients f32 [NB] (the last three pointers read only when grad_coefficients is given).  grad_vertices, grad_joints,
+ * grad_full_pose and grad_coefficients may each be NULL: a NULL input contributes nothing, a NULL output is not computed.  Its workspace
+ * is its own: coma_smplx_grad_workspace_bytes(V, J, NB) bytes (0 for V, J the calls refuse or NB outside [0, 1024]).  Refused as well:
+ * E outside [0, 4096], a NULL table with grad_joints and E > 0, with grad_coefficients NB outside [1, 1024] or a NULL shapedirs or
+ * J_regressor (without it NB outside [0, 1024]).  Up to 6 launches (see `full backward`).  Still not built on top of it: COAP's own
+ * backward, so src/application/optimize.py --use_collision stays refused. */
 size_t coma_smplx_workspace_bytes(int V, int J);
 size_t coma_smplx_shape_state_bytes(int V, int J);
 size_t coma_smplx_saved_bytes(int V, int J);
@@ -521,6 +552,13 @@ int coma_smplx_backward_f32(const float* grad_vertices, const float* posedirs, c
                             const float* hand_components, int V, int J, int hand_dim, int n_pca, const void* shape_state,
                             const void* saved, size_t saved_bytes, float* grad_theta, float* grad_transl, void* workspace,
                             size_t workspace_bytes, void* stream);
+size_t coma_smplx_grad_workspace_bytes(int V, int J, int NB);
+int coma_smplx_backward_full_f32(const float* grad_vertices, const float* grad_joints, const float* grad_full_pose, const float* posedirs,
+                                 const float* weights, const int32_t* parents, const float* hand_components, const int32_t* extra_index,
+                                 const float* extra_weight, int E, const float* shapedirs, const float* J_regressor, int NB, int V, int J,
+                                 int hand_dim, int n_pca, const void* shape_state, const void* saved, size_t saved_bytes,
+                                 float* grad_theta, float* grad_transl, float* grad_coefficients, void* workspace, size_t workspace_bytes,
+                                 void* stream);
 int coma_smplx_extra_joints_f32(const float* vertices, const float* transl, const int32_t* vertex_index, const float* vertex_weight, int V,
                                 int E, float* out, void* stream);
 

@@ -58,6 +58,38 @@ def smplx():
         emit(f"smplx.{name}.grad_transl", kw["transl"].grad)
 
 
+def smplx_full():
+    """The full backward (differentiable joints, full_pose and shape): the loss over all three outputs with two vertex picks and the
+    landmarks carrying gradient, on the same cases; digests of the gradients to the pose, transl and the coefficients."""
+    import torch
+    from coma_amd.body_model import DeviceSMPLX
+    from tests import smplx_grad_ref as GR
+    from tests import smplx_ref as S
+    t = lambda x, shape: torch.as_tensor(np.asarray(x, dtype=np.float32)).reshape(shape).to(DEV)
+    for name in ("moderate", "no_pca", "tiny_model", "smpl_like"):
+        model, fm = S.case_model(name)
+        inp = S.case_inputs(name)
+        gJ, gP = GR.case_upstream(name)
+        body = DeviceSMPLX(model, n_pca=max(fm["n_pca"], 1), use_pca=bool(fm["n_pca"]), device=DEV, extra_joint_vertex_ids=[0, fm["V"] - 1],
+                           differentiable=("joints", "full_pose", "shape"))
+        kw, at = {}, 0
+        for key, n in zip(POSE_KEYS, (3, body.num_body, 3, 3, 3, body.hand_size, body.hand_size)):
+            kw[key] = t(inp["theta"][at:at + n], (1, n)).requires_grad_(True)
+            at += n
+        kw["transl"] = t(inp["transl"], (1, 3)).requires_grad_(True)
+        kw["betas"] = t(inp["coefficients"][:body.num_betas], (1, -1)).requires_grad_(True)
+        kw["expression"] = t(inp["coefficients"][body.num_betas:], (1, -1)).requires_grad_(True) if body.num_expression_coeffs else None
+        out = body(**kw, return_verts=True, return_full_pose=True)
+        gE = np.random.RandomState(5).normal(size=(body.num_extra, 3))           # the extra joints' upstream gradient
+        ((out.vertices[0] * t(inp["g"], (-1, 3))).sum() + (out.joints[0] * t(np.concatenate([gJ, gE]), (-1, 3))).sum()
+         + (out.full_pose[0] * t(gP, (-1,))).sum()).backward()
+        emit(f"smplx_full.{name}.grad_theta", torch.cat([kw[k].grad.reshape(-1) for k in POSE_KEYS]))
+        emit(f"smplx_full.{name}.grad_transl", kw["transl"].grad)
+        emit(f"smplx_full.{name}.grad_betas", kw["betas"].grad)
+        if kw["expression"] is not None:
+            emit(f"smplx_full.{name}.grad_expression", kw["expression"].grad)
+
+
 def vposer():
     """Decode, decode-backward, encode at N = 1 and N = 3 (and the odd sizes H = 80, D = 7, NJ = 5); the angle prior and its backward."""
     import torch
@@ -179,7 +211,7 @@ def main():
     from coma_amd import _lib
     assert torch.cuda.is_available(), "the digests are of device results"
     print(f"# library: {_lib.LIB_PATH}", file=sys.stderr)
-    for part in (smplx, vposer, app_objective, volumes_and_depth, row_reductions):
+    for part in (smplx, smplx_full, vposer, app_objective, volumes_and_depth, row_reductions):
         part()
     torch.cuda.synchronize()
 
