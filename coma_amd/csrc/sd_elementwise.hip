@@ -13,6 +13,10 @@ namespace sd {
 using coma::check_launch;
 using coma::fail;
 
+// A 1-D launch of 256-thread blocks over n elements: gridDim.x holds at most 2^31 - 1 blocks.
+constexpr long long kMaxBlocks = 2147483647LL;
+constexpr long long kMaxElems = kMaxBlocks * 256;
+
 // one thread per (b, pixel)
 __global__ void cfg_ddim_kernel(const _Float16* __restrict__ eps_uc, int eps_ld, float* __restrict__ latents,
                                 float* __restrict__ x0_out, const _Float16* __restrict__ mask,
@@ -109,9 +113,12 @@ extern "C" int sd_cfg_ddim_step(const void* eps_uc, int eps_ld, float* latents, 
   if (!latents) return fail(COMA_E_INVALID, "sd_cfg_ddim_step: null latents");
   if (unet_in && (!mask || !masked_latents)) return fail(COMA_E_INVALID, "sd_cfg_ddim_step: mask inputs missing");
   if (batch <= 0 || hw <= 0) return fail(COMA_E_INVALID, "sd_cfg_ddim_step: bad sizes");
-  if (eps_uc && (!(alpha_t > 0.f) || alpha_t > 1.f || alpha_prev < 0.f || alpha_prev > 1.f))
+  if (eps_uc && (!(alpha_t > 0.f) || alpha_t > 1.f || !(alpha_prev >= 0.f) || alpha_prev > 1.f))
     return fail(COMA_E_INVALID, "sd_cfg_ddim_step: alphas out of range");
+  if (eps_uc && eps_ld < 4) return fail(COMA_E_INVALID, "sd_cfg_ddim_step: eps_ld = %d is below the 4 channels of a pixel", eps_ld);
+  if (((uintptr_t)unet_in) & 15) return fail(COMA_E_INVALID, "sd_cfg_ddim_step: unet_in must be 16-byte aligned");
   long long n = (long long)batch * hw;
+  if (n > kMaxElems) return fail(COMA_E_INVALID, "sd_cfg_ddim_step: batch * hw = %lld exceeds the grid limit of %lld blocks", n, kMaxBlocks);
   hipLaunchKernelGGL(cfg_ddim_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      (const _Float16*)eps_uc, eps_ld, latents, x0_out, (const _Float16*)mask, (const _Float16*)masked_latents,
                      (_Float16*)unet_in, batch, hw, guidance, sqrtf(alpha_t), sqrtf(1.0f - alpha_t), sqrtf(alpha_prev),
@@ -122,6 +129,8 @@ extern "C" int sd_cfg_ddim_step(const void* eps_uc, int eps_ld, float* latents, 
 extern "C" int sd_timestep_embedding_f16(const float* timesteps, int batch, int dim, void* out, void* stream) {
   if (sd::plan_recording()) return sd::record<sd::PK_TEMB>(timesteps, batch, dim, out);
   if (!timesteps || !out || batch <= 0 || dim <= 0 || dim % 2) return fail(COMA_E_INVALID, "sd_timestep_embedding_f16: bad args");
+  if ((long long)batch * dim > 2147483647LL)
+    return fail(COMA_E_INVALID, "sd_timestep_embedding_f16: batch * dim = %lld exceeds the int32 limit 2147483647", (long long)batch * dim);
   hipLaunchKernelGGL(timestep_embedding_kernel, dim3((batch * dim + 255) / 256), dim3(256), 0, (hipStream_t)stream, timesteps,
                      batch, dim, (_Float16*)out);
   return check_launch("timestep_embedding_kernel");
@@ -129,6 +138,9 @@ extern "C" int sd_timestep_embedding_f16(const float* timesteps, int batch, int 
 
 extern "C" int sd_nchw_to_nhwc_f16(const float* x, int batch, int c, int hw, int cpad, void* out, void* stream) {
   if (!x || !out || batch <= 0 || c <= 0 || hw <= 0 || cpad < c) return fail(COMA_E_INVALID, "sd_nchw_to_nhwc_f16: bad args");
+  if ((long long)batch * hw > kMaxElems / cpad)
+    return fail(COMA_E_INVALID, "sd_nchw_to_nhwc_f16: batch * hw * cpad = %lld * %d exceeds the grid limit of %lld blocks", (long long)batch * hw, cpad,
+                kMaxBlocks);
   long long n = (long long)batch * hw * cpad;
   hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, batch, c, hw,
                      cpad, (_Float16*)out);
@@ -137,6 +149,9 @@ extern "C" int sd_nchw_to_nhwc_f16(const float* x, int batch, int c, int hw, int
 
 extern "C" int sd_nhwc_to_nchw_f32(const void* x, int batch, int c, int hw, int ld, float* out, void* stream) {
   if (!x || !out || batch <= 0 || c <= 0 || hw <= 0 || ld < c) return fail(COMA_E_INVALID, "sd_nhwc_to_nchw_f32: bad args");
+  if ((long long)batch * hw > kMaxElems / c)
+    return fail(COMA_E_INVALID, "sd_nhwc_to_nchw_f32: batch * hw * c = %lld * %d exceeds the grid limit of %lld blocks", (long long)batch * hw, c,
+                kMaxBlocks);
   long long n = (long long)batch * hw * c;
   hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      (const _Float16*)x, batch, c, hw, ld, out);
@@ -146,6 +161,8 @@ extern "C" int sd_nhwc_to_nchw_f32(const void* x, int batch, int c, int hw, int 
 extern "C" int sd_image_to_u8(const void* x, int batch, int hw, int ld, int round_mode, uint8_t* out, void* stream) {
   if (!x || !out || batch <= 0 || hw <= 0 || ld < 3) return fail(COMA_E_INVALID, "sd_image_to_u8: bad args");
   long long npix = (long long)batch * hw;
+  if (npix > kMaxElems / 3)
+    return fail(COMA_E_INVALID, "sd_image_to_u8: batch * hw * 3 = %lld * 3 exceeds the grid limit of %lld blocks", npix, kMaxBlocks);
   hipLaunchKernelGGL(image_to_u8_kernel, dim3((unsigned)((npix * 3 + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      (const _Float16*)x, npix, ld, round_mode, out);
   return check_launch("image_to_u8_kernel");
@@ -167,7 +184,9 @@ __global__ void vae_sample_kernel(const _Float16* __restrict__ mom, int ld, cons
   int c = (int)(i & 3);
   float mean = (float)mom[p * ld + c];
   float logvar = fminf(fmaxf((float)mom[p * ld + 4 + c], -30.0f), 20.0f);
-  float v = (mean + __expf(0.5f * logvar) * (noise ? noise[i] : 0.0f)) * scale;
+  // expf, not __expf: the fast form rounds 0.5 logvar log2(e) (up to 14.4) before v_exp_f32, which at logvar = 20 alone costs up to
+  // 5.5 * 2^-24 of the result -- more than the whole formula otherwise loses (case vae-n257-ld16-both)
+  float v = (mean + expf(0.5f * logvar) * (noise ? noise[i] : 0.0f)) * scale;
   if (lat32) lat32[i] = v;
   if (lat16) lat16[i] = (_Float16)v;
 }
@@ -275,6 +294,8 @@ __global__ void mask_finish_kernel(const uint8_t* __restrict__ rowmax, const uin
 extern "C" int sd_vae_sample(const void* moments, int ld, const float* noise, float scale, int64_t npix, float* latents_f32,
                              void* latents_f16, void* stream) {
   if (!moments || npix <= 0 || ld < 8 || (!latents_f32 && !latents_f16)) return sd::fail(COMA_E_INVALID, "sd_vae_sample: bad args");
+  if (npix > sd::kMaxElems / 4)
+    return sd::fail(COMA_E_INVALID, "sd_vae_sample: npix * 4 = %lld * 4 exceeds the grid limit of %lld blocks", (long long)npix, sd::kMaxBlocks);
   hipLaunchKernelGGL(sd::vae_sample_kernel, dim3((unsigned)((npix * 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      (const _Float16*)moments, ld, noise, scale, (long long)npix, latents_f32, (_Float16*)latents_f16);
   return sd::check_launch("vae_sample_kernel");
@@ -282,6 +303,7 @@ extern "C" int sd_vae_sample(const void* moments, int ld, const float* noise, fl
 
 extern "C" int sd_add_noise(const float* x0, const float* noise, float alpha, int64_t n, float* out, void* stream) {
   if (!x0 || !noise || !out || n <= 0 || !(alpha > 0.f) || alpha > 1.f) return sd::fail(COMA_E_INVALID, "sd_add_noise: bad args");
+  if (n > sd::kMaxElems) return sd::fail(COMA_E_INVALID, "sd_add_noise: n = %lld exceeds the grid limit of %lld blocks", (long long)n, sd::kMaxBlocks);
   hipLaunchKernelGGL(sd::add_noise_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x0, noise,
                      sqrtf(alpha), sqrtf(1.0f - alpha), (long long)n, out);
   return sd::check_launch("add_noise_kernel");
@@ -294,6 +316,10 @@ extern "C" int sd_mask_adapt(const uint8_t* seg, const uint8_t* default_mask, in
     return sd::fail(COMA_E_INVALID, "sd_mask_adapt: null pointer");
   if (H <= 0 || W <= 0 || (H & 7) || (W & 7) || dilate_iters < 0 || cpad < 3)
     return sd::fail(COMA_E_INVALID, "sd_mask_adapt: bad sizes");
+  // H is gridDim.y; the kernel indexes a pixel as the int y * W + x
+  if (H > 65535) return sd::fail(COMA_E_INVALID, "sd_mask_adapt: H = %d exceeds the grid limit 65535", H);
+  if ((long long)H * W > 2147483647LL)
+    return sd::fail(COMA_E_INVALID, "sd_mask_adapt: H * W = %lld exceeds the int32 limit 2147483647", (long long)H * W);
   hipLaunchKernelGGL(sd::mask_adapt_kernel, dim3((W + 127) / 128, H), dim3(128), 0, (hipStream_t)stream, seg, default_mask, H, W,
                      dilate_iters, use_default, image_nchw, cpad, mask_full, (_Float16*)mask_latent, (_Float16*)masked_image);
   return sd::check_launch("mask_adapt_kernel");
@@ -308,6 +334,10 @@ extern "C" int sd_mask_adapt_batched(const uint8_t* seg, const uint8_t* default_
   if (batch <= 0 || batch > 65535 || H <= 0 || H > 65535 || W <= 0 || W > 16384 || (H & 7) || (W & 7) || dilate_iters < 0 || cpad < 8 ||
       (cpad & 7))
     return sd::fail(COMA_E_INVALID, "sd_mask_adapt_batched: bad sizes (H, W multiples of 8; cpad a multiple of 8)");
+  // area[b] is an int32 sum of u8 values: the largest sum an image can reach has to fit
+  if ((long long)H * W * 255 > 2147483647LL)
+    return sd::fail(COMA_E_INVALID, "sd_mask_adapt_batched: H * W * 255 = %lld exceeds the int32 limit 2147483647 of the area sum", (long long)H * W * 255);
+  if (((uintptr_t)masked_image) & 15) return sd::fail(COMA_E_INVALID, "sd_mask_adapt_batched: masked_image must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(area, 0, sizeof(int32_t) * (size_t)batch, st) != hipSuccess)
     return sd::fail(COMA_E_LAUNCH, "sd_mask_adapt_batched: memset failed");

@@ -162,7 +162,8 @@ int sd_attention_wide_f16(const void* q, const void* k, const void* vt, void* ou
 
 /* Token + position embedding of the CLIP text tower: out fp16 [seqs * len, width], row s * len + p = tok_emb[ids[s, p]] + pos_emb[p]
  * (summed in fp32, rounded once).  ids int32 [seqs, len]; tok_emb fp16 [vocab, width]; pos_emb fp16 [n_pos, width] (n_pos >= len);
- * width % 8 == 0, tables and output 16-byte aligned.  Ids out of [0, vocab): the KERNEL clamps every id into [0, vocab), so a bad id
+ * width % 8 == 0, tables and output 16-byte aligned; rows of pos_emb at and beyond len are never read (row s * len + p reads
+ * pos_emb[p], p < len), seqs * len <= 2^31 - 1.  Ids out of [0, vocab): the KERNEL clamps every id into [0, vocab), so a bad id
  * can never read outside the table; the Python host (coma_amd/sd/text.py) rejects such ids before they reach the device.
  * replaces: CLIPTextEmbeddings (token_embedding + position_embedding) inside transformers' CLIPTextModel,
  *           utils/adaptive_mask_inpainting.py:459-482. */
@@ -175,6 +176,8 @@ int sd_text_embed_f16(const int32_t* ids, int seqs, int len, const void* tok_emb
  * blocks of ONE fused q|k|v product, each with its own leading dimension; V is NOT transposed.  d = 64, 1 <= len <= 128, ld* >= heads*d,
  * ldq / ldk / ldv multiples of 8, q / k / v 16-byte aligned.  One workgroup per (sequence, head), K and V staged in LDS, fp32 scores and
  * an exact masked softmax over the whole row, fp16 output; keys after i are never read (the result at i does not depend on them).
+ * out needs 2-byte alignment only and any ldo >= heads * d; columns heads * d .. ld* - 1 of q / k / v are never read, those of out never
+ * written.  seqs, heads <= 65535.
  * A separate kernel from sd_attention_f16 (the UNet's).  replaces: CLIPAttention with the causal mask inside CLIPTextModel. */
 int sd_attention_causal_f16(const void* q, const void* k, const void* v, void* out, int seqs, int heads, int len, int d, int ldq, int ldk,
                             int ldv, int ldo, float scale, void* stream);
@@ -344,36 +347,56 @@ int sd_softmax_f16(void* x, int64_t rows, int n, int ld, float scale, void* stre
  * latents: fp32 [B, hw, 4] in/out;  x0_out: fp32 [B, hw, 4] or NULL (pred_original_sample)
  * mask: fp16 [B, hw] ; masked_latents fp16 [B, hw, 4]
  * unet_in: fp16 NHWC [2B, hw, 64]: channels [latents(4) | mask(1) | masked_latents(4) | zero pad] for both halves.
+ * Argument modes: eps_uc NULL = assembly only (latents are read, neither latents nor x0_out is written; the alphas are not looked at);
+ *   unet_in NULL = step only (mask / masked_latents may be NULL); x0_out NULL = not stored.  write_latents = 0 leaves `latents` as it
+ *   was, while channels 0 .. 3 of unet_in carry the NEW x_prev (the fp16 rounding of the fp32 value write_latents = 1 would store).
+ *   mask and masked_latents are copied bit for bit (signed zeros and subnormals included); channels 9 .. 63 are +0 and the two halves
+ *   of unet_in are identical.
+ * Accepted (anything else is COMA_E_INVALID before a launch): batch, hw > 0, batch * hw <= (2^31 - 1) * 256 (the grid limit); with
+ *   eps_uc: eps_ld >= 4 (channels 4 .. eps_ld - 1 are never read), 0 < alpha_t <= 1, 0 <= alpha_prev <= 1; unet_in 16-byte aligned
+ *   (a pixel leaves as eight 16-byte stores); latents / x0_out 4-byte, the fp16 inputs 2-byte.
  * replaces: utils/adaptive_mask_inpainting.py:990-996 (input assembly), :1010-1012 (CFG), :1015-1017 (DDIM step). */
 int sd_cfg_ddim_step(const void* eps_uc, int eps_ld, float* latents, float* x0_out, const void* mask,
                      const void* masked_latents, void* unet_in, int batch, int hw, float guidance, float alpha_t,
                      float alpha_prev, int write_latents, void* stream);
 
-/* Sinusoidal timestep embedding (flip_sin_to_cos, shift 0) -> fp16 [batch, dim]. */
+/* Sinusoidal timestep embedding (flip_sin_to_cos, shift 0) -> fp16 [batch, dim] = [cos(t f_k), k < dim / 2 | sin(t f_k)],
+ * f_k = exp(-ln(10000) k / (dim / 2)), evaluated in fp32 and rounded once.  dim > 0 and even, batch > 0, batch * dim <= 2^31 - 1. */
 int sd_timestep_embedding_f16(const float* timesteps, int batch, int dim, void* out, void* stream);
 
-/* NCHW fp32 <-> NHWC fp16 with channel padding / cropping (boundary conversions of the module API). */
+/* NCHW fp32 <-> NHWC fp16 with channel padding / cropping (boundary conversions of the module API).  To NHWC: every fp32 value is
+ * rounded to fp16 once (to nearest even: beyond 65519 -> inf), channels c .. cpad - 1 of out are written as +0; cpad >= c.  To NCHW: the
+ * exact fp32 value of every fp16; columns c .. ld - 1 of x are never read; ld >= c.  batch, c, hw > 0 and the element count of the launch
+ * (batch * hw * cpad, batch * hw * c) at most (2^31 - 1) * 256, the grid limit. */
 int sd_nchw_to_nhwc_f16(const float* x, int batch, int c, int hw, int cpad, void* out, void* stream);
 int sd_nhwc_to_nchw_f32(const void* x, int batch, int c, int hw, int ld, float* out, void* stream);
 
 /* VAE decode epilogue: NHWC fp16 [B, hw, ld] (3 valid channels, range ~[-1,1]) -> uint8 HWC image
  * (x/2+0.5).clamp(0,1)*255, truncated (round_mode 0: the `.astype(np.uint8)` of utils/adaptive_mask_inpainting.py:1114)
- * or rounded half-to-even (round_mode 1: diffusers' numpy_to_pil used for the final image, :1097). */
+ * or rounded half-to-even (round_mode 1: diffusers' numpy_to_pil used for the final image, :1097).  Every step is one fp32 operation;
+ * x / 2 + 0.5 of an fp16 x is exact in fp32 (a fused multiply-add gives the same value).  ld >= 3, channels 3 .. ld - 1 are never read;
+ * out is u8 [B * hw, 3]; batch * hw * 3 <= (2^31 - 1) * 256. */
 int sd_image_to_u8(const void* x, int batch, int hw, int ld, int round_mode, uint8_t* out, void* stream);
 
 /* VAE posterior sample: moments NHWC fp16 [npix, ld] = [mean(4) | logvar(4) | pad] ->
- * (mean + exp(0.5*clamp(logvar,-30,20)) * noise) * scale as fp32 [npix,4] and/or fp16 [npix,4] (noise NULL = mode).
+ * (mean + exp(0.5*clamp(logvar,-30,20)) * noise) * scale as fp32 [npix,4] and/or fp16 [npix,4] (noise NULL = the mode: mean * scale,
+ * one fp32 product).  The fp16 output is the rounding of the fp32 value, bit for bit what rounding latents_f32 gives.  ld >= 8,
+ * channels 8 .. ld - 1 are never read; at least one output; 0 < npix, npix * 4 <= (2^31 - 1) * 256.
  * replaces: `self.vae.encode(img).latent_dist.sample(generator)` * scaling_factor, utils/adaptive_mask_inpainting.py:675-684. */
 int sd_vae_sample(const void* moments, int ld, const float* noise, float scale, int64_t npix, float* latents_f32,
                   void* latents_f16, void* stream);
 
-/* out = sqrt(alpha) x0 + sqrt(1-alpha) noise  (scheduler.add_noise, utils/adaptive_mask_inpainting.py:658). */
+/* out = sqrt(alpha) x0 + sqrt(1-alpha) noise  (scheduler.add_noise, utils/adaptive_mask_inpainting.py:658).  0 < alpha <= 1
+ * (alpha = 1: out = x0 bit for bit, for finite noise), 0 < n <= (2^31 - 1) * 256. */
 int sd_add_noise(const float* x0, const float* noise, float alpha, int64_t n, float* out, void* stream);
 
 /* Mask adaptation glue of the adaptive loop, on device:
  *   mask = use_default ? default : AND(dilate_{3x3 ones, dilate_iters}(seg), default)     (u8 [H,W], 0/1)
  *   mask_latent  fp16 [H/8, W/8]        nearest down-sample (source pixel (8y, 8x))
  *   masked_image fp16 NHWC [H*W, cpad]  image * (mask < 0.5), image = fp32 NCHW [3,H,W] in [-1,1]
+ * A masked pixel is +0, an unmasked one the fp16 rounding of the image; ALL cpad channels of a pixel are written (3 .. cpad - 1 as +0),
+ * cpad >= 3.  seg counts as set where it is non-zero; the window is clipped at the image border.  seg may be NULL with use_default.
+ * Accepted: H, W > 0 and multiples of 8, H <= 65535 (the grid limit), H * W <= 2^31 - 1, dilate_iters >= 0.
  * replaces: utils/adaptive_mask_inpainting.py:1130-1141 (cv2.dilate / logical_and / prepare_mask_and_masked_image)
  *           and the mask interpolation of :686-694. */
 int sd_mask_adapt(const uint8_t* seg, const uint8_t* default_mask, int H, int W, int dilate_iters, int use_default,
@@ -386,6 +409,10 @@ int sd_mask_adapt(const uint8_t* seg, const uint8_t* default_mask, int H, int W,
  * masked_image fp16 NHWC [batch*H*W, cpad], cpad % 8 == 0: channels 0..7 are always written (3 data + zeros), channels >= 8
  * only when write_pad != 0 (a caller that zero-initialised the buffer once passes 0).  area: int32 [batch] (output);
  * scratch: u8 [batch,H,W] workspace.  seg / scratch may be NULL when force_default.
+ * The area test is the strict `<`: an area equal to area_thres keeps the segmentation.  area is always written (0 when force_default).
+ * Accepted: 0 < batch <= 65535; H, W > 0 and multiples of 8, H <= 65535, W <= 16384; H * W * 255 <= 2^31 - 1 (the largest value sum
+ * of an image has to fit the int32 area: 2064 x 4096 is already refused); cpad >= 8; masked_image 16-byte aligned (a pixel leaves as
+ * 16-byte stores).
  * replaces: utils/adaptive_mask_inpainting.py:1123-1141 (adapt_mask up to prepare_mask_latents), :686-694. */
 int sd_mask_adapt_batched(const uint8_t* seg, const uint8_t* default_mask, int batch, int H, int W, int dilate_iters,
                           int force_default, double area_thres, const float* image_nchw, int cpad, int write_pad,
