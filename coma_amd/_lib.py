@@ -1,4 +1,4 @@
-"""ctypes binding of libcoma_hip.so (the C ABI declared in include/coma_hip.h).
+"""ctypes binding of libcoma_hip.so (the C ABI declared in include/*.h, read by _abi.py).
 
 There is deliberately NO fallback: if the shared library is missing or a call is made with tensors
 that are not on a HIP device, this module raises.  The CPU oracle under oracle/ is test
@@ -12,162 +12,21 @@ import threading
 
 import torch
 
+from . import _abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # COMA_HIP_LIB=<path>: tuning aid -- load another BUILD of the library (A/B of two builds inside one GPU call: box-to-box spread is larger
 # than most of the effects being measured); the product and the tests use the in-tree library
 LIB_PATH = os.environ.get("COMA_HIP_LIB") or os.path.join(_HERE, "libcoma_hip.so")
-# = COMA_ABI_VERSION of include/coma_hip.h.  Bumped only when an EXISTING signature changes: a library that merely lacks an added
+# COMA_ABI_VERSION of include/coma_hip.h.  Bumped only when an EXISTING signature changes: a library that merely lacks an added
 # function is refused by lib() anyway, through the getattr of the missing symbol.
-ABI_VERSION = 11
+ABI_VERSION = _abi.DEFINES["COMA_ABI_VERSION"]
 
 _lib = None
 
-_vp, _i, _i64, _f, _d = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
-_fp3 = C.POINTER(C.c_float)
-
-# name -> (restype, argtypes); must list every function declared in include/coma_hip.h
-SIGNATURES = {
-    "coma_abi_version": (_i, []),
-    "coma_last_error": (C.c_char_p, []),
-    "coma_contact_accumulate_f32": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _i, _i, _i, _i, _fp3, _fp3, _f, _f, _f, _f,
-                                         _vp, _vp, _vp, _vp, _vp, _vp]),
-    "coma_contact_map_f32": (_i, [_vp, _vp, _fp3, _vp, _vp, _i64, _i, _f, _vp, _vp]),
-    "coma_significant_pairs_u8": (_i, [_vp, _f, _i, _i, _vp, _vp, _vp, _vp]),
-    "coma_masked_max_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
-    "coma_entropy_f32": (_i, [_vp, _i64, _i, _f, _f, _vp, _vp]),
-    "coma_row_argmax_i64": (_i, [_vp, _i64, _i, _i64, _i64, _vp, _vp, _vp]),
-    "coma_contact_select_u8": (_i, [_vp, _vp, _i, _i, _f, _vp, _vp]),
-    "coma_occupancy_splat": (_i, [_vp, _i, _i, _i, _vp, _d, _d, _vp, _vp]),
-    "coma_occupancy_reduce": (_i, [_vp, _vp, _i, _i64, _vp, _vp, _vp]),
-    "coma_occupancy_fused_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i]),
-    "coma_occupancy_fused": (_i, [_vp, _i, _i, _i, _vp, _d, _d, _d, _i, _vp, _i, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
-    "coma_nearest_vertex_i64": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
-    "coma_dlt_score_f64": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
-    "coma_ransac_mse_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _d, _vp, _vp, _vp]),
-    "coma_vertex_normals_f64": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _d, _vp, _vp]),
-    "coma_sample_eliminate_workspace_bytes": (C.c_size_t, [_i]),
-    "coma_sample_eliminate_f64": (_i, [_vp, _i, _i, _d, _d, _d, _vp, _vp, _vp]),
-    "coma_raster_workspace_bytes": (C.c_size_t, [_i, _i]),
-    "coma_raster_depth_f64": (_i, [_vp, _i, _vp, _i, C.POINTER(_d), C.POINTER(_d), _d, _i, _i, _vp, _vp, _vp]),
-    "coma_raster_status": (_i, [_vp, _vp]),
-    "coma_silhouette_iou": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
-    "coma_mesh_volume_workspace_bytes": (C.c_size_t, [_i]),
-    "coma_mesh_volume_f64": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp]),
-    "coma_column_crossings_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i64]),
-    "coma_intersection_columns": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _d, _d, _d, _i, _i, _i64, _vp, _vp, _vp, _vp]),
-    "coma_intersection_status": (_i, [_vp, _vp, C.POINTER(_i64)]),
-    "coma_shift_columns_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i64]),
-    "coma_shift_columns_prepare": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _d, _d, _d, _i, _i, _i64, _vp, _vp, _vp]),
-    "coma_shift_columns_status": (_i, [_vp, _vp, C.POINTER(_i64)]),
-    "coma_shift_profile": (_i, [_vp, _vp, _i, _vp, _vp]),
-    "coma_depth_optimize_state_bytes": (C.c_size_t, []),
-    "coma_depth_optimize_f64": (_i, [_vp, _vp, _i, _vp, C.POINTER(_d), _vp, _vp, _i, _i, _d, _d, _d, _d, _i, _vp, _vp, _vp, _vp, _vp]),
-    "coma_depth_optimize_status": (_i, [_vp, _vp, C.POINTER(_i)]),
-    "coma_coap_weights_floats": (C.c_size_t, [_i]),
-    "coma_coap_code_bytes": (C.c_size_t, [_i]),
-    "coma_coap_encode_workspace_bytes": (C.c_size_t, [_i, _i]),
-    "coma_coap_query_workspace_bytes": (C.c_size_t, [_i, _i]),
-    "coma_coap_encode_f32": (_i, [_vp, C.c_size_t, _vp, _vp, _vp, _i, C.POINTER(C.c_int32), C.POINTER(C.c_uint8), _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp,
-                                  C.c_size_t, _vp]),
-    "coma_coap_status": (_i, [_vp, _vp]),
-    "coma_coap_query_f32": (_i, [_vp, C.c_size_t, _vp, _i, _vp, _i, _vp, _fp3, _i, _vp, _vp, _vp, C.c_size_t, _vp]),
-    "coma_coap_collision_f32": (_i, [_vp, C.c_size_t, _vp, _i, _vp, _i, _vp, _fp3, _d, _vp, _vp, _vp, C.c_size_t, _vp]),
-    "coma_depth_optimize_coap_f64": (_i, [_vp, C.c_size_t, _vp, _i, _vp, _i, _d, _vp, C.c_size_t, _vp, _i, _vp, C.POINTER(_d), _vp, _vp, _i, _i,
-                                          _d, _d, _d, _d, _i, _vp, _vp, _vp, _vp, _vp]),
-    "coma_app_objective_workspace_bytes": (C.c_size_t, [_i, _i, _i]),
-    "coma_app_objective_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _fp3, _fp3, _fp3, _d, _vp, _vp, _i, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
-    "coma_smplx_workspace_bytes": (C.c_size_t, [_i, _i]),
-    "coma_smplx_shape_state_bytes": (C.c_size_t, [_i, _i]),
-    "coma_smplx_saved_bytes": (C.c_size_t, [_i, _i]),
-    "coma_smplx_shape_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, C.c_size_t, _vp]),
-    "coma_smplx_forward_f32": (_i, [_vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_size_t,
-                                    _vp, C.c_size_t, _vp]),
-    "coma_smplx_backward_f32": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _i, _vp, _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t,
-                                     _vp]),
-    "coma_smplx_grad_workspace_bytes": (C.c_size_t, [_i, _i, _i]),
-    "coma_smplx_backward_full_f32": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp,
-                                          C.c_size_t, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
-    "coma_smplx_extra_joints_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
-    "coma_vposer_saved_bytes": (C.c_size_t, [_i, _i, _i]),
-    "coma_vposer_workspace_bytes": (C.c_size_t, [_i, _i, _i]),
-    "coma_vposer_decode_f32": (_i, [_vp] * 7 + [_i, _i, _i, _i, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
-    "coma_vposer_decode_backward_f32": (_i, [_vp] * 4 + [_i, _i, _i, _i, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp]),
-    "coma_vposer_encode_f32": (_i, [_vp] * 9 + [_i, _i, _i, _i, _vp, _vp, _vp, C.c_size_t, _vp]),
-    "coma_angle_prior_f32": (_i, [_vp, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_float), _i, _vp, _vp]),
-    "coma_angle_prior_backward_f32": (_i, [_vp, _vp, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_float), _i, _vp, _vp]),
-    # include/sd_hip.h
-    "sd_conv_gemm_f16": (_i, [_vp, _vp]),
-    "sd_conv_gemm_workspace_bytes": (C.c_size_t, []),
-    "sd_conv_gemm_describe": (_i, [_vp, _vp]),
-    "sd_groupnorm_f16": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp, _vp, _vp]),
-    "sd_groupnorm_colstats_f16": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
-    "sd_layernorm_f16": (_i, [_vp, _i64, _i, _f, _vp, _vp, _vp, _vp]),
-    "sd_attention_f16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp]),
-    "sd_attention_wide_f16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp]),
-    "sd_xattn_chain_f16": (_i, [_vp] * 15 + [_i64, _i, _i, _i, _f, _vp, _i, _vp]),
-    "sd_groupnorm_table_f16": (_i, [_vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _i, _vp]),
-    "sd_xfront_f16": (_i, [_vp] * 11 + [_i64, _i, _i, _f, _vp]),
-    "sd_xtail_f16": (_i, [_vp] * 11 + [_i64, _vp]),
-    "sd_winograd_input_f16": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _f, _vp, _vp]),
-    "sd_winograd_weight_f16": (_i, [_vp, _i, _i, _f, _vp, _vp]),
-    "sd_winograd_output_f16": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _f, _vp, _vp]),
-    "sd_groupnorm_table_cat_f16": (_i, [_i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "sd_conv3x3_small_n_f16": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp]),
-    "sd_conv3x3_halo_f16": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
-    "sd_gn_winograd_input_f16": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _i, _f, _vp, _vp]),
-    "sd_im2col3x3_c3_f16": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
-    "sd_conv3x3_c3_f16": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
-    "sd_softmax_f16": (_i, [_vp, _i64, _i, _i, _f, _vp]),
-    "sd_cfg_ddim_step": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _f, _i, _vp]),
-    "sd_timestep_embedding_f16": (_i, [_vp, _i, _i, _vp, _vp]),
-    "sd_nchw_to_nhwc_f16": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
-    "sd_nhwc_to_nchw_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
-    "sd_image_to_u8": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
-    "sd_vae_sample": (_i, [_vp, _i, _vp, _f, _i64, _vp, _vp, _vp]),
-    "sd_add_noise": (_i, [_vp, _vp, _f, _i64, _vp, _vp]),
-    "sd_mask_adapt": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
-    "sd_model_create": (_i, [C.POINTER(_vp)]),
-    "sd_model_destroy": (_i, [_vp]),
-    "sd_model_register_buffer": (_i, [_vp, _vp, C.c_size_t, _i]),
-    "sd_model_bind": (_i, [_vp, C.c_char_p, _vp, C.c_size_t]),
-    "sd_model_binding": (_i, [_vp, C.c_char_p, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
-    "sd_model_record_begin": (_i, [_vp, C.c_char_p]),
-    "sd_model_record_end": (_i, [_vp]),
-    "sd_model_num_launches": (_i, [_vp, C.c_char_p]),
-    "sd_model_run": (_i, [_vp, C.c_char_p, _vp]),
-    "sd_model_replay": (_i, [_vp, C.c_char_p, _vp]),
-    "sd_model_prepare": (_i, [_vp, C.c_char_p]),
-    "sd_model_save": (_i, [_vp, C.c_char_p]),
-    "sd_model_load": (_i, [C.c_char_p, C.POINTER(_vp)]),
-    "sd_copy_d2d": (_i, [_vp, _vp, C.c_size_t, _vp]),
-    "sd_unet_set_context": (_i, [_vp, _vp, _vp]),
-    "sd_unet_forward": (_i, [_vp, _vp, _vp, _vp, _vp]),
-    "sd_vae_decode": (_i, [_vp, _vp, _vp, _vp]),
-    "sd_vae_encode": (_i, [_vp, _vp, _vp, _vp]),
-    "sd_text_encode": (_i, [_vp, _vp, _vp, _vp]),
-    "sd_text_embed_f16": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp]),
-    "sd_attention_causal_f16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp]),
-    "sd_mask_adapt_batched": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _d, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    # include/seg_hip.h
-    "seg_conv_gemm_f32": (_i, [_vp, _vp]),
-    "seg_conv_gemm_describe": (_i, [_vp, _vp]),
-    "seg_resize_normalize_u8": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _f, _f, _f, _vp, _vp, _vp, _vp]),
-    "seg_maxpool3x3s2_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
-    "seg_subsample2_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
-    "seg_memset": (_i, [_vp, _i, C.c_size_t, _vp]),
-    "seg_rpn_select": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _f, _f, _i, _i, _vp, _vp, _vp, _vp]),
-    "seg_rpn_select_levels": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _i, _vp, _vp, _vp, _vp, _vp]),
-    "seg_sort_candidates": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "seg_nms": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "seg_roi_align_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
-    "seg_box_predict": (_i, [_vp, _i, _vp, _vp, _i, _i, _f, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "seg_finalize_detections": (_i, [_vp, _vp, _i, _i, _f, _f, _i, _i, _vp, _vp, _vp]),
-    "seg_point_sample_f32": (_i, [_vp, _i, _i, _i, _i, _f, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _i, _i, _i, C.c_longlong, _vp]),
-    "seg_upsample2x_f32": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
-    "seg_topk_points": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "seg_point_logit_scatter": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp]),
-    "seg_paste_masks": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-}
+# name -> (restype, argtypes) and name -> parameter names of every function the headers declare (see _abi.py: there is no table to extend)
+SIGNATURES = {name: (res, [t for _, t in params]) for name, (res, params) in _abi.FUNCTIONS.items()}
+PARAMS = {name: tuple(n for n, _ in params) for name, (_, params) in _abi.FUNCTIONS.items()}
 
 
 class ComaHipError(RuntimeError):

@@ -12,6 +12,8 @@ import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
 
+from ._abi import header_paths
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
@@ -39,9 +41,7 @@ def _stale(out, deps):
 def build_lib(force=False, verbose=True):
     os.makedirs(OBJ, exist_ok=True)
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    headers.append(os.path.join(os.path.dirname(HERE), "include", "coma_hip.h"))
-    headers.append(os.path.join(os.path.dirname(HERE), "include", "sd_hip.h"))
-    headers.append(os.path.join(os.path.dirname(HERE), "include", "seg_hip.h"))
+    headers += header_paths()              # every *.h under include/: the listing the binding is parsed from
     jobs = []
     for src in _sources():
         s = os.path.join(CSRC, src)

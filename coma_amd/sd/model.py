@@ -8,9 +8,9 @@ import threading
 
 import torch
 
-from .. import _lib
+from .. import _abi, _lib
 
-BUF_PERSISTENT, BUF_ZEROED, BUF_IF_NEW = 1, 2, 4
+BUF_PERSISTENT, BUF_ZEROED, BUF_IF_NEW = (_abi.DEFINES["SD_BUF_" + k] for k in ("PERSISTENT", "ZEROED", "IF_NEW"))
 
 
 class _Recording(threading.local):

@@ -6,21 +6,15 @@ import ctypes as C
 
 import torch
 
-from .. import _lib
+from .. import _abi, _lib
 
-EPI_NONE, EPI_GEGLU, EPI_SILU, EPI_BIAS_ROWS, EPI_PERM16_N, EPI_PERM32_N, EPI_QUICK_GELU = 0, 1, 2, 4, 8, 16, 32
+EPI_NONE, EPI_GEGLU, EPI_SILU, EPI_BIAS_ROWS, EPI_PERM16_N, EPI_PERM32_N, EPI_QUICK_GELU = (
+    _abi.DEFINES["SD_EPI_" + k] for k in ("NONE", "GEGLU", "SILU", "BIAS_ROWS", "PERM16_N", "PERM32_N", "QUICK_GELU"))
 F16 = torch.float16
 
 
 class ConvGemmDesc(C.Structure):
-    _fields_ = [("a0", C.c_void_p), ("a1", C.c_void_p), ("c0", C.c_int), ("c1", C.c_int),
-                ("batch", C.c_int), ("in_h", C.c_int), ("in_w", C.c_int), ("out_h", C.c_int), ("out_w", C.c_int),
-                ("taps", C.c_int), ("stride", C.c_int), ("upsample", C.c_int), ("pad", C.c_int), ("n", C.c_int),
-                ("w", C.c_void_p), ("bias", C.c_void_p), ("bias_bn", C.c_void_p), ("ldbb", C.c_int), ("res", C.c_void_p), ("ldr", C.c_int),
-                ("out", C.c_void_p), ("ldo", C.c_int), ("epi", C.c_int), ("nbatch_z", C.c_int),
-                ("stride_a", C.c_int64), ("stride_w", C.c_int64), ("stride_out", C.c_int64), ("stride_res", C.c_int64),
-                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("colstats", C.c_void_p),
-                ("out_t", C.c_void_p), ("n_split", C.c_int), ("ldo_t", C.c_int), ("rows_per_sample", C.c_int), ("phase", C.c_int)]
+    _fields_ = _abi.STRUCTS["sd_conv_gemm_desc"]
 
 
 def _p(t, name="tensor", dtype=F16):
@@ -39,7 +33,7 @@ def _stream(t):
 
 class ConvGemmChoice(C.Structure):
     """sd_conv_gemm_choice of include/sd_hip.h: the kernel sd_conv_gemm_f16 runs for a descriptor."""
-    _fields_ = [(k, C.c_int) for k in ("bm", "bn", "bk", "stages", "waves", "tm", "spread", "m16", "ksplit", "tap_minor", "grid_x", "grid_y")]
+    _fields_ = _abi.STRUCTS["sd_conv_gemm_choice"]
 
     def asdict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}

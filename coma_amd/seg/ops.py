@@ -6,24 +6,19 @@ import ctypes as C
 
 import torch
 
-from .. import _lib
+from .. import _abi, _lib
 from ..sd.ops import _p, _stream
 
 F32, I32, U8, I64 = torch.float32, torch.int32, torch.uint8, torch.int64
 
 
 class SegConvDesc(C.Structure):
-    _fields_ = [("x", C.c_void_p), ("batch", C.c_int), ("in_h", C.c_int), ("in_w", C.c_int), ("c", C.c_int), ("ldx", C.c_int),
-                ("w", C.c_void_p), ("n", C.c_int), ("kpad", C.c_int), ("kh", C.c_int), ("kw", C.c_int), ("stride", C.c_int), ("pad", C.c_int),
-                ("out_h", C.c_int), ("out_w", C.c_int), ("bias", C.c_void_p), ("res", C.c_void_p), ("ldr", C.c_int), ("res_mode", C.c_int),
-                ("out", C.c_void_p), ("ldo", C.c_int), ("relu", C.c_int), ("m_dev", C.c_void_p), ("rows_per_item", C.c_int), ("unit_rows", C.c_int), ("tile", C.c_int),
-                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("split_k", C.c_int)]
+    _fields_ = _abi.STRUCTS["seg_conv_desc"]
 
 
 class SegConvChoice(C.Structure):
     """seg_conv_choice of include/seg_hip.h: the launch seg_conv_gemm_f32 makes for a descriptor."""
-    _fields_ = [(k, C.c_int) for k in ("tile", "bm", "bn", "uni", "pre", "splits", "nk", "nk_per", "grid_x", "grid_y", "ws_ld")] + \
-               [("slab_elems", C.c_longlong)]
+    _fields_ = _abi.STRUCTS["seg_conv_choice"]
 
     def asdict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}

@@ -25,7 +25,7 @@ import torch
 
 from tests import gemm_ref as gr
 from tests import norm_ref as nr
-from tests.norm_ref import F16, F32, F64, GUARD, LIP, PTR, U32, UD, Operand, Out, Result, Yardstick   # noqa: F401 (re-exported for the tests)
+from tests.norm_ref import F16, F32, F64, GUARD, LIP, PTR, U32, UD, Operand, Out, Result, Yardstick, call   # noqa: F401 (re-exported for the tests)
 
 TILE, CHUNK = 16, 64            # pixels per tile edge, input channels staged per pass (sd_haloconv.hip / sd_smallconv.hip)
 STRESS = ("exp-overflow", "large-positive", "zero-scale", "negative-scale", "shift-as-large-as-the-interior")
@@ -410,13 +410,6 @@ COLSTATS_REL = 1.001 * 2.0 ** -16
 
 
 # ------------------------------------------------------------------------------------------------------------------ refusals
-# argument order of the C entry points (include/sd_hip.h); `stream` is always passed as NULL
-ARGS = {
-    "sd_conv3x3_halo_f16": "x c gn_affine silu w bias res ldr batch h w_ n out ldo colstats",
-    "sd_conv3x3_small_n_f16": "x gn_affine silu w bias batch h w_ c n out ldo",
-    "sd_im2col3x3_c3_f16": "x ldx batch h w_ out",
-    "sd_conv3x3_c3_f16": "x ldx w32 bias batch h w_ n out ldo colstats",
-}
 OUTPUT_ARGS = {"out", "colstats"}
 
 _HALO = dict(x=PTR, c=64, gn_affine=None, silu=0, w=PTR, bias=None, res=None, ldr=0, batch=1, h=16, w_=16, n=128, out=PTR, ldo=0, colstats=None)
@@ -463,8 +456,3 @@ REFUSALS = {
         ("bad shape", dict(batch=0)), ("bad shape", dict(h=0)), ("bad shape", dict(w_=0)), ("bad shape", dict(h=-2)),
         ("too many pixels", dict(batch=2, h=32768, w_=32768)), ("too many pixels", dict(batch=32768, h=65536, w_=1))]),
 }
-
-
-def call(lib, entry, kw, resolve):
-    """entry(**kw, stream = NULL) through the ctypes library; resolve(name) -> the address to put where kw says PTR"""
-    return getattr(lib, entry)(*[resolve(name) if kw[name] is PTR else kw[name] for name in ARGS[entry].split()], None)

@@ -14,7 +14,7 @@ here is product code and nothing here needs a GPU.
 * ``check``       every assertion of a case on a set of outputs -- the device's, or the emulation's on the CPU.  Exact contracts bit for
                   bit; arithmetic results within max(4 e_emu, floor), the error normalised by the sum of magnitudes of the formula's terms.
 * ``branches`` / ``REACHABLE``  what each case reaches, and everything the eleven entry points have.
-* ``ARGS`` / ``REFUSALS``  per entry point an accepted base and every change the argument checks refuse, with the text.
+* ``REFUSALS``         per entry point an accepted base and every change the argument checks refuse, with the text.
 
 DESIGN.md section 3g has the numbers."""
 from __future__ import annotations
@@ -28,7 +28,7 @@ import torch
 
 from oracle import sd_oracle as so
 from tests import norm_ref as nr
-from tests.norm_ref import GUARD, PTR
+from tests.norm_ref import GUARD, PTR, Off, call   # noqa: F401 (call: re-exported for the tests)
 
 f16, f32, f64 = np.float16, np.float32, np.float64
 U32 = 2.0 ** -24
@@ -1022,24 +1022,6 @@ def check(c, got):
 
 
 # ------------------------------------------------------------------------------------------------------------------ refusals
-class Off(NamedTuple):
-    """a valid pointer moved by `bytes`"""
-    bytes: int
-
-
-ARGS = {
-    "sd_cfg_ddim_step": "eps_uc eps_ld latents x0_out mask masked_latents unet_in batch hw guidance alpha_t alpha_prev write_latents",
-    "sd_timestep_embedding_f16": "timesteps batch dim out",
-    "sd_nchw_to_nhwc_f16": "x batch c hw cpad out",
-    "sd_nhwc_to_nchw_f32": "x batch c hw ld out",
-    "sd_image_to_u8": "x batch hw ld round_mode out",
-    "sd_vae_sample": "moments ld noise scale npix latents_f32 latents_f16",
-    "sd_add_noise": "x0 noise alpha n out",
-    "sd_mask_adapt": "seg default_mask H W dilate_iters use_default image_nchw cpad mask_full mask_latent masked_image",
-    "sd_mask_adapt_batched": "seg default_mask batch H W dilate_iters force_default area_thres image_nchw cpad write_pad mask_full mask_latent masked_image area scratch",
-    "sd_text_embed_f16": "ids seqs len tok_emb vocab pos_emb n_pos width out",
-    "sd_attention_causal_f16": "q k v out seqs heads len d ldq ldk ldv ldo scale",
-}
 OUTPUT_ARGS = {"latents", "x0_out", "unet_in", "out", "latents_f32", "latents_f16", "mask_full", "mask_latent", "masked_image", "area", "scratch"}
 
 _DD = dict(eps_uc=PTR, eps_ld=4, latents=PTR, x0_out=PTR, mask=PTR, masked_latents=PTR, unet_in=PTR, batch=1, hw=4, guidance=7.5, alpha_t=0.5,
@@ -1110,13 +1092,3 @@ REFUSALS = {
         ("q / k / v must be 16-byte aligned", dict(q=Off(2))), ("q / k / v must be 16-byte aligned", dict(k=Off(8))), ("q / k / v must be 16-byte aligned", dict(v=Off(4))),
         ("out must be 2-byte aligned", dict(out=Off(1)))]),
 }
-
-
-def call(lib, entry, kw, resolve):
-    """entry(**kw, stream = NULL) through the ctypes library, as norm_ref.call: resolve(name) -> the address to put where kw says PTR;
-    Off(b) is that address + b"""
-    args = []
-    for name in ARGS[entry].split():
-        v = kw[name]
-        args.append(resolve(name) if v is PTR else resolve(name) + v.bytes if isinstance(v, Off) else v)
-    return getattr(lib, entry)(*args, None)

@@ -26,6 +26,8 @@ from typing import NamedTuple, Optional
 import numpy as np
 import torch
 
+from coma_amd import _lib
+
 F16, F32, F64 = torch.float16, torch.float32, torch.float64
 GUARD = 256                      # NaN (operands) / sentinel (outputs) elements in front of and behind every buffer
 SENTINEL_BITS = 0x7E5A           # fp16 NaN payload fp16 outputs are prefilled with
@@ -907,19 +909,13 @@ class _Ptr:
 
 PTR = _Ptr()        # "a valid non-null pointer": the tests put a dummy address (CPU) or a small device buffer (GPU) here
 
-# argument order of the C entry points (include/sd_hip.h); `stream` is always passed as NULL
-ARGS = {
-    "sd_groupnorm_f16": "x0 x1 c0 c1 batch hw groups eps gamma beta silu out stats",
-    "sd_groupnorm_colstats_f16": "x0 x1 c0 c1 batch hw groups eps gamma beta silu out stats colstats0 colstats1",
-    "sd_groupnorm_table_f16": "x0 c0 batch hw groups eps gamma beta stats colstats0 rows_per_slot",
-    "sd_groupnorm_table_cat_f16": "c0 c1 batch hw groups eps gamma beta stats colstats0 colstats1",
-    "sd_layernorm_f16": "x rows c eps gamma beta out",
-    "sd_softmax_f16": "x rows n ld scale",
-    "sd_winograd_input_f16": "x0 x1 c0 c1 batch h w upsample gn_affine silu vscale v",
-    "sd_winograd_weight_f16": "w n c uscale u",
-    "sd_winograd_output_f16": "m ldm batch h w n bias bias_bn ldbb res ldr out ldo silu mscale colstats",
-    "sd_gn_winograd_input_f16": "x0 x1 c0 c1 m ldm bias bias_bn ldbb batch h w groups eps gamma beta silu mscale v",
-}
+
+class Off(NamedTuple):
+    """a valid pointer moved by `bytes`"""
+    bytes: int
+
+
+
 OUTPUT_ARGS = {"out", "stats", "v", "u"}        # (softmax's x is written in place)
 
 _GN = dict(x0=PTR, x1=None, c0=16, c1=0, batch=1, hw=32, groups=2, eps=1e-5, gamma=PTR, beta=PTR, silu=1, out=PTR, stats=PTR)
@@ -1004,9 +1000,12 @@ REFUSALS = {
 
 
 def call(lib, entry, kw, resolve):
-    """entry(**kw, stream = NULL) through the ctypes library; resolve(name) -> the address to put where kw says PTR"""
+    """entry(**kw, stream = NULL) through the ctypes library, the keywords in the order of the header's own parameter names
+    (_lib.PARAMS); resolve(name) -> the address to put where kw says PTR; Off(b) is that address + b"""
+    *names, last = _lib.PARAMS[entry]
+    assert last == "stream", entry
     args = []
-    for name in ARGS[entry].split():
+    for name in names:
         v = kw[name]
-        args.append(resolve(name) if v is PTR else v)
+        args.append(resolve(name) if v is PTR else resolve(name) + v.bytes if isinstance(v, Off) else v)
     return getattr(lib, entry)(*args, None)

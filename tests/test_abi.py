@@ -4,7 +4,7 @@ import ctypes as C
 import os
 import re
 
-from coma_amd import _lib
+from coma_amd import _abi, _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -24,7 +24,8 @@ def test_every_declared_symbol_is_exported_and_bound(hip_lib):
     assert "coma_contact_accumulate_f32" in decl and len(decl) >= 10
     for name in decl:
         assert hasattr(hip_lib, name), f"{name} declared in include/ but not exported"
-    assert sorted(_lib.SIGNATURES) == decl, "ctypes signature table out of sync with the header"
+    # _declared() is a second, cruder reading of the headers than the parser the binding comes from: they must find the same names
+    assert sorted(_abi.FUNCTIONS) == decl == sorted(_lib.SIGNATURES) == sorted(_lib.PARAMS), "coma_amd/_abi.py and the headers disagree"
 
 
 def test_abi_version_11_and_error_text(hip_lib):

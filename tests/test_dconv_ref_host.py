@@ -11,6 +11,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from coma_amd import _lib
 from oracle import sd_oracle as so
 from tests import dconv_ref as dr
 from tests import norm_ref as nr
@@ -163,7 +164,7 @@ def test_the_table_reaches_every_branch_of_the_four_kernels():
 def test_every_refusal_gives_its_code_and_text_through_the_entry_point(entry, hip_lib):
     base, rows = dr.REFUSALS[entry]
     _dummy = _resolver()
-    assert len(rows) >= 10
+    assert len(rows) >= 10 and set(base) == set(_lib.PARAMS[entry][:-1])      # the header's own parameter names
     for text, change in rows:
         rc = dr.call(hip_lib, entry, {**base, **change}, _dummy)
         msg = hip_lib.coma_last_error().decode()

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+from coma_amd import _lib
 from oracle import sd_oracle as so
 from tests import elementwise_ref as er
 from tests import norm_ref as nr
@@ -277,7 +278,7 @@ def test_the_table_reaches_every_branch():
     for c in er.CASES:
         count[c.entry] = count.get(c.entry, 0) + 1
     print("ELEMENTWISE_TABLE " + " ".join(f"{k}={v}" for k, v in sorted(count.items())) + f" total={len(er.CASES)} branches={len(er.REACHABLE)}")
-    assert set(count) == set(er.ARGS) == set(er.REFUSALS) and len(count) == 11
+    assert set(count) == set(er.REFUSALS) <= set(_lib.PARAMS) and len(count) == 11
     dd = [c for c in er.CASES if isinstance(c, er.DD)]
     assert {c.B * c.hw for c in dd} == {1, 255, 256, 257, 513} and {c.B for c in dd} == {1, 2, 3} and {c.eps_ld for c in dd} == {4, 8, 64, 72}
     assert {c.guidance for c in dd} == {0.0, 1.0, 7.5, 11.0}
@@ -329,7 +330,7 @@ def test_a_broken_kernel_fails_a_named_case(mut):
 def test_every_refusal_gives_its_code_and_text_through_the_entry_point(entry, hip_lib):
     base, rows = er.REFUSALS[entry]
     _dummy = _resolver()
-    assert len(rows) >= 7 and set(base) == set(er.ARGS[entry].split())
+    assert len(rows) >= 7 and set(base) == set(_lib.PARAMS[entry][:-1])       # the header's own parameter names
     for text, change in rows:
         rc = er.call(hip_lib, entry, {**base, **change}, _dummy)
         msg = hip_lib.coma_last_error().decode()

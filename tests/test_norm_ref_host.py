@@ -12,6 +12,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from coma_amd import _lib
 from oracle import sd_oracle as so
 from tests import norm_ref as nr
 
@@ -180,7 +181,7 @@ def _resolver():
 def test_every_refusal_gives_its_code_and_text_through_the_entry_point(entry, hip_lib):
     base, rows = nr.REFUSALS[entry]
     _dummy = _resolver()
-    assert len(rows) >= 5
+    assert len(rows) >= 5 and set(base) == set(_lib.PARAMS[entry][:-1])       # the header's own parameter names
     for text, change in rows:
         rc = nr.call(hip_lib, entry, {**base, **change}, _dummy)
         msg = hip_lib.coma_last_error().decode()
