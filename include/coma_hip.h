@@ -624,6 +624,111 @@ int coma_angle_prior_f32(const float* pose, int N, int P, const int32_t* index, 
 int coma_angle_prior_backward_f32(const float* pose, const float* grad_out, int N, int P, const int32_t* index, const float* sign, int K,
                                   float* grad_pose, void* stream);
 
+/* The fitting app's whole Adam loop: E iterations of decode -> skin -> objective -> backward -> Adam enqueued by one call (N = 1).
+ * replaces: the loop of src/application/optimize.py:252-307 with the parameter set of :236-250 and torch.optim.Adam, i.e. what
+ *           this repository's fit() drives from Python through four autograd Functions and torch's optimiser.
+ * Every stage is the existing entry point, called from C on the caller's stream with buffers carved from ONE workspace; the new
+ * kernels only move numbers between them and take the step.  PINNED against the reference's own parts (its vendored SMPLX class and
+ * VPoser class, SMPLifyAnglePrior, the objective's own lines, torch.optim.Adam) run on the CPU in f64
+ * (tests/golden/app_fit_golden.npz), through the f64 restatement tests/fit_ref.py.
+ *   parameters     p f64 [P] = [global_orient 3 | transl 3 | left hand hs | right hand hs | embedding D], hs = n_pca when n_pca > 0,
+ *                  else hand_dim; P = 6 + 2 hs + D.  Kept in `state` with Adam's m, v, the running products p1, p2, the iteration
+ *                  count and the status word.  coma_app_fit_init_f64 writes p0 (f64 [P], device), m = v = 0, p1 = p2 = 1, count 0;
+ *                  a second coma_app_fit_f32 on the same state continues where the first stopped.
+ *   launches       per iteration, in order, no host synchronisation, no floating-point atomics:
+ *                   1 fit_assemble_kernel    theta f32 = [fl32(global_orient) | body_pose, left for 3 | lead_fixed 9 | fl32(hands)]
+ *                                            (the layout of coma_smplx_forward_f32), z = fl32(embedding), transl = fl32(transl)
+ *                   2 coma_vposer_decode_f32 z -> aa f32 [3 NJ]
+ *                   3 fit_pose_kernel        aa into theta's body_pose slot; prior_i = exp(sign_i aa[index_i])^2 and their sum,
+ *                                            i ascending through the workgroup tree, f64 (not rounded to f32)
+ *                   4 coma_smplx_forward_f32 theta, transl -> raw vertices f32
+ *                   5 fit_scale_kernel       vs = fl32(raw fl32(scale_factor)), written to `vertices`
+ *                   6 coma_app_objective_f32 vs -> terms f32 [2], g_o, g_c
+ *                   7 fit_seed_kernel        g = fl32(fl32(fl32(fl32(w_o) g_o) + fl32(fl32(w_c) g_c)) fl32(scale_factor)): f32, unfused, the
+ *                                            order of torch's eager ops in the Python path, whose seed it therefore equals bit for bit
+ *                   8 coma_smplx_backward_f32 g -> grad_theta, grad_transl
+ *                   9 fit_prior_grad_kernel  grad_aa_j = fl32(grad_theta[3 + j] + bending_prior_weight (sum over i with index_i == j,
+ *                                            ascending, of 2 sign_i prior_i)) in f64
+ *                  10 coma_vposer_decode_backward_f32 grad_aa -> grad_z
+ *                  11 fit_step_kernel        one workgroup, below
+ *   gradient       g f64 [P] in p's order: grad_theta's global_orient and hand entries and grad_transl as they are (f32 values), and
+ *                  grad_z + (2 z) (body_pose_weight^2 pprior_weight) with z the f64 embedding.
+ *   Adam           torch's form in f64, no FMA, per component: m = b1 m + (1 - b1) g; v = b2 v + ((1 - b2) g) g; p1 = p1 b1,
+ *                  p2 = p2 b2; p = p - ((lr / (1 - p1)) m) / (sqrt(v) / sqrt(1 - p2) + 1e-8); b1 = 0.9, b2 = 0.999.
+ *   records        losses f64 [E,5] = {total, pprior, weighted angle prior, orientation term, contact term} at the parameters BEFORE
+ *                  the step: pprior = ((sum z^2) body_pose_weight^2) pprior_weight (tree sum over the f64 embedding), weighted
+ *                  prior = bending_prior_weight sum prior, the two terms unweighted as coma_app_objective_f32 gives them, total =
+ *                  ((pprior + weighted prior) + orientation_weight t_o) + contact_weight t_c in f64.  traj f64 [E+1, P] (may be
+ *                  NULL): row 0 = p before the call's first iteration, row e + 1 = p after iteration e.  grad0 f64 [P] (may be
+ *                  NULL) = g of the call's first iteration.  vertices f32 [V,3] = vs of the LAST iteration's forward -- the forward
+ *                  before the last step, which is what the reference saves.
+ *   non-finite     the step kernel looks at every g and every updated p; if one is not finite it applies NOTHING: p, m, v and the
+ *                  products stay, the count still advances, and the first such iteration is recorded in `state`.  Later iterations
+ *                  run on the frozen, finite parameters, so no kernel ever reads a non-finite parameter (the records of such
+ *                  iterations are written all the same: traj repeats p, losses may hold non-finite numbers).
+ *                  coma_app_fit_status(state, stream, iteration) is the ONE call that waits; it returns COMA_E_INVALID and the
+ *                  iteration (HOST pointer, may be NULL), counted from the last init.  It also reports a state that no init has
+ *                  written, or one of another P: such a call leaves the state's parameters and every record but `vertices` as
+ *                  they were (`vertices` then holds no result).
+ * Descriptor: model pointers as coma_smplx_forward_f32 takes them, decoder pointers as coma_vposer_decode_f32, objective pointers as
+ * coma_app_objective_f32, the prior's as coma_angle_prior_f32 (index into the 3 NJ body pose).  HOST pointers, read during the call:
+ * parents, obj_normal, principle_vec, sub_principle_vec, prior_index, prior_sign; everything else lives on the device.
+ * state: coma_app_fit_state_bytes(P) bytes (0 for P outside [7, 512]), 16-byte aligned.  workspace:
+ * coma_app_fit_workspace_bytes(V, F, J, k, H, NJ, n_theta) bytes, 16-byte aligned (0 where one of the called entry points would
+ * refuse the sizes or n_theta = 3 NJ + 12 + 2 hs is outside [3 NJ + 12, 3 NJ + 12 + 192]: hs <= 96); it holds theta, z, aa, the raw vertices, both models' saved
+ * blocks and workspaces, the objective's workspace, terms, g_o, g_c, g and every gradient: no allocation inside the call.
+ * Refused before any launch (COMA_E_INVALID, nothing written): a NULL descriptor, state or workspace, or required pointer; E outside
+ * [1, 4096]; sizes the called entry points refuse (V, F, J, k, hand_dim, n_pca, a bad parent, D, H, NJ, the prior's K or an index
+ * outside [0, 3 NJ)); 3 NJ + 12 != 3 J - 2 hand_dim; P != 6 + 2 hs + D; eps < 0 or principle vectors that are not orthogonal; a
+ * non-finite lr, weight or scale_factor; a state or workspace too small or misaligned. */
+typedef struct coma_app_fit_desc {
+  /* body model: coma_smplx_forward_f32 / coma_smplx_backward_f32 */
+  const float* posedirs;
+  const float* weights;
+  const int32_t* parents;          /* HOST i32 [J] */
+  const float* hand_components;    /* may be NULL when n_pca == 0 or hand_dim == 0 */
+  const float* pose_mean;          /* may be NULL */
+  const void* shape_state;
+  const float* lead_fixed;         /* f32 [9]: jaw, left eye, right eye; zeros in the app */
+  int V, J, hand_dim, n_pca;
+  /* pose decoder: coma_vposer_decode_f32 / coma_vposer_decode_backward_f32 */
+  const float* W1;
+  const float* b1;
+  const float* W2;
+  const float* b2;
+  const float* W3;
+  const float* b3;
+  int D, H, NJ;
+  /* angle prior: coma_angle_prior_f32, on the body pose (P = 3 NJ) */
+  const int32_t* prior_index;      /* HOST i32 [prior_K] */
+  const float* prior_sign;         /* HOST f32 [prior_K] */
+  int prior_K;
+  /* objective: coma_app_objective_f32 */
+  const int32_t* faces;
+  const int32_t* vf_offsets;
+  const int32_t* vf_faces;
+  const float* orientation_gt;
+  const float* obj_normal;         /* HOST f32 [3] */
+  const float* principle_vec;      /* HOST f32 [3] */
+  const float* sub_principle_vec;  /* HOST f32 [3] */
+  const int32_t* selected;         /* may be NULL when k == 0 */
+  const float* targets;            /* may be NULL when k == 0 */
+  int F, k;
+  double eps;
+  /* the fit */
+  int P, E;
+  double lr, body_pose_weight, bending_prior_weight, pprior_weight, orientation_weight, contact_weight, scale_factor;
+  double* traj;                    /* f64 [E+1, P] or NULL */
+  double* losses;                  /* f64 [E, 5] */
+  double* grad0;                   /* f64 [P] or NULL */
+  float* vertices;                 /* f32 [V, 3] */
+} coma_app_fit_desc;
+size_t coma_app_fit_state_bytes(int P);
+size_t coma_app_fit_workspace_bytes(int V, int F, int J, int k, int H, int NJ, int n_theta);
+int coma_app_fit_init_f64(const double* p0, int P, void* state, size_t state_bytes, void* stream);
+int coma_app_fit_f32(const coma_app_fit_desc* d, void* state, size_t state_bytes, void* workspace, size_t workspace_bytes, void* stream);
+int coma_app_fit_status(const void* state, void* stream, int* iteration);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Digests of the fitting kernels' outputs: one `name sha256` line per output tensor, seeded, for comparing two BUILDS of the library
-bit for bit (the kernels of csrc/smplx.hip, vposer.hip, app_objective.hip, mesh_volume.hip, depth_opt.hip and reduce.hip use fixed
+bit for bit (the kernels of csrc/smplx.hip, vposer.hip, app_objective.hip, app_fit.hip, mesh_volume.hip, depth_opt.hip and reduce.hip use fixed
 summation shapes, so equal code gives equal bits).  Run it once per build in separate processes and diff the outputs:
 
     COMA_HIP_LIB=/path/to/other/libcoma_hip.so python scripts/fit_digests.py > a.txt
@@ -132,6 +132,26 @@ def app_objective():
         emit(f"app.k{k}.grad_contact", g_c)
 
 
+def app_fit():
+    """The fitting app's whole loop (coma_app_fit_f32) on the golden cases: 45 and 6 hand components, and no selected vertices."""
+    from coma_amd.app import ComaObjective, DeviceFit
+    from coma_amd.body_model import DeviceSMPLX
+    from coma_amd.pose_prior import DeviceAnglePrior, DeviceVPoser
+    from tests import fit_ref as R
+    from tests import vposer_ref as V
+    golden = R.load_golden()
+    c = V.case_shape(R.DECODER)
+    for name in R.CASE_NAMES:
+        model, _, w, n_pca, _, _ = R.case_models(name)
+        o = R.golden_objective(*golden, name)
+        fit = DeviceFit(DeviceSMPLX(model, n_pca=n_pca, device=DEV, extra_joint_vertex_ids=[]), DeviceVPoser(w, c["H"], c["D"], [1, c["NJ"], 3], device=DEV),
+                        DeviceAnglePrior(DEV), ComaObjective(o["faces"], o["gt"], o["obj_normal"], o["sel"], o["targets"], o["p"], o["sub_p"], o["eps"], device=DEV))
+        got = fit.run(num_iters=R.ITERS, betas=[R.DEFAULT_BETAS], record=True, **R.WEIGHTS)
+        emit(f"app_fit.{name}.traj", got["parameters"])
+        emit(f"app_fit.{name}.losses", got["loss_terms"])
+        emit(f"app_fit.{name}.vertices", got["vertices"])
+
+
 def bumpy_sphere(n_lat, n_lon, seed, centre, radius):
     """A closed, outward-facing latitude-longitude sphere with a seeded radial bump per vertex: F = 2 n_lon (n_lat - 1) faces."""
     rng = np.random.default_rng(seed)
@@ -211,7 +231,7 @@ def main():
     from coma_amd import _lib
     assert torch.cuda.is_available(), "the digests are of device results"
     print(f"# library: {_lib.LIB_PATH}", file=sys.stderr)
-    for part in (smplx, smplx_full, vposer, app_objective, volumes_and_depth, row_reductions):
+    for part in (smplx, smplx_full, vposer, app_objective, app_fit, volumes_and_depth, row_reductions):
         part()
     torch.cuda.synchronize()
 

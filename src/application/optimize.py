@@ -18,13 +18,15 @@ The hooks own their torch arithmetic; the optimiser stays torch.optim.Adam besid
     (utils.vposer), which this repository does not carry -- a clear error says so;
   * angle_prior(body_pose [1,63]) -> tensor, summed.  Default: likewise.
 --use_collision is REFUSED: COAP (a learned occupancy network with a downloaded checkpoint) is unpinned and not reproduced, as in the
-depth stage.  Three flags are added: --num_iters (the reference's loop count, 2000, is a literal there), --body_model {smplx,device}
+depth stage.  Four flags are added: --num_iters (the reference's loop count, 2000, is a literal there), --body_model {smplx,device}
 (default smplx, the hook described above; device = coma_amd.body_model.DeviceSMPLX, the same model files read with NumPy and the
 skinning and its backward run by the library's own kernels) and --pose_prior {vposer,device} (default vposer, the two hooks described
 above; device = coma_amd.pose_prior.DeviceVPoser on the same experiment directory, imports/vposer, read with configparser and
 torch.load, and coma_amd.pose_prior.DeviceAnglePrior: decoder, its backward and the prior run by the library's own kernels).  With
 --body_model device --pose_prior device the loop needs no third-party package; the torch arithmetic left in it is Adam and the
-embedding's pow(2).sum().
+embedding's pow(2).sum().  --loop {torch,device} (default torch: fit() below, the Python loop with torch.optim.Adam) chooses who runs the
+iterations; device = coma_amd.app.DeviceFit, which needs both device flags and hands the whole loop -- Adam included -- to the library:
+one C call enqueues every launch of up to 4096 iterations and nothing waits for the device until the fit is over.
 """
 import argparse
 import os
@@ -40,6 +42,10 @@ if ROOT not in sys.path:
 BODY_MOCAP_PATH = "imports/hand4whole/common/utils_hand4whole/human_model_files/"
 VPOSER_PATH = "imports/vposer"
 DEFAULT_BETAS = [[-0.00982137, 0.03693837, 0.0949352, -0.01299302, 0.00492086, -0.04505398, -0.0008909, -0.00054313, 0.03646483, -0.00803524]]
+LOOP_NEEDS_BODY_MODEL = "--loop device needs --body_model device: the device loop drives coma_amd.body_model.DeviceSMPLX, not a body-model hook"
+LOOP_NEEDS_POSE_PRIOR = "--loop device needs --pose_prior device: the device loop drives coma_amd.pose_prior's decoder and angle prior, not hooks"
+LOOP_TAKES_NO_HOOKS = ("--loop device builds its own body model, pose decoder and angle prior from --body_model device --pose_prior device; "
+                       "hooks passed to main() cannot be used with it")
 COLLISION_REFUSAL = ("--use_collision is not supported: the reference's collision term is COAP's (a learned occupancy network whose "
                      "checkpoint is not available to this project); run without it")
 
@@ -123,12 +129,16 @@ def fit(objective_loss, body_model, pose_decoder, angle_prior, lr, body_pose_wei
 
 def optimize_smpl(supercategory, category, coma_path, asset_downsample_pth, eps, principle_vec, sub_principle_vec, reference_object_vertex_index,
                   lr, body_pose_weight, bending_prior_weight, pprior_weight, orientation_weight, contact_weight, contact_threshold, scale_factor,
-                  use_collision, save_dir="", num_iters=2000, body_model=None, pose_decoder=None, angle_prior=None, device="cuda", record=False):
+                  use_collision, save_dir="", num_iters=2000, body_model=None, pose_decoder=None, angle_prior=None, device="cuda", record=False,
+                  loop="torch"):
     """The reference's optimize_smpl with the three third-party models as hooks (None = the reference's own, imported lazily).
     coma_path / asset_downsample_pth: the pickles, or the dicts they hold.  Writes {save_dir}/{supercategory}/{category}/optimized.obj
-    and returns fit()'s dict plus the faces and the path."""
+    and returns fit()'s dict plus the faces and the path.  loop="device": the iterations run in coma_amd.app.DeviceFit, which takes
+    the library's own DeviceSMPLX, DeviceVPoser and DeviceAnglePrior as the three models and nothing else."""
     if use_collision:
         raise NotImplementedError(COLLISION_REFUSAL)
+    if loop not in ("torch", "device"):
+        raise ValueError(f"optimize_smpl: loop must be 'torch' or 'device', got {loop!r}")
     from coma_amd.app import ComaObjective
     body_model = body_model if body_model is not None else default_body_model(device)
     pose_decoder = pose_decoder if pose_decoder is not None else default_pose_decoder(device)
@@ -136,8 +146,14 @@ def optimize_smpl(supercategory, category, coma_path, asset_downsample_pth, eps,
     faces = np.asarray(body_model.faces).astype(np.int64)
     objective = ComaObjective.from_state(coma_path, asset_downsample_pth, faces, reference_object_vertex_index, contact_threshold,
                                          principle_vec, sub_principle_vec, eps, device)
-    out = fit(lambda vertices: objective.loss(vertices, orientation_weight, contact_weight), body_model, pose_decoder, angle_prior, lr,
-              body_pose_weight, bending_prior_weight, pprior_weight, scale_factor, num_iters, device, record=record)
+    if loop == "device":
+        from coma_amd.app import DeviceFit
+        out = DeviceFit(body_model, pose_decoder, angle_prior, objective).run(lr, body_pose_weight, bending_prior_weight, pprior_weight,
+                                                                               orientation_weight, contact_weight, scale_factor, num_iters,
+                                                                               betas=DEFAULT_BETAS, record=record)
+    else:
+        out = fit(lambda vertices: objective.loss(vertices, orientation_weight, contact_weight), body_model, pose_decoder, angle_prior, lr,
+                  body_pose_weight, bending_prior_weight, pprior_weight, scale_factor, num_iters, device, record=record)
     out["faces"] = faces
     out["path"] = None
     if out["vertices"] is not None:
@@ -172,7 +188,14 @@ def build_parser():
     p.add_argument("--pose_prior", choices=("vposer", "device"), default=argparse.SUPPRESS,
                    help="vposer (default): the reference's VPoser loader and angle prior (third party); device: coma_amd.pose_prior on the same "
                         "experiment directory")
+    p.add_argument("--loop", choices=("torch", "device"), default=argparse.SUPPRESS,
+                   help="torch (default): the Python loop with torch.optim.Adam; device: coma_amd.app.DeviceFit, the whole loop in one library call "
+                        "(needs --body_model device --pose_prior device)")
     return p
+
+
+def loop_choice(args):
+    return getattr(args, "loop", "torch")
 
 
 def body_model_choice(args):
@@ -197,6 +220,13 @@ def device_pose_prior(device="cuda"):
 def main(args, body_model=None, pose_decoder=None, angle_prior=None):
     if args.use_collision:
         raise SystemExit(COLLISION_REFUSAL)
+    if loop_choice(args) == "device":
+        if body_model_choice(args) != "device":
+            raise SystemExit(LOOP_NEEDS_BODY_MODEL)
+        if pose_prior_choice(args) != "device":
+            raise SystemExit(LOOP_NEEDS_POSE_PRIOR)
+        if body_model is not None or pose_decoder is not None or angle_prior is not None:
+            raise SystemExit(LOOP_TAKES_NO_HOOKS)
     if body_model is None and body_model_choice(args) == "device":
         body_model = device_body_model()
     if pose_prior_choice(args) == "device" and (pose_decoder is None or angle_prior is None):
@@ -210,7 +240,7 @@ def main(args, body_model=None, pose_decoder=None, angle_prior=None):
                          orientation_weight=args.orientation_weight, contact_weight=args.contact_weight,
                          contact_threshold=args.contact_threshold, scale_factor=args.scale_factor, use_collision=args.use_collision,
                          save_dir=args.save_dir, num_iters=args.num_iters, body_model=body_model, pose_decoder=pose_decoder,
-                         angle_prior=angle_prior)
+                         angle_prior=angle_prior, **({"loop": "device"} if loop_choice(args) == "device" else {}))
 
 
 if __name__ == "__main__":
