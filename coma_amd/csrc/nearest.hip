@@ -2,10 +2,19 @@
 // replaces: utils/coma.py:87-91 -- argmin_v sum((p_i - m_v)^2) over an f64 [V,P] table, first minimum
 // wins ties (np.argmin).  One workgroup per query point, threads strided over the mesh vertices
 // (coalesced 24-B records), f64 arithmetic in the reference's order ((dx^2+dy^2)+dz^2, no FMA), then a
-// (distance, index) lexicographic min-reduction so the tie-break is identical.
+// (distance, index) lexicographic min-reduction so the tie-break is identical.  np.argmin's NaN rule as well: a NaN distance
+// counts as the minimum and the first one wins (nn_better, the mirror image of reduce.hip's np_better).
 #include "common.h"
 
 namespace coma {
+
+// is (d, i) ahead of (bd, bi) in np.argmin's order?  A NaN beats any number, the lower index decides between equals.
+__device__ __forceinline__ bool nn_better(double d, int i, double bd, int bi) {
+  const bool dn = d != d, bn = bd != bd;
+  if (dn != bn) return dn;
+  if (dn) return i < bi;
+  return d < bd || (d == bd && i < bi);
+}
 
 __global__ __launch_bounds__(256) void nearest_vertex_kernel(const double* __restrict__ pts,
                                                              const double* __restrict__ verts, int V,
@@ -20,22 +29,22 @@ __global__ __launch_bounds__(256) void nearest_vertex_kernel(const double* __res
     double dx = px - verts[3 * (int64_t)v + 0], dy = py - verts[3 * (int64_t)v + 1],
            dz = pz - verts[3 * (int64_t)v + 2];
     double d = (dx * dx + dy * dy) + dz * dz;
-    if (d < best) { best = d; bi = v; }   // ascending v per thread: strict < keeps the first minimum
+    if (nn_better(d, v, best, bi)) { best = d; bi = v; }   // (+inf, 0x7fffffff) loses to every vertex, a +inf distance included
   }
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) {
     double od = __shfl_xor(best, m);
     int oi = __shfl_xor(bi, m);
-    if (od < best || (od == best && oi < bi)) { best = od; bi = oi; }
+    if (nn_better(od, oi, best, bi)) { best = od; bi = oi; }
   }
   if ((threadIdx.x & 63) == 0) { sd[threadIdx.x >> 6] = best; si[threadIdx.x >> 6] = bi; }
   __syncthreads();
   if (threadIdx.x == 0) {
     for (int w = 1; w < 4; ++w)
-      if (sd[w] < best || (sd[w] == best && si[w] < bi)) { best = sd[w]; bi = si[w]; }
-    // a NaN row never satisfies d < best; np.argmin would return the first NaN -- report 0 like an
-    // all-NaN argmin of an empty comparison chain only if nothing was ever selected
-    idx[blockIdx.x] = (bi == 0x7fffffff) ? 0 : (int64_t)bi;
+      if (nn_better(sd[w], si[w], best, bi)) { best = sd[w]; bi = si[w]; }
+    // V >= 1, so thread 0 has taken vertex 0 at the least and the start value is gone: a row of +inf distances gives 0, a row with
+    // NaN distances its first NaN, every other row its first minimum -- np.argmin in all three
+    idx[blockIdx.x] = (int64_t)bi;
   }
 }
 

@@ -43,6 +43,7 @@ extern "C" int coma_vertex_normals_f64(const double* verts, const int32_t* faces
                                        const int32_t* vf_faces, int S, int V, int F, double eps, double* normals, void* stream) {
   if (!verts || !faces || !vf_offsets || !vf_faces || !normals) return fail(COMA_E_INVALID, "coma_vertex_normals_f64: null pointer");
   if (S <= 0 || V <= 0 || F <= 0) return fail(COMA_E_INVALID, "coma_vertex_normals_f64: bad sizes");
+  if (S > 65535) return fail(COMA_E_INVALID, "coma_vertex_normals_f64: S = %d exceeds the grid limit 65535", S);   // S is gridDim.y
   hipLaunchKernelGGL(vertex_normals_kernel, dim3((V + 127) / 128, S), dim3(128), 0, (hipStream_t)stream, verts, faces, vf_offsets,
                      vf_faces, V, eps, normals);
   return check_launch("vertex_normals_kernel");

@@ -216,11 +216,12 @@ extern "C" int coma_significant_pairs_u8(const float* cnt, float threshold, int 
   int64_t M = (int64_t)H * O;
   hipLaunchKernelGGL(pairs_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      cnt, threshold, M, pairs);
+  if (int rc = check_launch("pairs_kernel")) return rc;
   int bx = (int)((O + 255) / 256);
   int by = (H + 3) / 4;
   hipLaunchKernelGGL(any_kernel, dim3((unsigned)(bx > by ? bx : by), 2), dim3(256), 0, (hipStream_t)stream,
                      pairs, H, O, col_any, row_any);
-  return check_launch("pairs/any kernels");
+  return check_launch("any_kernel");
 }
 
 extern "C" int coma_masked_max_f32(const float* contact, const uint8_t* col_any, const uint8_t* row_any,
@@ -238,6 +239,7 @@ extern "C" int coma_row_argmax_i64(const float* x, int64_t rows, int n, int64_t 
   if (!x || (!idx && !val)) return fail(COMA_E_INVALID, "coma_row_argmax_i64: null pointer");
   if (rows <= 0 || n <= 0 || row_stride < n || col_offset < 0) return fail(COMA_E_INVALID, "coma_row_argmax_i64: bad sizes");
   const int64_t blocks = (rows + kRowWaves - 1) / kRowWaves;
+  if (blocks > 0x7fffffffLL) return fail(COMA_E_INVALID, "coma_row_argmax_i64: rows too large");
   hipLaunchKernelGGL(row_argmax_kernel, dim3((unsigned)blocks), dim3(kRowWaves * kWave), 0, (hipStream_t)stream, x, rows, n,
                      row_stride, col_offset, idx, val);
   return check_launch("row_argmax_kernel");

@@ -143,9 +143,11 @@ extern "C" int coma_ransac_mse_f64(const double* views, const double* tri, const
                                    int C, int J, double threshold, double* mse, int* counts, void* stream) {
   if (!views || !tri || !cand_view || !cand_xy || !sel || !mse || !counts) return fail(COMA_E_INVALID, "coma_ransac_mse_f64: null pointer");
   if (C < 0 || J <= 0) return fail(COMA_E_INVALID, "coma_ransac_mse_f64: bad sizes C=%d J=%d", C, J);
+  if (C > 65535) return fail(COMA_E_INVALID, "coma_ransac_mse_f64: C = %d exceeds the grid limit 65535", C);   // C is gridDim.y
   if (C == 0) return COMA_OK;
   hipLaunchKernelGGL(ransac_mse_kernel, dim3((unsigned)((C + 127) / 128), (unsigned)C), dim3(128), 0, (hipStream_t)stream, views, tri,
                      cand_view, cand_xy, sel, C, J, mse);
+  if (int rc = check_launch("ransac_mse_kernel")) return rc;
   hipLaunchKernelGGL(ransac_count_kernel, dim3((unsigned)C), dim3(128), 0, (hipStream_t)stream, mse, C, threshold, counts);
-  return check_launch("ransac kernels");
+  return check_launch("ransac_count_kernel");
 }

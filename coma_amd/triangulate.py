@@ -48,11 +48,24 @@ def _f64(x, device):
     return torch.as_tensor(np.ascontiguousarray(x), dtype=torch.float64).to(device).contiguous()
 
 
+def _checked_indices(index, n, who, what):
+    """`index` as a contiguous int32 host array, or ValueError: the kernels follow these indices as given (include/coma_hip.h)."""
+    a = np.asarray(index)
+    if a.size and not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"{who} must hold integers (got {a.dtype})")
+    a = a.astype(np.int64).reshape(-1)
+    bad = np.nonzero((a < 0) | (a >= n))[0]
+    if bad.size:
+        raise ValueError(f"{who}[{int(bad[0])}] = {int(a[bad[0]])} is outside [0, {what} = {n})")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
 def dlt_score(views, ref_view, ref_xy, cand_view, cand_xy, device="cuda"):
     """views [V,28]; ref_xy [J,2]; cand_view [P] view index per candidate; cand_xy [P,J,2] ->
     (tri [P,J,3], ref_mse [P], other_mse [P]) f64 device tensors."""
+    cand_view = _checked_indices(cand_view, len(views), "dlt_score: cand_view", "n_views")
     v, rxy, cxy = _f64(views, device), _f64(ref_xy, device), _f64(cand_xy, device)
-    cv = torch.as_tensor(np.ascontiguousarray(cand_view), dtype=torch.int32).to(device)
+    cv = torch.from_numpy(cand_view).to(device)
     P, J = int(cxy.shape[0]), int(rxy.shape[0])
     tri = torch.empty(P, J, 3, dtype=torch.float64, device=device)
     rm, om = torch.empty(P, dtype=torch.float64, device=device), torch.empty(P, dtype=torch.float64, device=device)
@@ -67,7 +80,7 @@ def dlt_score(views, ref_view, ref_xy, cand_view, cand_xy, device="cuda"):
 def ransac_matrix(dev_state, tri, sel, threshold):
     """mse [C,C] and inlier counts [C] over the selected candidates `sel` (indices into the scored candidates)."""
     v, cv, cxy = dev_state
-    s = torch.as_tensor(np.ascontiguousarray(sel), dtype=torch.int32).to(tri.device)
+    s = torch.from_numpy(_checked_indices(sel, int(cv.numel()), "ransac_matrix: sel", "P")).to(tri.device)
     C, J = int(s.numel()), int(tri.shape[1])
     mse = torch.empty(C, C, dtype=torch.float64, device=tri.device)
     counts = torch.empty(C, dtype=torch.int32, device=tri.device)

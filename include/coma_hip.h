@@ -82,7 +82,7 @@ int coma_contact_map_f32(float* prob, const float* sphere_grid, const float* pri
  * col_any u8 [O], row_any u8 [H] = any over the other axis;
  * which = 0 ("human"): out f32 [H] = max over {o : col_any[o]} contact[h,o], zeros if none
  * which = 1 ("obj")  : out f32 [O] = max over {h : row_any[h]} contact[h,o], zeros if none.
- * contact/out may be NULL (pairs + any vectors only). */
+ * The maximum propagates NaN (np.max); elements of contact outside the mask are not read.  Every pointer is required. */
 int coma_significant_pairs_u8(const float* cnt, float threshold, int H, int O, uint8_t* pairs,
                               uint8_t* col_any, uint8_t* row_any, void* stream);
 int coma_masked_max_f32(const float* contact, const uint8_t* col_any, const uint8_t* row_any, int H,
@@ -144,7 +144,8 @@ int coma_occupancy_fused(const float* q, int S, int H, int R, const double* cent
 
 /* K7  nearest-vertex index map (first minimum wins ties).
  * replaces: utils/coma.py:87-91 (argmin over f64 squared distances).
- * points f64 [P,3], verts f64 [V,3] -> idx i64 [P]; bit-exact. */
+ * points f64 [P,3], verts f64 [V,3] -> idx i64 [P]; bit-exact against np.argmin of ((dx^2 + dy^2) + dz^2), its NaN rule included:
+ * a NaN distance counts as the minimum and the first one wins; a row of +inf distances gives 0.  P = 0 writes nothing. */
 int coma_nearest_vertex_i64(const double* points, const double* verts, int P, int V, int64_t* idx,
                             void* stream);
 
@@ -153,13 +154,17 @@ int coma_nearest_vertex_i64(const double* points, const double* verts, int P, in
  * views f64 [n_views][28]: per camera {rot[9], trans[3]} of get_projection_matrix (:164-183), {mr[9] = R C, tmr[3] = t R C} of
  * get_view2joints_render (:185-200), scale, max(resolution), resolution/2 (x, y) -- built on the host with the reference's own
  * expressions.  ref_xy f64 [J,2] pixel joints of the reference view; cand_view i32 [P], cand_xy f64 [P,J,2] ->
- * tri f64 [P,J,3], ref_mse / other_mse f64 [P].  <= 1e-9 relative against np.linalg.pinv on well-conditioned pairs. */
+ * tri f64 [P,J,3], ref_mse / other_mse f64 [P].  <= 1e-9 relative against np.linalg.pinv on well-conditioned pairs.
+ * cand_view lives on the device and is followed as given: every entry must lie in [0, n_views), which is the caller's to validate
+ * (coma_amd/triangulate.py does, on the host, before the launch).  P = 0 writes nothing. */
 int coma_dlt_score_f64(const double* views, int n_views, int ref_view, const double* ref_xy, const int* cand_view,
                        const double* cand_xy, int P, int J, double* tri, double* ref_mse, double* other_mse, void* stream);
 
 /* RANSAC reprojection matrix over the selected candidates sel i32 [C] (indices into the P candidates above):
  * mse[a][b] = mean_j |xy_b[j] - render_{view(b)}(tri_a[j])|^2, counts[a] = #{b : mse[a][b] < threshold}.
- * replaces: src/generation/optimize_depth.py:329-350 (the candidates^2 loop). */
+ * replaces: src/generation/optimize_depth.py:329-350 (the candidates^2 loop).
+ * sel and cand_view are followed as given: the entry point is told neither P nor n_views, so sel[] in [0, P) and cand_view[sel[]] in
+ * [0, n_views) are the caller's to validate (coma_amd/triangulate.py does).  C <= 65535 (one grid row per candidate); C = 0 writes nothing. */
 int coma_ransac_mse_f64(const double* views, const double* tri, const int* cand_view, const double* cand_xy, const int* sel,
                         int C, int J, double threshold, double* mse, int* counts, void* stream);
 
@@ -167,7 +172,9 @@ int coma_ransac_mse_f64(const double* views, const double* tri, const int* cand_
  * replaces: open3d TriangleMesh.compute_vertex_normals() + normalize_vectors_np in
  *           prepare_affordance_extraction_inputs (utils/coma.py:672-686).
  * verts f64 [S,V,3]; faces i32 [F,3]; vf_offsets i32 [V+1] / vf_faces i32 [3F]: vertex -> incident faces (CSR, ascending
- * face index: the order in which open3d accumulates); eps >= 0 applies the reference's second v/(|v|+eps); normals f64 [S,V,3]. */
+ * face index: the order in which open3d accumulates); eps >= 0 applies the reference's second v/(|v|+eps); normals f64 [S,V,3].
+ * A vertex without faces, or whose face normals cancel, gets (0, 0, 1).  faces, vf_offsets and vf_faces are followed as given: vertex
+ * indices in [0, V), face indices in [0, F) and offsets ascending within [0, 3F] are the caller's to validate.  S <= 65535. */
 int coma_vertex_normals_f64(const double* verts, const int32_t* faces, const int32_t* vf_offsets, const int32_t* vf_faces,
                             int S, int V, int F, double eps, double* normals, void* stream);
 
