@@ -9,23 +9,22 @@ sd_attention_wide_f16): plain torch on the CPU, nothing here is product code and
 * ``emulation_bound``           an a-priori, element-wise worst-case bound of the emulation's own error (the emulation's stated bound).
 * packing helpers               lay q / k / out / V^T into flat buffers with a leading dimension and a column offset; everything the
                                 contract of include/sd_hip.h says is NOT read is NaN, V^T pad columns ("must be finite") are 1e4, `out`
-                                is prefilled with a NaN bit pattern, so an element the kernel should have written and did not shows too.
+                                is prefilled with a NaN bit pattern, so an element the kernel should have written and did not shows too
+                                (the guard width, that pattern, the seed and ``device_bound`` are tests/domain_kit.py's).
 * ``CASES``                     the table of launches, shared by the host test (which computes e_emu for every row) and the GPU test.
 """
 from __future__ import annotations
 
 import functools
-import zlib
 from typing import NamedTuple, Optional, Tuple
 
 import torch
 
-F16, F32, F64 = torch.float16, torch.float32, torch.float64
+from tests import domain_kit as kit
+from tests.domain_kit import F16, F32, F64, GUARD, device_bound      # (GUARD: NaN halves after the last row of every operand)
+
 LOG2E = 1.4426950408889634
 PAD_VALUE = 1.0e4            # V^T pad columns lk .. ldv-1: finite, and large enough that a non-zero weight on one of them shows
-SENTINEL_BITS = 0x7E5A       # fp16 NaN payload `out` is prefilled with
-GUARD = 256                  # NaN halves after the last row of every operand
-FLOOR = 2.0 ** -10           # one fp16 ulp of a query's largest output
 
 
 # ---------------------------------------------------------------------------------------------------------------- references
@@ -111,11 +110,6 @@ def query_error(got, ref, heads):
     return ((g - r).abs().amax(-1) / r.abs().amax(-1)).transpose(1, 2)
 
 
-def device_bound(e_emu):
-    """ISSUE / DESIGN.md: four times the emulation's own error, never below one fp16 ulp of the query's largest output."""
-    return max(4.0 * e_emu, FLOOR)
-
-
 # ---------------------------------------------------------------------------------------------------------------- packing
 def roundup(n, m):
     return (n + m - 1) // m * m
@@ -184,7 +178,7 @@ def pack_vt_perm32(v, ldv):
 
 def new_out(B, lq, ldo):
     """`out` [B, lq, ldo] + GUARD, every half the sentinel NaN."""
-    return torch.full((B * lq * ldo + GUARD,), SENTINEL_BITS, dtype=torch.int16).view(F16)
+    return kit.sentinel(B * lq * ldo + GUARD, F16)
 
 
 def split_out(buf, B, lq, C, ldo):
@@ -320,13 +314,9 @@ def _build_cases():
 CASES = _build_cases()
 
 
-def _seed(*key):
-    return zlib.crc32(repr(key).encode())
-
-
 @functools.lru_cache(maxsize=2)
 def _inputs(d, B, H, lq, lk, data):
-    g = torch.Generator().manual_seed(_seed(d, B, H, lq, lk, data))
+    g = kit.gen(repr((d, B, H, lq, lk, data)))
     C = H * d
     q, k, v = (torch.randn(B, n, C, generator=g).to(F16) for n in (lq, lk, lk))
     scale = d ** -0.5

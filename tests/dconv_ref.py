@@ -1,6 +1,6 @@
 """Test helper for the direct ("halo-patch") 3x3 convolutions (coma_amd/csrc/sd_haloconv.hip, sd_smallconv.hip): plain torch on the CPU,
-nothing here is product code and nothing here needs a GPU.  The mould is tests/norm_ref.py; its packing helpers, allowances and row error
-and tests/gemm_ref.py's in-order fp32 sum are used, not copied.
+nothing here is product code and nothing here needs a GPU.  The buffers (Operand / Out, pack, new_out, masks), the seeds, the exact SiLU
+and the row error are tests/domain_kit.py's; tests/norm_ref.py's allowances and tests/gemm_ref.py's in-order fp32 sum are used, not copied.
 
 * ``CASES``            the table of launches, one named tuple type per entry point (HC: sd_conv3x3_halo_f16, SN: sd_conv3x3_small_n_f16,
                        C3: sd_conv3x3_c3_f16, IC: sd_im2col3x3_c3_f16), shared by tests/test_dconv_ref_host.py and
@@ -13,7 +13,8 @@ and tests/gemm_ref.py's in-order fp32 sum are used, not copied.
                        to fp16) and the emulation's own a-priori bound, element by element.
 * ``yardstick``        e_emu = the emulation's largest row error, the device bound max(4 e_emu, 2^-10), emulation / a-priori bound.
 * ``branches``         a transcript of what a case reaches in the kernels, written beside the table; ``REACHABLE`` is everything they have.
-* ``REFUSALS``         per entry point: an accepted base argument list and every change the argument checks refuse, with the text.
+* ``REFUSALS``         per entry point: an accepted base argument list and every change the argument checks refuse, with the text (the
+                       kit's PTR; its check_refusals puts the rows to the entry points).
 
 DESIGN.md section 3f has the numbers."""
 from __future__ import annotations
@@ -25,7 +26,9 @@ import torch
 
 from tests import gemm_ref as gr
 from tests import norm_ref as nr
-from tests.norm_ref import F16, F32, F64, GUARD, LIP, PTR, U32, UD, Operand, Out, Result, Yardstick, call   # noqa: F401 (re-exported for the tests)
+from tests import domain_kit as kit
+from tests.domain_kit import F16, F32, F64, PTR, U32, Operand, Out
+from tests.norm_ref import LIP, UD, Result, Yardstick
 
 TILE, CHUNK = 16, 64            # pixels per tile edge, input channels staged per pass (sd_haloconv.hip / sd_smallconv.hip)
 STRESS = ("exp-overflow", "large-positive", "zero-scale", "negative-scale", "shift-as-large-as-the-interior")
@@ -212,12 +215,12 @@ def _table(g, B, c, stress):
 @functools.lru_cache(maxsize=2)
 def inputs(c):
     """name -> Operand of everything the launch reads"""
-    g = nr._gen(c.id)
+    g = kit.gen(c.id)
     M = c.B * c.h * c.w
     if isinstance(c, (HC, SN)):
-        d = dict(x=Operand(nr._randn(g, M, c.c, scale=1.5, shift=0.3), c.c))
-        w = nr._randn(g, c.n, 9 * c.c, scale=(9 * c.c) ** -0.5)
-        bias = nr._randn(g, 1, c.n)
+        d = dict(x=Operand(kit.randn16(g, M, c.c, scale=1.5, shift=0.3), c.c))
+        w = kit.randn16(g, c.n, 9 * c.c, scale=(9 * c.c) ** -0.5)
+        bias = kit.randn16(g, 1, c.n)
         if isinstance(c, SN):                                   # rows of w and entries of bias at and beyond n are outside the contract: NaN
             w = torch.cat([w, torch.full((16 - c.n, 9 * c.c), float("nan"), dtype=F16)])
             bias = torch.cat([bias, torch.full((1, 8 - c.n), float("nan"), dtype=F16)], 1)
@@ -227,18 +230,18 @@ def inputs(c):
         if c.bias:
             d["bias"] = Operand(bias, bias.shape[1])
         if isinstance(c, HC) and c.res:
-            d["res"] = Operand(nr._randn(g, M, c.n), c.ldr or c.n)
+            d["res"] = Operand(kit.randn16(g, M, c.n), c.ldr or c.n)
         return d
-    x = nr._randn(g, M, 3)
+    x = kit.randn16(g, M, 3)
     if isinstance(c, IC):                                       # signed zeros: the gather moves bits
         z = torch.rand(M, 3, generator=g)
         x = torch.where(z < 0.1, torch.tensor(-0.0, dtype=F16), torch.where(z < 0.2, torch.tensor(0.0, dtype=F16), x))
         return dict(x=Operand(x, c.ldx))
     w32 = torch.zeros(c.n, 32, dtype=F16)                        # the five zero pad columns include/sd_hip.h demands
-    w32[:, :27] = nr._randn(g, c.n, 27, scale=27 ** -0.5)
+    w32[:, :27] = kit.randn16(g, c.n, 27, scale=27 ** -0.5)
     d = dict(x=Operand(x, c.ldx), w32=Operand(w32, 32))
     if c.bias:
-        d["bias"] = Operand(nr._randn(g, 1, c.n), c.n)
+        d["bias"] = Operand(kit.randn16(g, 1, c.n), c.n)
     return d
 
 
@@ -290,8 +293,8 @@ def activate(x, tab, B, act):
     y32 = y.to(F32)                                             # fmaf of exact inputs: the float64 value rounded once
     err = U32 * y.abs()
     if act == 2:
-        y = nr._silu(y)
-        y32 = y32 * (1.0 / (1.0 + nr._exp32(-y32)))             # exp(100) = inf in fp32, 1 / inf = 0, f * 0 = -0: finite, as on the device
+        y = kit.silu(y)
+        y32 = y32 * (1.0 / (1.0 + kit.exp32(-y32)))             # exp(100) = inf in fp32, 1 / inf = 0, f * 0 = -0: finite, as on the device
         err = LIP * err + (UD + 4 * U32) * y.abs()
     return y.view(-1, C), y32.view(-1, C), err.view(-1, C)
 
@@ -334,7 +337,7 @@ def convolve(a, a_emu, e_a, w, B, h, wd, chunk, bias=None, res=None):
     mag = conv64(img(a).abs(), w.abs())
     e_in = conv64(img(e_a), w.abs())
     err = e_in + (K + 4) * U32 * (mag + e_in)
-    acc = gr._sum_in_order(_chunked(taps(img(a_emu)), chunk), _chunked(w.contiguous(), chunk), 0, K)
+    acc = gr.sum_in_order(_chunked(taps(img(a_emu)), chunk), _chunked(w.contiguous(), chunk), 0, K)
     if bias is not None:
         ref, acc, mag = ref + bias.to(F64), acc + bias.to(F32), mag + bias.to(F64).abs()
         err = err + U32 * (mag + err)
@@ -351,7 +354,7 @@ def activated(c):
     d = inputs(c)
     y, y32, _ = activate(d["x"].t, d["gn_affine"].t if c.act else None, c.B, c.act)
     a, a_emu = y.to(F16), y32.to(F16)
-    return a, a_emu, torch.where(a == a_emu, torch.zeros_like(y), nr._ulp16(y))
+    return a, a_emu, torch.where(a == a_emu, torch.zeros_like(y), nr.ulp16(y))
 
 
 @functools.lru_cache(maxsize=2)
@@ -366,7 +369,7 @@ def results(c):
         x = d["x"].t
         w = d["w32"].t[:, :27].reshape(c.n, 9, 3)
         ref, acc, err = convolve(x, x, torch.zeros(x.shape, dtype=F64), w, c.B, c.h, c.w, 3, d["bias"].t if c.bias else None)
-        return dict(out=Result(ref, acc.to(F16), nr._final16(ref, err)))
+        return dict(out=Result(ref, acc.to(F16), nr.final16(ref, err)))
     a, a_emu, e_a = activated(c)
     w = d["w"].t[:c.n].reshape(c.n, 9, c.c)
     bias = d["bias"].t[:, :c.n] if c.bias else None
@@ -374,7 +377,7 @@ def results(c):
     if isinstance(c, SN):                                       # channels n .. 7 of every pixel: zeros
         pad = lambda t: torch.cat([t, torch.zeros(t.shape[0], 8 - c.n, dtype=t.dtype)], 1)
         ref, acc, err = pad(ref), pad(acc), pad(err)
-    return dict(out=Result(ref, acc.to(F16), nr._final16(ref, err)))
+    return dict(out=Result(ref, acc.to(F16), nr.final16(ref, err)))
 
 
 def row_error(c, got, ref):
@@ -382,8 +385,8 @@ def row_error(c, got, ref):
     the 3-channel kernels (and a packed row of im2col).  A small_n pixel has at most four values, and one of them can cancel to zero: its
     yardstick row is the SAMPLE, the largest |ref| over all pixels and channels of that sample."""
     if isinstance(c, SN):
-        return nr.row_error(got.reshape(c.B, -1), ref.reshape(c.B, -1))
-    return nr.row_error(got, ref)
+        return kit.row_error(got.reshape(c.B, -1), ref.reshape(c.B, -1))
+    return kit.row_error(got, ref)
 
 
 def yardstick(c):
@@ -394,13 +397,13 @@ def yardstick(c):
         assert bool(torch.isfinite(a.float()).all()) and bool(torch.isfinite(a_emu.float()).all()), c.id
     worst = float(((r.emu.to(F64) - r.ref).abs() / r.stated).max())
     e_emu = float(row_error(c, r.emu, r.ref).max())
-    return Yardstick(e_emu, nr.device_bound(e_emu), worst)
+    return Yardstick(e_emu, kit.device_bound(e_emu), worst)
 
 
 def colstats_expected(c, out_buf):
     """float64 sums, sums of squares and sums of magnitudes per slot and column of the DEVICE's own stored output; a slot is one 16 x 16
     tile, its index (sample, tile row, tile column); with n > 128 the column index is global -> three [slots, n]"""
-    v = nr.body(outputs(c)["out"], out_buf).to(F64).view(c.B, c.h // TILE, TILE, c.w // TILE, TILE, c.n).permute(0, 1, 3, 2, 4, 5).reshape(-1, 256, c.n)
+    v = kit.body(outputs(c)["out"], out_buf).to(F64).view(c.B, c.h // TILE, TILE, c.w // TILE, TILE, c.n).permute(0, 1, 3, 2, 4, 5).reshape(-1, 256, c.n)
     return v.sum(1), (v * v).sum(1), v.abs().sum(1)
 
 

@@ -14,39 +14,30 @@ here is product code and nothing here needs a GPU.
 * ``check``       every assertion of a case on a set of outputs -- the device's, or the emulation's on the CPU.  Exact contracts bit for
                   bit; arithmetic results within max(4 e_emu, floor), the error normalised by the sum of magnitudes of the formula's terms.
 * ``branches`` / ``REACHABLE``  what each case reaches, and everything the eleven entry points have.
-* ``REFUSALS``         per entry point an accepted base and every change the argument checks refuse, with the text.
+* ``REFUSALS``    per entry point an accepted base and every change the argument checks refuse, with the text (tests/domain_kit.py's PTR /
+                  Off; its check_refusals puts the rows to the entry points).  The guard width, the sentinels, pack_rows and bits are the
+                  kit's too.
 
 DESIGN.md section 3g has the numbers."""
 from __future__ import annotations
 
 import functools
-import zlib
 from typing import NamedTuple
 
 import numpy as np
 import torch
 
 from oracle import sd_oracle as so
-from tests import norm_ref as nr
-from tests.norm_ref import GUARD, PTR, Off, call   # noqa: F401 (call: re-exported for the tests)
+from tests import domain_kit as kit
+from tests.domain_kit import GUARD, PTR, U32, Off, bits
 
 f16, f32, f64 = np.float16, np.float32, np.float64
-U32 = 2.0 ** -24
-SENT8 = 0xA5                    # u8 outputs are prefilled with it
 SEG_GUARD, DFLT_GUARD, ID_GUARD = 255, 1, 0x7FFFFFFF
 INT32_MAX = 2 ** 31 - 1
 GRID_ELEMS = INT32_MAX * 256    # elements of the largest 1-D launch of 256-thread blocks
 
 # floors of the device bound (the counted rounding of the storage format; the derivations are at `_stated`)
 FLOOR_X0, FLOOR_XPREV, FLOOR_NOISE, FLOOR_TEMB, FLOOR_ATT = 12 * U32, 16 * U32, 5 * U32, 2.0 ** -12, 2.0 ** -11
-
-
-def _rng(name):
-    return np.random.default_rng(zlib.crc32(name.encode()))
-
-
-def _exp32(v):
-    return np.exp(v.astype(f64)).astype(f32)
 
 
 def _sqrt32(v):
@@ -364,24 +355,13 @@ def _poison(dtype):
 
 def pack_in(body, ld=None, poison=None, off=0):
     """body [rows, width] -> guard | off | rows x ld, gap columns poisoned | guard"""
-    body = np.atleast_2d(np.ascontiguousarray(body))
-    r, w = body.shape
-    ld = w if ld is None else ld
-    dt = body.dtype.type
-    p = _poison(dt) if poison is None else poison
-    buf = np.full(GUARD + off + r * ld + GUARD, p, dtype=dt)
-    buf[GUARD + off:GUARD + off + r * ld].reshape(r, ld)[:, :w] = body
-    return In(torch.from_numpy(buf), off)
+    body = np.ascontiguousarray(body)
+    return In(torch.from_numpy(kit.pack_rows(body, _poison(body.dtype.type) if poison is None else poison, ld, off)), off)
 
 
 def _sentinel(n, dt):
-    if dt == f16:
-        return np.full(n, nr.SENTINEL_BITS, np.uint16).view(f16)
-    if dt == f32:
-        return np.full(n, nr.SENTINEL_BITS32, np.uint32).view(f32)
-    if dt == np.int32:
-        return np.full(n, nr.SENTINEL_BITS32, np.int32)
-    return np.full(n, SENT8, np.uint8)
+    """the kit's sentinel; the one int32 output (`area`) starts as the bits of the fp32 pattern"""
+    return kit.sentinel(n, f32).view(np.int32) if dt == np.int32 else kit.sentinel(n, dt)
 
 
 def new_out(rows, width, ld, dt, off=0, must_cols=None, init=None, written=True, finite=True):
@@ -404,15 +384,6 @@ def body(o, buf, rows, ld):
     return a[GUARD + o.off:GUARD + o.off + rows * ld].reshape(rows, ld)
 
 
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({2: np.uint16, 4: np.uint32, 1: np.uint8, 8: np.uint64}[a.dtype.itemsize])
-
-
-def sentinel_of(dt):
-    return {torch.float16: nr.SENTINEL_BITS, torch.float32: nr.SENTINEL_BITS32, torch.int32: nr.SENTINEL_BITS32, torch.uint8: SENT8}[dt]
-
-
 # ------------------------------------------------------------------------------------------------------------------ data
 SPECIAL32 = np.array([0.0, -0.0, 1.0, -1.0, 65504.0, -65504.0, 65519.996, -65519.996, 65520.0, -65520.0, 65536.0, 1e6, -3e38, np.inf, -np.inf,
                       1 + 2.0 ** -11, 1 + 3 * 2.0 ** -11, -(1 + 2.0 ** -11), 1 + 2.0 ** -11 + 2.0 ** -23, 1 + 2.0 ** -11 - 2.0 ** -24, 2047.0, 2049.0, 2051.0,
@@ -421,7 +392,7 @@ SPECIAL32 = np.array([0.0, -0.0, 1.0, -1.0, 65504.0, -65504.0, 65519.996, -65519
                      dtype=f32)
 
 
-def _interesting32(g, n):
+def interesting32(g, n):
     x = (g.standard_normal(n) * np.exp(g.uniform(-12, 6, n))).astype(f32)
     k = min(n, SPECIAL32.size)
     x[g.permutation(n)[:k]] = g.permutation(SPECIAL32)[:k]
@@ -442,7 +413,7 @@ LOGVARS = np.array([-40, -30.5, -30, 0, 19.5, 20, 25, np.inf, -np.inf, -3.25, 1.
 
 @functools.lru_cache(maxsize=4)
 def _mask_data(c: MA):
-    g = _rng("mask-" + c.name)                     # (not the id: the batched twin of a single-image case has the same data)
+    g = kit.rng("mask-" + c.name)                     # (not the id: the batched twin of a single-image case has the same data)
     B, H, W = c.B, c.H, c.W
     seg = np.zeros((B, H, W), np.uint8)
     for b in range(B):
@@ -476,7 +447,7 @@ def _mask_data(c: MA):
 @functools.lru_cache(maxsize=4)
 def data(c):
     """name -> numpy array: the operands of a case without their packing"""
-    g = _rng(c.id)
+    g = kit.rng(c.id)
     if isinstance(c, DD):
         n = c.B * c.hw
         sp16 = np.array([0.0, -0.0, 1.0, 6e-8, -6e-8, 3e-5, 0.5], dtype=f16)
@@ -489,7 +460,7 @@ def data(c):
     if isinstance(c, TE):
         return dict(t=np.array(c.t, dtype=f32))
     if isinstance(c, NC):
-        return dict(x=_interesting32(g, c.B * c.c * c.hw))
+        return dict(x=interesting32(g, c.B * c.c * c.hw))
     if isinstance(c, NH):
         h = g.integers(0, 1 << 16, c.B * c.hw * c.c).astype(np.uint16)
         h = np.where((h & 0x7FFF) > 0x7C00, h & 0x83FF, h).astype(np.uint16)                    # NaN patterns become subnormals
@@ -525,7 +496,7 @@ def data(c):
                 v=g.standard_normal((rows, w)).astype(f16), scale=0.125)
 
 
-def _ca_lds(c):
+def ca_lds(c):
     w = c.heads * 64
     return (3 * w + 8,) * 3 if c.layout == "packed" else (w + 8, w + 16, w + 24)
 
@@ -589,7 +560,7 @@ def plan(c):
     if c.layout == "packed":
         ins = dict(qkv=pack_in(np.concatenate([d["q"], d["k"], d["v"]], -1), 3 * w + 8))
     else:
-        ins = {k: pack_in(d[k], ld) for k, ld in zip("qkv", _ca_lds(c))}
+        ins = {k: pack_in(d[k], ld) for k, ld in zip("qkv", ca_lds(c))}
     return ins, dict(out=new_out(rows, w, w + c.dldo, f16, off=1))           # out sits one half off: 2-byte alignment is all the contract asks
 
 
@@ -625,7 +596,7 @@ def launch(ops, c, p):
         ops.text_embed(p["ids"], p["tok"], p["pos"], p["out"], seqs=c.seqs, len_=c.len, vocab=c.vocab, n_pos=c.n_pos, width=c.width)
     else:
         w = c.heads * 64
-        ldq, ldk, ldv = _ca_lds(c)
+        ldq, ldk, ldv = ca_lds(c)
         q, k, v = (p["qkv"], p["qkv"][w:], p["qkv"][2 * w:]) if c.layout == "packed" else (p["q"], p["k"], p["v"])
         ops.attention_causal(q, k, v, p["out"], seqs=c.seqs, heads=c.heads, len_=c.len, d=64, ldq=ldq, ldk=ldk, ldv=ldv, ldo=w + c.dldo, scale=d["scale"])
 
@@ -808,7 +779,7 @@ def emulate(c, mut=None):
     if isinstance(c, TE):
         half = c.dim // 2
         arg = (f32(-9.210340371976184) * np.arange(half, dtype=f32)) / f32(half)
-        a = d["t"][:, None] * _exp32(arg)[None]
+        a = d["t"][:, None] * kit.exp32(arg)[None]
         return dict(out=_to16(np.concatenate([np.cos(a.astype(f64)), np.sin(a.astype(f64))], -1).astype(f32)).reshape(c.B, c.dim))
     if isinstance(c, NC):
         out = np.zeros((c.B, c.hw, c.cpad), f16)
@@ -826,7 +797,7 @@ def emulate(c, mut=None):
         lo, hi = (-20, 20) if mut == "logvar-clamp-20" else (-30, 20)
         mean, lv = d["mom"][:, :4].astype(f32), np.minimum(np.maximum(d["mom"][:, 4:].astype(f32), f32(lo)), f32(hi))
         nz = d["noise"] if c.noise else np.zeros_like(mean)
-        v = (mean + _exp32(f32(0.5) * lv) * nz) * f32(d["scale"])
+        v = (mean + kit.exp32(f32(0.5) * lv) * nz) * f32(d["scale"])
         return {k: val for k, val in (("lat32", v), ("lat16", _to16(v).reshape(v.shape))) if k in plan(c)[1]}
     if isinstance(c, AN):
         a = f32(c.alpha)
@@ -891,7 +862,7 @@ def emulate(c, mut=None):
             for e in range(64):
                 S = _fma32(Q[:, e:e + 1], K[None, :, e], S)
             S = np.where(valid, S * sc, f32(-np.inf))
-            E = np.where(valid, _exp32(S - S.max(-1, keepdims=True)), f32(0))
+            E = np.where(valid, kit.exp32(S - S.max(-1, keepdims=True)), f32(0))
             tot = np.zeros(ln, f32)
             for j in range(ln):
                 tot = tot + E[:, j]
@@ -1013,7 +984,7 @@ def check(c, got):
             full = bool(c.single and not p) or bool(c.write_pad and not p)
             ncol = cp if full else 8
             assert not m[:, 3:ncol].any(), p + "padding channels must be +0"
-            assert bool((m[:, ncol:] == nr.SENTINEL_BITS).all()), p + "channels >= 8 are left alone without write_pad"
+            assert bool((m[:, ncol:] == kit.sentinel_bits(f16)).all()), p + "channels >= 8 are left alone without write_pad"
             if p or not c.single:
                 _same(got[p + "area"].astype(np.int64), ref["area"], p + "area")
     else:

@@ -11,7 +11,8 @@ needs a GPU.
                        from the reference e_emu -- each element's error over the largest |ref| of its output row -- the device bound
                        max(4 e_emu, 2^-10), and the emulation's own a-priori bound.
 * ``pack``             flat buffers as the kernel sees them: 256 NaN halves in front of and behind every operand, NaN gap columns and
-                       inter-problem gaps, a NaN-filled workspace, sentinel-filled outputs with guards.
+                       inter-problem gaps, a NaN-filled workspace, sentinel-filled outputs with guards (the guard width, the sentinels,
+                       the seeds, the device bound and the refusal rows' PTR are tests/domain_kit.py's).
 * ``written_mask`` ... which elements of `out` / `out_t` / `colstats` a launch must write; everything else must keep the sentinel.
 
 DESIGN.md section 3c has the numbers."""
@@ -19,18 +20,14 @@ from __future__ import annotations
 
 import functools
 import math
-import zlib
 from dataclasses import dataclass
 from typing import NamedTuple, Optional, Tuple
 
 import torch
 
-F16, F32, F64 = torch.float16, torch.float32, torch.float64
-GUARD = 256                      # NaN (operands) / sentinel (outputs) elements in front of and behind every buffer
-SENTINEL_BITS = 0x7E5A           # fp16 NaN payload `out` / `out_t` are prefilled with
-SENTINEL_BITS32 = 0x7FC5A5A5     # fp32 NaN payload `colstats` is prefilled with
-FLOOR = 2.0 ** -10               # one fp16 ulp of a row's largest value
-U32 = 2.0 ** -24                 # unit roundoff of fp32
+from tests import domain_kit as kit
+from tests.domain_kit import F16, F32, F64, GUARD, PTR, U32, device_bound, exp32
+
 LIP = 1.13                       # Lipschitz constant of SiLU / quick GELU (1.0999) and of the erf GELU (1.129)
 SAMPLE_ABOVE = 2.0e9             # multiply-adds of a launch above which only sampled_rows() are compared
 EPI_GEGLU, EPI_SILU, EPI_BIAS_ROWS, EPI_PERM16, EPI_PERM32, EPI_QGELU = 1, 2, 4, 8, 16, 32
@@ -203,12 +200,8 @@ class Inputs(NamedTuple):
     res: Optional[torch.Tensor]     # fp16 [nz, M, n]
 
 
-def _seed(name):
-    return zlib.crc32(name.encode())
-
-
 def make_inputs(c: Case) -> Inputs:
-    g = torch.Generator().manual_seed(_seed(c.name))
+    g = kit.gen(c.name)
     ctot = c.c0 + c.c1
     x = torch.randn(c.nz, c.B, c.H, c.W, ctot, generator=g).to(F16)
     if c.phase:
@@ -291,13 +284,13 @@ def sampled_rows(c: Case):
     edge = (r // c.out_w == 0) | (r // c.out_w == c.out_h - 1) | (r % c.out_w == 0) | (r % c.out_w == c.out_w - 1)
     pick[:c.rpb] |= edge
     pick[M - c.rpb:] |= edge
-    g = torch.Generator().manual_seed(_seed(c.name + "/rows"))
+    g = kit.gen(c.name + "/rows")
     pick[torch.randperm(M, generator=g)[:256]] = True
     return torch.nonzero(pick).flatten()
 
 
 # ---------------------------------------------------------------------------------------------------------------- arithmetic
-def _sum_in_order(A, Wm, lo, hi):
+def sum_in_order(A, Wm, lo, hi):
     """fp32 sum over k = lo .. hi-1 of A[:, k] * Wm[:, k], added in index order (an fp16 x fp16 product is exact in fp32)."""
     s = torch.zeros(A.shape[0], Wm.shape[0], dtype=F32)
     At, Wt = A.to(F32).t().contiguous(), Wm.to(F32).t().contiguous()
@@ -311,25 +304,21 @@ def emulate_product(A, Wm, ksplit, bk):
     ceil(K / bk / ksplit) K tiles on its own, the splits then added in fp32 in split order."""
     K = A.shape[1]
     if ksplit <= 1:
-        return _sum_in_order(A, Wm, 0, K)
+        return sum_in_order(A, Wm, 0, K)
     per = -(-(K // bk) // ksplit) * bk
     tot = torch.zeros(A.shape[0], Wm.shape[0], dtype=F32)
     for s in range(ksplit):
         lo, hi = s * per, min((s + 1) * per, K)
-        tot += _sum_in_order(A, Wm, lo, max(lo, hi))
+        tot += sum_in_order(A, Wm, lo, max(lo, hi))
     return tot
-
-
-def _exp32(v):
-    return torch.exp(v.to(F64)).to(F32)                 # a correctly rounded fp32 exp, whatever the host's vector library does
 
 
 def _act(epi, v):
     """SiLU / quick GELU of fp32 or float64 `v` in its own precision, the exponential exact."""
     if epi & EPI_SILU:
-        return v / (1 + (torch.exp(-v) if v.dtype == F64 else _exp32(-v)))
+        return v / (1 + (torch.exp(-v) if v.dtype == F64 else exp32(-v)))
     if epi & EPI_QGELU:
-        return v / (1 + (torch.exp(-1.702 * v) if v.dtype == F64 else _exp32(-(v * 1.702))))
+        return v / (1 + (torch.exp(-1.702 * v) if v.dtype == F64 else exp32(-(v * 1.702))))
     return v
 
 
@@ -403,11 +392,6 @@ def row_error(got, ref, cols, split=None):
     return (g - r).abs().amax(-1) / r.abs().amax(-1)
 
 
-def device_bound(e_emu):
-    """Four times the emulation's own error, never below one fp16 ulp of the row's largest value."""
-    return max(4.0 * e_emu, FLOOR)
-
-
 class Yardstick(NamedTuple):
     rows: torch.Tensor          # product rows compared [R]; a phase case: rows of `out` (pixels of the upsampled image)
     ref: torch.Tensor           # float64 [nz, R, n-or-N-or-n/2]: the epilogue's values, out_t columns included
@@ -467,7 +451,7 @@ def _nan(n):
     return torch.full((n,), float("nan"), dtype=F16)
 
 
-def _pack(blocks, ld, width, stride):
+def pack_blocks(blocks, ld, width, stride):
     """blocks [Z, rows, width] -> flat fp16: GUARD NaN | problem z at z * stride, rows of ld halves | GUARD NaN; gap columns and the
     space between problems NaN.  The kernel's pointer is buf[GUARD:]."""
     Z, R, _ = blocks.shape
@@ -491,15 +475,15 @@ def pack(c: Case, inp: Inputs) -> Packed:
     sa, sw, _, sr = c.strides()
     npix = c.B * c.H * c.W
     x = inp.x.reshape(c.nz, npix, c.c0 + c.c1)
-    a0 = _pack(x[:, :, :c.c0], c.c0, c.c0, sa)
-    a1 = _pack(x[:, :, c.c0:], c.c1, c.c1, 0) if c.c1 else None
+    a0 = pack_blocks(x[:, :, :c.c0], c.c0, c.c0, sa)
+    a1 = pack_blocks(x[:, :, c.c0:], c.c1, c.c1, 0) if c.c1 else None
     if c.phase:
-        w = tuple(_pack(phase_weights(inp.w[0], ph)[None], c.K, c.K, 0) for ph in c.phases)
+        w = tuple(pack_blocks(phase_weights(inp.w[0], ph)[None], c.K, c.K, 0) for ph in c.phases)
     else:
-        w = (_pack(inp.w, c.K, c.K, sw),)
-    bias = _pack(inp.bias[None, None], inp.bias.numel(), inp.bias.numel(), 0) if inp.bias is not None else None
-    bias_bn = _pack(inp.bias_bn[None], c.ldbb, c.n, 0) if inp.bias_bn is not None else None
-    res = _pack(inp.res, c.ldr, c.n, sr) if inp.res is not None else None
+        w = (pack_blocks(inp.w, c.K, c.K, sw),)
+    bias = pack_blocks(inp.bias[None, None], inp.bias.numel(), inp.bias.numel(), 0) if inp.bias is not None else None
+    bias_bn = pack_blocks(inp.bias_bn[None], c.ldbb, c.n, 0) if inp.bias_bn is not None else None
+    res = pack_blocks(inp.res, c.ldr, c.n, sr) if inp.res is not None else None
     return Packed(a0, a1, w, bias, bias_bn, res)
 
 
@@ -517,15 +501,15 @@ def colstats_slots(c: Case):
 
 
 def new_out(c: Case):
-    return torch.full((GUARD + out_elems(c) + GUARD,), SENTINEL_BITS, dtype=torch.int16).view(F16)
+    return kit.sentinel(GUARD + out_elems(c) + GUARD, F16)
 
 
 def new_out_t(c: Case):
-    return torch.full((GUARD + math.prod(out_t_shape(c)) + GUARD,), SENTINEL_BITS, dtype=torch.int16).view(F16)
+    return kit.sentinel(GUARD + math.prod(out_t_shape(c)) + GUARD, F16)
 
 
 def new_colstats(c: Case):
-    return torch.full((GUARD + colstats_slots(c) * 2 * c.n + GUARD,), SENTINEL_BITS32, dtype=torch.int32).view(F32)
+    return kit.sentinel(GUARD + colstats_slots(c) * 2 * c.n + GUARD, F32)
 
 
 def new_workspace(c: Case):
@@ -804,10 +788,10 @@ CASES = _build_cases()
 
 
 # ---------------------------------------------------------------------------------------------------------------- refusals
-PTR = "a valid pointer"          # placeholder: an integer address (host test) or a small device tensor (GPU test)
+# (PTR, the kit's placeholder: an integer address in the host test, a small device tensor in the GPU test)
 REFUSAL_BASE = dict(batch=1, in_h=8, in_w=8, c0=64, n=64, taps=9)
 _OUT_T = dict(taps=1, c0=320, n=1280, batch=2, in_h=4, in_w=8, out_t=PTR, n_split=640, rows_per_sample=32, ldo_t=32, ldo=640)
-_PHASE = dict(taps=4, phase=1, in_h=4, in_w=8)
+PHASE_BASE = dict(taps=4, phase=1, in_h=4, in_w=8)
 # (text of coma_last_error, changes to REFUSAL_BASE): every refusal of sd_conv_gemm_f16 that a descriptor can reach, each through sizes and
 # flags alone.  The one that none can: "out_t: the ..-column tile of this shape does not divide n_split" -- n_split and n are multiples of
 # 640, so the tile is 320, 128 or 64 columns wide (the 256-wide tiles lose to the 320-wide one whenever N % 320 == 0); the check guards
@@ -820,16 +804,16 @@ REFUSALS = (
     ("phase must be 0..4", dict(phase=5, taps=4)),
     ("phase must be 0..4", dict(phase=-1)),
     ("a phase launch needs taps = 4", dict(phase=1)),                                        # taps = 9
-    ("a phase launch needs taps = 4", dict(_PHASE, stride=2)),
-    ("a phase launch needs taps = 4", dict(_PHASE, in_w=6)),                                 # not a power of two
-    ("a phase launch needs taps = 4", dict(_PHASE, out_h=8)),
-    ("a phase launch needs taps = 4", dict(_PHASE, n=68)),
-    ("a phase launch needs taps = 4", dict(_PHASE, ldo=68)),
-    ("a phase launch needs taps = 4", dict(_PHASE, res=PTR)),
-    ("a phase launch needs taps = 4", dict(_PHASE, bias_bn=PTR)),
-    ("a phase launch needs taps = 4", dict(_PHASE, epi=EPI_SILU)),
-    ("a phase launch needs taps = 4", dict(_PHASE, nbatch_z=2)),
-    ("the output of a phase launch must stay below 2 GiB", dict(_PHASE, in_h=1024, in_w=1024, n=256)),
+    ("a phase launch needs taps = 4", dict(PHASE_BASE, stride=2)),
+    ("a phase launch needs taps = 4", dict(PHASE_BASE, in_w=6)),                                 # not a power of two
+    ("a phase launch needs taps = 4", dict(PHASE_BASE, out_h=8)),
+    ("a phase launch needs taps = 4", dict(PHASE_BASE, n=68)),
+    ("a phase launch needs taps = 4", dict(PHASE_BASE, ldo=68)),
+    ("a phase launch needs taps = 4", dict(PHASE_BASE, res=PTR)),
+    ("a phase launch needs taps = 4", dict(PHASE_BASE, bias_bn=PTR)),
+    ("a phase launch needs taps = 4", dict(PHASE_BASE, epi=EPI_SILU)),
+    ("a phase launch needs taps = 4", dict(PHASE_BASE, nbatch_z=2)),
+    ("the output of a phase launch must stay below 2 GiB", dict(PHASE_BASE, in_h=1024, in_w=1024, n=256)),
     (r"taps must be 1 or 9 \(4 only with a phase\)", dict(taps=4)),
     ("taps must be 1 or 9", dict(taps=3)),
     ("stride must be 1 or 2", dict(stride=3)),
@@ -895,7 +879,7 @@ REFUSALS = (
     ("colstats needs M % 32 == 0", dict(colstats=PTR, n=128, epi=EPI_GEGLU)),
     ("colstats needs M % 32 == 0", dict(colstats=PTR, nbatch_z=2)),
     ("colstats needs M % 32 == 0", dict(colstats=PTR, taps=1, batch=32768, in_h=1, in_w=1, out_h=16, out_w=16, n=128)),   # (M + 512) ldo 2 >= 2 GiB
-    (r"colstats of a phase launch needs in_h \* in_w % 32 == 0", dict(_PHASE, colstats=PTR, batch=2, in_h=4, in_w=4)),
-    (r"colstats of a phase launch needs in_h \* in_w % 32 == 0", dict(_PHASE, colstats=PTR, batch=2, in_h=12, in_w=4)),
+    (r"colstats of a phase launch needs in_h \* in_w % 32 == 0", dict(PHASE_BASE, colstats=PTR, batch=2, in_h=4, in_w=4)),
+    (r"colstats of a phase launch needs in_h \* in_w % 32 == 0", dict(PHASE_BASE, colstats=PTR, batch=2, in_h=12, in_w=4)),
     ("grid too large", dict(taps=1, c0=32, batch=65536, in_h=1, in_w=1, out_h=128, out_w=128, n=1 << 20)),
 )

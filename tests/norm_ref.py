@@ -10,78 +10,41 @@ nothing here is product code and nothing here needs a GPU.
                        order), e_emu = the emulation's largest row error (each element's error over the largest |ref| of its output row), the
                        device bound max(4 e_emu, 2^-10), and the emulation's own a-priori bound (``stated``; the derivations are at the
                        functions that compute them).
-* ``pack`` / ``new_out``  flat buffers as the kernels see them: 256 NaN elements in front of and behind every operand, NaN gap columns,
-                       outputs filled with a sentinel NaN pattern and guarded exactly where the documented size ends.
+* ``inputs`` / ``outputs``  give tests/domain_kit.py's Operand / Out records; its pack / new_out / masks make of them the flat buffers as the
+                       kernels see them: 256 NaN elements in front of and behind every operand, NaN gap columns, outputs filled with a
+                       sentinel NaN pattern and guarded exactly where the documented size ends.
 * ``groupnorm_route``, ``layernorm_instantiation``, ``gn_wino_vec``, ``wino_output_kernel``  a transcript of the dispatch of the entry points,
                        written beside the table: which kernel a row reaches.  ``REACHABLE`` is every branch the entry points have.
-* ``REFUSALS``         per entry point: a base argument list that is accepted, and every change the argument checks refuse, with the text.
+* ``REFUSALS``         per entry point: a base argument list that is accepted, and every change the argument checks refuse, with the text;
+                       written with the kit's PTR / Off and put to the entry points by its check_refusals.
 
 DESIGN.md section 3e has the numbers."""
 from __future__ import annotations
 
 import functools
-import zlib
-from typing import NamedTuple, Optional
+from typing import NamedTuple
 
 import numpy as np
 import torch
 
-from coma_amd import _lib
+from tests import domain_kit as kit
+from tests.domain_kit import (F16, F32, F64, GUARD, PTR, U32, Operand, Out, body, device_bound, exp32, gen, masks, new_out, pack,  # noqa: F401
+                              randn16, row_error, sum32)            # (pack / new_out / masks: a case's buffers, also through this module)
 
-F16, F32, F64 = torch.float16, torch.float32, torch.float64
-GUARD = 256                      # NaN (operands) / sentinel (outputs) elements in front of and behind every buffer
-SENTINEL_BITS = 0x7E5A           # fp16 NaN payload fp16 outputs are prefilled with
-SENTINEL_BITS32 = 0x7FC5A5A5     # fp32 NaN payload fp32 outputs (stats, colstats) are prefilled with
-FLOOR = 2.0 ** -10               # one fp16 ulp of a row's largest value
-U32 = 2.0 ** -24                 # unit roundoff of fp32
 UD = 4 * U32                     # allowance for one fp32 division, rsqrt or reciprocal
 LIP = 1.1                        # Lipschitz constant of SiLU (1.0999)
 GN_MAX_C, GN_SMALL_ITEMS, GN_WINO_MAX_SLICE = 2560, 5120, 20480
+# fp32 operators of the oracle against float64: a few hundred fp32 roundings (statistics over up to 16 k elements, summed pairwise or
+# by vector lanes, then about ten operations per element) -> 2^-24 * 128 = 2^-17 of (1 + the output's largest value)
+ORACLE_LIMIT = 2.0 ** -17
 
 BT = torch.tensor([[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]], dtype=F64)
 GM = torch.tensor([[1, 0, 0], [.5, .5, .5], [.5, -.5, .5], [0, 0, 1]], dtype=F64)
 AT = torch.tensor([[1, 1, 1, 0], [0, 1, -1, -1]], dtype=F64)
 
 
-def _seed(name):
-    return zlib.crc32(name.encode())
-
-
-def _gen(name):
-    return torch.Generator().manual_seed(_seed(name))
-
-
-def _randn(g, *shape, scale=1.0, shift=0.0):
-    return (torch.randn(*shape, generator=g) * scale + shift).to(F16)
-
-
-def _exp32(v):
-    return torch.exp(v.to(F64)).to(F32)                 # a correctly rounded fp32 exp, whatever the host's vector library does
-
-
-def _silu(v):
-    """SiLU of fp32 or float64 `v` in its own precision, the exponential exact."""
-    return v / (1 + (torch.exp(-v) if v.dtype == F64 else _exp32(-v)))
-
-
-def _sum32(t, dim=-1):
-    """fp32 sum along `dim`, one addition after the other in index order (numpy's accumulate is a sequential fp32 loop;
-    tests/test_norm_ref_host.py checks that against a Python loop)."""
-    a = np.ascontiguousarray(t.to(F32).movedim(dim, -1).numpy())
-    return torch.from_numpy(np.add.accumulate(a, axis=-1, dtype=np.float32)[..., -1].copy())
-
-
-def row_error(got, ref):
-    """max over an output row of |got - ref| / max |ref| of that row -> [R].  A row whose reference is zero throughout (planes of an
-    upsampled image, where B^T d B subtracts a pixel from its own copy) has to be reproduced exactly: 0 if it is, inf if not."""
-    num, den = (got.to(F64) - ref).abs().amax(-1), ref.abs().amax(-1)
-    exact = torch.where(num > 0, torch.full_like(num, float("inf")), torch.zeros_like(num))
-    return torch.where(den > 0, num / den.clamp(min=1e-300), torch.where(num.isnan(), num, exact))
-
-
-def device_bound(e_emu):
-    """Four times the emulation's own error, never below one fp16 ulp of the row's largest value."""
-    return max(4.0 * e_emu, FLOOR)
+def close_to_oracle(ref, theirs):
+    return float((ref - theirs.to(F64)).abs().max()) <= ORACLE_LIMIT * (1 + float(ref.abs().max()))
 
 
 # ------------------------------------------------------------------------------------------------------------------ the table
@@ -352,61 +315,6 @@ CASES = _build_cases()
 
 
 # ------------------------------------------------------------------------------------------------------------------ operands
-class Operand(NamedTuple):
-    t: torch.Tensor             # [rows, width], fp16 or fp32
-    ld: int
-    off: int = 0                # extra NaN elements between the front guard and the data (a pointer moved off its alignment)
-
-
-class Out(NamedTuple):
-    rows: int
-    width: int
-    ld: int
-    dtype: torch.dtype
-    must: Optional[int] = None  # flat outputs (rows == 1): the first `must` elements have to be written, the others up to `width` may be
-
-
-def pack(op: Operand):
-    """guard | off | rows x ld with NaN gap columns | guard, everything outside the data NaN"""
-    r, wd = op.t.shape
-    buf = torch.full((GUARD + op.off + r * op.ld + GUARD,), float("nan"), dtype=op.t.dtype)
-    buf[GUARD + op.off:GUARD + op.off + r * op.ld].view(r, op.ld)[:, :wd] = op.t
-    return buf
-
-
-def sentinel(n, dtype):
-    if dtype == F16:
-        return torch.full((n,), SENTINEL_BITS, dtype=torch.int16).view(F16)
-    return torch.full((n,), SENTINEL_BITS32, dtype=torch.int32).view(F32)
-
-
-def new_out(o: Out):
-    return sentinel(GUARD + o.rows * o.ld + GUARD, o.dtype)
-
-
-def masks(o: Out):
-    """(must, may): elements of new_out(o) the launch has to write / is allowed to write"""
-    may = torch.zeros(GUARD + o.rows * o.ld + GUARD, dtype=torch.bool)
-    may[GUARD:GUARD + o.rows * o.ld].view(o.rows, o.ld)[:, :o.width] = True
-    if o.must is None:
-        return may, may
-    must = torch.zeros_like(may)
-    must[GUARD:GUARD + o.must] = True
-    return must, may
-
-
-def body(o: Out, buf):
-    return buf[GUARD:GUARD + o.rows * o.ld].view(o.rows, o.ld)[:, :o.width]
-
-
-def bits(t):
-    return t.view(torch.int16 if t.dtype == F16 else torch.int32)
-
-
-def sentinel_bits(dtype):
-    return SENTINEL_BITS if dtype == F16 else SENTINEL_BITS32
-
-
 def gn_stats_floats(c: GN):
     """the documented size of `stats`: the affine table, then the partial sums"""
     return c.B * c.C * 2 + c.B * -(-c.hw // 64) * c.G * 2
@@ -421,13 +329,13 @@ def _colsums(x, rps):
 @functools.lru_cache(maxsize=2)
 def inputs(c):
     """name -> Operand of everything the launch reads (and `x` of softmax, which it also writes)"""
-    g = _gen(c.id)
+    g = gen(c.id)
     if isinstance(c, GN):
         if c.dist == "const":
             x = torch.full((c.B * c.hw, c.C), 3.0, dtype=F16)
         else:
-            x = _randn(g, c.B * c.hw, c.C, scale=0.25 if c.dist == "shift" else 1.0, shift=8.0 if c.dist == "shift" else 0.0)
-        d = dict(gamma=Operand(_randn(g, 1, c.C, shift=1.0, scale=0.5), c.C), beta=Operand(_randn(g, 1, c.C), c.C))
+            x = randn16(g, c.B * c.hw, c.C, scale=0.25 if c.dist == "shift" else 1.0, shift=8.0 if c.dist == "shift" else 0.0)
+        d = dict(gamma=Operand(randn16(g, 1, c.C, shift=1.0, scale=0.5), c.C), beta=Operand(randn16(g, 1, c.C), c.C))
         if c.entry != "table_cat":
             d["x0"] = Operand(x[:, :c.c0].contiguous(), c.c0)
             if c.c1:
@@ -438,11 +346,11 @@ def inputs(c):
                 d["colstats1"] = Operand(_colsums(x[:, c.c0:], c.rps).view(-1, c.c1), c.c1)
         return d
     if isinstance(c, LN):
-        base = _randn(g, min(c.rows, 2048), c.c) * _randn(g, min(c.rows, 2048), 1, shift=1.5, scale=0.5) + _randn(g, min(c.rows, 2048), 1)
+        base = randn16(g, min(c.rows, 2048), c.c) * randn16(g, min(c.rows, 2048), 1, shift=1.5, scale=0.5) + randn16(g, min(c.rows, 2048), 1)
         x = base.repeat(-(-c.rows // base.shape[0]), 1)[:c.rows].contiguous()
-        return dict(x=Operand(x, c.c), gamma=Operand(_randn(g, 1, c.c, shift=1.0, scale=0.5), c.c), beta=Operand(_randn(g, 1, c.c), c.c))
+        return dict(x=Operand(x, c.c), gamma=Operand(randn16(g, 1, c.c, shift=1.0, scale=0.5), c.c), beta=Operand(randn16(g, 1, c.c), c.c))
     if isinstance(c, SM):
-        x = _randn(g, c.rows, c.n, scale=2.0)
+        x = randn16(g, c.rows, c.n, scale=2.0)
         if c.kind == "equal":
             x = x[:, :1].repeat(1, c.n)
         if c.kind == "underflow":
@@ -451,7 +359,7 @@ def inputs(c):
         return dict(x=Operand(x, c.n + c.dld))
     if isinstance(c, WI):
         hs, ws, C = c.h >> c.up, c.w >> c.up, c.c0 + c.c1
-        x = _randn(g, c.B * hs * ws, C)
+        x = randn16(g, c.B * hs * ws, C)
         d = dict(x0=Operand(x[:, :c.c0].contiguous(), c.c0))
         if c.c1:
             d["x1"] = Operand(x[:, c.c0:].contiguous(), c.c1)
@@ -460,30 +368,30 @@ def inputs(c):
             d["gn_affine"] = Operand(tab, 2)
         return d
     if isinstance(c, WW):
-        return dict(w=Operand(_randn(g, c.n * 9, c.c, scale=0.2), c.c))
+        return dict(w=Operand(randn16(g, c.n * 9, c.c, scale=0.2), c.c))
     if isinstance(c, WO):
         T = c.B * (c.h // 2) * (c.w // 2)
-        d = dict(m=Operand(_randn(g, 16 * T, c.n, scale=1.0 / c.mscale), c.n + c.dldm))
+        d = dict(m=Operand(randn16(g, 16 * T, c.n, scale=1.0 / c.mscale), c.n + c.dldm))
         if c.bias:
-            d["bias"] = Operand(_randn(g, 1, c.n), c.n)
+            d["bias"] = Operand(randn16(g, 1, c.n), c.n)
         if c.bias_bn:
-            d["bias_bn"] = Operand(_randn(g, c.B, c.n), c.n + c.dldbb)
+            d["bias_bn"] = Operand(randn16(g, c.B, c.n), c.n + c.dldbb)
         if c.res:
-            d["res"] = Operand(_randn(g, c.B * c.h * c.w, c.n), c.n + c.dldr)
+            d["res"] = Operand(randn16(g, c.B * c.h * c.w, c.n), c.n + c.dldr)
         return d
     C, hw = c.C, c.h * c.w
-    d = dict(gamma=Operand(_randn(g, 1, C, shift=1.0, scale=0.5), C, c.gamma_off), beta=Operand(_randn(g, 1, C), C))
+    d = dict(gamma=Operand(randn16(g, 1, C, shift=1.0, scale=0.5), C, c.gamma_off), beta=Operand(randn16(g, 1, C), C))
     if c.mode == 0:
-        x = _randn(g, c.B * hw, C, shift=0.5)
+        x = randn16(g, c.B * hw, C, shift=0.5)
         d["x0"] = Operand(x[:, :c.c0].contiguous(), c.c0)
         if c.c1:
             d["x1"] = Operand(x[:, c.c0:].contiguous(), c.c1)
     else:
-        d["m"] = Operand(_randn(g, 16 * c.B * hw // 4, C, scale=1.0 / c.mscale), C + c.dldm)
+        d["m"] = Operand(randn16(g, 16 * c.B * hw // 4, C, scale=1.0 / c.mscale), C + c.dldm)
         if c.bias:
-            d["bias"] = Operand(_randn(g, 1, C), C)
+            d["bias"] = Operand(randn16(g, 1, C), C)
         if c.bias_bn:
-            d["bias_bn"] = Operand(_randn(g, c.B, C), C + c.dldbb)
+            d["bias_bn"] = Operand(randn16(g, c.B, C), C + c.dldbb)
     return d
 
 
@@ -552,7 +460,7 @@ class Result(NamedTuple):
                                 # every summation order)
 
 
-def _final16(ref, err):
+def final16(ref, err):
     """a-priori bound after the last fp16 rounding: `err` bounds the fp32 value to first order, 1.002 covers what first order leaves out
     (the rounding acts on the computed value: 2^-11 err; each 2^-24 acts on a computed partial), 2^-25 = half the fp16 subnormal spacing"""
     return 1.002 * err + 2.0 ** -11 * ref.abs() + 2.0 ** -25
@@ -561,7 +469,7 @@ def _final16(ref, err):
 def _gn_sums(c, terms):
     """terms [B, G, n] -> (float64 sum, sum of magnitudes, fp32 sum in index order)"""
     t64 = terms.to(F64)
-    return t64.sum(-1), t64.abs().sum(-1), _sum32(terms).to(F64)
+    return t64.sum(-1), t64.abs().sum(-1), sum32(terms).to(F64)
 
 
 def gn_statistics(c, d, x=None, e_x=None):
@@ -641,12 +549,12 @@ def gn_apply(c, x, aff, silu, e_x=None):
     err = err + U32 * (y.abs() + err)
     y32 = (x64 * sc32.to(F64)[:, None] + sh32.to(F64)[:, None]).to(F32)                # fmaf: one rounding
     if silu:
-        y, y32 = _silu(y), _silu(y32)
+        y, y32 = kit.silu(y), kit.silu(y32)
         err = LIP * err + 8 * U32 * y.abs()
     return y.view(-1, C), y32.view(-1, C), err.view(-1, C)
 
 
-def _cat(d):
+def cat(d):
     return torch.cat([d[k].t for k in ("x0", "x1") if k in d], -1)
 
 
@@ -709,7 +617,7 @@ def wino_output(m, B, h, w, mscale, bias, bias_bn, res, silu):
     y, y32 = Y + add64, Y32 + add32
     err = 8 * U32 * mag
     if silu:
-        y, y32 = _silu(y), _silu(y32)
+        y, y32 = kit.silu(y), kit.silu(y32)
         err = LIP * err + 8 * U32 * y.abs()
     y, y32, err = (v.reshape(B * h * w, n) for v in (y, y32, err))
     if res is not None:
@@ -718,7 +626,7 @@ def wino_output(m, B, h, w, mscale, bias, bias_bn, res, silu):
     return y, y32, err
 
 
-def _ulp16(v):
+def ulp16(v):
     """a bound of the distance between the fp16 roundings of two values near v that straddle a rounding boundary: one fp16 ulp"""
     return 2.0 ** -10 * v.abs() + 2.0 ** -24
 
@@ -728,14 +636,14 @@ def results(c):
     """output name -> Result"""
     d = inputs(c)
     if isinstance(c, GN):
-        x = None if c.entry == "table_cat" else _cat(d) if c.entry != "table_cs" and c.entry != "table" else d["x0"].t
+        x = None if c.entry == "table_cat" else cat(d) if c.entry != "table_cs" and c.entry != "table" else d["x0"].t
         st = gn_statistics(c, d, x)
         aff = gn_affine(c, st, d["gamma"].t, d["beta"].t)
         sc, sh, sc32, sh32, e_sc, e_sh = aff
         out = {}
         if c.entry in ("gn", "gn_cs"):
             y, y32, err = gn_apply(c, x, aff, c.silu)
-            out["out"] = Result(y, y32.to(F16), _final16(y, err))
+            out["out"] = Result(y, y32.to(F16), final16(y, err))
         else:
             tab = lambda a, b: torch.stack([a, b], -1).reshape(-1, 2)
             out["stats"] = Result(tab(sc, sh), tab(sc32, sh32), 1.002 * tab(e_sc, e_sh) + 2.0 ** -126)
@@ -746,7 +654,7 @@ def results(c):
         return dict(x=softmax(d["x"].t, c.scale))
     if isinstance(c, WI):
         hs, ws, C = c.h >> c.up, c.w >> c.up, c.c0 + c.c1
-        x, e_img = _cat(d), None
+        x, e_img = cat(d), None
         img = x.view(c.B, hs, ws, C)
         img32 = img
         if c.affine:                                            # storage point: the activated tensor is rounded to fp16 before the transform
@@ -756,14 +664,14 @@ def results(c):
             y32 = y.to(F32)                                     # fmaf of exact inputs: the float64 value rounded once
             e = U32 * y.abs()
             if c.silu:
-                y, y32, e = _silu(y), _silu(y32), LIP * e + 8 * U32 * _silu(y).abs()
+                y, y32, e = kit.silu(y), kit.silu(y32), LIP * e + 8 * U32 * kit.silu(y).abs()
             img, img32 = y.to(F16), y32.to(F16)
-            e_img = _ulp16(y)                                   # the two roundings differ by at most one fp16 ulp
+            e_img = ulp16(y)                                   # the two roundings differ by at most one fp16 ulp
         if c.up:
             rep = lambda t: None if t is None else t.repeat_interleave(2, 1).repeat_interleave(2, 2)
             img, img32, e_img = rep(img), rep(img32), rep(e_img)
         V, _, err = wino_input(img, c.vscale, e_img)
-        return dict(v=Result(V, wino_input32(img32, c.vscale), _final16(V, err)))
+        return dict(v=Result(V, wino_input32(img32, c.vscale), final16(V, err)))
     if isinstance(c, WW):
         g = d["w"].t.view(c.n, 3, 3, c.c)
         U = c.uscale * torch.einsum("ak,nklc,bl->abnc", GM, g.to(F64), GM).reshape(16 * c.n, c.c)
@@ -775,20 +683,20 @@ def results(c):
         u32 = torch.stack([us * t[:, :, 0], us * (half * ((t[:, :, 0] + t[:, :, 1]) + t[:, :, 2])), us * (half * ((t[:, :, 0] - t[:, :, 1]) + t[:, :, 2])),
                            us * t[:, :, 2]], 2)                 # [n, a, b, c]
         # two levels of three-term sums: 4 roundings of partial sums bounded by |G| |g| |G^T| (the halvings and the scale are exact)
-        return dict(u=Result(U, u32.permute(1, 2, 0, 3).reshape(16 * c.n, c.c).to(F16), _final16(U, 4 * U32 * mag)))
+        return dict(u=Result(U, u32.permute(1, 2, 0, 3).reshape(16 * c.n, c.c).to(F16), final16(U, 4 * U32 * mag)))
     if isinstance(c, WO):
         get = lambda k: d[k].t if k in d else None
         y, y32, err = wino_output(d["m"].t, c.B, c.h, c.w, c.mscale, get("bias"), get("bias_bn"), get("res"), c.silu)
-        return dict(out=Result(y, y32.to(F16), _final16(y, err)))
+        return dict(out=Result(y, y32.to(F16), final16(y, err)))
     # ---- GroupNorm + Winograd input in one launch
     e_x = None
     if c.mode == 0:
-        x = x_emu = _cat(d)
+        x = x_emu = cat(d)
     else:                                                       # storage point: mscale A^T m A + bias + bias_bn is rounded to fp16 before the statistics
         get = lambda k: d[k].t if k in d else None
         y, y32, err = wino_output(d["m"].t, c.B, c.h, c.w, c.mscale, get("bias"), get("bias_bn"), None, 0)
         x, x_emu = y.to(F16), y32.to(F16)
-        e_x = torch.where(x == x_emu, torch.zeros_like(y), _ulp16(y))
+        e_x = torch.where(x == x_emu, torch.zeros_like(y), ulp16(y))
     st_ref = gn_statistics(c, d, x, None)
     aff_ref = gn_affine(c, st_ref, d["gamma"].t, d["beta"].t)
     aff_emu = gn_affine(c, gn_statistics(c, d, x_emu), d["gamma"].t, d["beta"].t)
@@ -798,9 +706,9 @@ def results(c):
     _, _, err = gn_apply(c, x, aff_b, c.silu, e_x)
     _, y32, _ = gn_apply(c, x_emu, aff_emu, c.silu)
     act, act32 = y.to(F16), y32.to(F16)                         # storage point: the activated tensor
-    e_img = (err + _ulp16(y)).view(c.B, c.h, c.w, c.C)
+    e_img = (err + ulp16(y)).view(c.B, c.h, c.w, c.C)
     V, _, verr = wino_input(act.view(c.B, c.h, c.w, c.C), 1.0, e_img)
-    return dict(v=Result(V, wino_input32(act32.view(c.B, c.h, c.w, c.C)), _final16(V, verr)))
+    return dict(v=Result(V, wino_input32(act32.view(c.B, c.h, c.w, c.C)), final16(V, verr)))
 
 
 def layernorm(x, gamma, beta, eps):
@@ -823,12 +731,12 @@ def layernorm(x, gamma, beta, eps):
     e_rstd = rstd * (0.5 * et / (t - et) + UD)
     err = ga.abs() * (rstd * ed + dd.abs() * e_rstd) + 3 * U32 * ((dd * rstd * ga).abs() + y.abs())
     x32, C32 = x.to(F32), torch.tensor(float(C), dtype=F32)
-    mean32 = (_sum32(x32) / C32)[:, None]
+    mean32 = (sum32(x32) / C32)[:, None]
     d32 = x32 - mean32
-    var32 = _sum32(d32 * d32) / C32
+    var32 = sum32(d32 * d32) / C32
     rstd32 = ((var32 + torch.tensor(eps, dtype=F32)).to(F64) ** -0.5).to(F32)[:, None]
     y32 = d32 * rstd32 * gamma.to(F32) + beta.to(F32)
-    return Result(y, y32.to(F16), _final16(y, err))
+    return Result(y, y32.to(F16), final16(y, err))
 
 
 def softmax(x, scale):
@@ -843,9 +751,9 @@ def softmax(x, scale):
     a = U32 * (t.abs() + m.abs() + (t - m).abs()) + U32
     rel = a + (n - 1) * U32 + a.amax(-1, keepdim=True) + UD + U32
     t32 = x.to(F32) * torch.tensor(scale, dtype=F32)
-    e32 = _exp32(t32 - t32.amax(-1, keepdim=True))
-    inv = (1.0 / _sum32(e32).to(F64)).to(F32)[:, None]
-    return Result(ref, (e32 * inv).to(F16), _final16(ref, ref * rel))
+    e32 = exp32(t32 - t32.amax(-1, keepdim=True))
+    inv = (1.0 / sum32(e32).to(F64)).to(F32)[:, None]
+    return Result(ref, (e32 * inv).to(F16), final16(ref, ref * rel))
 
 
 class Yardstick(NamedTuple):
@@ -864,7 +772,7 @@ def compared_rows(c):
         pick = torch.zeros(c.rows, dtype=torch.bool)
         pick[:300] = True
         pick[-300:] = True
-        pick[torch.randperm(c.rows, generator=_gen(c.id + "/rows"))[:256]] = True
+        pick[torch.randperm(c.rows, generator=gen(c.id + "/rows"))[:256]] = True
         return torch.nonzero(pick).flatten()
     return None
 
@@ -902,20 +810,6 @@ def colstats_expected(c: WO, out_buf):
 
 
 # ------------------------------------------------------------------------------------------------------------------ refusals
-class _Ptr:
-    def __repr__(self):
-        return "PTR"
-
-
-PTR = _Ptr()        # "a valid non-null pointer": the tests put a dummy address (CPU) or a small device buffer (GPU) here
-
-
-class Off(NamedTuple):
-    """a valid pointer moved by `bytes`"""
-    bytes: int
-
-
-
 OUTPUT_ARGS = {"out", "stats", "v", "u"}        # (softmax's x is written in place)
 
 _GN = dict(x0=PTR, x1=None, c0=16, c1=0, batch=1, hw=32, groups=2, eps=1e-5, gamma=PTR, beta=PTR, silu=1, out=PTR, stats=PTR)
@@ -997,15 +891,3 @@ REFUSALS = {
         ("ldm = 18", dict(_GW1, ldm=18)), ("ldm = 8", dict(_GW1, ldm=8)),
         ("ldbb = 8 must be", dict(_GW1, bias_bn=PTR, ldbb=8)), ("ldbb = 18 must be", dict(_GW1, bias_bn=PTR, ldbb=18))]),
 }
-
-
-def call(lib, entry, kw, resolve):
-    """entry(**kw, stream = NULL) through the ctypes library, the keywords in the order of the header's own parameter names
-    (_lib.PARAMS); resolve(name) -> the address to put where kw says PTR; Off(b) is that address + b"""
-    *names, last = _lib.PARAMS[entry]
-    assert last == "stream", entry
-    args = []
-    for name in names:
-        v = kw[name]
-        args.append(resolve(name) if v is PTR else resolve(name) + v.bytes if isinstance(v, Off) else v)
-    return getattr(lib, entry)(*args, None)

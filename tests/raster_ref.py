@@ -50,11 +50,11 @@ def snap(verts, R, t, scale, W, H):
     return su.astype(np.int64), sv.astype(np.int64), cz
 
 
-def _edge(Px, Py, Qx, Qy, x, y):
+def edge(Px, Py, Qx, Qy, x, y):
     return (Qx - Px) * (y - Py) - (Qy - Py) * (x - Px)
 
 
-def _owns_ties(Px, Py, Qx, Qy):
+def owns_ties(Px, Py, Qx, Qy):
     dx, dy = Qx - Px, Qy - Py
     return dy < 0 or (dy == 0 and dx > 0)
 
@@ -70,7 +70,7 @@ def raster_depth(verts, faces, R, t, scale, W, H):
     for ia, ib, ic in faces.tolist():
         ax, ay, bx, by, cx, cy = X[ia], Y[ia], X[ib], Y[ib], X[ic], Y[ic]
         za, zb, zc = Z[ia], Z[ib], Z[ic]
-        area = _edge(ax, ay, bx, by, cx, cy)
+        area = edge(ax, ay, bx, by, cx, cy)
         if area == 0:
             continue
         if area < 0:
@@ -81,8 +81,8 @@ def raster_depth(verts, faces, R, t, scale, W, H):
             continue
         px = (256 * np.arange(x0, x1 + 1, dtype=np.int64) + 128)[None, :]
         py = (256 * np.arange(y0, y1 + 1, dtype=np.int64) + 128)[:, None]
-        e0, e1, e2 = _edge(bx, by, cx, cy, px, py), _edge(cx, cy, ax, ay, px, py), _edge(ax, ay, bx, by, px, py)
-        t0, t1, t2 = _owns_ties(bx, by, cx, cy), _owns_ties(cx, cy, ax, ay), _owns_ties(ax, ay, bx, by)
+        e0, e1, e2 = edge(bx, by, cx, cy, px, py), edge(cx, cy, ax, ay, px, py), edge(ax, ay, bx, by, px, py)
+        t0, t1, t2 = owns_ties(bx, by, cx, cy), owns_ties(cx, cy, ax, ay), owns_ties(ax, ay, bx, by)
         inside = ((e0 > 0) | ((e0 == 0) & t0)) & ((e1 > 0) | ((e1 == 0) & t1)) & ((e2 > 0) | ((e2 == 0) & t2))
         if not inside.any():
             continue

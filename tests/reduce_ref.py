@@ -5,7 +5,8 @@ CPU only: the table of launches (CASES), what each reaches (branches), its opera
 float64 / np.longdouble NumPy written from the reference's formulas (reference; oracle/coma_oracle.py and oracle/triangulation_oracle.py
 hold the same formulas and tests/test_reduce_ref_host.py compares), the kernel's own formula in its own precision and summation shape
 (emulate: lane-strided partial sums, then the xor butterfly), the assertions the device is held to (check), and every argument check
-(REFUSALS).  tests/test_coma_small_domain_gpu.py launches the table; tests/test_reduce_ref_host.py checks the table itself.
+(REFUSALS, written with tests/domain_kit.py's PTR; the guard width, the sentinels, pack_rows and the seeds are the kit's too).
+tests/test_coma_small_domain_gpu.py launches the table; tests/test_reduce_ref_host.py checks the table itself.
 
 The bound.  Bit for bit (NaN-ness compared for NaNs): pairs / col_any / row_any, the masked maximum (a maximum rounds nothing), idx and
 val of the row argmax, contact_select (one correctly rounded f32 division per element, then comparisons), the nearest vertex (f64, no
@@ -16,37 +17,21 @@ on the same case, norm the sum of magnitudes of the formula's terms, floor the c
 import ctypes
 import functools
 import math
-import zlib
 from typing import NamedTuple, Optional
 
 import numpy as np
 
 from coma_amd import _lib
-from tests import norm_ref as nr
-from tests.norm_ref import PTR, call  # noqa: F401  (the refusal rows are written with norm_ref's PTR and put through its call())
+from tests import domain_kit as kit
+from tests.domain_kit import PTR, U32, bits, sentinel
 
 f32, f64, i32, i64, u8 = np.float32, np.float64, np.int32, np.int64, np.uint8
-GUARD = nr.GUARD
-U32, U64 = 2.0 ** -24, 2.0 ** -53
+U64 = 2.0 ** -53
 WAVE, ROW_WAVES = 64, 4
 NAN, INF = float("nan"), float("inf")
-# what outputs are pre-filled with: NaNs with a payload for the floats, 0xA5 bytes for the integers (no result of the table equals one)
-SENTINEL = {np.dtype(f32): np.array([nr.SENTINEL_BITS32], np.uint32).view(f32)[0], np.dtype(f64): np.array([0x7FF8A5A5A5A5A5A5], np.uint64).view(f64)[0],
-            np.dtype(i64): np.array([0xA5A5A5A5A5A5A5A5], np.uint64).view(i64)[0], np.dtype(i32): np.array([0xA5A5A5A5], np.uint32).view(i32)[0],
-            np.dtype(u8): u8(0xA5)}
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({1: np.uint8, 4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
-
-
-def sentinel(n, dtype):
-    return np.full(n, SENTINEL[np.dtype(dtype)], dtype=dtype)
-
-
-def _rng(name):
-    return np.random.default_rng(zlib.crc32(name.encode()))
+# what outputs are pre-filled with (the kit's sentinels): NaNs with a payload for the floats, 0xA5 bytes for the integers (no result of
+# the table equals one)
+SENTINEL = {np.dtype(t): sentinel(1, t)[0] for t in (f32, f64, i64, i32, u8)}
 
 
 class Case:
@@ -129,7 +114,7 @@ CASES = _build_cases()
 ENTRIES = sorted({c.entry for c in CASES})
 
 
-def _one_cell(H, O):
+def one_cell(H, O):
     """the cell of a `one` mask: the last row (>= 4 where H allows) and a column past the first lane stride / workgroup where O allows"""
     return H - 1, (O - 1 if O > 256 else 64 + (O - 65) // 2 if O > 64 else O - 1)
 
@@ -164,7 +149,7 @@ def branches(c):
         if w is None and c.H * c.O > 256:
             b.add(f"{tag}:pairs-second-workgroup")
         if c.mask == "one":
-            h0, o0 = _one_cell(c.H, c.O)
+            h0, o0 = one_cell(c.H, c.O)
             b |= {f"{tag}:only-column-past-{t}" for t in (64, 256) if o0 >= t} | ({f"{tag}:only-row-past-4"} if h0 >= 4 else set())
     elif e == "contact_select_u8":
         b |= {f"{e}:threshold-equal", f"{e}:nan-path"} if c.H * c.O > 1 else set()
@@ -346,7 +331,7 @@ def csr(faces, V):
 @functools.lru_cache(maxsize=None)
 def _data(cid):
     c = BY_ID[cid]
-    e, g = c.entry[5:], _rng(cid)
+    e, g = c.entry[5:], kit.rng(cid)
     if e in ("contact_map_f32", "entropy_f32"):
         prob = _histogram_rows(g, c.M, c.N, c.n_bin, e == "contact_map_f32")
         if (c.M, c.N) == (2, 8):
@@ -368,7 +353,7 @@ def _data(cid):
             cnt = np.minimum(cnt, 4).astype(f32)
         if c.mask == "one":
             cnt = np.minimum(cnt, 4).astype(f32)
-            cnt[_one_cell(H, O)] = thr                          # equal to the threshold: >= sets it
+            cnt[one_cell(H, O)] = thr                          # equal to the threshold: >= sets it
         if c.mask == "random" and H * O > 1:
             cnt[H // 2, O // 2] = NAN                           # NaN >= thr is false
             cnt[0, 0] = thr
@@ -451,8 +436,8 @@ def _data(cid):
             verts[v, 1] = NAN
         return dict(points=pts, verts=verts)
     if e == "vertex_normals_f64":
-        v, faces = _mesh(_rng(f"mesh-{c.V}"), c.V)
-        gs = _rng(f"samples-{c.V}")                             # (the same samples for every eps and for the poisoned twin)
+        v, faces = _mesh(kit.rng(f"mesh-{c.V}"), c.V)
+        gs = kit.rng(f"samples-{c.V}")                             # (the same samples for every eps and for the poisoned twin)
         verts = np.stack([v] + [v + gs.normal(scale=0.03, size=v.shape) for _ in range(c.S - 1)])
         if c.V > 4:
             verts[:, 43:46] = [[0, 0, 0], [1, 1, 1], [2, 2, 2]]
@@ -500,9 +485,7 @@ class Out(NamedTuple):
 
 
 def pack(body, guard_value):
-    buf = np.full(body.size + 2 * GUARD, guard_value, dtype=body.dtype)
-    buf[GUARD:GUARD + body.size] = body.reshape(-1)
-    return buf
+    return kit.pack_rows(body.reshape(-1), guard_value)
 
 
 def _out(n, dtype, written=True, finite=True, init=None):
@@ -583,7 +566,7 @@ def arguments(c, ptr):
 
 
 def launch(lib, c, ptr):
-    return call(lib, c.entry, arguments(c, ptr), None)
+    return kit.call(lib, c.entry, arguments(c, ptr), None)
 
 
 # ------------------------------------------------------------------------------------------------------------------ the kernels' summation shapes

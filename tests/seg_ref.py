@@ -1,6 +1,7 @@
 """Case tables and references of the domain tests of the person-segmentation kernels (coma_amd/csrc/seg_gemm.hip, seg_ops.hip): what
 tests/test_seg_gemm_domain_gpu.py and tests/test_seg_ops_domain_gpu.py launch, and what tests/test_seg_ref_host.py checks on the CPU.  No
-GPU is needed to import this module.
+GPU is needed to import this module.  The guards (at this suite's width of 64), the sentinels, the seeds and the refusal rows' PTR are
+tests/domain_kit.py's.
 
 Every case is one launch (or one short chain) with an id.  make_*_inputs draws the operands from a generator seeded by the id; every
 operand element the contract says is not read is NaN (integer buffers: an index no reference could use), every output starts as SENTINEL
@@ -12,8 +13,8 @@ t = (real k terms) + 3: the forward bound of ANY fp32 summation order with one r
 included.  The integer family (operands in [-4, 4]) keeps every partial sum below 2^24, so any order is exact: bit for bit."""
 from __future__ import annotations
 
+import functools
 import math
-import zlib
 from dataclasses import dataclass, replace
 from typing import Optional, Tuple
 
@@ -22,45 +23,24 @@ import torch
 import torch.nn.functional as F
 
 from oracle import seg_oracle as so
+from tests import domain_kit as kit
+from tests.domain_kit import PTR, U32 as U
 
 F32, F64, I32, I64, U8 = torch.float32, torch.float64, torch.int32, torch.int64, torch.uint8
-U = 2.0 ** -24
 GUARD = 64                                   # elements in front of and behind every device buffer (a multiple of 16 bytes for every type)
-SENTINEL_BITS = 0x7FC5A5A5                   # a quiet NaN no kernel produces
 NAN = float("nan")
+seed_of, rng_of, gen_of = kit.seed, kit.rng, kit.gen            # (case id, salt) -> the crc32 seed / a numpy / a torch generator
+# the kit's guards, at this suite's width: NaN for floats, `fill` (default -1 / 0xA5 for bytes) for integers
+guarded, guards_intact = functools.partial(kit.guarded, guard=GUARD), functools.partial(kit.guards_intact, guard=GUARD)
 
 
 def gamma(t):
     return t * U / (1.0 - t * U)
 
 
-def seed_of(case_id, salt=0):
-    return zlib.crc32(case_id.encode()) + salt
-
-
 def sentinel(*shape):
-    """An fp32 tensor of SENTINEL."""
-    return torch.full(shape, SENTINEL_BITS, dtype=I32).view(F32)
-
-
-def bits(t):
-    """The bit patterns of a tensor as integers of its width."""
-    return t.view({4: I32, 8: I64, 1: U8, 2: torch.int16}[t.element_size()]) if t.dtype.is_floating_point else t
-
-
-def guarded(body, fill=None):
-    """body flattened between two guards: NaN for floats, `fill` (default -1 / 0xA5 for bytes) for integers."""
-    body = body.contiguous().reshape(-1)
-    if fill is None:
-        fill = NAN if body.dtype.is_floating_point else (0xA5 if body.dtype == U8 else -1)
-    g = torch.full((GUARD,), fill, dtype=body.dtype)
-    return torch.cat([g, body, g])
-
-
-def guards_intact(flat, fill=None):
-    """Both guards of a buffer built by guarded() still hold their fill, bit for bit."""
-    g = guarded(flat[GUARD:-GUARD].new_zeros(0), fill) if fill is not None else guarded(flat.new_zeros(0))
-    return torch.equal(bits(flat[:GUARD]), bits(g[:GUARD])) and torch.equal(bits(flat[-GUARD:]), bits(g[GUARD:]))
+    """An fp32 tensor of the sentinel, a quiet NaN no kernel produces."""
+    return kit.sentinel(math.prod(shape), F32).view(shape)
 
 
 # ====================================================================================================================== the fp32 GEMM
@@ -332,7 +312,6 @@ def gemm_fake_tensors(c):
 
 
 # (text the refusal must contain, changes to GEMM_REFUSAL_BASE); PTR = any valid address
-PTR = object()
 GEMM_REFUSAL_BASE = dict(x=PTR, w=PTR, out=PTR, batch=1, in_h=4, in_w=4, c=32, n=16, kpad=32)
 GEMM_REFUSALS = [
     ("null pointer", dict(x=None)),
@@ -406,20 +385,11 @@ def level_boundary_boxes():
 
 
 # ====================================================================================================================== the operators
-SENT_I32 = -1515870811                      # 0xA5A5A5A5
-SENT_U8 = 0xA5
+SENT_I32, SENT_U8 = kit.sentinel_bits(I32), kit.sentinel_bits(U8)     # 0xA5A5A5A5 (as int32: negative), 0xA5
 
 
 def sentinel_i32(*shape):
-    return torch.full(shape, SENT_I32, dtype=I32)
-
-
-def rng_of(case_id, salt=0):
-    return np.random.default_rng(seed_of(case_id, salt))
-
-
-def gen_of(case_id, salt=0):
-    return torch.Generator().manual_seed(seed_of(case_id, salt))
+    return kit.sentinel(math.prod(shape), I32).view(shape)
 
 
 def desc_keys(scores, low):

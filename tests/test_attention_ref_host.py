@@ -7,6 +7,7 @@ import torch
 
 from oracle import sd_oracle as so
 from tests import attention_ref as ar
+from tests import domain_kit as kit
 
 F16 = torch.float16
 
@@ -56,14 +57,14 @@ def test_packed_buffers_poison_everything_the_contract_leaves_unread():
     buf = ar.pack_rows(q, C + 16, col0=8)
     body = buf[8:8 + B * L * (C + 16)].view(B, L, C + 16)
     assert torch.equal(body[:, :, :C], q) and bool(body[:, :, C:].isnan().all())
-    assert bool(buf[:8].isnan().all()) and bool(buf[8 + B * L * (C + 16):].isnan().all()) and buf.numel() == 8 + B * L * (C + 16) + ar.GUARD
+    assert bool(buf[:8].isnan().all()) and bool(buf[8 + B * L * (C + 16):].isnan().all()) and buf.numel() == 8 + B * L * (C + 16) + kit.GUARD
     qk = ar.pack_fused_qk(q, k)
     body = qk[:B * L * 2 * C].view(B, L, 2 * C)
     assert torch.equal(body[:, :, :C], q) and torch.equal(body[:, :, C:], k)
     assert bool(qk[B * L * 2 * C:].isnan().all())
     out = ar.new_out(B, L, C + 8)
     written, rest = ar.split_out(out, B, L, C, C + 8)
-    assert bool(written.isnan().all()) and rest.numel() == B * L * 8 + ar.GUARD and bool((rest == ar.SENTINEL_BITS).all())
+    assert bool(written.isnan().all()) and rest.numel() == B * L * 8 + kit.GUARD and bool((rest == kit.sentinel_bits(F16)).all())
 
 
 def test_the_table_reaches_every_kernel_of_the_file():

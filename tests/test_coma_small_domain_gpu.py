@@ -13,19 +13,16 @@ measured device error); (b) everything the contract says is written is free of t
 bits; (d) a second launch into fresh buffers gives the same bits.  Float operands sit between NaN guards and everything the contract
 says is not read is NaN (contact outside the mask, a row outside [col_offset, col_offset + n)), so a read outside the contract fails (a)
 or (b).  Every case is inside the accepted domain; two launches and one synchronize per case."""
-import ctypes
-import re
-
 import numpy as np
 import pytest
 import torch
 
+from tests import domain_kit as kit
 from tests import reduce_ref as rr
 
-COMA_E_INVALID = -1
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-G = rr.GUARD
+G = kit.GUARD
 
 
 def _upload(buf):
@@ -37,23 +34,16 @@ def _body_ptr(t):
 
 
 def launch_twice(lib, c, ins, outs):
-    """Two launches of the case, each into fresh outputs, then ONE synchronize -> two dicts name -> device buffer (guards included).
-    A refusal by the argument checks fails its own case; any other error ends the session: nothing more is started on the device."""
-    both = []
-    try:
-        for _ in range(2):
-            bufs = {name: _upload(rr.pack(o.init, rr.SENTINEL[o.init.dtype])) for name, o in outs.items()}
-            rc = rr.launch(lib, c, {**{k: _body_ptr(t) for k, t in ins.items()}, **{k: _body_ptr(t) for k, t in bufs.items()}})
-            if rc != 0:
-                msg = lib.coma_last_error().decode()
-                if rc == COMA_E_INVALID:
-                    pytest.fail(f"{c.id}: refused inside the accepted domain: {msg}")
-                raise RuntimeError(f"{c.entry} returned {rc}: {msg}")
-            both.append(bufs)
-        torch.cuda.synchronize()
-    except Exception as e:
-        pytest.exit(f"{c.id}: {type(e).__name__}: {e}", returncode=3)
-    return both
+    """Two launches of the case through the C ABI, each into fresh outputs -> two dicts name -> device buffer (guards included).  The fault
+    policy is the kit's: here a refusal is a return code, which fails the case; any other code ends the session."""
+    def launch(bufs):
+        rc = rr.launch(lib, c, {**{k: _body_ptr(t) for k, t in ins.items()}, **{k: _body_ptr(t) for k, t in bufs.items()}})
+        if rc == kit.COMA_E_INVALID:
+            pytest.fail(f"{c.id}: refused inside the accepted domain: {lib.coma_last_error().decode()}")
+        if rc != 0:
+            raise RuntimeError(f"{c.entry} returned {rc}: {lib.coma_last_error().decode()}")
+
+    return kit.launch_twice(lambda: {name: _upload(rr.pack(o.init, rr.SENTINEL[o.init.dtype])) for name, o in outs.items()}, launch, c.id)
 
 
 @pytest.mark.parametrize("case", rr.CASES, ids=lambda c: c.id)
@@ -68,11 +58,11 @@ def test_small_domain(hip_lib, case):
     for name, o in outs.items():
         buf, again = first[name].cpu().numpy(), second[name].cpu().numpy()
         start = rr.pack(o.init, rr.SENTINEL[o.init.dtype])
-        assert np.array_equal(rr.bits(buf[:G]), rr.bits(start[:G])) and np.array_equal(rr.bits(buf[-G:]), rr.bits(start[-G:])), f"(c) a guard of `{name}` was written"
-        assert np.array_equal(rr.bits(buf), rr.bits(again)), f"(d) the second launch differs in `{name}`"
+        assert np.array_equal(kit.bits(buf[:G]), kit.bits(start[:G])) and np.array_equal(kit.bits(buf[-G:]), kit.bits(start[-G:])), f"(c) a guard of `{name}` was written"
+        assert np.array_equal(kit.bits(buf), kit.bits(again)), f"(d) the second launch differs in `{name}`"
         got[name] = buf[G:-G]
     for k, i in pins.items():                                   # operands come back as they went in
-        assert np.array_equal(rr.bits(ins[k].cpu().numpy()), rr.bits(rr.pack(i.body, i.poison))), f"operand `{k}` was written"
+        assert np.array_equal(kit.bits(ins[k].cpu().numpy()), kit.bits(rr.pack(i.body, i.poison))), f"operand `{k}` was written"
     fig = rr.check(c, got)                                      # (a), (b), and (c) inside the bodies
     for name, f in fig.items():
         print(f"SMALL_DOMAIN {c.id} entry={c.entry} out={name} e_emu={f.e_emu:.3e} bound={f.bound:.3e} device={f.err:.3e}")
@@ -86,20 +76,6 @@ def test_refusals_are_reported_not_launched(hip_lib):
     and the text, and every output buffer keeps its sentinel.  tests/test_reduce_ref_host.py has put the same rows to the same entry points
     on the CPU, where a wrongly accepted row cannot launch."""
     assert torch.cuda.is_available()
-    small = torch.zeros(1 << 16, dtype=torch.float32, device=DEV)
-    start = rr.sentinel(1 << 16, np.float32)
-    outs = {name: _upload(start) for name in rr.OUTPUT_ARGS}
-    vec = (ctypes.c_float * 3)(0.0, 0.0, 1.0)                   # principle_vec is read on the host
-    resolve = lambda name: ctypes.addressof(vec) if name in rr.HOST_ARGS else (outs[name] if name in outs else small).data_ptr()
-    n = 0
-    for entry, (base, rows) in sorted(rr.REFUSALS.items()):
-        for text, change in rows:
-            rc = rr.call(hip_lib, entry, {**base, **change}, resolve)
-            msg = hip_lib.coma_last_error().decode()
-            assert rc == COMA_E_INVALID and re.search(re.escape(entry) + ": .*" + re.escape(text), msg), (entry, change, rc, msg)
-            n += 1
-    assert n == sum(len(rows) for _, rows in rr.REFUSALS.values()) and n >= 80
-    torch.cuda.synchronize()
-    for name, buf in outs.items():
-        assert np.array_equal(rr.bits(buf.cpu().numpy()), rr.bits(start)), name
-    assert not bool(small.cpu().any())
+    resolve, outs, small = kit.device_resolver(rr.OUTPUT_ARGS, rr.HOST_ARGS)
+    assert kit.check_refusals(hip_lib, rr.REFUSALS, resolve, expect_control=False) >= 80
+    kit.refusal_outputs_untouched(outs, small)

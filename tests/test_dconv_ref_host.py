@@ -5,8 +5,6 @@ through the REAL entry points with dummy non-null pointers: the argument checks 
 returns COMA_E_INVALID with its text and a wrongly accepted one fails at launch with another code.  The per-case yardstick e_emu (and
 with it the bound tests/test_sd_dconv_domain_gpu.py holds the device to) is printed here, without a GPU:
 `pytest -s tests/test_dconv_ref_host.py`."""
-import re
-
 import pytest
 import torch
 import torch.nn.functional as F
@@ -14,11 +12,11 @@ import torch.nn.functional as F
 from coma_amd import _lib
 from oracle import sd_oracle as so
 from tests import dconv_ref as dr
+from tests import domain_kit as kit
 from tests import norm_ref as nr
-from tests.test_norm_ref_host import ORACLE_LIMIT, _close, _resolver
 
 F16, F32, F64 = torch.float16, torch.float32, torch.float64
-COMA_E_INVALID = -1
+_close = nr.close_to_oracle
 
 
 def _conv2d64(a, w, B, h, wd):
@@ -42,8 +40,8 @@ def test_reference_is_conv2d_and_the_emulation_is_within_its_stated_bound(case):
             for tap in range(9):
                 yy, xx = py + tap // 3 - 1, px + tap % 3 - 1
                 want = x[b, yy, xx] if 0 <= yy < c.h and 0 <= xx < c.w else torch.zeros(3, dtype=F16)
-                assert torch.equal(nr.bits(r.emu[m, 3 * tap:3 * tap + 3]), nr.bits(want.contiguous())), (m, tap)
-        assert not bool(nr.bits(r.emu[:, 27:]).any())
+                assert torch.equal(kit.bits(r.emu[m, 3 * tap:3 * tap + 3]), kit.bits(want.contiguous())), (m, tap)
+        assert not bool(kit.bits(r.emu[:, 27:]).any())
     else:
         if isinstance(c, dr.C3):
             theirs = _conv2d64(d["x"].t, d["w32"].t[:, :27].reshape(c.n, 9, 3), c.B, c.h, c.w)
@@ -66,49 +64,49 @@ def test_reference_agrees_with_the_oracle(silu):
     against the oracle's groupnorm_ref, and the convolution of the stored tensor against the oracle's conv_ref."""
     g = torch.Generator().manual_seed(11 + silu)
     B, h, wd, C, n, G = 2, 16, 32, 64, 128, 32
-    x = nr._randn(g, B * h * wd, C, scale=1.5, shift=0.3)
-    gamma, beta = nr._randn(g, C, shift=1.0, scale=0.5), nr._randn(g, C)
+    x = kit.randn16(g, B * h * wd, C, scale=1.5, shift=0.3)
+    gamma, beta = kit.randn16(g, C, shift=1.0, scale=0.5), kit.randn16(g, C)
     xg = x.to(F64).view(B, h * wd, G, C // G)
     mean, var = xg.mean((1, 3), keepdim=True), xg.var((1, 3), unbiased=False, keepdim=True)
     sc = ((var + 1e-6) ** -0.5).expand(B, 1, G, C // G).reshape(B, C) * gamma.to(F64)
     sh = beta.to(F64) - mean.expand(B, 1, G, C // G).reshape(B, C) * sc
     tab = torch.stack([sc, sh], -1).reshape(B * C, 2)
     y, _, _ = dr.activate(x, tab, B, 2 if silu else 1)
-    assert ORACLE_LIMIT == 2.0 ** -17 and _close(y, so.groupnorm_ref(x, gamma, beta, batch=B, hw=h * wd, groups=G, eps=1e-6, silu=silu))
+    assert nr.ORACLE_LIMIT == 2.0 ** -17 and _close(y, so.groupnorm_ref(x, gamma, beta, batch=B, hw=h * wd, groups=G, eps=1e-6, silu=silu))
     a = y.to(F16)
-    w, bias, res = nr._randn(g, n, 9, C, scale=(9 * C) ** -0.5), nr._randn(g, n), nr._randn(g, B * h * wd, n)
+    w, bias, res = kit.randn16(g, n, 9, C, scale=(9 * C) ** -0.5), kit.randn16(g, n), kit.randn16(g, B * h * wd, n)
     ref, _, _ = dr.convolve(a, a, torch.zeros(a.shape, dtype=F64), w, B, h, wd, dr.CHUNK, bias[None], res)
     assert _close(ref, so.conv_ref(a.float(), w, batch=B, h=h, w_=wd, taps=9, bias=bias, res=res))
 
 
 def test_packed_buffers_poison_everything_the_contract_leaves_unread():
-    G = nr.GUARD
+    G = kit.GUARD
     by_id = {c.id: c for c in dr.CASES}
     c = by_id["halo-n256-ldo+8-ldr+24"]
     d, o = dr.inputs(c), dr.outputs(c)
     M = c.B * c.h * c.w
-    res = nr.pack(d["res"])
+    res = kit.pack(d["res"])
     assert d["res"].ld == 280 and res.numel() == 2 * G + M * 280 and int(res.isnan().sum()) == 2 * G + M * 24
     for name in ("x", "w", "bias", "gn_affine"):
-        buf = nr.pack(d[name])
+        buf = kit.pack(d[name])
         assert int(buf.isnan().sum()) == 2 * G and bool(buf[:G].isnan().all()) and bool(buf[-G:].isnan().all()), name
-    must, may = nr.masks(o["out"])
+    must, may = kit.masks(o["out"])
     assert o["out"].ld == 264 and int(must.sum()) == M * 256 and not bool(must[G:-G].view(M, 264)[:, 256:].any())
-    assert o["colstats"].rows == c.B * 2 * 2 and o["colstats"].dtype == F32 and bool(nr.new_out(o["colstats"]).isnan().all())
+    assert o["colstats"].rows == c.B * 2 * 2 and o["colstats"].dtype == F32 and bool(kit.new_out(o["colstats"]).isnan().all())
     # small_n: rows of w and entries of bias at and beyond n; 8 channels of a pixel owned, the others of ldo = 72 not
     s = by_id["small_n-ldo72-c320-n4"]
     d, o = dr.inputs(s), dr.outputs(s)
     assert d["w"].t.shape == (16, 9 * 320) and bool(d["w"].t[4:].isnan().all()) and not bool(d["w"].t[:4].isnan().any())
     assert d["bias"].t.shape == (1, 8) and bool(d["bias"].t[0, 4:].isnan().all())
-    assert int(nr.masks(o["out"])[0].sum()) == s.h * s.w * 8 and o["out"].ld == 72
+    assert int(kit.masks(o["out"])[0].sum()) == s.h * s.w * 8 and o["out"].ld == 72
     # the 3-channel image: channels 3 .. ldx - 1 NaN; w32 keeps its five zero columns
     t = next(x for x in dr.CASES if isinstance(x, dr.C3) and x.ldx == 64)
     d = dr.inputs(t)
-    xb = nr.pack(d["x"])[G:-G].view(-1, 64)
+    xb = kit.pack(d["x"])[G:-G].view(-1, 64)
     assert bool(xb[:, 3:].isnan().all()) and not bool(xb[:, :3].isnan().any()) and not bool(d["w32"].t[:, 27:].any()) and bool(d["w32"].t[:, :27].any())
     # im2col: signed zeros in the data
     i = dr.inputs(by_id["im2col-11x13-b2-block-crossings"])["x"].t
-    assert int((nr.bits(i) == -0x8000).sum()) > 10 and int((nr.bits(i) == 0).sum()) > 10
+    assert int((kit.bits(i) == -0x8000).sum()) > 10 and int((kit.bits(i) == 0).sum()) > 10
 
 
 def test_stress_tables_hold_what_they_name_and_stay_finite():
@@ -119,8 +117,8 @@ def test_stress_tables_hold_what_they_name_and_stay_finite():
         tab = d["gn_affine"].t.view(c.B, c.c, 2)
         assert bool((tab[:, 2, 0] == 0).all()) and bool((tab[:, 3, 0] < 0).all())
         if c.act == 2:
-            assert float(y[:, :, 0].abs().max()) < 1e-38 and bool((nr.bits(y32[:, :, 0].to(F16)) == -0x8000).all())       # exp overflows: -0
-            assert bool((y[:, :, 2] == nr._silu(tab[:, None, 2, 1].to(F64))).all())
+            assert float(y[:, :, 0].abs().max()) < 1e-38 and bool((kit.bits(y32[:, :, 0].to(F16)) == -0x8000).all())       # exp overflows: -0
+            assert bool((y[:, :, 2] == kit.silu(tab[:, None, 2, 1].to(F64))).all())
         else:
             assert float(y[:, :, 0].max()) < -95
         assert float(y[:, :, 1].min()) > 195 and float(y[:, :, c.c - 1].mean()) > 2 and float(y[:, :, 2].min()) > 1.5
@@ -163,13 +161,6 @@ def test_the_table_reaches_every_branch_of_the_four_kernels():
 @pytest.mark.parametrize("entry", sorted(dr.REFUSALS), ids=str)
 def test_every_refusal_gives_its_code_and_text_through_the_entry_point(entry, hip_lib):
     base, rows = dr.REFUSALS[entry]
-    _dummy = _resolver()
     assert len(rows) >= 10 and set(base) == set(_lib.PARAMS[entry][:-1])      # the header's own parameter names
-    for text, change in rows:
-        rc = dr.call(hip_lib, entry, {**base, **change}, _dummy)
-        msg = hip_lib.coma_last_error().decode()
-        assert rc == COMA_E_INVALID and re.search(re.escape(entry) + ": .*" + re.escape(text), msg), (entry, change, rc, msg)
     # the control: the base row passes every argument check and only fails where the launch needs a device
-    if not torch.cuda.is_available():
-        rc = dr.call(hip_lib, entry, dict(base), _dummy)
-        assert rc not in (0, COMA_E_INVALID), (entry, rc, hip_lib.coma_last_error().decode())
+    kit.check_refusals(hip_lib, {entry: dr.REFUSALS[entry]}, kit.host_resolver(), expect_control=not torch.cuda.is_available())

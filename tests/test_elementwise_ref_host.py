@@ -6,7 +6,6 @@ through the REAL entry points with dummy non-null pointers: the argument checks 
 row returns COMA_E_INVALID with its text and a wrongly accepted one fails at launch with another code.  The per-case yardstick e_emu is
 printed here, without a GPU: `pytest -s tests/test_elementwise_ref_host.py`."""
 import os
-import re
 
 import numpy as np
 import pytest
@@ -14,14 +13,12 @@ import torch
 
 from coma_amd import _lib
 from oracle import sd_oracle as so
+from tests import domain_kit as kit
 from tests import elementwise_ref as er
-from tests import norm_ref as nr
-from tests.test_norm_ref_host import _resolver
 
-COMA_E_INVALID = -1
 f16, f32, f64 = np.float16, np.float32, np.float64
 BY_ID = {c.id: c for c in er.CASES}
-G = er.GUARD
+G = kit.GUARD
 
 
 def _bodies(c, src):
@@ -60,15 +57,15 @@ def test_conversions_by_bits_are_torchs_and_numpys():
     h = np.arange(1 << 16, dtype=np.uint16)
     h = h[(h & 0x7FFF) <= 0x7C00]
     mine = er.f16_bits_to_f32(h)
-    assert np.array_equal(er.bits(mine), er.bits(h.view(f16).astype(f32)))
+    assert np.array_equal(kit.bits(mine), kit.bits(h.view(f16).astype(f32)))
     assert torch.equal(torch.from_numpy(mine).view(torch.int32), torch.from_numpy(h.view(f16).copy()).float().view(torch.int32))
     g = np.random.default_rng(3)
-    x = np.concatenate([er.SPECIAL32, er._interesting32(g, 200000), (mine.astype(f64) * (1 + 2.0 ** -11)).astype(f32), np.nextafter(mine, f32(np.inf)),
+    x = np.concatenate([er.SPECIAL32, er.interesting32(g, 200000), (mine.astype(f64) * (1 + 2.0 ** -11)).astype(f32), np.nextafter(mine, f32(np.inf)),
                         np.nextafter(mine, f32(-np.inf)), ((mine.astype(f64) + np.roll(mine, 1).astype(f64)) / 2).astype(f32)])
     x = x[~np.isnan(x)]
     got = er.f32_to_f16_bits(x)
     with np.errstate(over="ignore"):
-        assert np.array_equal(got, er.bits(x.astype(f16)))
+        assert np.array_equal(got, kit.bits(x.astype(f16)))
     assert torch.equal(torch.from_numpy(got.view(np.int16)), torch.from_numpy(x).to(torch.float16).view(torch.int16))
     b = lambda v: int(er.f32_to_f16_bits(np.array([v], f32))[0])
     assert b(65520.0) == 0x7C00 and b(-65520.0) == 0xFC00 and b(65519.996) == 0x7BFF and b(2.0 ** -25) == 0 and b(1.5 * 2.0 ** -24) == 2
@@ -92,7 +89,7 @@ def test_ddim_reference_is_the_oracles():
     assert (last["alpha_t"], last["alpha_prev"]) == (float(alphas[1]), float(alphas[0]))
     for c in (x for x in er.CASES if isinstance(x, er.DD) and x.mode != "step"):
         d = er.data(c)
-        both = np.concatenate([er.bits(d["mask"]), er.bits(d["masked"]).reshape(-1)])
+        both = np.concatenate([kit.bits(d["mask"]), kit.bits(d["masked"]).reshape(-1)])
         if c.B * c.hw > 100:
             assert (both == 0x8000).any() and (both == 0).any() and ((both & 0x7C00 == 0) & (both & 0x3FF != 0)).any(), c.id     # -0, +0, subnormals
     p1, p0, t1 = (er.data(BY_ID[i]) for i in ("ddim-n257-ld72-g11-prev1", "ddim-n513-ld64-prev0", "ddim-n256-ld8-t1"))
@@ -121,7 +118,7 @@ def test_layout_references_are_torchs_permute_and_conversion():
     for c in (x for x in er.CASES if isinstance(x, er.NH)):
         x = torch.from_numpy(er.data(c)["x"].copy()).view(c.B, c.hw, c.c)
         theirs = x.permute(0, 2, 1).float().reshape(1, -1)
-        assert np.array_equal(er.bits(er.reference(c)["out"]), er.bits(theirs.numpy())), c.id
+        assert np.array_equal(kit.bits(er.reference(c)["out"]), kit.bits(theirs.numpy())), c.id
         assert bool(er.plan(c)[0]["x"].buf[G:-G].view(-1, c.ld)[:, c.c:].isnan().all())
     every = np.concatenate([er.f32_to_f16_bits(er.data(c)["x"]) for c in er.CASES if isinstance(c, er.NC)])
     assert {0, 0x8000, 0x7C00, 0xFC00, 1, 2, 0x3C00, 0x3C02}.issubset(set(every.tolist()))
@@ -132,7 +129,7 @@ def test_image_table_is_exhaustive_and_lands_on_ties():
     x = er.data(c)["x"]
     assert x.shape == (er.N_F16, 3) and er.N_F16 == 63490
     for ch in range(3):
-        assert np.unique(er.bits(x[:, ch])).size == er.N_F16
+        assert np.unique(kit.bits(x[:, ch])).size == er.N_F16
     v = np.clip(x[:, 0].astype(f64) * 0.5 + 0.5, 0, 1) * 255                                   # float64: exact for the halved value, one rounding away for the product
     v32 = (np.clip(x[:, 0].astype(f32) * f32(0.5) + f32(0.5), 0, 1) * f32(255)).astype(f64)
     ties = v32[(v32 - np.floor(v32)) == 0.5]
@@ -140,7 +137,7 @@ def test_image_table_is_exhaustive_and_lands_on_ties():
     print(f"ELEMENTWISE_U8 values landing on k + 0.5: {sorted(set(ties.tolist()))}")
     r, t = er.emulate(c)["out"][:, 0], er.emulate(BY_ID["u8-ld64-trunc"])["out"][:, 0]
     assert np.array_equal(t, np.floor(v32).astype(np.uint8)) and np.array_equal(r, np.rint(v32).astype(np.uint8))
-    assert int(r[er.bits(x[:, 0]) == 0][0]) == 128 and int(t[er.bits(x[:, 0]) == 0][0]) == 127
+    assert int(r[kit.bits(x[:, 0]) == 0][0]) == 128 and int(t[kit.bits(x[:, 0]) == 0][0]) == 127
     assert int((r != t).sum()) > 10000 and int(np.abs(r.astype(int) - np.rint(v)).max()) <= 1
     assert bool(er.plan(c)[0]["x"].buf[G:-G].view(-1, 64)[:, 3:].isnan().all())
 
@@ -237,7 +234,7 @@ def test_the_poison_is_effective():
     assert not np.array_equal(stray, er.reference(tx)["out"][row])
     # outputs: the sentinel everywhere, guards and gap columns outside `must`
     o = er.plan(BY_ID["causal-len65-h1"])[1]["out"]
-    assert o.off == 1 and bool((nr.bits(o.buf) == nr.SENTINEL_BITS).all()) and int(o.must.sum()) == 65 * 64 and not bool(o.must[:G + 1].any())
+    assert o.off == 1 and bool((kit.bits(o.buf) == kit.sentinel_bits(o.buf.dtype)).all()) and int(o.must.sum()) == 65 * 64 and not bool(o.must[:G + 1].any())
     assert not bool(o.must[G + 1:G + 1 + 65 * 67].view(65, 67)[:, 64:].any())
     m = er.plan(BY_ID["maskB-8x8-k8-one-pad64"])[1]["masked"]
     assert int(m.must.sum()) == 64 * 8 and int(er.plan(BY_ID["maskB-16x264-k264-one-pad64w"])[1]["masked"].must.sum()) == 16 * 264 * 64
@@ -259,7 +256,7 @@ def test_text_and_causal_references_are_torchs():
         s = s.masked_fill(torch.triu(torch.ones(c.len, c.len, dtype=torch.bool), 1), float("-inf"))
         theirs = (torch.softmax(s, -1) @ v).transpose(1, 2).reshape(c.seqs * c.len, c.heads * 64).numpy()
         assert float(np.abs(r.ref - theirs).max()) <= 1e-12 * float(np.abs(theirs).max()), c.id
-        ldq, ldk, ldv = er._ca_lds(c)
+        ldq, ldk, ldv = er.ca_lds(c)
         w = c.heads * 64
         assert all(ld >= w and ld % 8 == 0 for ld in (ldq, ldk, ldv)) and (c.layout == "packed" or len({ldq, ldk, ldv}) == 3)
     sharp = er.reference(BY_ID["causal-len128-h12-s2-sharp"])["out"]
@@ -329,16 +326,9 @@ def test_a_broken_kernel_fails_a_named_case(mut):
 @pytest.mark.parametrize("entry", sorted(er.REFUSALS), ids=str)
 def test_every_refusal_gives_its_code_and_text_through_the_entry_point(entry, hip_lib):
     base, rows = er.REFUSALS[entry]
-    _dummy = _resolver()
     assert len(rows) >= 7 and set(base) == set(_lib.PARAMS[entry][:-1])       # the header's own parameter names
-    for text, change in rows:
-        rc = er.call(hip_lib, entry, {**base, **change}, _dummy)
-        msg = hip_lib.coma_last_error().decode()
-        assert rc == COMA_E_INVALID and re.search(re.escape(entry) + ": .*" + re.escape(text), msg), (entry, change, rc, msg)
     # the control: the base row passes every argument check and only fails where the launch needs a device
-    if not torch.cuda.is_available():
-        rc = er.call(hip_lib, entry, dict(base), _dummy)
-        assert rc not in (0, COMA_E_INVALID), (entry, rc, hip_lib.coma_last_error().decode())
+    kit.check_refusals(hip_lib, {entry: er.REFUSALS[entry]}, kit.host_resolver(), expect_control=not torch.cuda.is_available())
 
 
 def test_the_area_limit_is_where_the_int32_sum_ends():

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import domain_kit as kit
 from tests import gemm_ref as gr
 
 F16, F64 = torch.float16, torch.float64
@@ -61,7 +62,7 @@ def test_two_sources_are_their_concatenation():
     inp = gr.make_inputs(c)
     assert float((gr.reference(c, inp) - _seven_loops(c, inp)).abs().max()) <= 1e-12
     pk = gr.pack(c, inp)
-    G = gr.GUARD
+    G = kit.GUARD
     assert torch.equal(pk.a0[G:-G].view(12, 32), inp.x[0].reshape(12, 96)[:, :32]) and torch.equal(pk.a1[G:-G].view(12, 64), inp.x[0].reshape(12, 96)[:, 32:])
 
 
@@ -96,7 +97,7 @@ def test_perm_and_geglu_helpers_agree_with_the_products():
 
 def test_packed_buffers_poison_everything_the_contract_leaves_unread():
     c = next(x for x in gr.CASES if x.name == "z-gap-both")
-    inp, G = gr.make_inputs(c), gr.GUARD
+    inp, G = gr.make_inputs(c), kit.GUARD
     pk = gr.pack(c, inp)
     sa, sw, so, _ = c.strides()
     npix = c.B * c.H * c.W
@@ -110,8 +111,8 @@ def test_packed_buffers_poison_everything_the_contract_leaves_unread():
     out = gr.new_out(c)
     m = gr.written_mask(c)
     assert m.numel() == out.numel() and int(m.sum()) == c.nz * c.M * c.n and not bool(m[:G].any()) and not bool(m[-G:].any())
-    assert bool((out.view(torch.int16) == gr.SENTINEL_BITS).all()) and bool(gr.new_workspace(c2).isnan().all())
-    assert bool((gr.new_colstats(c2).view(torch.int32) == gr.SENTINEL_BITS32).all())
+    assert bool((kit.bits(out) == kit.sentinel_bits(out.dtype)).all()) and bool(gr.new_workspace(c2).isnan().all())
+    assert bool((kit.bits(gr.new_colstats(c2)) == kit.sentinel_bits(torch.float32)).all())
 
 
 def test_sampled_rows_hold_what_they_must():
@@ -180,7 +181,7 @@ def test_reachable_is_what_a_sweep_of_describe_produces(ops):
 
 
 def _resolve(kw, ptr):
-    return {k: (ptr(k) if v is gr.PTR else v) for k, v in kw.items()}
+    return {k: (ptr(k) if v is kit.PTR else v) for k, v in kw.items()}
 
 
 def test_every_refusal_gives_its_code_and_text_through_describe(ops, hip_lib):

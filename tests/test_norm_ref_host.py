@@ -5,8 +5,6 @@ and every refusal row through the REAL entry points with dummy non-null pointers
 device a refused row returns COMA_E_INVALID with its text and a wrongly accepted one fails at launch with another code.  The per-case
 yardstick e_emu (and with it the bound tests/test_sd_norm_domain_gpu.py holds the device to) is printed here, without a GPU:
 `pytest -s tests/test_norm_ref_host.py`."""
-import re
-
 import numpy as np
 import pytest
 import torch
@@ -14,22 +12,16 @@ import torch.nn.functional as F
 
 from coma_amd import _lib
 from oracle import sd_oracle as so
+from tests import domain_kit as kit
 from tests import norm_ref as nr
 
 F16, F32, F64 = torch.float16, torch.float32, torch.float64
-COMA_E_INVALID = -1
-# fp32 operators of the oracle against float64: a few hundred fp32 roundings (statistics over up to 16 k elements, summed pairwise or
-# by vector lanes, then about ten operations per element) -> 2^-24 * 128 = 2^-17 of (1 + the output's largest value)
-ORACLE_LIMIT = 2.0 ** -17
-
-
-def _close(ref, theirs):
-    return float((ref - theirs.to(F64)).abs().max()) <= ORACLE_LIMIT * (1 + float(ref.abs().max()))
+_close = nr.close_to_oracle
 
 
 def test_sum32_adds_in_index_order():
     x = (torch.randn(3, 5000, generator=torch.Generator().manual_seed(1)) * 3 + 1).to(F32)
-    got = nr._sum32(x)
+    got = kit.sum32(x)
     for r in range(3):
         s = np.float32(0)
         for v in x[r].numpy():
@@ -43,7 +35,7 @@ def test_sum32_adds_in_index_order():
 def test_groupnorm_reference_agrees_with_the_oracle(case):
     c, d = case, nr.inputs(case)
     ref = nr.results(c)["out"].ref
-    theirs = so.groupnorm_ref(nr._cat(d), d["gamma"].t[0], d["beta"].t[0], batch=c.B, hw=c.hw, groups=c.G, eps=c.eps, silu=bool(c.silu))
+    theirs = so.groupnorm_ref(nr.cat(d), d["gamma"].t[0], d["beta"].t[0], batch=c.B, hw=c.hw, groups=c.G, eps=c.eps, silu=bool(c.silu))
     assert ref.dtype == F64 and ref.shape == theirs.shape and _close(ref, theirs)
 
 
@@ -51,7 +43,7 @@ def test_column_sum_statistics_are_the_tensor_statistics():
     """a GroupNorm fed by column sums against the oracle on the tensor: the fp32 column sums carry 2^-24 of each slot's sum"""
     c = next(x for x in nr.CASES if x.id == "gn_cs-c8-c24-g2")
     d = nr.inputs(c)
-    theirs = so.groupnorm_ref(nr._cat(d), d["gamma"].t[0], d["beta"].t[0], batch=c.B, hw=c.hw, groups=c.G, eps=c.eps, silu=True)
+    theirs = so.groupnorm_ref(nr.cat(d), d["gamma"].t[0], d["beta"].t[0], batch=c.B, hw=c.hw, groups=c.G, eps=c.eps, silu=True)
     assert _close(nr.results(c)["out"].ref, theirs)
     t = next(x for x in nr.CASES if x.id == "table_cs-cg16-rps256")
     d = nr.inputs(t)
@@ -90,8 +82,8 @@ def test_winograd_chain_is_the_direct_convolution(up):
     """input transform -> 16 plane products -> output transform, all float64, against the direct convolution and against the oracle's"""
     g = torch.Generator().manual_seed(7 + up)
     B, h, wd, C, n = 2, 4 << up, 6 << up, 16, 8
-    src = nr._randn(g, B, h >> up, wd >> up, C)
-    w = nr._randn(g, n, 9, C, scale=0.2)
+    src = kit.randn16(g, B, h >> up, wd >> up, C)
+    w = kit.randn16(g, n, 9, C, scale=0.2)
     img = src.repeat_interleave(2, 1).repeat_interleave(2, 2) if up else src
     T = B * (h // 2) * (wd // 2)
     V = nr.wino_input(img, 0.25)[0].view(16, T, C)
@@ -108,32 +100,32 @@ def test_winograd_chain_is_the_direct_convolution(up):
 
 
 def test_packed_buffers_poison_everything_the_contract_leaves_unread():
-    G = nr.GUARD
+    G = kit.GUARD
     c = next(x for x in nr.CASES if x.id == "wino_out-cs-h4-n256-all")
     d, o = nr.inputs(c), nr.outputs(c)
     for name, ld in (("m", c.n + 8), ("res", c.n + 16), ("bias_bn", c.n + 8), ("bias", c.n)):
-        buf = nr.pack(d[name])
+        buf = kit.pack(d[name])
         r = d[name].t.shape[0]
         assert d[name].ld == ld and buf.numel() == 2 * G + r * ld and bool(buf[:G].isnan().all()) and bool(buf[-G:].isnan().all())
         b2 = buf[G:-G].view(r, ld)
         assert torch.equal(b2[:, :c.n], d[name].t) and bool(b2[:, c.n:].isnan().all()) and int(buf.isnan().sum()) == 2 * G + r * (ld - c.n)
-    out = nr.new_out(o["out"])
-    must, may = nr.masks(o["out"])
-    assert bool((nr.bits(out) == nr.SENTINEL_BITS).all()) and bool(out.isnan().all()) and int(must.sum()) == c.B * c.h * c.w * c.n
+    out = kit.new_out(o["out"])
+    must, may = kit.masks(o["out"])
+    assert bool((kit.bits(out) == kit.sentinel_bits(F16)).all()) and bool(out.isnan().all()) and int(must.sum()) == c.B * c.h * c.w * c.n
     assert not bool(must[:G].any()) and not bool(must[-G:].any()) and not bool(must[G:-G].view(-1, c.n + 8)[:, c.n:].any()) and must is may
-    cs = nr.new_out(o["colstats"])
-    assert cs.numel() == 2 * G + c.B * c.h * c.w // 32 * 2 * c.n and bool((nr.bits(cs) == nr.SENTINEL_BITS32).all()) and bool(cs.isnan().all())
+    cs = kit.new_out(o["colstats"])
+    assert cs.numel() == 2 * G + c.B * c.h * c.w // 32 * 2 * c.n and bool((kit.bits(cs) == kit.sentinel_bits(F32)).all()) and bool(cs.isnan().all())
     # stats: guarded exactly where batch * C * 2 + batch * ceil(hw / 64) * groups * 2 floats end; only the table has to be written
     t = next(x for x in nr.CASES if x.id == "table-hw65-c320")
     st = nr.outputs(t)["stats"]
-    must, may = nr.masks(st)
+    must, may = kit.masks(st)
     assert st.width == 2 * 320 * 2 + 2 * 2 * 32 * 2 and int(may.sum()) == st.width and int(must.sum()) == 2 * 320 * 2 and bool(must[G:G + 1280].all())
     assert nr.outputs(next(x for x in nr.CASES if x.id == "gn-hw65-c320"))["stats"].must == 0
     # a pointer moved off its alignment: the halves in front of it are NaN too; softmax's buffer carries its data between NaN gap columns
     gm = nr.inputs(next(x for x in nr.CASES if x.id == "gn_wino-m0-cg8-gamma+4"))["gamma"]
-    assert gm.off == 4 and bool(nr.pack(gm)[:G + 4].isnan().all()) and torch.equal(nr.pack(gm)[G + 4:-G], gm.t[0])
+    assert gm.off == 4 and bool(kit.pack(gm)[:G + 4].isnan().all()) and torch.equal(kit.pack(gm)[G + 4:-G], gm.t[0])
     s = next(x for x in nr.CASES if x.id == "softmax-n7-ld+3")
-    assert int(nr.pack(nr.inputs(s)["x"]).isnan().sum()) == 2 * G + s.rows * 3
+    assert int(kit.pack(nr.inputs(s)["x"]).isnan().sum()) == 2 * G + s.rows * 3
 
 
 def test_the_table_reaches_every_branch_of_the_ten_entry_points():
@@ -169,24 +161,9 @@ def test_emulation_is_within_its_stated_bound(case):
     assert y.bound == max(4 * y.e_emu, 2.0 ** -10) and 0 <= y.e_emu < 2.0 ** -6            # a yardstick this loose would measure nothing
 
 
-def _resolver():
-    """PTR -> a dummy address that is never dereferenced; on a machine with a device, small real buffers instead"""
-    if not torch.cuda.is_available():
-        return lambda name: 0x7000000000 + 0x1000 * (sum(name.encode()) % 251)
-    keep = {}
-    return lambda name: keep.setdefault(name, torch.zeros(1 << 16, dtype=F32, device="cuda")).data_ptr()
-
-
 @pytest.mark.parametrize("entry", sorted(nr.REFUSALS), ids=str)
 def test_every_refusal_gives_its_code_and_text_through_the_entry_point(entry, hip_lib):
     base, rows = nr.REFUSALS[entry]
-    _dummy = _resolver()
     assert len(rows) >= 5 and set(base) == set(_lib.PARAMS[entry][:-1])       # the header's own parameter names
-    for text, change in rows:
-        rc = nr.call(hip_lib, entry, {**base, **change}, _dummy)
-        msg = hip_lib.coma_last_error().decode()
-        assert rc == COMA_E_INVALID and re.search(re.escape(entry) + ": .*" + re.escape(text), msg), (entry, change, rc, msg)
     # the control: the base row passes every argument check and only fails where the launch needs a device
-    if not torch.cuda.is_available():
-        rc = nr.call(hip_lib, entry, dict(base), _dummy)
-        assert rc not in (0, COMA_E_INVALID), (entry, rc, hip_lib.coma_last_error().decode())
+    kit.check_refusals(hip_lib, {entry: nr.REFUSALS[entry]}, kit.host_resolver(), expect_control=not torch.cuda.is_available())

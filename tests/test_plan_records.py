@@ -10,9 +10,9 @@ import os
 import pytest
 import torch
 
+from tests.domain_kit import COMA_E_INVALID
 from tests.golden import make_plan_records as gen
 
-COMA_E_INVALID = -1
 SD_EPI_ALL = 1 | 2 | 4 | 8 | 16 | 32        # include/sd_hip.h: GEGLU | SILU | BIAS_ROWS | PERM16_N | PERM32_N | QUICK_GELU
 
 

@@ -5,9 +5,6 @@ very assertions the device is held to, the poison, that each deliberately broken
 the REAL entry points with dummy non-null pointers (the argument checks run before any HIP call, so without a device a refused row
 returns COMA_E_INVALID with its text and a wrongly accepted one fails at launch with another code), and the host-side index checks of
 coma_amd/triangulate.py.  The per-case yardstick e_emu is printed here, without a GPU: `pytest -s tests/test_reduce_ref_host.py`."""
-import ctypes
-import re
-
 import numpy as np
 import pytest
 import torch
@@ -15,10 +12,9 @@ import torch
 from coma_amd import _lib
 from oracle import coma_oracle as orc
 from oracle import triangulation_oracle as T
+from tests import domain_kit as kit
 from tests import reduce_ref as rr
-from tests.test_norm_ref_host import _resolver
 
-COMA_E_INVALID = -1
 f32, f64 = np.float32, np.float64
 BY_ID = rr.BY_ID
 
@@ -83,10 +79,10 @@ def test_the_data_holds_what_the_table_says():
         if c.mask == "none":
             assert not d["pairs"].any()
         elif c.mask == "one":
-            assert int(d["pairs"].sum()) == 1 and d["pairs"][rr._one_cell(c.H, c.O)] == 1 and d["cnt"][rr._one_cell(c.H, c.O)] == d["thr"]
+            assert int(d["pairs"].sum()) == 1 and d["pairs"][rr.one_cell(c.H, c.O)] == 1 and d["cnt"][rr.one_cell(c.H, c.O)] == d["thr"]
         elif c.H * c.O > 1:
             assert np.isnan(d["cnt"]).sum() == 1 and bool((d["cnt"] == d["thr"]).any()) and 0 < d["pairs"].sum() < d["pairs"].size
-    assert rr._one_cell(4, 257) == (3, 256) and rr._one_cell(7, 300) == (6, 299) and rr._one_cell(5, 65)[1] == 64 and rr._one_cell(130, 3)[0] == 129
+    assert rr.one_cell(4, 257) == (3, 256) and rr.one_cell(7, 300) == (6, 299) and rr.one_cell(5, 65)[1] == 64 and rr.one_cell(130, 3)[0] == 129
     for c in (x for x in rr.CASES if x.entry == "coma_masked_max_f32"):
         d, ref = rr.data(c), rr.reference(c)["out"]
         live = np.outer(np.ones(c.H, bool), d["col_any"] != 0) if c.which == 0 else np.outer(d["row_any"] != 0, np.ones(c.O, bool))
@@ -228,7 +224,7 @@ def test_the_emulation_passes_the_device_checks(case):
     ins, outs = rr.plan(c)
     for name, i in ins.items():
         buf = rr.pack(i.body, i.poison)
-        assert buf.size == i.body.size + 2 * rr.GUARD and (bool(np.isnan(buf[:rr.GUARD]).all()) if buf.dtype.kind == "f" else bool((buf[:rr.GUARD] == i.poison).all()))
+        assert buf.size == i.body.size + 2 * kit.GUARD and (bool(np.isnan(buf[:kit.GUARD]).all()) if buf.dtype.kind == "f" else bool((buf[:kit.GUARD] == i.poison).all()))
     for name, o in outs.items():
         assert o.init.size == o.must.size == o.finite.size and (o.must.all() or not o.must.any())
 
@@ -248,9 +244,9 @@ def test_a_stray_read_shows():
     assert np.array_equal(orc.nearest_vertex(d["points"], ext), [255, 255])
     # outputs start as the sentinel; none of the table's results equals one
     for dt in (np.float32, np.float64, np.int64, np.int32, np.uint8):
-        s = rr.sentinel(3, dt)
+        s = kit.sentinel(3, dt)
         assert s.dtype == dt and (np.isnan(s).all() if s.dtype.kind == "f" else (s < 0).all() or dt == np.uint8)
-    assert rr.bits(rr.sentinel(1, np.float32))[0] == 0x7FC5A5A5
+    assert kit.bits(kit.sentinel(1, np.float32))[0] == 0x7FC5A5A5
 
 
 # mutation -> cases that have to notice it
@@ -286,35 +282,20 @@ def test_a_broken_kernel_fails_a_named_case(mut):
 
 
 # ------------------------------------------------------------------------------------------------------------------ refusals
-def _host_resolver():
-    """PTR -> a dummy address that is never dereferenced (small device buffers where there is a device); principle_vec is read on the
-    host by coma_contact_map_f32, so it gets real host memory"""
-    dummy, vec = _resolver(), (ctypes.c_float * 3)(0.0, 0.0, 1.0)
-    resolve = lambda name: ctypes.addressof(vec) if name in rr.HOST_ARGS else dummy(name)
-    resolve.keep = vec
-    return resolve
-
-
 @pytest.mark.parametrize("entry", sorted(rr.REFUSALS), ids=str)
 def test_every_refusal_gives_its_code_and_text_through_the_entry_point(entry, hip_lib):
+    """(principle_vec is read on the host by coma_contact_map_f32, so the resolver gives it real host memory)"""
     base, rows = rr.REFUSALS[entry]
-    resolve = _host_resolver()
     assert len(rows) >= 6 and set(base) == set(_lib.PARAMS[entry][:-1])       # the header's own parameter names
-    for text, change in rows:
-        rc = rr.call(hip_lib, entry, {**base, **change}, resolve)
-        msg = hip_lib.coma_last_error().decode()
-        assert rc == COMA_E_INVALID and re.search(re.escape(entry) + ": .*" + re.escape(text), msg), (entry, change, rc, msg)
     # the control: the base row passes every argument check and only fails where the launch needs a device
-    if not torch.cuda.is_available():
-        rc = rr.call(hip_lib, entry, dict(base), resolve)
-        assert rc not in (0, COMA_E_INVALID), (entry, rc, hip_lib.coma_last_error().decode())
+    kit.check_refusals(hip_lib, {entry: rr.REFUSALS[entry]}, kit.host_resolver(rr.HOST_ARGS), expect_control=not torch.cuda.is_available())
 
 
 def test_empty_launches_return_ok_without_a_device(hip_lib):
     """P = 0 and C = 0 return COMA_OK before any HIP call"""
-    resolve = _host_resolver()
+    resolve = kit.host_resolver(rr.HOST_ARGS)
     for entry, change in (("coma_nearest_vertex_i64", dict(P=0)), ("coma_dlt_score_f64", dict(P=0)), ("coma_ransac_mse_f64", dict(C=0))):
-        assert rr.call(hip_lib, entry, {**rr.REFUSALS[entry][0], **change}, resolve) == 0, entry
+        assert kit.call(hip_lib, entry, {**rr.REFUSALS[entry][0], **change}, resolve) == 0, entry
     total = sum(len(rows) for _, rows in rr.REFUSALS.values())
     print(f"REDUCE_REFUSALS {total} rows over {len(rr.REFUSALS)} entry points")
     assert total >= 80

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from tests import attention_ref as ar
+from tests import domain_kit as kit
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -27,7 +28,8 @@ def ops(hip_lib):
 
 
 def launch(ops, c, q, k, v):
-    """Pack the operands of case c as its `ld` / `vt` say, launch twice into fresh sentinel-filled buffers -> (out1, out2) flat, on the CPU."""
+    """Pack the operands of case c as its `ld` / `vt` say, launch twice into fresh sentinel-filled buffers (under the kit's fault policy:
+    a launch error ends the session) -> (out1, out2) flat, on the CPU."""
     ld = c.leading_dims()
     C = c.C
     if c.ld in ("fused", "fusedx"):
@@ -39,13 +41,14 @@ def launch(ops, c, q, k, v):
     vt = {"plain": ar.pack_vt_plain, "perm16": ar.pack_vt_perm16, "perm32": ar.pack_vt_perm32}[c.vt](v, ld["ldv"]).to(DEV)
     kw = dict(batch=c.B, heads=c.H, lq=c.lq, lk=c.lk, d=c.d, ldq=ld["ldq"], ldk=ld["ldk"], ldv=ld["ldv"], ldo=ld["ldo"], scale=c.d ** -0.5)
     outs = []
-    for _ in range(2):
-        out = ar.new_out(c.B, c.lq, ld["ldo"]).to(DEV)
-        if c.kind == "wide":
-            ops.attention_wide(qd, kd, vt, out, **kw)
-        else:
-            ops.attention(qd, kd, vt, out, vt_perm16=c.vt == "perm16", pipelined=True if c.kind == "sp" else None, **kw)
-        outs.append(out.cpu())
+    with kit.device_guard(c.id):
+        for _ in range(2):
+            out = ar.new_out(c.B, c.lq, ld["ldo"]).to(DEV)
+            if c.kind == "wide":
+                ops.attention_wide(qd, kd, vt, out, **kw)
+            else:
+                ops.attention(qd, kd, vt, out, vt_perm16=c.vt == "perm16", pipelined=True if c.kind == "sp" else None, **kw)
+            outs.append(out.cpu())
     return outs
 
 
@@ -61,7 +64,7 @@ def test_attention_domain(ops, case):
     dev = float(err.nan_to_num(nan=float("inf")).max())
     print(f"ATTN_DOMAIN {c.id} family={c.family} e_emu={y.e_emu:.3e} bound={y.bound:.3e} device={dev:.3e}")
     assert bool(torch.isfinite(got.float()).all()), "(b) NaN / Inf (or an unwritten element) in the written region"
-    assert bool((rest == ar.SENTINEL_BITS).all()), "(c) a gap column or the guard of `out` was written"
+    assert bool((rest == kit.sentinel_bits(F16)).all()), "(c) a gap column or the guard of `out` was written"
     assert torch.equal(out1.view(torch.int16), out2.view(torch.int16)), "(d) the second launch differs"
     worst = int(err.flatten().argmax())
     assert dev <= y.bound, f"(a) query error {dev:.3e} > {y.bound:.3e} (e_emu {y.e_emu:.3e}) at compared slice / query {divmod(worst, c.lq)}"
@@ -113,4 +116,4 @@ def test_attention_argument_errors_are_reported_not_launched(ops):
     refused(ops.attention_wide, "sd_attention_wide_f16: K / V\\^T slice of one \\(batch, head\\) exceeds 2 GiB", wok, d=512, ldq=512, ldk=512, ldo=512,
             ldv=1 << 21)
     torch.cuda.synchronize()
-    assert bool((out.cpu().view(torch.int16) == ar.SENTINEL_BITS).all())
+    assert bool((out.cpu().view(torch.int16) == kit.sentinel_bits(F16)).all())

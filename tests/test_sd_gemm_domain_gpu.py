@@ -14,13 +14,13 @@ import pytest
 import torch
 
 from coma_amd._lib import ComaHipError
+from tests import domain_kit as kit
 from tests import gemm_ref as gr
 
-COMA_E_INVALID = -1
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 F16, F64 = torch.float16, torch.float64
-G = gr.GUARD
+G = kit.GUARD
 
 
 @pytest.fixture(scope="module")
@@ -38,19 +38,10 @@ def run(ops, c, dev):
     ws = gr.new_workspace(c).to(DEV) if c.ws_slabs else None
     ptr = dict(dev, out=out[G:], out_t=None if out_t is None else out_t[G:], colstats=None if cs is None else cs[G:],
                workspace=None if ws is None else ws[G:])
-    try:
+    with kit.device_guard(c.id):
         for launch in range(max(1, len(c.phases))):
             ops.conv_gemm(ptr["a0"], dev["w"][launch], ptr["out"], **gr.launch_kwargs(c, ptr, launch))
-        torch.cuda.synchronize()
-    except Exception as e:
-        if isinstance(e, ComaHipError) and f"failed ({COMA_E_INVALID})" in str(e):
-            raise                       # refused by the argument checks: nothing was launched, this case alone fails
-        pytest.exit(f"{c.id}: {type(e).__name__}: {e}", returncode=3)     # a launch error: nothing more is started on the device
     return tuple(None if t is None else t.cpu() for t in (out, out_t, cs, ws))
-
-
-def bits(t):
-    return t.view(torch.int16 if t.dtype == F16 else torch.int32)
 
 
 @pytest.mark.parametrize("case", gr.CASES, ids=lambda c: c.id)
@@ -71,27 +62,20 @@ def test_conv_gemm_domain(ops, case):
     device = float(err.nan_to_num(nan=float("inf")).max())
     print(f"GEMM_DOMAIN {c.id} family={c.pool} e_emu={y.e_emu:.3e} bound={y.bound:.3e} device={device:.3e}")
 
-    mask = gr.written_mask(c)
-    assert bool(torch.isfinite(out[mask].float()).all()), "(b) NaN / Inf (or an unwritten element) in the written region of `out`"
-    assert bool((bits(out)[~mask] == gr.SENTINEL_BITS).all()), "(c) a gap column, guard, foreign parity or inter-problem gap of `out` was written"
-    assert torch.equal(bits(out), bits(out2)), "(d) the second launch differs in `out`"
+    mask = gr.written_mask(c)                                   # (outside it: gap columns, guards, foreign parity, inter-problem gaps)
+    kit.check_written("out", out, out2, gr.new_out(c), mask, mask)
     if c.out_t:
         mt = gr.out_t_written_mask(c)
-        assert bool(torch.isfinite(out_t[mt].float()).all()), "(b) NaN / Inf (or an unwritten element) in out_t"
-        assert bool((bits(out_t)[~mt] == gr.SENTINEL_BITS).all()), "(c) a gap column or the guard of out_t was written"
-        assert torch.equal(bits(out_t), bits(out_t2)), "(d) the second launch differs in out_t"
+        kit.check_written("out_t", out_t, out_t2, gr.new_out_t(c), mt, mt)
     if c.ws_slabs:
         assert bool(ws[:G].isnan().all()) and bool(ws[-G:].isnan().all()), "(c) the workspace was written outside its workspace_bytes"
     if c.colstats:
         slots, sums, squares, mags = gr.colstats_expected(c, out)
         body = cs[G:-G].view(gr.colstats_slots(c), 2, c.n)
-        assert torch.equal(bits(cs), bits(cs2)), "(d) the second launch differs in colstats"
-        rest = torch.ones(gr.colstats_slots(c), dtype=torch.bool)
-        rest[slots] = False
-        assert bool((bits(body)[rest] == gr.SENTINEL_BITS32).all()) and bool((bits(cs)[:G] == gr.SENTINEL_BITS32).all()) and \
-            bool((bits(cs)[-G:] == gr.SENTINEL_BITS32).all()), "(c) a colstats slot of another phase or the guard was written"
+        mine = torch.zeros(cs.numel(), dtype=torch.bool)        # (outside it: the slots of another phase and the guards)
+        mine[G:-G].view(gr.colstats_slots(c), 2 * c.n)[slots] = True
+        kit.check_written("colstats", cs, cs2, gr.new_colstats(c), mine, mine)
         gs, gq = body[slots, 0].to(F64), body[slots, 1].to(F64)
-        assert bool(torch.isfinite(gs).all()) and bool(torch.isfinite(gq).all()), "(b) NaN / Inf (or an unwritten element) in colstats"
         # 32 fp32 additions in any order: 31 roundings of at most 2^-24 of a partial sum <= 2^-19 of the sum of magnitudes
         assert bool(((gs - sums).abs() <= 2.0 ** -19 * mags).all()), "colstats: column sums"
         assert bool(((gq - squares).abs() <= 2.0 ** -19 * squares).all()), "colstats: sums of squares"
@@ -105,11 +89,11 @@ def test_conv_gemm_refusals_are_reported_not_launched(ops):
     first put to sd_conv_gemm_describe, which launches nothing: a row the library accepted would otherwise launch over these small buffers."""
     small = torch.zeros(4096, dtype=F16, device=DEV)
     small32 = torch.zeros(4096, dtype=torch.float32, device=DEV)
-    out = torch.full((4096,), gr.SENTINEL_BITS, dtype=torch.int16).view(F16).to(DEV)
+    out = kit.sentinel(4096, F16).to(DEV)
     base = dict(gr.REFUSAL_BASE, a0=small, w=small, out=out)
     n = 0
     for text, change in gr.REFUSALS:
-        kw = {k: ((small32 if k == "colstats" else small) if v is gr.PTR else v) for k, v in {**base, **change}.items()}
+        kw = {k: ((small32 if k == "colstats" else small) if v is kit.PTR else v) for k, v in {**base, **change}.items()}
         if kw["out"] is None:
             continue                                             # the wrapper takes its stream from `out`; the host test covers this row
         with pytest.raises(ComaHipError, match=text):
@@ -119,4 +103,4 @@ def test_conv_gemm_refusals_are_reported_not_launched(ops):
         n += 1
     assert n == len(gr.REFUSALS) - 1
     torch.cuda.synchronize()
-    assert bool((out.cpu().view(torch.int16) == gr.SENTINEL_BITS).all())
+    assert bool((kit.bits(out.cpu()) == kit.sentinel_bits(F16)).all())

@@ -17,12 +17,13 @@ import pytest
 import torch
 
 from coma_amd._lib import ComaHipError
+from tests import domain_kit as kit
 from tests import gemm_ref as gr
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 F16, F64 = torch.float16, torch.float64
-G = gr.GUARD
+G = kit.GUARD
 SAME = ("bm", "bn", "bk", "stages", "waves", "tm", "spread", "m16", "ksplit", "tap_minor")     # what decides the bits of a launch
 
 
@@ -55,17 +56,13 @@ def run(ops, c, dev, w_all, one_launch):
     out = gr.new_out(c).to(DEV)
     cs = gr.new_colstats(c).to(DEV) if c.colstats else None
     ptr = dict(dev, out=out[G:], colstats=None if cs is None else cs[G:])
-    if one_launch:
-        ops.conv_gemm(ptr["a0"], w_all[G:], ptr["out"], **z_kwargs(c, ptr))
-    else:
-        for launch in range(4):
-            ops.conv_gemm(ptr["a0"], dev["w"][launch], ptr["out"], **gr.launch_kwargs(c, ptr, launch))
-    torch.cuda.synchronize()
+    with kit.device_guard(f"{c.id} ({'one launch' if one_launch else 'four launches'})"):
+        if one_launch:
+            ops.conv_gemm(ptr["a0"], w_all[G:], ptr["out"], **z_kwargs(c, ptr))
+        else:
+            for launch in range(4):
+                ops.conv_gemm(ptr["a0"], dev["w"][launch], ptr["out"], **gr.launch_kwargs(c, ptr, launch))
     return out.cpu(), None if cs is None else cs.cpu()
-
-
-def bits(t):
-    return t.view(torch.int16 if t.dtype == F16 else torch.int32)
 
 
 def check_form(c, y, out, cs, what):
@@ -74,10 +71,10 @@ def check_form(c, y, out, cs, what):
     print(f"ZPHASE {c.id} {what}: tile={c.tile} e_emu={y.e_emu:.3e} bound={y.bound:.3e} device={device:.3e}")
     mask = gr.written_mask(c)
     assert bool(torch.isfinite(out[mask].float()).all()), f"{what}: NaN / Inf (or an unwritten element) in the written region of `out`"
-    assert bool((bits(out)[~mask] == gr.SENTINEL_BITS).all()), f"{what}: a gap column or guard of `out` was written"
+    assert bool((kit.bits(out)[~mask] == kit.sentinel_bits(F16)).all()), f"{what}: a gap column or guard of `out` was written"
     if c.colstats:
         slots, sums, squares, mags = gr.colstats_expected(c, out)
-        assert slots.numel() == gr.colstats_slots(c) and bool((bits(cs)[:G] == gr.SENTINEL_BITS32).all()) and bool((bits(cs)[-G:] == gr.SENTINEL_BITS32).all())
+        assert slots.numel() == gr.colstats_slots(c) and bool((kit.bits(cs)[:G] == kit.sentinel_bits(torch.float32)).all()) and bool((kit.bits(cs)[-G:] == kit.sentinel_bits(torch.float32)).all())
         body = cs[G:-G].view(gr.colstats_slots(c), 2, c.n)
         gs, gq = body[slots, 0].to(F64), body[slots, 1].to(F64)
         assert bool(torch.isfinite(gs).all()) and bool(torch.isfinite(gq).all()), f"{what}: NaN / Inf (or an unwritten slot) in colstats"
@@ -105,7 +102,7 @@ def test_one_launch_of_four_phases(ops, name, B, H, W, c0, n, flags):
     dev = {k: (None if v is None else v.to(DEV)[G:]) for k, v in pk._asdict().items() if k != "w"}
     dev["w"] = tuple(w.to(DEV)[G:] for w in pk.w)
     # the four phase matrices stride_w = n * K apart, NaN guards around them
-    w_all = gr._pack(torch.stack([gr.phase_weights(inp.w[0], ph) for ph in (1, 2, 3, 4)]).reshape(1, 4 * c.n, c.K), c.K, c.K, 0).to(DEV)
+    w_all = gr.pack_blocks(torch.stack([gr.phase_weights(inp.w[0], ph) for ph in (1, 2, 3, 4)]).reshape(1, 4 * c.n, c.K), c.K, c.K, 0).to(DEV)
 
     four, four_cs = run(ops, c, dev, w_all, one_launch=False)
     one, one_cs = run(ops, c, dev, w_all, one_launch=True)
@@ -122,9 +119,9 @@ def test_one_launch_of_four_phases(ops, name, B, H, W, c0, n, flags):
     else:
         assert same
     if same:
-        assert torch.equal(bits(one), bits(four)), "one launch and four launches of the same kernel differ in `out`"
+        assert torch.equal(kit.bits(one), kit.bits(four)), "one launch and four launches of the same kernel differ in `out`"
         if c.colstats:
-            assert torch.equal(bits(one_cs), bits(four_cs)), "one launch and four launches of the same kernel differ in colstats"
+            assert torch.equal(kit.bits(one_cs), kit.bits(four_cs)), "one launch and four launches of the same kernel differ in colstats"
     if c.M <= 512:
         # ... and the convolution the long way: 3x3 over the nearest-x2 image with the unsummed weights
         ref = gr.reference_3x3_upsampled(c, inp)
@@ -139,15 +136,15 @@ def test_what_a_single_phase_refuses_the_one_launch_form_refuses(ops):
     given): refused with COMA_E_INVALID, nothing launched (`out` keeps its sentinel).  A residual is one of the rows."""
     small = torch.zeros(4096, dtype=F16, device=DEV)
     small32 = torch.zeros(4096, dtype=torch.float32, device=DEV)
-    out = torch.full((4096,), gr.SENTINEL_BITS, dtype=torch.int16).view(F16).to(DEV)
+    out = kit.sentinel(4096, F16).to(DEV)
     base = dict(gr.REFUSAL_BASE, a0=small, w=small, out=out)
     rows = [(text, change) for text, change in gr.REFUSALS if change.get("phase") == 1]
     assert len(rows) >= 12 and any("res" in ch for _, ch in rows) and any("colstats" in ch for _, ch in rows)
-    ok = dict(base, **gr._PHASE)
+    ok = dict(base, **gr.PHASE_BASE)
     ok.update(phase=5, nbatch_z=4, stride_w=ok["n"] * 4 * ok["c0"])
     assert ops.conv_gemm_describe(**ok).grid_y == 4                              # the control: the rows are refused for their change alone
     for text, change in rows:
-        kw = {k: ((small32 if k == "colstats" else small) if v is gr.PTR else v) for k, v in {**base, **change}.items()}
+        kw = {k: ((small32 if k == "colstats" else small) if v is kit.PTR else v) for k, v in {**base, **change}.items()}
         with pytest.raises(ComaHipError, match=r"failed \(-1\)"):                # the single phase, as the table says
             ops.conv_gemm_describe(**kw)
         kw.update(phase=5, nbatch_z=change.get("nbatch_z", 4), stride_w=kw["n"] * 4 * kw["c0"])
@@ -160,4 +157,4 @@ def test_what_a_single_phase_refuses_the_one_launch_form_refuses(ops):
         with pytest.raises(ComaHipError, match=r"failed \(-1\)"):
             ops.conv_gemm_describe(**dict(ok, **change))
     torch.cuda.synchronize()
-    assert bool((out.cpu().view(torch.int16) == gr.SENTINEL_BITS).all())
+    assert bool((kit.bits(out.cpu()) == kit.sentinel_bits(F16)).all())

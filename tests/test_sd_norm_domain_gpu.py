@@ -15,19 +15,16 @@ batch * C * 2 + batch * ceil(hw / 64) * groups * 2 floats end) keeps the sentine
 gives the same bits.  Every operand element the contract says is not read is NaN, so a read outside the contract poisons (a) or (b).
 Where include/sd_hip.h promises bit equality it is asserted: mode 0 of sd_gn_winograd_input_f16 against sd_groupnorm_f16 (one-launch route)
 -> sd_winograd_input_f16."""
-import re
-
 import pytest
 import torch
 
-from coma_amd._lib import ComaHipError
+from tests import domain_kit as kit
 from tests import norm_ref as nr
 
-COMA_E_INVALID = -1
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 F16, F32, F64 = torch.float16, torch.float32, torch.float64
-G = nr.GUARD
+G = kit.GUARD
 
 
 @pytest.fixture(scope="module")
@@ -37,29 +34,18 @@ def ops(hip_lib):
     return ops
 
 
-def guarded(call, what):
-    """A refusal by the argument checks fails its own case; any other error ends the session: nothing more is started on the device."""
-    try:
-        r = call()
-        torch.cuda.synchronize()
-        return r
-    except Exception as e:
-        if isinstance(e, ComaHipError) and f"failed ({COMA_E_INVALID})" in str(e):
-            raise
-        pytest.exit(f"{what}: {type(e).__name__}: {e}", returncode=3)
-
-
 def run(ops, c, dev, outs):
     """The launch of the case into fresh sentinel-filled outputs -> name -> flat device buffer (guards included)."""
     bufs = {}
     for name, o in outs.items():
-        buf = nr.new_out(o).to(DEV)
+        buf = kit.new_out(o).to(DEV)
         if isinstance(c, nr.SM):                                 # in place: the data between sentinel gap columns and guards
             buf[G:-G].view(o.rows, o.ld)[:, :o.width] = dev["x_data"]
         bufs[name] = buf
     p = {k: v for k, v in dev.items() if k != "x_data"}
     p.update({name: buf[G:] for name, buf in bufs.items()})
-    guarded(lambda: nr.launch(ops, c, p), c.id)
+    with kit.device_guard(c.id):
+        nr.launch(ops, c, p)
     return bufs
 
 
@@ -72,24 +58,21 @@ def test_norm_domain(ops, case):
     if isinstance(c, nr.SM):
         dev = dict(x_data=inp["x"].t.to(DEV))
     else:
-        dev = {k: nr.pack(op).to(DEV)[G + op.off:] for k, op in inp.items()}
+        dev = {k: kit.pack(op).to(DEV)[G + op.off:] for k, op in inp.items()}
     first = run(ops, c, dev, outs)
     second = run(ops, c, dev, outs)
 
     device = 0.0
     for name, o in outs.items():
-        buf, sent = first[name], nr.sentinel_bits(o.dtype)
-        must, may = (m.to(DEV) for m in nr.masks(o))
-        assert bool(torch.isfinite(buf[must].float()).all()), f"(b) NaN / Inf (or an unwritten element) in what the launch owns of `{name}`"
-        assert bool((nr.bits(buf)[~may] == sent).all()), f"(c) a guard or gap column of `{name}` was written"
-        assert torch.equal(nr.bits(buf), nr.bits(second[name])), f"(d) the second launch differs in `{name}`"
+        buf = first[name].cpu()
+        kit.check_written(name, buf, second[name].cpu(), kit.new_out(o), *kit.masks(o))
         if name not in res:
             continue
         r = res[name]
-        got = buf[G:G + o.must].view(-1, 2) if o.must else nr.body(o, buf)         # the table at the start of `stats`, or the whole output
-        got = (got if rows is None else got[rows.to(DEV)]).cpu()
+        got = buf[G:G + o.must].view(-1, 2) if o.must else kit.body(o, buf)        # the table at the start of `stats`, or the whole output
+        got = got if rows is None else got[rows]
         if o.dtype == F16:
-            err = nr.row_error(got, r.ref).nan_to_num(nan=float("inf"))
+            err = kit.row_error(got, r.ref).nan_to_num(nan=float("inf"))
             device = float(err.max())
             worst = int(err.argmax())
             print(f"NORM_DOMAIN {c.id} family={c.family} e_emu={y.e_emu:.3e} bound={y.bound:.3e} device={device:.3e}")
@@ -101,7 +84,7 @@ def test_norm_domain(ops, case):
             assert float(over.max()) <= 1.0, f"(a) table entry {divmod(int(over.argmax()), 2)} is {float(over.max()):.3e} of its fp32 bound"
     if isinstance(c, nr.WO) and c.cs:
         sums, squares, mags = nr.colstats_expected(c, first["out"].cpu())
-        body = nr.body(outs["colstats"], first["colstats"]).cpu().view(-1, 2, c.n).to(F64)
+        body = kit.body(outs["colstats"], first["colstats"]).cpu().view(-1, 2, c.n).to(F64)
         # 32 fp32 additions in any order: 31 roundings of at most 2^-24 of a partial sum <= 2^-19 of the sum of magnitudes
         assert bool(((body[:, 0] - sums).abs() <= 2.0 ** -19 * mags).all()), "colstats: column sums"
         assert bool(((body[:, 1] - squares).abs() <= 2.0 ** -19 * squares).all()), "colstats: sums of squares"
@@ -111,30 +94,18 @@ def test_norm_domain(ops, case):
         n1 = torch.empty(c.B * c.h * c.w, c.C, dtype=F16, device=DEV)
         stats = torch.empty(ops.gn_scratch_floats(c.B, c.h * c.w, c.G, c.C), dtype=F32, device=DEV)
         v2 = torch.empty(16 * c.B * c.h * c.w // 4, c.C, dtype=F16, device=DEV)
-        guarded(lambda: ops.groupnorm(dev["x0"], dev["gamma"], dev["beta"], n1, stats, batch=c.B, hw=c.h * c.w, c0=c.c0, x1=dev.get("x1"), c1=c.c1,
-                                      groups=c.G, eps=c.eps, silu=bool(c.silu)), c.id + " (unfused GroupNorm)")
-        guarded(lambda: ops.winograd_input(n1, v2, batch=c.B, h=c.h, w=c.w, c0=c.C), c.id + " (unfused input transform)")
-        assert torch.equal(nr.bits(nr.body(outs["v"], first["v"])), nr.bits(v2)), "mode 0 differs from sd_groupnorm_f16 -> sd_winograd_input_f16"
+        with kit.device_guard(c.id + " (unfused GroupNorm)"):
+            ops.groupnorm(dev["x0"], dev["gamma"], dev["beta"], n1, stats, batch=c.B, hw=c.h * c.w, c0=c.c0, x1=dev.get("x1"), c1=c.c1, groups=c.G,
+                          eps=c.eps, silu=bool(c.silu))
+        with kit.device_guard(c.id + " (unfused input transform)"):
+            ops.winograd_input(n1, v2, batch=c.B, h=c.h, w=c.w, c0=c.C)
+        assert torch.equal(kit.bits(kit.body(outs["v"], first["v"])), kit.bits(v2)), "mode 0 differs from sd_groupnorm_f16 -> sd_winograd_input_f16"
 
 
 def test_refusals_are_reported_not_launched(ops, hip_lib):
     """Every row of norm_ref.REFUSALS through the real entry points, with small device buffers where the row wants a pointer: the code and
     the text, and every output buffer keeps its sentinel.  tests/test_norm_ref_host.py has put the same rows to the same entry points on
     the CPU, where a wrongly accepted row cannot launch."""
-    small = torch.zeros(1 << 16, dtype=F32, device=DEV)
-    outs = {name: nr.sentinel(1 << 16, F32).to(DEV) for name in nr.OUTPUT_ARGS}
-    resolve = lambda name: (outs[name] if name in outs else small).data_ptr()
-    n = 0
-    for entry, (base, rows) in sorted(nr.REFUSALS.items()):
-        for text, change in rows:
-            rc = nr.call(hip_lib, entry, {**base, **change}, resolve)
-            msg = hip_lib.coma_last_error().decode()
-            if rc == 0:
-                torch.cuda.synchronize()
-            assert rc == COMA_E_INVALID and re.search(re.escape(entry) + ": .*" + re.escape(text), msg), (entry, change, rc, msg)
-            n += 1
-    assert n == sum(len(rows) for _, rows in nr.REFUSALS.values()) and n > 120
-    torch.cuda.synchronize()
-    for name, buf in outs.items():
-        assert bool((nr.bits(buf.cpu()) == nr.SENTINEL_BITS32).all()), name
-    assert not bool(small.cpu().any())
+    resolve, outs, small = kit.device_resolver(nr.OUTPUT_ARGS)
+    assert kit.check_refusals(hip_lib, nr.REFUSALS, resolve, expect_control=False) > 120
+    kit.refusal_outputs_untouched(outs, small)

@@ -31,6 +31,7 @@ import functools
 import pytest
 import torch
 
+from tests import domain_kit as kit
 from tests import rowtile_ref as rr
 
 pytestmark = pytest.mark.gpu
@@ -130,12 +131,15 @@ def run_chain_case(ops, rps, B, lk, ldv2, kind="randn", eps=1e-5, stages=False, 
     truth, rest = (rr.xchain(*inp, rows_per_sample=rps, eps=eps, exact=e) for e in (True, False))
     vt2 = vt_perm16(ops, inp[8], ldv2)
     ck = Check(case)
-    o_h2, o_n3, _ = launch_chain(ops, inp, vt2, rps=rps, lk=lk, eps=eps)
+    with kit.device_guard(case):                                # (the kit's fault policy: a launch error ends the session)
+        o_h2, o_n3, _ = launch_chain(ops, inp, vt2, rps=rps, lk=lk, eps=eps)
     ck.rows("h2", o_h2, truth["h2"], rest["h2"])
     ck.rows("n3", o_n3, truth["n3"], rest["n3"])
     if stages:
         for stage, name in ((1, "h1"), (2, "n2"), (3, "q2"), (4, "a2")):
-            ck.rows(name, launch_chain(ops, inp, vt2, rps=rps, lk=lk, eps=eps, stage=stage)[2], truth[name], rest[name])
+            with kit.device_guard(f"{case} stage {stage}"):
+                dbg = launch_chain(ops, inp, vt2, rps=rps, lk=lk, eps=eps, stage=stage)[2]
+            ck.rows(name, dbg, truth[name], rest[name])
     if junk:
         # the pad positions of vt2 belong to no key: whatever finite values they hold, the result is the same bits
         j = torch.arange(ldv2)
@@ -143,7 +147,8 @@ def run_chain_case(ops, rps, B, lk, ldv2, kind="randn", eps=1e-5, stages=False, 
         assert int(pad.sum()) == ldv2 - lk
         vj = vt2.clone()
         vj[:, :, pad] = torch.where(torch.arange(int(pad.sum())) % 2 == 0, 1000.0, -1000.0).to(F16)
-        j_h2, j_n3, _ = launch_chain(ops, inp, vj, rps=rps, lk=lk, eps=eps)
+        with kit.device_guard(case + " (junk pad)"):
+            j_h2, j_n3, _ = launch_chain(ops, inp, vj, rps=rps, lk=lk, eps=eps)
         ck.true(torch.equal(j_h2, o_h2) and torch.equal(j_n3, o_n3), "junk in the pad positions of vt2 changed the result")
     ck.done()
 
@@ -216,8 +221,11 @@ def run_front_case(ops, L, B, ldv, kind="randn", eps=1e-5):
     truth, rest = (rr.xfront(*inp, rows_per_sample=L, gn_eps=1e-6, eps=eps, exact=e) for e in (True, False))
     dinp = [dv(t) for t in (x, gng, gnb, wpi, bpi, g1, b1, torch.cat([wq, wk]), wv)]
     ck = Check(case)
-    for how, table in front_tables(ops, x, dinp[0], dinp[1], dinp[2], B, L):
-        o_h, o_qk, o_vt = launch_front(ops, dinp, table, B=B, L=L, ldv=ldv, eps=eps)
+    with kit.device_guard(case + " (tables)"):
+        tables = front_tables(ops, x, dinp[0], dinp[1], dinp[2], B, L)
+    for how, table in tables:
+        with kit.device_guard(f"{case} [table from {how}]"):
+            o_h, o_qk, o_vt = launch_front(ops, dinp, table, B=B, L=L, ldv=ldv, eps=eps)
         ck.rows(f"[table from {how}] h", o_h, truth["h"], rest["h"])
         ck.rows(f"[table from {how}] qk", o_qk, truth["qk"], rest["qk"])
         v = ops.perm16_columns(o_vt[:, :, :L].cpu()).transpose(1, 2).reshape(B * L, C)       # PERM16 is its own inverse
@@ -269,12 +277,14 @@ def launch_tail(ops, dargs, M, stats=True):
 def check_tail(ops, ck, inp, M):
     truth, rest = (rr.xtail(*inp, exact=e) for e in (True, False))
     dargs = tail_device_args(inp)
-    out, cs = launch_tail(ops, dargs, M)
+    with kit.device_guard(ck.case):
+        out, cs = launch_tail(ops, dargs, M)
     ck.rows("out", out, truth, rest)
     o = out.double().cpu().reshape(M // 32, 32, C)              # column sums of the STORED values: 32 fp32 additions of fp16 numbers
     ck.true(torch.allclose(cs[:, 0].double().cpu(), o.sum(1), rtol=1e-5, atol=1e-5), "colstats: sums")
     ck.true(torch.allclose(cs[:, 1].double().cpu(), (o * o).sum(1), rtol=1e-5, atol=1e-5), "colstats: sums of squares")
-    out2, _ = launch_tail(ops, dargs, M, stats=False)
+    with kit.device_guard(ck.case + " (no colstats)"):
+        out2, _ = launch_tail(ops, dargs, M, stats=False)
     ck.true(torch.equal(out, out2), "out differs between the launches with and without colstats")
     return out
 
@@ -324,8 +334,9 @@ def _bench_inputs(which):
                 tail=lambda: tail_inputs(BENCH_B * BENCH_L))[which]()
 
 
-def _all_equal(runs):
-    torch.cuda.synchronize()
+def _all_equal(what, launch):
+    with kit.device_guard(what):                                # twelve back-to-back launches, one synchronize behind them
+        runs = [launch() for _ in range(12)]
     for r in runs[1:]:
         for got, first in zip(r, runs[0]):
             assert torch.equal(got, first)
@@ -338,7 +349,7 @@ def test_xattn_chain_race_screen(ops):
     inp = _bench_inputs("chain")
     dinp = [dv(t) for t in inp]
     vt2 = dv(vt_perm16(ops, inp[8], 80))
-    _all_equal([launch_chain(ops, dinp, vt2, rps=BENCH_L, lk=77)[:2] for _ in range(12)])
+    _all_equal("xattn_chain race screen", lambda: launch_chain(ops, dinp, vt2, rps=BENCH_L, lk=77)[:2])
 
 
 def test_xfront_race_screen(ops):
@@ -346,12 +357,12 @@ def test_xfront_race_screen(ops):
     dinp = [dv(t) for t in (x, gng, gnb, wpi, bpi, g1, b1, torch.cat([wq, wk]), wv)]
     table = torch.zeros(ops.gn_scratch_floats(BENCH_B, BENCH_L), dtype=torch.float32, device=DEV)
     ops.groupnorm_table(dinp[0], dinp[1], dinp[2], table, batch=BENCH_B, hw=BENCH_L, c0=C, eps=1e-6)
-    _all_equal([launch_front(ops, dinp, table, B=BENCH_B, L=BENCH_L, ldv=BENCH_L, eps=1e-5) for _ in range(12)])
+    _all_equal("xfront race screen", lambda: launch_front(ops, dinp, table, B=BENCH_B, L=BENCH_L, ldv=BENCH_L, eps=1e-5))
 
 
 def test_xtail_race_screen(ops):
     dargs = tail_device_args(_bench_inputs("tail"))
-    _all_equal([launch_tail(ops, dargs, BENCH_B * BENCH_L) for _ in range(12)])
+    _all_equal("xtail race screen", lambda: launch_tail(ops, dargs, BENCH_B * BENCH_L))
 
 
 # ============================================================================================================================== refusals

@@ -13,9 +13,9 @@ import pytest
 import torch
 
 from coma_amd._lib import ComaHipError
+from tests import domain_kit as kit
 from tests import seg_ref as sr
 
-COMA_E_INVALID = -1
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 G = sr.GUARD
@@ -33,13 +33,8 @@ def run(ops, c, dev):
     out = sr.guarded(sr.sentinel(c.m, c.ldo_)).to(DEV)
     ws = sr.guarded(torch.full((c.ws_slabs * c.slab_elems,), sr.NAN)).to(DEV) if c.ws_slabs else None
     t = dict(dev, workspace=None if ws is None else ws[G:])
-    try:
+    with kit.device_guard(c.id):
         ops.conv_gemm(dev["x"], dev["w"], out[G:], **sr.gemm_kwargs(c, t))
-        torch.cuda.synchronize()
-    except Exception as e:
-        if isinstance(e, ComaHipError) and f"failed ({COMA_E_INVALID})" in str(e):
-            raise                       # refused by the argument checks: nothing was launched, this case alone fails
-        pytest.exit(f"{c.id}: {type(e).__name__}: {e}", returncode=3)     # a launch error: nothing more is started on the device
     return out.cpu(), None if ws is None else ws.cpu()
 
 
@@ -60,9 +55,9 @@ def test_seg_conv_gemm_domain(ops, case, family):
     valid = mask[:, :c.n]
 
     assert bool(torch.isfinite(body[mask]).all()), "(b) NaN / Inf (or an unwritten element) in the written region of `out`"
-    assert bool((sr.bits(body)[~mask] == sr.SENTINEL_BITS).all()), "(c) a gap column or a gated-out row of `out` was written"
+    assert bool((kit.bits(body)[~mask] == kit.sentinel_bits(torch.float32)).all()), "(c) a gap column or a gated-out row of `out` was written"
     assert sr.guards_intact(out), "(c) a guard of `out` was written"
-    assert torch.equal(sr.bits(out), sr.bits(out2)), "(d) the second launch differs"
+    assert torch.equal(kit.bits(out), kit.bits(out2)), "(d) the second launch differs"
     if ws is not None:
         assert sr.guards_intact(ws), "(c) the workspace was written outside its workspace_bytes"
     err = (got.double() - ref).abs()[valid]
@@ -85,7 +80,7 @@ def test_seg_conv_gemm_refusals_are_reported_not_launched(ops):
     n = 0
     for text, change in sr.GEMM_REFUSALS:
         kw = {**sr.GEMM_REFUSAL_BASE, **change}
-        kw = {k: ((cnt if k == "m_dev" else out if k == "out" else small) if v is sr.PTR else v) for k, v in kw.items()}
+        kw = {k: ((cnt if k == "m_dev" else out if k == "out" else small) if v is kit.PTR else v) for k, v in kw.items()}
         x, w, o = kw.pop("x"), kw.pop("w"), kw.pop("out")
         with pytest.raises(ComaHipError, match=r"seg_conv_gemm_describe failed \(-1\): seg_conv_gemm_f32: .*" + text):
             ops.conv_gemm_describe(x, w, o, **kw)
@@ -94,4 +89,4 @@ def test_seg_conv_gemm_refusals_are_reported_not_launched(ops):
         n += 1
     assert n == len(sr.GEMM_REFUSALS)
     torch.cuda.synchronize()
-    assert bool((sr.bits(out.cpu()) == sr.SENTINEL_BITS).all())
+    assert bool((kit.bits(out.cpu()) == kit.sentinel_bits(torch.float32)).all())

@@ -14,8 +14,8 @@ import torch
 import torch.nn.functional as F
 from PIL import Image
 
-from coma_amd._lib import ComaHipError
 from oracle import seg_oracle as so
+from tests import domain_kit as kit
 from tests import seg_ref as sr
 
 pytestmark = pytest.mark.gpu
@@ -62,22 +62,18 @@ def i32_out(*shape):
 
 
 def launch(what, fn):
-    """Run the launches of `fn`; a launch error ends the session's device work, a refusal fails this case alone."""
-    try:
+    """Run the launches of `fn` under the kit's fault policy: a launch error ends the session's device work, a refusal fails this case
+    alone."""
+    with kit.device_guard(what):
         fn()
-        torch.cuda.synchronize()
-    except Exception as e:
-        if isinstance(e, ComaHipError) and "failed (-1)" in str(e):
-            raise
-        pytest.exit(f"{what}: {type(e).__name__}: {e}", returncode=3)
 
 
 def same_bits(a, b):
-    return all(torch.equal(sr.bits(x), sr.bits(y)) for x, y in zip(a, b))
+    return all(torch.equal(kit.bits(x), kit.bits(y)) for x, y in zip(a, b))
 
 
 def is_sentinel(t):
-    return sr.bits(t) == (sr.SENTINEL_BITS if t.dtype == F32 else sr.SENT_I32 if t.dtype == I32 else sr.SENT_U8)
+    return kit.bits(t) == (kit.sentinel_bits(torch.float32) if t.dtype == F32 else sr.SENT_I32 if t.dtype == I32 else sr.SENT_U8)
 
 
 # ------------------------------------------------------------------ memset, pooling, resize
@@ -233,9 +229,9 @@ def test_sort_candidates(ops, cap):
         n = len(order)
         assert int(nv[b]) == n, (b, int(nv[b]), n)
         assert np.array_equal(ssrc[b, :n].numpy(), order * 3 + 1), f"(a) image {b}: order"
-        assert np.array_equal(sr.bits(ss[b, :n]).numpy(), scores[b, order].view(np.int32)) and np.array_equal(sg[b, :n].numpy(), group[b, order])
+        assert np.array_equal(kit.bits(ss[b, :n]).numpy(), scores[b, order].view(np.int32)) and np.array_equal(sg[b, :n].numpy(), group[b, order])
         assert np.array_equal(sb[b, :n].numpy(), boxes[b, order])
-        assert bool((sb[b, n:] == 0).all()) and bool((sr.bits(ss[b, n:]) == 0).all()) and bool((sg[b, n:] == -1).all()) and bool((ssrc[b, n:] == -1).all())
+        assert bool((sb[b, n:] == 0).all()) and bool((kit.bits(ss[b, n:]) == 0).all()) and bool((sg[b, n:] == -1).all()) and bool((ssrc[b, n:] == -1).all())
 
 
 @pytest.mark.parametrize("case", sr.NMS_CASES, ids=lambda c: c.id)
@@ -362,7 +358,7 @@ def test_box_predict(ops, case):
                 assert float((got_p[:n][fin] - ref["probs"][fin]).abs().max() / ref["probs"][fin].abs().max()) <= 1e-5
                 assert bool(got_p[:n][~fin].isnan().all())
             assert bool(is_sentinel(got_p[n:]).all()), "(c) probability rows past the count"
-            sets.append({(v, tuple(sr.bits(cb[b, s]).tolist()), int(ks[s] >> np.uint64(32))) for s, v in enumerate(low)})
+            sets.append({(v, tuple(kit.bits(cb[b, s]).tolist()), int(ks[s] >> np.uint64(32))) for s, v in enumerate(low)})
             if b == 0 and n:
                 assert not any(v // 80 in (0, 1) for v in low), "rows 0 (every probability AT the threshold) and 1 (an infinite logit) give no candidate"
         if int(res[0][3][b]) <= c.cap:
@@ -392,9 +388,9 @@ def test_finalize_detections(ops):
         bb[:, 1::2] *= torch.tensor(np.float32(96) / np.float32(800))
         bb = so.clip_boxes(bb, 96, 128)
         ne = ((bb[:, 2] - bb[:, 0]) > 0) & ((bb[:, 3] - bb[:, 1]) > 0)
-        assert torch.equal(ob[b, :n].isnan(), bb.isnan()) and torch.equal(sr.bits(ob[b, :n].nan_to_num(7.0)), sr.bits(bb.nan_to_num(7.0)))
+        assert torch.equal(ob[b, :n].isnan(), bb.isnan()) and torch.equal(kit.bits(ob[b, :n].nan_to_num(7.0)), kit.bits(bb.nan_to_num(7.0)))
         assert torch.equal(valid[b, :n].bool(), ne)
-        assert bool((sr.bits(ob[b, n:]) == 0).all()) and bool((valid[b, n:] == 0).all())
+        assert bool((kit.bits(ob[b, n:]) == 0).all()) and bool((valid[b, n:] == 0).all())
     assert valid[0].tolist() == [1, 0, 0, 1, 0, 1] and bool(ob[0, 4, 0].isnan())
 
 
@@ -416,7 +412,7 @@ def test_point_sample(ops, case):
                                                                 ldo=ldo, col0=c.col0, n_copies=c.n_copies, copy_stride=stride))
         res.append(out.cpu())
     out = res[0]
-    assert torch.equal(sr.bits(out), sr.bits(res[1])), "(d)"
+    assert torch.equal(kit.bits(out), kit.bits(res[1])), "(d)"
     cc = sr.sample_coords(c, coords, rois)
     worst, worst_rel = 0.0, 0.0
     written = torch.zeros(c.n_copies * stride, dtype=torch.bool)
@@ -454,7 +450,7 @@ def test_upsample2x(ops, s):
         launch(f"upsample2x s={s}", lambda: ops.upsample2x(dv(m), dv(np.asarray(counts, np.int32), fill=-7), out.t, batch=B, R=R, s=s))
         res.append(out.cpu())
     out = res[0]
-    assert torch.equal(sr.bits(out), sr.bits(res[1]))
+    assert torch.equal(kit.bits(out), kit.bits(res[1]))
     ref = F.interpolate(m[:4, None].double(), scale_factor=2, mode="bilinear", align_corners=False)[:, 0]
     mag = F.interpolate(m[:4, None].double().abs(), scale_factor=2, mode="bilinear", align_corners=False)[:, 0]
     err = (out[:4].double() - ref).abs()
@@ -479,7 +475,7 @@ def test_topk_points(ops, s, k):
     for r, kind in enumerate(sr.TOPK_KINDS[:-1]):
         want, wc = sr.topk_reference(m[r], k)
         assert torch.equal(idx[r].long(), want), f"(a) {kind}: indices"
-        assert torch.equal(sr.bits(crd[r]), sr.bits(wc)), f"(a) {kind}: coordinates"
+        assert torch.equal(kit.bits(crd[r]), kit.bits(wc)), f"(a) {kind}: coordinates"
     assert bool(is_sentinel(idx[R - 1]).all()) and bool(is_sentinel(crd[R - 1]).all()), "(c) the map past the count"
 
 
@@ -506,11 +502,11 @@ def test_point_logit_scatter(ops, kdim, ldx, s, with_idx):
                                                                            s=s))
         res.append(mp.cpu())
     got = res[0]
-    assert torch.equal(sr.bits(got), sr.bits(res[1]))
+    assert torch.equal(kit.bits(got), kit.bits(res[1]))
     worst = 0.0
     for r in range(B * R):
         if r % R >= counts[r // R]:
-            assert torch.equal(sr.bits(got[r]), sr.bits(before[r])), "(c) a map past the count"
+            assert torch.equal(kit.bits(got[r]), kit.bits(before[r])), "(c) a map past the count"
             continue
         xs, wr = x[r * P:(r + 1) * P, :kdim].double(), w[classes[r]].double()
         ref, mag = xs @ wr + bias[classes[r]].double(), xs.abs() @ wr.abs() + bias[classes[r]].double().abs()
@@ -519,7 +515,7 @@ def test_point_logit_scatter(ops, kdim, ldx, s, with_idx):
         worst = max(worst, float((err / (sr.gamma(kdim + 1) * mag)).max()))
         rest = torch.ones(s * s, dtype=torch.bool)
         rest[where] = False
-        assert torch.equal(sr.bits(got[r][rest]), sr.bits(before[r][rest])), "(c) a pixel outside idx"
+        assert torch.equal(kit.bits(got[r][rest]), kit.bits(before[r][rest])), "(c) a pixel outside idx"
     print(f"SEG_DOMAIN point_logit kdim={kdim}: worst |err| / bound = {worst:.3f}")
     assert worst <= 1.0
 
@@ -562,9 +558,9 @@ def test_operator_refusals_are_reported_not_launched(ops, hip_lib):
     argument names keeps its sentinel."""
     buf = sr.sentinel(1 << 16).to(DEV)
     for fn, text, args in sr.OPS_REFUSALS:
-        a = [C.c_void_p(buf.data_ptr()) if v is sr.PTR else v for v in args] + [None]
+        a = [C.c_void_p(buf.data_ptr()) if v is kit.PTR else v for v in args] + [None]
         assert getattr(hip_lib, fn)(*a) == -1, (fn, args)
         msg = hip_lib.coma_last_error().decode()
         assert msg.startswith(fn + ":") and re.search(text, msg), (fn, msg)
     torch.cuda.synchronize()
-    assert bool((sr.bits(buf.cpu()) == sr.SENTINEL_BITS).all())
+    assert bool((kit.bits(buf.cpu()) == kit.sentinel_bits(torch.float32)).all())

@@ -12,6 +12,7 @@ import torch
 
 from coma_amd._lib import ComaHipError
 from oracle import seg_oracle as so
+from tests import domain_kit as kit
 from tests import seg_ref as sr
 
 
@@ -112,11 +113,11 @@ def test_gemm_references(case):
 
 def test_gemm_refusals_raise_through_describe(ops, hip_lib):
     for text, change in sr.GEMM_REFUSALS:
-        kw = {k: (4096 if v is sr.PTR else v) for k, v in {**sr.GEMM_REFUSAL_BASE, **change}.items()}
+        kw = {k: (4096 if v is kit.PTR else v) for k, v in {**sr.GEMM_REFUSAL_BASE, **change}.items()}
         x, w, out = kw.pop("x"), kw.pop("w"), kw.pop("out")
         with pytest.raises(ComaHipError, match=r"seg_conv_gemm_describe failed \(-1\): seg_conv_gemm_f32: .*" + text):
             ops.conv_gemm_describe(x, w, out, **kw)
-    kw = {k: (4096 if v is sr.PTR else v) for k, v in sr.GEMM_REFUSAL_BASE.items()}
+    kw = {k: (4096 if v is kit.PTR else v) for k, v in sr.GEMM_REFUSAL_BASE.items()}
     x, w, out = kw.pop("x"), kw.pop("w"), kw.pop("out")
     assert ops.conv_gemm_describe(x, w, out, **kw).tile == 3                         # the base row itself is accepted
     ch = ops.SegConvChoice()
@@ -164,7 +165,7 @@ def test_operator_refusals_raise_before_any_launch(hip_lib):
                                                      "seg_sort_candidates", "seg_nms", "seg_roi_align_f32", "seg_box_predict", "seg_finalize_detections",
                                                      "seg_point_sample_f32", "seg_upsample2x_f32", "seg_topk_points", "seg_point_logit_scatter", "seg_paste_masks"}
     for fn, text, args in sr.OPS_REFUSALS:
-        a = [C.c_void_p(4096) if v is sr.PTR else v for v in args] + [None]
+        a = [C.c_void_p(4096) if v is kit.PTR else v for v in args] + [None]
         assert getattr(hip_lib, fn)(*a) == -1, (fn, args)
         msg = hip_lib.coma_last_error().decode()
         assert msg.startswith(fn + ":") and re.search(text, msg), (fn, msg)

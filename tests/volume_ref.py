@@ -36,7 +36,7 @@ def crossings(verts, faces, x0, y0, s, W, H):
     for ia, ib, ic in faces.tolist():
         ax, ay, bx, by, cx, cy = X[ia], Y[ia], X[ib], Y[ib], X[ic], Y[ic]
         za, zb, zc = Zd[ia], Zd[ib], Zd[ic]
-        area = RR._edge(ax, ay, bx, by, cx, cy)
+        area = RR.edge(ax, ay, bx, by, cx, cy)
         if area == 0:
             continue
         sigma = 1 if area > 0 else -1
@@ -48,8 +48,8 @@ def crossings(verts, faces, x0, y0, s, W, H):
             continue
         px = (256 * np.arange(i0, i1 + 1, dtype=np.int64) + 128)[None, :]
         py = (256 * np.arange(j0, j1 + 1, dtype=np.int64) + 128)[:, None]
-        e0, e1, e2 = RR._edge(bx, by, cx, cy, px, py), RR._edge(cx, cy, ax, ay, px, py), RR._edge(ax, ay, bx, by, px, py)
-        t0, t1, t2 = RR._owns_ties(bx, by, cx, cy), RR._owns_ties(cx, cy, ax, ay), RR._owns_ties(ax, ay, bx, by)
+        e0, e1, e2 = RR.edge(bx, by, cx, cy, px, py), RR.edge(cx, cy, ax, ay, px, py), RR.edge(ax, ay, bx, by, px, py)
+        t0, t1, t2 = RR.owns_ties(bx, by, cx, cy), RR.owns_ties(cx, cy, ax, ay), RR.owns_ties(ax, ay, bx, by)
         inside = ((e0 > 0) | ((e0 == 0) & t0)) & ((e1 > 0) | ((e1 == 0) & t1)) & ((e2 > 0) | ((e2 == 0) & t2))
         if not inside.any():
             continue
