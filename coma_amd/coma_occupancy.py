@@ -180,20 +180,21 @@ class ComA_Occupancy:
         self._splat(q)
 
     def _window(self):
-        """Candidate cells per axis a sample can reach (what coma_occupancy_fused is told; it rounds up to a power of two)."""
+        """Candidate cells per axis a sample can reach (what coma_occupancy_fused is told; it rounds up to a power of two and refuses
+        less than this very expression: occ_window_needed in csrc/occupancy.hip)."""
         voxel, thres = float(self.spatial_grid_metadata["voxel_size"]), float(self.rel_dist_thres)
         return int(np.ceil(2.0 * thres / voxel - 1e-9)) + 2
 
     def _fusable(self, extra=0):
         """Can the fused pass take the staged samples (+ `extra` more)?  Mirrors every size check of coma_occupancy_fused:
-        cubic grid, R*R % 4 == 0, an x-plane fits the LDS slab, window <= 16 cells (scale_tolerance is a free CLI float) and
-        fewer than 65536 samples per call (16-bit counters)."""
+        cubic grid, R*R % 4 == 0, an x-plane fits the LDS slab, window <= 16 cells (scale_tolerance is a free CLI float), fewer
+        than 65536 samples per call (16-bit counters) and a 16-byte aligned grid (a caller may have assigned a view)."""
         R = self.spatial_res
         w = self._window()
         w2 = w if w <= 2 else 1 << (w - 1).bit_length()
         staged = sum(int(p.shape[0]) for p in self._pending) + int(extra)
         return (self.N_x == self.N_y == self.N_z == R and (R * R) % 4 == 0 and R * R <= 20480 and R <= 255 and w2 <= 16
-                and staged < 65536)
+                and staged < 65536 and self._grid.data_ptr() % 16 == 0)
 
     def _flush(self):
         pend, self._pending = self._pending, []

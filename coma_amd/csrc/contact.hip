@@ -27,6 +27,7 @@ constexpr int SC = 8;    // samples per scalar chunk (PT*SC == 64 lanes)
 constexpr int NB = 4;    // bins per lane
 constexpr int kBinsPerChunk = NB * kWave;
 constexpr int kWavesPerBlock = 4;
+constexpr int kMaxBins = 65535 * kBinsPerChunk;   // grid y
 constexpr float kPi = 3.14159265358979323846f;
 
 struct ContactArgs {
@@ -246,6 +247,8 @@ extern "C" int coma_contact_accumulate_f32(const float* human_verts, const float
     return fail(COMA_E_INVALID, "coma_contact_accumulate_f32: null pointer");
   if (S < 0 || H <= 0 || O <= 0 || N <= 0)
     return fail(COMA_E_INVALID, "coma_contact_accumulate_f32: bad sizes S=%d H=%d O=%d N=%d", S, H, O, N);
+  if (N > kMaxBins)   // the 256-bin chunks walk grid y, which holds 65535 workgroups
+    return fail(COMA_E_INVALID, "coma_contact_accumulate_f32: N=%d exceeds %d bins (65535 chunks of 256 along grid y)", N, kMaxBins);
   if (obj_sample_stride != 0 && obj_sample_stride != (int64_t)O * 3)
     return fail(COMA_E_INVALID, "coma_contact_accumulate_f32: obj_sample_stride must be 0 or 3*O");
   if (!(normal_gaussian_sigma > 0.f) || !(spatial_grid_size > 0.f))

@@ -44,12 +44,12 @@ __global__ __launch_bounds__(kSplatWaves* kWave) void occupancy_splat_kernel(
       empty |= n[c] <= 0;
     }
     if (empty) continue;   // wave-uniform: vertex farther than thres from the whole grid
-    const int total = n[0] * n[1] * n[2];
-    for (int t = lane; t < total; t += kWave) {
-      int iz = t % n[2];
-      int r = t / n[2];
-      int iy = r % n[1];
-      int ix = r / n[1];
+    const int64_t total = (int64_t)n[0] * n[1] * n[2];   // (a threshold that spans the grid: R^3 passes 2^31 from R = 1291)
+    for (int64_t t = lane; t < total; t += kWave) {
+      int iz = (int)(t % n[2]);
+      int64_t r = t / n[2];
+      int iy = (int)(r % n[1]);
+      int ix = (int)(r / n[1]);
       ix += lo[0]; iy += lo[1]; iz += lo[2];
       double dx = centers[ix] - qc[0];
       double dy = centers[R + iy] - qc[1];
@@ -66,7 +66,7 @@ __global__ __launch_bounds__(256) void occupancy_rowsum_kernel(const float* __re
   __shared__ float part[4];
   const float* row = counts + (int64_t)blockIdx.x * R3;
   float s = 0.0f;
-  if ((R3 & 3) == 0) {                       // 16-byte loads, four independent partial sums
+  if ((R3 & 3) == 0 && (reinterpret_cast<uintptr_t>(counts) & 15) == 0) {   // 16-byte loads, four independent partial sums
     const float4* row4 = reinterpret_cast<const float4*>(row);
     float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     for (int64_t i = threadIdx.x; i < (R3 >> 2); i += 256) {
@@ -152,6 +152,10 @@ constexpr int kFusedListCap = 512;                               // items of one
 // a (sample, x-plane) incidence as the fused pass stages it in LDS: the record + the plane
 struct OccItem { float x, y, z; unsigned pack; };                // pack: lo_y | lo_z << 8 | plane << 16
 
+__device__ __forceinline__ bool occ_finite3(float x, float y, float z) {
+  return fabsf(x) < __builtin_inff() && fabsf(y) < __builtin_inff() && fabsf(z) < __builtin_inff();
+}
+
 __device__ __forceinline__ void axis_range(double qc, double thres, double c0, double inv, int R, int& lo, int& n) {
   int a = (int)floor((qc - thres - c0) * inv - 0.01);           // conservative (0.01-voxel margin), as in the splat kernel
   int b = (int)ceil((qc + thres - c0) * inv + 0.01);
@@ -188,7 +192,9 @@ __global__ __launch_bounds__(256) void occupancy_rowprep_kernel(const float* __r
     int lo[3], n[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) axis_range(qc[c], thres, cen[c * R], inv, R, lo[c], n[c]);
-    if (n[0] <= 0 || n[1] <= 0 || n[2] <= 0) continue;
+    // a NaN / Inf coordinate hits no cell in the reference (every comparison with NaN is false); here it must not reach the f32
+    // decision below, which reads the SIGN BIT of d -- and a NaN has one
+    if (n[0] <= 0 || n[1] <= 0 || n[2] <= 0 || !occ_finite3(qp[0], qp[1], qp[2])) continue;
     // exact count of one x-plane: the reference's predicate, (dx*dx + dy*dy) + dz*dz < t2 in f64, every product rounded on its own
     auto plane_exact = [&](int ix) {
       const double dx = cen[ix] - qc[0];
@@ -264,8 +270,8 @@ __global__ __launch_bounds__(256) void occupancy_rowprep_kernel(const float* __r
     axis_range((double)fx, thres, cen[0], inv, R, lo[0], n[0]);
     axis_range((double)fy, thres, cen[R], inv, R, lo[1], n[1]);
     axis_range((double)fz, thres, cen[2 * R], inv, R, lo[2], n[2]);
-    const bool empty = n[0] <= 0 || n[1] <= 0 || n[2] <= 0;
-    if (empty) continue;
+    const bool empty = n[0] <= 0 || n[1] <= 0 || n[2] <= 0 || !occ_finite3(fx, fy, fz);
+    if (empty) continue;                                          // (no incidence: the fused pass never sees a non-finite position)
     // one complete 16-byte incidence per (sample, x-plane): the fused pass reads its slab's bucket with ONE coalesced load per item
     // (r3 first kept 4-byte (sample | plane) words + one record per (row, sample): a dependent gather, i.e. one more global latency per row)
     const unsigned yz = (unsigned)lo[1] | ((unsigned)lo[2] << 8);
@@ -503,6 +509,8 @@ __global__ __launch_bounds__(256) void occupancy_groupmax_kernel(const float* __
 
 using namespace coma;
 
+static bool occ_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 extern "C" int coma_occupancy_splat(const float* q, int S, int H, int R, const double* centers,
                                     double voxel, double thres, float* counts, void* stream) {
   if (!q || !centers || !counts) return fail(COMA_E_INVALID, "coma_occupancy_splat: null pointer");
@@ -518,9 +526,13 @@ extern "C" int coma_occupancy_reduce(float* counts, const uint8_t* select, int H
                                      float* rowsum, float* out, void* stream) {
   if (!counts || !rowsum || !out) return fail(COMA_E_INVALID, "coma_occupancy_reduce: null pointer");
   if (H <= 0 || R3 <= 0) return fail(COMA_E_INVALID, "coma_occupancy_reduce: bad sizes");
+  // four cells per thread need R3 % 4 == 0 (every row then starts on a quad) AND 16-byte aligned counts / out; otherwise one cell each
+  const bool quads = (R3 & 3) == 0 && occ_aligned16(counts) && occ_aligned16(out);
+  if ((quads ? (R3 / 4 + 255) / 256 : (R3 + 255) / 256) > 0x7fffffffLL)
+    return fail(COMA_E_INVALID, "coma_occupancy_reduce: R3=%lld needs more than 2^31 - 1 workgroups", (long long)R3);
   hipLaunchKernelGGL(occupancy_rowsum_kernel, dim3((unsigned)H), dim3(256), 0, (hipStream_t)stream, counts,
                      R3, rowsum);
-  if ((R3 & 3) == 0) {
+  if (quads) {
     const int64_t blocks = (R3 / 4 + 255) / 256;
     hipLaunchKernelGGL(occupancy_norm_max4_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
                        counts, select, rowsum, H, R3, out);
@@ -536,6 +548,8 @@ extern "C" int coma_occupancy_reduce(float* counts, const uint8_t* select, int H
 // workspace layout: [items: H * S * window 16-byte incidences | plane_off: H * (R + 1) words | partial maxima: groups * R^3 f32]
 static size_t occ_ws_items(int S, int H, int window) { return occ_align256((size_t)S * H * window * sizeof(OccItem)); }
 static size_t occ_ws_off(int H, int R) { return occ_align256((size_t)H * (R + 1) * sizeof(unsigned)); }
+// candidate cells per axis a threshold of thres / voxel cells needs (coma_amd/coma_occupancy.py ComA_Occupancy._window is the same expression)
+static int occ_window_needed(double voxel, double thres) { return (int)ceil(2.0 * thres / voxel - 1e-9) + 2; }
 static int occ_pow2_window(int window) {
   if (window > 2 && (window & (window - 1))) { int w2 = 1; while (w2 < window) w2 <<= 1; window = w2; }   // cell decode by shifts
   return window;
@@ -570,6 +584,15 @@ extern "C" int coma_occupancy_fused(const float* q, int S, int H, int R, const d
   if (groups > H) groups = H;
   const size_t lds = 2 * ((((size_t)P * RR * 2 + 15) / 16) * 16) + (size_t)kFusedListCap * sizeof(OccItem) + (size_t)3 * R * sizeof(double) + 256 * sizeof(float);   // two counter buffers, quotient table
   if (S >= 65536) return fail(COMA_E_INVALID, "coma_occupancy_fused: S=%d >= 65536 samples per call (16-bit counters)", S);
+  // hits past the first `window` cells of a candidate range would be dropped from the grid and the row sum alike
+  if (!(2.0 * thres / voxel <= 64.0) || window < occ_window_needed(voxel, thres))
+    return fail(COMA_E_INVALID, "coma_occupancy_fused: window=%d cells (rounded up to a power of two) < the %d that thres / voxel = %g needs",
+                window, 2.0 * thres / voxel <= 64.0 ? occ_window_needed(voxel, thres) : 66, thres / voxel);
+  // thres_sq_cut is the smallest double whose square root is >= thres: its own root reaches thres, its predecessor's does not
+  if (!(thres_sq_cut > 0.0) || !(sqrt(thres_sq_cut) >= thres) || !(sqrt(nextafter(thres_sq_cut, 0.0)) < thres))
+    return fail(COMA_E_INVALID, "coma_occupancy_fused: thres_sq_cut=%.17g is not the smallest double whose square root is >= thres=%.17g", thres_sq_cut, thres);
+  if (!occ_aligned16(counts) || !occ_aligned16(out) || !occ_aligned16(workspace))
+    return fail(COMA_E_INVALID, "coma_occupancy_fused: %s must be 16-byte aligned", !occ_aligned16(counts) ? "counts" : !occ_aligned16(out) ? "out" : "workspace");
   hipStream_t st = (hipStream_t)stream;
   unsigned char* wsb = reinterpret_cast<unsigned char*>(workspace);
   OccItem* items = reinterpret_cast<OccItem*>(wsb);

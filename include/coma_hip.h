@@ -31,7 +31,9 @@ extern "C" {
 #define COMA_ABI_VERSION 11  /* 11: seg_conv_gemm_describe added; seg_conv_gemm_f32 refuses a forced split_k whose slabs the workspace does not hold (it ran with fewer slices); 10: sd_conv_gemm_describe added; sd_conv_gemm_f16 refuses a column bias with SD_EPI_PERM16_N / SD_EPI_PERM32_N and colstats in a phase launch with in_h * in_w % 32 != 0 */
 /* The version counts CHANGES of existing signatures, not additions: a function that is only added (the text tower, the sample
  * elimination, the rasteriser, the mesh volume functions, the coma_vposer_* and coma_angle_prior_* functions) leaves it alone, because a library without it already fails to load
- * (coma_amd/_lib.py binds every declared name). */
+ * (coma_amd/_lib.py binds every declared name).  An argument check that is only added (coma_occupancy_fused's window, thres_sq_cut
+ * and alignment checks, coma_contact_accumulate_f32's limit on N, coma_occupancy_reduce's limit on R3) leaves it alone as well: the
+ * call was outside the documented contract before, and is told so now. */
 
 #define COMA_OK 0
 #define COMA_E_INVALID (-1) /* bad argument (null pointer, non-positive size, unsupported shape) */
@@ -52,8 +54,10 @@ const char* coma_last_error(void);
  * sphere_grid               : f32 [N,3]   (the f32 rounding of get_uniform_points_on_sphere, :18-26)
  * principle_vec/sub_vec     : HOST pointers, 3 floats each
  * prob_h_wrt_o, prob_o_wrt_h: f32 [H,O,N] in/out ;  nom, den, cnt : f32 [H,O] in/out
- * Numerics: distance/threshold test bit-exact w.r.t. the reference's f32 sequence; the histogram is
- * evaluated in f32 (reference: f64 intermediates rounded into f32 sums), parity <= 1e-3 relative.
+ * Numerics: distance/threshold test bit-exact w.r.t. the reference's f32 sequence (cnt and den are exact); the histogram is
+ * evaluated in f32 (reference: f64 intermediates rounded into f32 sums), parity <= 1e-3 relative.  The weights of one call are
+ * summed in f32 as 2^64 * w and rescaled once, so a bin the reference keeps as an f32 denormal is kept here too.
+ * S = 0 is accepted and writes nothing.  N <= 65535 * 256 (the 256-bin chunks walk grid y); a larger N is refused.
  * ------------------------------------------------------------------------------------------- */
 int coma_contact_accumulate_f32(const float* human_verts, const float* human_normals,
                                 const float* obj_verts, const float* obj_normals,
@@ -114,7 +118,8 @@ int coma_contact_select_u8(const float* nom, const float* den, int H, int O, flo
  *           voxel_size * f32(index) is rounded to f32 there, so the table is NOT start+voxel*(i+.5))
  * voxel   : centre spacing (2.4/R), used only to bound the candidate box
  * thres   : voxel*scale_tolerance (:242), the f64 threshold of the test d < thres
- * counts  : f32 [H,R,R,R] in/out; integer-valued, bit-exact (f64 distance, (x+y)+z order). */
+ * counts  : f32 [H,R,R,R] in/out; integer-valued, bit-exact (f64 distance, (x+y)+z order) while a cell stays below 2^24.
+ * A sample with a NaN or infinite coordinate hits no cell.  S = 0 is accepted and writes nothing. */
 int coma_occupancy_splat(const float* q, int S, int H, int R, const double* centers, double voxel,
                          double thres, float* counts, void* stream);
 
@@ -122,7 +127,11 @@ int coma_occupancy_splat(const float* q, int S, int H, int R, const double* cent
  * replaces: utils/coma_occupancy.py:297-312 (normalize_prob_grid_for_spatials + max over humans).
  * counts [H,R3] in/out -> counts/rowsum (no eps: an empty row becomes NaN, as in the reference);
  * select u8 [H] or NULL (= all) picks the rows the max runs over; out f32 [R3];
- * rowsum f32 [H] is scratch/output.  NaN propagates like torch.max. */
+ * rowsum f32 [H] is scratch/output.  NaN propagates like torch.max.  A select without any row set leaves out = -inf everywhere.
+ * rowsum is an f32 sum of the cells in the kernel's own order: exact, hence equal to coma_occupancy_fused's, while the row's hit
+ * total is below 2^24; above that it is one of several roundings and the quotients follow it.
+ * With R3 % 4 == 0 and counts and out both 16-byte aligned the cells go four at a time; any other R3 or alignment is accepted
+ * and takes the one-cell kernels, same bits.  R3 needing more than 2^31 - 1 workgroups is refused. */
 int coma_occupancy_reduce(float* counts, const uint8_t* select, int H, int64_t R3, float* rowsum,
                           float* out, void* stream);
 
@@ -136,7 +145,16 @@ int coma_occupancy_reduce(float* counts, const uint8_t* select, int H, int64_t R
  * window       : candidate cells per axis, >= the number of voxel centres an open interval of length 2*thres (+ the 0.01-voxel
  *                margins) can contain: ceil(2*scale_tolerance) + 2;
  * workspace    : coma_occupancy_fused_workspace_bytes(S, H, R, window) bytes of device scratch (16 bytes per (vertex, sample) + 4 bytes per
- *                (vertex, sample, window plane) + the per-group maxima).  R*R % 4 == 0, R*R <= 20480. */
+ *                (vertex, sample, window plane) + the per-group maxima).  R*R % 4 == 0, R*R <= 20480: the latter binds before the
+ *                R <= 255 of the 8-bit cell indices, so R <= 142 in effect.
+ * Refused (COMA_E_INVALID): a window whose power-of-two rounding is below ceil(2*thres/voxel - 1e-9) + 2 (hits past the first
+ * `window` cells of a range would be dropped from the grid and the row sum alike); a thres_sq_cut that is not the cut of thres
+ * (checked with two host sqrt); counts, out or workspace not 16-byte aligned (all three are accessed 16 bytes at a time).
+ * counts is overwritten (every cell, every row), not added to.  A select without any row set leaves out = -inf everywhere, as in
+ * coma_occupancy_reduce.  A sample with a NaN or infinite coordinate hits no cell.  rowsum[h] is the correctly rounded f32 of the
+ * exact integer hit total (a 32-bit count: S * window^3 < 2^32) and every quotient the correctly rounded f32 division by it, also
+ * above 2^24, where coma_occupancy_reduce's f32 row sum may round differently (reachable from about 11 700 samples at
+ * scale_tolerance 7). */
 size_t coma_occupancy_fused_workspace_bytes(int S, int H, int R, int window);
 int coma_occupancy_fused(const float* q, int S, int H, int R, const double* centers, double voxel, double thres,
                          double thres_sq_cut, int window, const uint8_t* select, int write_raw, float* counts, float* rowsum,
