@@ -3,7 +3,9 @@
 
 `DeviceSMPLX` has the call shape of the third-party `smplx` package's model object, which is what the `body_model` hooks of
 src/application/optimize.py and src/generation/optimize_depth.py call: keyword tensors in, an object with .vertices [1,V,3],
-.joints, .full_pose and .faces out.  `.vertices` is the output of a torch.autograd.Function whose backward is the device backward, so
+.joints, .full_pose and .faces out.  `batch_size=N` (the package's own constructor argument) poses N bodies per call through the
+batched entry points (coma_smplx_*_batch_f32): every output gains the leading dimension N, and body n has the bits of a single-body
+call on the same inputs.  `.vertices` is the output of a torch.autograd.Function whose backward is the device backward, so
 a pose decoder or a prior on the other side of the hook keeps differentiating through torch.
 
 By default `.joints` and `.full_pose` carry no gradient and betas / expression must not require grad.  `differentiable=` opts in, any
@@ -17,7 +19,8 @@ Deviations from the package, all refused or stated rather than silently differen
   * by default NO gradient with respect to betas or expression (the call raises if either requires grad) and none through `.joints`
     or `.full_pose`; each needs its entry in `differentiable=`;
   * no gradient with respect to the model's own tensors (shapedirs, posedirs, weights), no double backward;
-  * batch size 1 only;
+  * at batch_size > 1 no gradient to betas or expression ("shape" is refused in the constructor), and betas / expression are one row
+    for all bodies or one row per body; DeviceVPoser, ComaObjective and DeviceFit are not batched and the CLIs pose one body;
   * the package's table of vertex ids for the extra joints (nose, eyes, ears, toes, heels, finger tips) is not shipped: it is taken
     from `smplx.vertex_ids` when that package imports, may be passed in, and otherwise `.joints` is [J posed joints | landmarks] and
     `extra_joint_source` says "landmarks only";
@@ -37,6 +40,7 @@ from . import _lib
 
 SHAPE_SPACE_DIM, EXPRESSION_SPACE_DIM = 300, 100
 MAX_JOINTS = 64
+MAX_BATCH = 1024                                                         # the batched entry points' bound on N
 MAX_GRAD_EXTRA_JOINTS = 4096                                             # the full backward's bound on E
 DIFFERENTIABLE = ("joints", "full_pose", "shape")
 # the package's order of the extra joints (vertex_joint_selector.py): face and feet, then the finger tips of both hands
@@ -68,14 +72,21 @@ def _row(x, n, name):
 
 class DeviceSMPLX:
     def __init__(self, model, n_pca=45, flat_hand_mean=False, use_pca=True, device="cuda", num_betas=10, num_expression_coeffs=10,
-                 extra_joint_vertex_ids=None, differentiable=()):
+                 extra_joint_vertex_ids=None, differentiable=(), batch_size=1):
         """model: a dict of arrays with the keys of an SMPL-X model file (v_template, shapedirs, posedirs, J_regressor, kintree_table,
         weights, f, hands_components{l,r}, hands_mean{l,r}, lmk_faces_idx, lmk_bary_coords).  differentiable: a subset of
-        DIFFERENTIABLE, what besides .vertices -> pose / transl takes part in autograd (module docstring); empty = none."""
+        DIFFERENTIABLE, what besides .vertices -> pose / transl takes part in autograd (module docstring); empty = none.  batch_size: the
+        bodies posed per call; every pose argument and transl is then [batch_size, n] or [1, n], betas and expression likewise."""
         dev = _lib.need_device(device, "DeviceSMPLX", resolve=False)
+        if isinstance(batch_size, bool) or not isinstance(batch_size, (int, np.integer)) or not 1 <= batch_size <= MAX_BATCH:
+            raise ValueError(f"DeviceSMPLX: batch_size={batch_size!r} must be an integer in [1, {MAX_BATCH}]")
+        self.batch_size = int(batch_size)
         if isinstance(differentiable, str) or not set(differentiable) <= set(DIFFERENTIABLE):
             raise ValueError(f"DeviceSMPLX: differentiable={differentiable!r} must be a collection of names out of {DIFFERENTIABLE}")
         self.differentiable = frozenset(differentiable)
+        if "shape" in self.differentiable and self.batch_size > 1:
+            raise ValueError(f"DeviceSMPLX: differentiable \"shape\" with batch_size={self.batch_size}: the batched backward has no gradient to "
+                             f"betas or expression; use batch_size=1 for it")
         need = ("v_template", "shapedirs", "posedirs", "J_regressor", "kintree_table", "weights", "f", "hands_componentsl", "hands_componentsr",
                 "hands_meanl", "hands_meanr", "lmk_faces_idx", "lmk_bary_coords")
         missing = [k for k in need if k not in model]
@@ -162,7 +173,7 @@ class DeviceSMPLX:
 
     @classmethod
     def from_file(cls, model_path, gender="neutral", num_pca_comps=45, flat_hand_mean=False, use_pca=True, device="cuda", num_betas=10,
-                  num_expression_coeffs=10, extra_joint_vertex_ids=None, differentiable=()):
+                  num_expression_coeffs=10, extra_joint_vertex_ids=None, differentiable=(), batch_size=1):
         """model_path: the model file itself, or -- the path rule of the package's `create(model_path, model_type="smplx")` -- a
         directory whose `smplx/` sub-directory holds SMPLX_{GENDER}.npz; read with NumPy alone."""
         pth = model_path
@@ -175,7 +186,8 @@ class DeviceSMPLX:
         with np.load(pth, allow_pickle=True) as data:
             model = {k: data[k] for k in data.files}
         return cls(model, n_pca=num_pca_comps, flat_hand_mean=flat_hand_mean, use_pca=use_pca, device=device, num_betas=num_betas,
-                   num_expression_coeffs=num_expression_coeffs, extra_joint_vertex_ids=extra_joint_vertex_ids, differentiable=differentiable)
+                   num_expression_coeffs=num_expression_coeffs, extra_joint_vertex_ids=extra_joint_vertex_ids, differentiable=differentiable,
+                   batch_size=batch_size)
 
     def _upload(self):
         if self._uploaded:
@@ -195,6 +207,14 @@ class DeviceSMPLX:
         if self.differentiable:
             self._grad_ws_bytes = int(L.coma_smplx_grad_workspace_bytes(self.V, self.J, self.num_betas + self.num_expression_coeffs))
             self._grad_ws = torch.empty([self._grad_ws_bytes], dtype=torch.uint8, device=dev)
+        if self.batch_size > 1:                                          # scratch of the batched calls; `saved` is per forward
+            N = self.batch_size
+            self._batch_ws_bytes, self._batch_saved_bytes, self._batch_grad_ws_bytes = (int(f(self.V, self.J, N)) for f in (
+                L.coma_smplx_batch_workspace_bytes, L.coma_smplx_batch_saved_bytes, L.coma_smplx_batch_grad_workspace_bytes))
+            self._batch_ws = torch.empty([self._batch_ws_bytes], dtype=torch.uint8, device=dev)
+            self._batch_grad_ws = torch.empty([self._batch_grad_ws_bytes], dtype=torch.uint8, device=dev)
+            self._shape_stride = (self._shape_bytes + 15) // 16 * 16
+            self._batch_shape_state, self._batch_shape_keys = None, None
         self._uploaded = True
 
     # ---- the three device calls ----
@@ -325,6 +345,8 @@ class DeviceSMPLX:
         sizes = (("global_orient", global_orient, 3), ("body_pose", body_pose, self.num_body), ("jaw_pose", jaw_pose, 3),
                  ("leye_pose", leye_pose, 3), ("reye_pose", reye_pose, 3), ("left_hand_pose", left_hand_pose, self.hand_size),
                  ("right_hand_pose", right_hand_pose, self.hand_size), ("transl", transl, 3))
+        if self.batch_size > 1:
+            return self._call_batch(sizes, betas, expression, return_verts, return_full_pose)
         rows = [(name, _row(x, n, name), n) for name, x, n in sizes]          # shapes first: nothing has touched the device yet
         coefficients = self._shape_stage(betas, expression)                 # a device tensor with differentiable "shape", else None
         parts = []
@@ -343,6 +365,121 @@ class DeviceSMPLX:
         return SimpleNamespace(vertices=vertices[None] if return_verts else None, joints=joints[None],
                                full_pose=full_pose[None] if return_full_pose else None, faces=self.faces, betas=betas, expression=expression,
                                global_orient=global_orient, body_pose=body_pose, jaw_pose=jaw_pose, transl=transl)
+
+    # ---- batch_size > 1 ----
+    def _rows(self, x, n, name):
+        """A call argument of a batched object as a 2-D tensor [1 or batch_size, n] (None stays None)."""
+        if x is None:
+            return None
+        if not torch.is_tensor(x):
+            x = torch.as_tensor(np.asarray(x, dtype=np.float32))
+        if x.dim() == 1:
+            x = x[None]
+        if x.dim() != 2 or x.shape[1] != n:
+            raise ValueError(f"{name}: expected [{self.batch_size},{n}] or [1,{n}], got shape {tuple(x.shape)}")
+        if x.shape[0] not in (1, self.batch_size):
+            raise ValueError(f"{name}: leading dimension {x.shape[0]} is neither 1 nor batch_size={self.batch_size}")
+        return x
+
+    def _shape_stage_batch(self, betas, expression):
+        """The shape stage for a batch: ONE state when betas and expression are both [1, n] (or absent), else batch_size states,
+        each written by coma_smplx_shape_f32 and re-run only when ITS row of coefficients differs from the last call's (compared on
+        the host as at batch size 1; the same tensors at the same version counters are not looked at again) -> (buffer, stride)."""
+        for x, name in ((betas, "betas"), (expression, "expression")):
+            if torch.is_tensor(x) and x.requires_grad:
+                raise _lib.ComaHipError(f"DeviceSMPLX: {name} requires grad, and the batched device body model has no gradient with respect "
+                                        f"to {name}")
+        source = (betas, expression)
+        version = tuple(x._version if torch.is_tensor(x) else None for x in source)
+        if self._shape_source is not None and version == self._shape_version and all(
+                (x is None and y is None) or (torch.is_tensor(x) and x is y) for x, y in zip(source, self._shape_source)):
+            return self._batch_shape_state, (self._shape_stride if len(self._batch_shape_keys) > 1 else 0)
+        parts = []
+        for x, n, name in ((betas, self.num_betas, "betas"), (expression, self.num_expression_coeffs, "expression")):
+            x = self._rows(x, n, name)
+            parts.append(np.zeros([1, n], np.float32) if x is None else x.detach().to(torch.float32).cpu().numpy())
+        B = max(p.shape[0] for p in parts)
+        coef = np.ascontiguousarray(np.concatenate([np.broadcast_to(p, (B, p.shape[1])) for p in parts], 1), dtype=np.float32)
+        self._upload()
+        keys = [row.tobytes() for row in coef]
+        old = self._batch_shape_keys
+        stale = list(range(B)) if old is None or len(old) != B else [n for n in range(B) if keys[n] != old[n]]
+        if stale:
+            if self.differentiable or old is None or len(old) != B:     # with `differentiable`, forwards in flight keep the states they ran on
+                stale = list(range(B))
+                self._batch_shape_state = torch.empty([B * self._shape_stride], dtype=torch.uint8, device=self.device)
+            d_coef = torch.from_numpy(coef).to(self.device)
+            f32 = torch.float32
+            with _lib.on_device(self.device) as stream:
+                for n in stale:
+                    rc = _lib.lib().coma_smplx_shape_f32(_lib.ptr(self._v_template, f32), _lib.ptr(self._shapedirs, f32),
+                                                         C.c_void_p(d_coef.data_ptr() + 4 * n * coef.shape[1]), _lib.ptr(self._J_regressor, f32), self.V,
+                                                         self.J, coef.shape[1], C.c_void_p(self._batch_shape_state.data_ptr() + n * self._shape_stride),
+                                                         self._shape_bytes, stream)
+                    _lib.check(rc, "coma_smplx_shape_f32")
+                    self.shape_stage_runs += 1
+        self._batch_shape_keys, self._shape_source, self._shape_version = keys, source, version
+        return self._batch_shape_state, (self._shape_stride if B > 1 else 0)
+
+    def _forward_batch(self, theta, transl, shape_state, shape_stride):
+        """theta f32 [N, num_theta], transl f32 [N, 3] or None (device, contiguous) -> vertices [N,V,3], joints [N, J + extra, 3],
+        full_pose [N, 3J], saved: all new tensors."""
+        f32, dev, N = torch.float32, self.device, self.batch_size
+        vertices = torch.empty([N, self.V, 3], dtype=f32, device=dev)
+        joints = torch.empty([N, self.J, 3], dtype=f32, device=dev)
+        full_pose = torch.empty([N, 3 * self.J], dtype=f32, device=dev)
+        saved = torch.empty([self._batch_saved_bytes], dtype=torch.uint8, device=dev)
+        L = _lib.lib()
+        with _lib.on_device(dev) as stream:
+            rc = L.coma_smplx_forward_batch_f32(_lib.ptr(theta, f32, "theta"), _lib.ptr(transl, f32, "transl"), _lib.ptr(self._posedirs, f32),
+                                                _lib.ptr(self._weights, f32), self._parents, _lib.ptr(self._comps, f32), _lib.ptr(self._mean, f32),
+                                                self.V, self.J, self.hand_dim, self.num_pca_comps, N, _lib.ptr(shape_state), shape_stride,
+                                                _lib.ptr(vertices), _lib.ptr(joints), _lib.ptr(full_pose), _lib.ptr(saved), self._batch_saved_bytes,
+                                                _lib.ptr(self._batch_ws), self._batch_ws_bytes, stream)
+            _lib.check(rc, "coma_smplx_forward_batch_f32")
+            if self.num_extra:
+                extra = torch.empty([N, self.num_extra, 3], dtype=f32, device=dev)
+                rc = L.coma_smplx_extra_joints_batch_f32(_lib.ptr(vertices), _lib.ptr(transl, f32), _lib.ptr(self._extra_index, torch.int32),
+                                                         _lib.ptr(self._extra_weight, f32), self.V, self.num_extra, N, _lib.ptr(extra), stream)
+                _lib.check(rc, "coma_smplx_extra_joints_batch_f32")
+                joints = torch.cat([joints, extra], 1)
+        return vertices, joints, full_pose, saved
+
+    def _backward_batch(self, grad_vertices, grad_joints, grad_full_pose, saved, shape_state, shape_stride):
+        """The batched backward of ONE forward; each gradient f32 on the device or None = absent -> (g_theta [N, NT], g_transl [N, 3])."""
+        f32, dev, N = torch.float32, self.device, self.batch_size
+        g_theta = torch.empty([N, self.num_theta], dtype=f32, device=dev)
+        g_transl = torch.empty([N, 3], dtype=f32, device=dev)
+        with _lib.on_device(dev) as stream:
+            rc = _lib.lib().coma_smplx_backward_batch_f32(
+                _lib.ptr(grad_vertices, f32, "grad_vertices"), _lib.ptr(grad_joints, f32, "grad_joints"), _lib.ptr(grad_full_pose, f32, "grad_full_pose"),
+                _lib.ptr(self._posedirs, f32), _lib.ptr(self._weights, f32), self._parents, _lib.ptr(self._comps, f32),
+                _lib.ptr(self._extra_index, torch.int32), _lib.ptr(self._extra_weight, f32), self.num_extra, self.V, self.J, self.hand_dim,
+                self.num_pca_comps, N, _lib.ptr(shape_state), shape_stride, _lib.ptr(saved), self._batch_saved_bytes, _lib.ptr(g_theta),
+                _lib.ptr(g_transl), _lib.ptr(self._batch_grad_ws), self._batch_grad_ws_bytes, stream)
+        _lib.check(rc, "coma_smplx_backward_batch_f32")
+        return g_theta, g_transl
+
+    def _call_batch(self, sizes, betas, expression, return_verts, return_full_pose):
+        """__call__ at batch_size > 1: a [1, n] argument is expanded to [N, n] BEFORE the autograd function, so autograd sums its
+        gradient over the bodies."""
+        N = self.batch_size
+        rows = [(name, self._rows(x, n, name), n) for name, x, n in sizes]     # shapes first: nothing has touched the device yet
+        shape_state, shape_stride = self._shape_stage_batch(betas, expression)
+        parts = []
+        for name, x, n in rows:
+            if x is None:
+                x = None if name == "transl" else torch.zeros([N, n], dtype=torch.float32, device=self.device)
+            elif not x.is_cuda or x.device != self.device:
+                raise _lib.ComaHipError(f"{name} must live on {self.device} (got {x.device}); there is no CPU path")
+            parts.append(x if x is None else x.to(torch.float32).expand(N, n))
+        transl = parts.pop()
+        theta = torch.cat(parts, 1)
+        vertices, joints, full_pose = _BatchFunction.apply(self, theta, transl, shape_state, shape_stride)
+        named = dict(zip((name for name, _, _ in sizes), (x for _, x, _ in sizes)))
+        return SimpleNamespace(vertices=vertices if return_verts else None, joints=joints, full_pose=full_pose if return_full_pose else None,
+                               faces=self.faces, betas=betas, expression=expression, global_orient=named["global_orient"],
+                               body_pose=named["body_pose"], jaw_pose=named["jaw_pose"], transl=transl)
 
 
 class _SkinFunction(torch.autograd.Function):
@@ -386,3 +523,32 @@ class _FullFunction(torch.autograd.Function):
         g_theta, g_transl, g_coef = model._backward_full(f32(grad_vertices), f32(grad_joints), f32(grad_full_pose), ctx.saved, ctx.shape_state,
                                                          want_coefficients)
         return None, g_theta, (g_transl if ctx.has_transl else None), g_coef
+
+
+class _BatchFunction(torch.autograd.Function):
+    """batch_size > 1: the batched forward, and the batched backward from whichever outputs `differentiable` names.  The forward's
+    saved block and the shape states it ran on belong to this node: a second forward before the backward disturbs nothing."""
+
+    @staticmethod
+    def forward(ctx, model, theta, transl, shape_state, shape_stride):
+        vertices, joints, full_pose, saved = model._forward_batch(theta.detach().contiguous(), None if transl is None else transl.detach().contiguous(),
+                                                                   shape_state, shape_stride)
+        ctx.model, ctx.saved, ctx.shape_state, ctx.shape_stride, ctx.has_transl = model, saved, shape_state, shape_stride, transl is not None
+        dead = [t for name, t in (("joints", joints), ("full_pose", full_pose)) if name not in model.differentiable]
+        if dead:
+            ctx.mark_non_differentiable(*dead)
+        ctx.set_materialize_grads(False)
+        return vertices, joints, full_pose
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_vertices, grad_joints, grad_full_pose):
+        model = ctx.model
+        if "joints" not in model.differentiable:
+            grad_joints = None
+        if "full_pose" not in model.differentiable:
+            grad_full_pose = None
+        f32 = lambda g: None if g is None else g.to(torch.float32).contiguous()
+        g_theta, g_transl = model._backward_batch(f32(grad_vertices), f32(grad_joints), f32(grad_full_pose), ctx.saved, ctx.shape_state,
+                                                  ctx.shape_stride)
+        return None, g_theta, (g_transl if ctx.has_transl else None), None, None

@@ -24,6 +24,11 @@
 // kPSplit workgroups per column block, so that about a thousand workgroups keep loads in flight; backward reads the same rows as
 // P dot products, one workgroup each.  No transposed copy.  No floating-point atomics: every sum over vertices is per-workgroup
 // (fixed order inside), then one fixed-order pass over the workgroups, so two calls give the same bits.
+//
+// The BATCHED forms (coma_smplx_*_batch_f32: N bodies in the launches of one) share the arithmetic of every stage with the
+// single-body kernels as device functions, so body n of a batch has the bits of the single-body call.  What changes is how often
+// the operands move: a sweep over posedirs serves kChunk bodies (their features in LDS, one f64 sum per body in registers), a
+// skinning workgroup stages its weights tile once and walks kSkinChunk bodies over it, the pose stage runs one workgroup per body.
 #include "common.h"
 #include "coma_device.h"
 
@@ -38,6 +43,10 @@ constexpr int kTile = 128;        // vertices (and threads) per skinning workgro
 constexpr int kPSplit = 8;        // splits of the P rows of posedirs in the forward
 constexpr int kMaxRows = (9 * (kMaxJ - 1) + kPSplit - 1) / kPSplit;
 constexpr int kMaxPca = 64;
+// the batched forms (coma_smplx_*_batch_f32)
+constexpr int kMaxBatch = 1024;
+constexpr int kChunk = 8;         // C: bodies served by one sweep over posedirs (16 VGPRs of f64 sums per thread; forward LDS 71 x 8 f64)
+constexpr int kSkinChunk = 2;     // bodies one skinning workgroup walks over its staged weights tile
 
 struct Tree { int32_t parent[kMaxJ]; };
 
@@ -163,37 +172,77 @@ struct PoseArgs {
   float* full_pose;       // [3J] or null
 };
 
-__global__ __launch_bounds__(kBlock) void smplx_pose_kernel(PoseArgs a) {
+// what differs from body to body of a batch; the single-body kernel passes PoseArgs' own pointers
+struct PoseBody {
+  const float* theta;
+  const float* transl;
+  const double* j_rest;
+  double* s_pose;
+  double* s_A;
+  double* feat;
+  float* joints;
+  float* full_pose;
+};
+
+__device__ __forceinline__ void pose_forward(const PoseArgs& a, const PoseBody& b) {
   __shared__ double pose[3 * kMaxJ], R[9 * kMaxJ], G[12 * kMaxJ];
   const int t = threadIdx.x, J = a.J;
   const int nb = a.n_pca > 0 ? 3 * J - 2 * a.hd : 3 * J;
   for (int k = t; k < 3 * J; k += kBlock) {
     double v;
     if (k < nb) {
-      v = (double)a.theta[k];
+      v = (double)b.theta[k];
     } else {
       const int h = (k - nb) / a.hd, kk = (k - nb) % a.hd;
       v = 0.0;
-      for (int i = 0; i < a.n_pca; ++i) v = v + (double)a.theta[nb + h * a.n_pca + i] * (double)a.comps[(int64_t)(h * a.n_pca + i) * a.hd + kk];
+      for (int i = 0; i < a.n_pca; ++i) v = v + (double)b.theta[nb + h * a.n_pca + i] * (double)a.comps[(int64_t)(h * a.n_pca + i) * a.hd + kk];
     }
     if (a.mean) v = v + (double)a.mean[k];
     pose[k] = v;
-    a.s_pose[k] = v;
-    if (a.full_pose) a.full_pose[k] = (float)v;
+    b.s_pose[k] = v;
+    if (b.full_pose) b.full_pose[k] = (float)v;
   }
   __syncthreads();
-  pose_chain(pose, a.j_rest, a.tree, J, R, G);
+  pose_chain(pose, b.j_rest, a.tree, J, R, G);
   for (int q = t; q < 12 * J; q += kBlock) {
     const int i = q / 12, r = (q % 12) / 4, c = q % 4;
     const double* Gi = G + 12 * i + 4 * r;
     double v = Gi[c];
     if (c == 3) {
-      v = v - ((Gi[0] * a.j_rest[3 * i] + Gi[1] * a.j_rest[3 * i + 1]) + Gi[2] * a.j_rest[3 * i + 2]);
-      a.joints[3 * i + r] = (float)(Gi[3] + (a.transl ? (double)a.transl[r] : 0.0));
+      v = v - ((Gi[0] * b.j_rest[3 * i] + Gi[1] * b.j_rest[3 * i + 1]) + Gi[2] * b.j_rest[3 * i + 2]);
+      b.joints[3 * i + r] = (float)(Gi[3] + (b.transl ? (double)b.transl[r] : 0.0));
     }
-    a.s_A[q] = v;
+    b.s_A[q] = v;
   }
-  for (int q = t; q < 9 * (J - 1); q += kBlock) a.feat[q] = R[9 + q] - ((q % 9) % 4 == 0 ? 1.0 : 0.0);
+  for (int q = t; q < 9 * (J - 1); q += kBlock) b.feat[q] = R[9 + q] - ((q % 9) % 4 == 0 ? 1.0 : 0.0);
+}
+
+__global__ __launch_bounds__(kBlock) void smplx_pose_kernel(PoseArgs a) {
+  pose_forward(a, PoseBody{a.theta, a.transl, a.j_rest, a.s_pose, a.s_A, a.feat, a.joints, a.full_pose});
+}
+
+// How a batched call finds body n: the f32 arrays are dense [N, ...]; the shape states and saved blocks are `stride` bytes apart.
+struct BatchStrides {
+  int N, NT;
+  size_t shape, saved;      // bytes; shape = 0: one shape state for all bodies
+};
+
+template <typename T>
+__device__ __forceinline__ T* at_bytes(T* p, size_t bytes) {
+  return (T*)((char*)p + bytes);
+}
+template <typename T>
+__device__ __forceinline__ const T* at_bytes(const T* p, size_t bytes) {
+  return (const T*)((const char*)p + bytes);
+}
+
+// one workgroup per body; PoseArgs holds body 0's pointers
+__global__ __launch_bounds__(kBlock) void smplx_pose_batch_kernel(PoseArgs a, BatchStrides st) {
+  const size_t n = blockIdx.x;
+  const int J = a.J;
+  pose_forward(a, PoseBody{a.theta + n * st.NT, a.transl ? a.transl + 3 * n : nullptr, at_bytes(a.j_rest, n * st.shape), at_bytes(a.s_pose, n * st.saved),
+                           at_bytes(a.s_A, n * st.saved), a.feat + n * (size_t)(9 * (J - 1)), a.joints + n * (size_t)(3 * J),
+                           a.full_pose ? a.full_pose + n * (size_t)(3 * J) : nullptr});
 }
 
 // ---- skinning stage ----
@@ -212,6 +261,37 @@ __global__ __launch_bounds__(kBlock) void smplx_offsets_kernel(const float* __re
 #pragma unroll 8
   for (int p = p0; p < p1; ++p) acc = acc + f[p - p0] * (double)col[(int64_t)p * n3];
   part[(int64_t)s * n3 + i] = acc;
+}
+
+// The batched form: grid (column blocks, kPSplit, chunks of kChunk bodies).  The chunk's features of this split sit in LDS as
+// [row][body]; every posedirs element is loaded once and used for all bodies of the chunk, each body's sum in a register of its own
+// and in the single-body kernel's order.  part is [N][kPSplit][3V].  With P = 0 it writes the zeros the single-body call memsets.
+__global__ __launch_bounds__(kBlock) void smplx_offsets_batch_kernel(const float* __restrict__ posedirs, const double* __restrict__ feat, int P,
+                                                                    int n3, int rows, int N, double* __restrict__ part) {
+  __shared__ double f[kMaxRows * kChunk];
+  const int s = blockIdx.y, n0 = blockIdx.z * kChunk, nc = min(kChunk, N - n0);
+  const int p0 = s * rows, p1 = min(P, p0 + rows);
+  for (int q = threadIdx.x; q < (p1 - p0) * kChunk; q += kBlock) {
+    const int r = q / kChunk, c = q % kChunk;
+    f[q] = c < nc ? feat[(int64_t)(n0 + c) * P + p0 + r] : 0.0;
+  }
+  __syncthreads();
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n3) return;
+  double acc[kChunk];
+#pragma unroll
+  for (int c = 0; c < kChunk; ++c) acc[c] = 0.0;
+  const float* col = posedirs + i;
+#pragma unroll 4
+  for (int p = p0; p < p1; ++p) {
+    const double x = (double)col[(int64_t)p * n3];
+    const double* fp = f + (p - p0) * kChunk;
+#pragma unroll
+    for (int c = 0; c < kChunk; ++c) acc[c] = acc[c] + fp[c] * x;
+  }
+#pragma unroll
+  for (int c = 0; c < kChunk; ++c)
+    if (c < nc) part[((int64_t)(n0 + c) * kPSplit + s) * n3 + i] = acc[c];
 }
 
 struct SkinArgs {
@@ -245,27 +325,65 @@ __device__ __forceinline__ void blend(const float* w, const double* Al, int J, d
   }
 }
 
+// vertex v of one body (thread t of its tile): the pose offset from the eight partial sums, the blend, the vertex
+__device__ __forceinline__ void skin_vertex(const float* Wt, const double* Al, int V, int J, int64_t v, int t, const double* __restrict__ part,
+                                            const double* __restrict__ v_shaped, const float* __restrict__ transl, double* __restrict__ v_posed,
+                                            float* __restrict__ vertices) {
+  const int64_t n3 = 3 * (int64_t)V;
+  double vp[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    double off = 0.0;
+    for (int s = 0; s < kPSplit; ++s) off = off + part[s * n3 + 3 * v + c];
+    vp[c] = v_shaped[3 * v + c] + off;
+    v_posed[3 * v + c] = vp[c];
+  }
+  double T[12];
+  blend(Wt + t * J, Al, J, T);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const double x = ((T[4 * c] * vp[0] + T[4 * c + 1] * vp[1]) + T[4 * c + 2] * vp[2]) + T[4 * c + 3];
+    vertices[3 * v + c] = (float)(x + (transl ? (double)transl[c] : 0.0));
+  }
+}
+
 __global__ __launch_bounds__(kTile) void smplx_skin_kernel(SkinArgs a) {
   __shared__ float Wt[kTile * kMaxJ];
   __shared__ double Al[12 * kMaxJ];
   const int n = stage_tile(a.weights, a.A, a.V, a.J, Wt, Al);
   const int t = threadIdx.x;
   if (t >= n) return;
-  const int64_t v = (int64_t)blockIdx.x * kTile + t, n3 = 3 * (int64_t)a.V;
-  double vp[3];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    double off = 0.0;
-    for (int s = 0; s < kPSplit; ++s) off = off + a.part[s * n3 + 3 * v + c];
-    vp[c] = a.v_shaped[3 * v + c] + off;
-    a.v_posed[3 * v + c] = vp[c];
-  }
-  double T[12];
-  blend(Wt + t * a.J, Al, a.J, T);
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const double x = ((T[4 * c] * vp[0] + T[4 * c + 1] * vp[1]) + T[4 * c + 2] * vp[2]) + T[4 * c + 3];
-    a.vertices[3 * v + c] = (float)(x + (a.transl ? (double)a.transl[c] : 0.0));
+  skin_vertex(Wt, Al, a.V, a.J, (int64_t)blockIdx.x * kTile + t, t, a.part, a.v_shaped, a.transl, a.v_posed, a.vertices);
+}
+
+// the weights of this workgroup's tile of vertices into LDS (no barrier: the first stage_A gives it) -> the vertices in the tile
+__device__ __forceinline__ int stage_weights(const float* __restrict__ weights, int V, int J, float* Wt) {
+  const int v0 = blockIdx.x * kTile, n = min(kTile, V - v0);
+  const float* src = weights + (int64_t)v0 * J;
+  for (int q = threadIdx.x; q < n * J; q += kTile) Wt[q] = src[q];
+  return n;
+}
+
+// the next body's transforms into LDS, once every thread is done with the previous body's
+__device__ __forceinline__ void stage_A(const double* __restrict__ A, int J, double* Al) {
+  __syncthreads();
+  for (int q = threadIdx.x; q < 12 * J; q += kTile) Al[q] = A[q];
+  __syncthreads();
+}
+
+// The batched form: grid (tiles, chunks of kSkinChunk bodies); SkinArgs holds body 0's pointers, part is [N][kPSplit][3V].  The
+// weights tile is staged once and the chunk's bodies walk over it.
+__global__ __launch_bounds__(kTile) void smplx_skin_batch_kernel(SkinArgs a, BatchStrides st) {
+  __shared__ float Wt[kTile * kMaxJ];
+  __shared__ double Al[12 * kMaxJ];
+  const int n = stage_weights(a.weights, a.V, a.J, Wt);
+  const int t = threadIdx.x, b0 = blockIdx.y * kSkinChunk, b1 = min(st.N, b0 + kSkinChunk);
+  const size_t n3 = 3 * (size_t)a.V;
+  for (size_t b = b0; b < (size_t)b1; ++b) {
+    stage_A(at_bytes(a.A, b * st.saved), a.J, Al);
+    if (t < n)
+      skin_vertex(Wt, Al, a.V, a.J, (int64_t)blockIdx.x * kTile + t, t, a.part + b * kPSplit * n3, at_bytes(a.v_shaped, b * st.shape),
+                  a.transl ? a.transl + 3 * b : nullptr, at_bytes(a.v_posed, b * st.saved), a.vertices + b * n3);
   }
 }
 
@@ -281,39 +399,62 @@ struct SkinBwdArgs {
   double* dA_part;          // workspace [blocks][12 J + 3]: the block's share of dL/dA, then of dL/dtransl
 };
 
+// one body's tile, weights and transforms staged: g_vposed of its vertices, then the tile's share of dL/dA and dL/dtransl
+template <typename TG>
+__device__ __forceinline__ void skin_bwd_tile(const float* Wt, const double* Al, double* gl, double* vl, int n, int J, const TG* __restrict__ grad,
+                                              const double* __restrict__ v_posed, double* __restrict__ gvp, double* __restrict__ dA_part) {
+  const int t = threadIdx.x;
+  if (t < n) {
+    const int64_t v = (int64_t)blockIdx.x * kTile + t;
+    const double g[3] = {load(grad, 3 * v), load(grad, 3 * v + 1), load(grad, 3 * v + 2)};
+    double T[12];
+    blend(Wt + t * J, Al, J, T);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      gvp[3 * v + c] = (T[c] * g[0] + T[4 + c] * g[1]) + T[8 + c] * g[2];
+      gl[3 * t + c] = g[c];
+      vl[4 * t + c] = v_posed[3 * v + c];
+    }
+    vl[4 * t + 3] = 1.0;
+  }
+  __syncthreads();
+  const int nq = 12 * J + 3;
+  double* out = dA_part + (int64_t)blockIdx.x * nq;
+  for (int q = t; q < nq; q += kTile) {
+    double acc = 0.0;
+    if (q < 12 * J) {
+      const int j = q / 12, r = (q % 12) / 4, c = q % 4;
+      for (int u = 0; u < n; ++u) acc = acc + ((double)Wt[u * J + j] * gl[3 * u + r]) * vl[4 * u + c];
+    } else {
+      const int r = q - 12 * J;
+      for (int u = 0; u < n; ++u) acc = acc + gl[3 * u + r];
+    }
+    out[q] = acc;
+  }
+}
+
 template <typename TG>
 __global__ __launch_bounds__(kTile) void smplx_skin_bwd_kernel(SkinBwdArgs<TG> a) {
   __shared__ float Wt[kTile * kMaxJ];
   __shared__ double Al[12 * kMaxJ];
   __shared__ double gl[3 * kTile], vl[4 * kTile];
   const int n = stage_tile(a.weights, a.A, a.V, a.J, Wt, Al);
-  const int t = threadIdx.x;
-  if (t < n) {
-    const int64_t v = (int64_t)blockIdx.x * kTile + t;
-    const double g[3] = {load(a.grad, 3 * v), load(a.grad, 3 * v + 1), load(a.grad, 3 * v + 2)};
-    double T[12];
-    blend(Wt + t * a.J, Al, a.J, T);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      a.gvp[3 * v + c] = (T[c] * g[0] + T[4 + c] * g[1]) + T[8 + c] * g[2];
-      gl[3 * t + c] = g[c];
-      vl[4 * t + c] = a.v_posed[3 * v + c];
-    }
-    vl[4 * t + 3] = 1.0;
-  }
-  __syncthreads();
-  const int nq = 12 * a.J + 3;
-  double* out = a.dA_part + (int64_t)blockIdx.x * nq;
-  for (int q = t; q < nq; q += kTile) {
-    double acc = 0.0;
-    if (q < 12 * a.J) {
-      const int j = q / 12, r = (q % 12) / 4, c = q % 4;
-      for (int u = 0; u < n; ++u) acc = acc + ((double)Wt[u * a.J + j] * gl[3 * u + r]) * vl[4 * u + c];
-    } else {
-      const int r = q - 12 * a.J;
-      for (int u = 0; u < n; ++u) acc = acc + gl[3 * u + r];
-    }
-    out[q] = acc;
+  skin_bwd_tile(Wt, Al, gl, vl, n, a.J, a.grad, a.v_posed, a.gvp, a.dA_part);
+}
+
+// The batched form: grid (tiles, chunks of kSkinChunk bodies); the args hold body 0's pointers, grad and gvp are [N][3V], dA_part is
+// [N][tiles][12 J + 3].  stage_A's first barrier also keeps a body's gl / vl until every thread has summed over them.
+template <typename TG>
+__global__ __launch_bounds__(kTile) void smplx_skin_bwd_batch_kernel(SkinBwdArgs<TG> a, BatchStrides st) {
+  __shared__ float Wt[kTile * kMaxJ];
+  __shared__ double Al[12 * kMaxJ];
+  __shared__ double gl[3 * kTile], vl[4 * kTile];
+  const int n = stage_weights(a.weights, a.V, a.J, Wt);
+  const int b0 = blockIdx.y * kSkinChunk, b1 = min(st.N, b0 + kSkinChunk);
+  const size_t n3 = 3 * (size_t)a.V, per_body = (size_t)gridDim.x * (12 * a.J + 3);
+  for (size_t b = b0; b < (size_t)b1; ++b) {
+    stage_A(at_bytes(a.A, b * st.saved), a.J, Al);
+    skin_bwd_tile(Wt, Al, gl, vl, n, a.J, a.grad + b * n3, at_bytes(a.v_posed, b * st.saved), a.gvp + b * n3, a.dA_part + b * per_body);
   }
 }
 
@@ -327,6 +468,32 @@ __global__ __launch_bounds__(kBlock) void smplx_feature_bwd_kernel(const float* 
   for (int i = threadIdx.x; i < n3; i += kBlock) acc = acc + (double)row[i] * gvp[i];
   const double s = block_sum<kBlock>(acc, lds);
   if (threadIdx.x == 0) dfeat[blockIdx.x] = s;
+}
+
+// The batched form: grid (P rows, chunks of kChunk bodies); one read of the row serves the chunk's dot products, each with the
+// single-body kernel's 256 strided partial sums and tree.  gvp is [N][3V], dfeat [N][P].
+__global__ __launch_bounds__(kBlock) void smplx_feature_bwd_batch_kernel(const float* __restrict__ posedirs, const double* __restrict__ gvp, int n3,
+                                                                        int P, int N, double* __restrict__ dfeat) {
+  __shared__ double lds[kBlock];
+  const int n0 = blockIdx.y * kChunk, nc = min(kChunk, N - n0);
+  const float* row = posedirs + (int64_t)blockIdx.x * n3;
+  const double* g0 = gvp + (int64_t)n0 * n3;
+  double acc[kChunk];
+#pragma unroll
+  for (int c = 0; c < kChunk; ++c) acc[c] = 0.0;
+#pragma unroll 2
+  for (int i = threadIdx.x; i < n3; i += kBlock) {
+    const double x = (double)row[i];
+#pragma unroll
+    for (int c = 0; c < kChunk; ++c)
+      if (c < nc) acc[c] = acc[c] + x * g0[(int64_t)c * n3 + i];
+  }
+#pragma unroll
+  for (int c = 0; c < kChunk; ++c)
+    if (c < nc) {                                           // nc is the workgroup's: every thread reaches the same barriers
+      const double s = block_sum<kBlock>(acc[c], lds);
+      if (threadIdx.x == 0) dfeat[(int64_t)(n0 + c) * P + blockIdx.x] = s;
+    }
 }
 
 struct PoseBwdArgs {
@@ -347,48 +514,61 @@ struct PoseBwdArgs {
   double* dJ_out;           // dL/dJ_rest [J,3]
 };
 
-__global__ __launch_bounds__(kBlock) void smplx_pose_bwd_kernel(PoseBwdArgs a) {
+// what differs from body to body of a batch; the single-body kernel passes PoseBwdArgs' own pointers
+struct PoseBwdBody {
+  const double* s_pose;
+  const double* j_rest;
+  const double* dA_part;
+  const double* dfeat;
+  float* grad_theta;
+  float* grad_transl;
+  const float* gJ;
+  const float* gP;
+  double* dJ_out;
+};
+
+__device__ __forceinline__ void pose_backward(const PoseBwdArgs& a, const PoseBwdBody& b) {
   __shared__ double pose[3 * kMaxJ], R[9 * kMaxJ], G[12 * kMaxJ], dG[12 * kMaxJ], dR[9 * kMaxJ], dJ[3 * kMaxJ];
   const int t = threadIdx.x, J = a.J;
-  for (int k = t; k < 3 * J; k += kBlock) pose[k] = a.s_pose[k];
+  for (int k = t; k < 3 * J; k += kBlock) pose[k] = b.s_pose[k];
   __syncthreads();
-  pose_chain(pose, a.j_rest, a.tree, J, R, G);
+  pose_chain(pose, b.j_rest, a.tree, J, R, G);
   // dL/dA and dL/dtransl: the workgroups' shares in block order; dA into G's place is not possible (G is needed), so into dR/dG
   const int nq = 12 * J + 3;
   double* dA = dG;                                        // dG is built from dA in place below
   for (int q = t; q < nq; q += kBlock) {
     double acc = 0.0;
-    for (int b = 0; b < a.nblk; ++b) acc = acc + a.dA_part[(int64_t)b * nq + q];
+    for (int w = 0; w < a.nblk; ++w) acc = acc + b.dA_part[(int64_t)w * nq + q];
     if (q < 12 * J) {
       dA[q] = acc;
     } else {
       const int r = q - 12 * J;
-      if (a.gJ) {                                           // joints_i = G_i.t + transl, and the extra joints' direct term
+      if (b.gJ) {                                           // joints_i = G_i.t + transl, and the extra joints' direct term
         double posed = 0.0, direct = 0.0;
-        for (int i = 0; i < J; ++i) posed = posed + (double)a.gJ[3 * i + r];
+        for (int i = 0; i < J; ++i) posed = posed + (double)b.gJ[3 * i + r];
         for (int e = 0; e < a.E; ++e) {
           const double w = ((double)a.extra_w[3 * e] + (double)a.extra_w[3 * e + 1]) + (double)a.extra_w[3 * e + 2];
-          direct = direct + (1.0 - w) * (double)a.gJ[3 * (J + e) + r];
+          direct = direct + (1.0 - w) * (double)b.gJ[3 * (J + e) + r];
         }
         acc = (acc + posed) + direct;
       }
-      a.grad_transl[r] = (float)acc;
+      b.grad_transl[r] = (float)acc;
     }
   }
   __syncthreads();
   // A = [G.R | G.t - G.R J]: dG.t = dA.t, dG.R = dA.R - dA.t J^T   (each entry reads its own row's dA.t, which is not rewritten)
   for (int q = t; q < 12 * J; q += kBlock) {
     const int i = q / 12, r = (q % 12) / 4, c = q % 4;
-    if (c < 3) dG[q] = dA[q] - dA[12 * i + 4 * r + 3] * a.j_rest[3 * i + c];
+    if (c < 3) dG[q] = dA[q] - dA[12 * i + 4 * r + 3] * b.j_rest[3 * i + c];
   }
-  if (a.dJ_out)                                           // ... and dJ_i = -G_i.R^T dA_i.t
+  if (b.dJ_out)                                           // ... and dJ_i = -G_i.R^T dA_i.t
     for (int q = t; q < 3 * J; q += kBlock) {
       const int i = q / 3, c = q % 3;
       dJ[q] = -((G[12 * i + c] * dA[12 * i + 3] + G[12 * i + 4 + c] * dA[12 * i + 7]) + G[12 * i + 8 + c] * dA[12 * i + 11]);
     }
   __syncthreads();
-  if (a.gJ) {                                             // dG_i.t += dL/djoints_i, once dA.t has been read
-    for (int q = t; q < 3 * J; q += kBlock) dG[12 * (q / 3) + 4 * (q % 3) + 3] = dG[12 * (q / 3) + 4 * (q % 3) + 3] + (double)a.gJ[q];
+  if (b.gJ) {                                             // dG_i.t += dL/djoints_i, once dA.t has been read
+    for (int q = t; q < 3 * J; q += kBlock) dG[12 * (q / 3) + 4 * (q % 3) + 3] = dG[12 * (q / 3) + 4 * (q % 3) + 3] + (double)b.gJ[q];
     __syncthreads();
   }
   for (int i = J - 1; i >= 1; --i) {
@@ -396,19 +576,19 @@ __global__ __launch_bounds__(kBlock) void smplx_pose_bwd_kernel(PoseBwdArgs a) {
     if (t < 9) {                                          // dR_i = G_p.R^T dG_i.R + dL/dfeature
       const int r = t / 3, c = t % 3;
       double v = (G[12 * p + r] * dG[12 * i + c] + G[12 * p + 4 + r] * dG[12 * i + 4 + c]) + G[12 * p + 8 + r] * dG[12 * i + 8 + c];
-      dR[9 * i + t] = v + a.dfeat[9 * (i - 1) + t];
+      dR[9 * i + t] = v + b.dfeat[9 * (i - 1) + t];
     } else if (t >= 16 && t < 28) {                       // dG_p.R += dG_i.R R_i^T + dG_i.t t_i^T;  dG_p.t += dG_i.t
       const int e = t - 16, r = e / 4, c = e % 4;
       const double* di = dG + 12 * i + 4 * r;
       double add;
       if (c < 3) {
-        const double tc = a.j_rest[3 * i + c] - a.j_rest[3 * p + c];
+        const double tc = b.j_rest[3 * i + c] - b.j_rest[3 * p + c];
         add = ((di[0] * R[9 * i + 3 * c] + di[1] * R[9 * i + 3 * c + 1]) + di[2] * R[9 * i + 3 * c + 2]) + di[3] * tc;
       } else {
         add = di[3];
       }
       dG[12 * p + e] = dG[12 * p + e] + add;
-    } else if (t >= 32 && t < 35 && a.dJ_out) {            // G_i.t = G_p.R (J_i - J_p) + G_p.t: u = G_p.R^T dG_i.t to J_i, -u to J_p
+    } else if (t >= 32 && t < 35 && b.dJ_out) {            // G_i.t = G_p.R (J_i - J_p) + G_p.t: u = G_p.R^T dG_i.t to J_i, -u to J_p
       const int c = t - 32;
       const double u = (G[12 * p + c] * dG[12 * i + 3] + G[12 * p + 4 + c] * dG[12 * i + 7]) + G[12 * p + 8 + c] * dG[12 * i + 11];
       dJ[3 * i + c] = dJ[3 * i + c] + u;
@@ -416,10 +596,10 @@ __global__ __launch_bounds__(kBlock) void smplx_pose_bwd_kernel(PoseBwdArgs a) {
     }
     __syncthreads();
   }
-  if (a.dJ_out) {                                         // the root: G_0.t = J_0
+  if (b.dJ_out) {                                         // the root: G_0.t = J_0
     if (t >= 32 && t < 35) dJ[t - 32] = dJ[t - 32] + dG[4 * (t - 32) + 3];
     __syncthreads();
-    for (int q = t; q < 3 * J; q += kBlock) a.dJ_out[q] = dJ[q];
+    for (int q = t; q < 3 * J; q += kBlock) b.dJ_out[q] = dJ[q];
   }
   if (t < 9) dR[t] = dG[4 * (t / 3) + t % 3];
   __syncthreads();
@@ -427,26 +607,38 @@ __global__ __launch_bounds__(kBlock) void smplx_pose_bwd_kernel(PoseBwdArgs a) {
   if (t < J) {
     double dr[3];
     rodrigues_backward(pose + 3 * t, dR + 9 * t, dr);
-    if (a.gP) {                                           // full_pose = assembled theta + pose_mean
-      dr[0] = dr[0] + (double)a.gP[3 * t]; dr[1] = dr[1] + (double)a.gP[3 * t + 1]; dr[2] = dr[2] + (double)a.gP[3 * t + 2];
+    if (b.gP) {                                           // full_pose = assembled theta + pose_mean
+      dr[0] = dr[0] + (double)b.gP[3 * t]; dr[1] = dr[1] + (double)b.gP[3 * t + 1]; dr[2] = dr[2] + (double)b.gP[3 * t + 2];
     }
     dpose[3 * t] = dr[0]; dpose[3 * t + 1] = dr[1]; dpose[3 * t + 2] = dr[2];
   }
   __syncthreads();
   const int nb = a.n_pca > 0 ? 3 * J - 2 * a.hd : 3 * J;
-  for (int k = t; k < nb; k += kBlock) a.grad_theta[k] = (float)dpose[k];
+  for (int k = t; k < nb; k += kBlock) b.grad_theta[k] = (float)dpose[k];
   for (int q = t; q < 2 * a.n_pca; q += kBlock) {           // the hand components transposed
     const int h = q / a.n_pca;
     double acc = 0.0;
     for (int kk = 0; kk < a.hd; ++kk) acc = acc + (double)a.comps[(int64_t)q * a.hd + kk] * dpose[nb + h * a.hd + kk];
-    a.grad_theta[nb + q] = (float)acc;
+    b.grad_theta[nb + q] = (float)acc;
   }
 }
 
+__global__ __launch_bounds__(kBlock) void smplx_pose_bwd_kernel(PoseBwdArgs a) {
+  pose_backward(a, PoseBwdBody{a.s_pose, a.j_rest, a.dA_part, a.dfeat, a.grad_theta, a.grad_transl, a.gJ, a.gP, a.dJ_out});
+}
+
+// one workgroup per body; PoseBwdArgs holds body 0's pointers, gJ is [N][J + E, 3]; no gradient to the rest joints
+__global__ __launch_bounds__(kBlock) void smplx_pose_bwd_batch_kernel(PoseBwdArgs a, BatchStrides st) {
+  const size_t n = blockIdx.x;
+  const int J = a.J;
+  pose_backward(a, PoseBwdBody{at_bytes(a.s_pose, n * st.saved), at_bytes(a.j_rest, n * st.shape), a.dA_part + n * a.nblk * (size_t)(12 * J + 3),
+                               a.dfeat + n * (size_t)(9 * (J - 1)), a.grad_theta + n * st.NT, a.grad_transl + 3 * n,
+                               a.gJ ? a.gJ + n * (size_t)(3 * (J + a.E)) : nullptr, a.gP ? a.gP + n * (size_t)(3 * J) : nullptr, nullptr});
+}
+
 // ---- extra joints ----
-__global__ __launch_bounds__(kBlock) void smplx_gather_kernel(const float* __restrict__ vertices, const float* __restrict__ transl,
-                                                             const int32_t* __restrict__ idx, const float* __restrict__ w, int V, int E,
-                                                             float* __restrict__ out) {
+__device__ __forceinline__ void gather_extra(const float* __restrict__ vertices, const float* __restrict__ transl, const int32_t* __restrict__ idx,
+                                             const float* __restrict__ w, int V, int E, float* __restrict__ out) {
   const int q = blockIdx.x * kBlock + threadIdx.x;
   if (q >= 3 * E) return;
   const int e = q / 3, c = q % 3;
@@ -460,6 +652,20 @@ __global__ __launch_bounds__(kBlock) void smplx_gather_kernel(const float* __res
   out[q] = (float)(acc + tr);
 }
 
+__global__ __launch_bounds__(kBlock) void smplx_gather_kernel(const float* __restrict__ vertices, const float* __restrict__ transl,
+                                                             const int32_t* __restrict__ idx, const float* __restrict__ w, int V, int E,
+                                                             float* __restrict__ out) {
+  gather_extra(vertices, transl, idx, w, V, E, out);
+}
+
+// grid (blocks of 3E, N): vertices [N][V,3], transl [N][3] or null, out [N][E,3]; one table for all bodies
+__global__ __launch_bounds__(kBlock) void smplx_gather_batch_kernel(const float* __restrict__ vertices, const float* __restrict__ transl,
+                                                                   const int32_t* __restrict__ idx, const float* __restrict__ w, int V, int E,
+                                                                   float* __restrict__ out) {
+  const size_t n = blockIdx.y;
+  gather_extra(vertices + n * 3 * (size_t)V, transl ? transl + 3 * n : nullptr, idx, w, V, E, out + n * 3 * (size_t)E);
+}
+
 // ---- the full backward's own passes ----
 constexpr int kMaxE = 4096;       // extra joints whose gradient is scattered back
 constexpr int kEffChunk = 768;    // table entries in LDS per pass
@@ -467,9 +673,8 @@ constexpr int kEffChunk = 768;    // table entries in LDS per pass
 // The effective vertex gradient: g_eff[v] = g[v] (zeros without g) + the sum over the table entries (e, i) with index v, in ascending
 // (e, i), of w[e,i] gJ_extra[e].  Written as a gather -- every vertex scans the whole table from LDS -- so repeated indices (a vertex
 // pick is (i, i, i), landmark faces share vertices) add in the table's order without atomics; an index outside [0, V) matches nothing.
-__global__ __launch_bounds__(kBlock) void smplx_effective_grad_kernel(const float* __restrict__ g, const float* __restrict__ gJ_extra,
-                                                                     const int32_t* __restrict__ idx, const float* __restrict__ w, int V, int E,
-                                                                     double* __restrict__ g_eff) {
+__device__ __forceinline__ void effective_grad(const float* __restrict__ g, const float* __restrict__ gJ_extra, const int32_t* __restrict__ idx,
+                                               const float* __restrict__ w, int V, int E, double* __restrict__ g_eff) {
   __shared__ int32_t li[kEffChunk];
   __shared__ double lw[3 * kEffChunk];
   const int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -490,6 +695,20 @@ __global__ __launch_bounds__(kBlock) void smplx_effective_grad_kernel(const floa
         if (li[q] == (int32_t)v) acc = acc + D3{lw[3 * q], lw[3 * q + 1], lw[3 * q + 2]};
   }
   if (v < V) { g_eff[3 * v] = acc.x; g_eff[3 * v + 1] = acc.y; g_eff[3 * v + 2] = acc.z; }
+}
+
+__global__ __launch_bounds__(kBlock) void smplx_effective_grad_kernel(const float* __restrict__ g, const float* __restrict__ gJ_extra,
+                                                                     const int32_t* __restrict__ idx, const float* __restrict__ w, int V, int E,
+                                                                     double* __restrict__ g_eff) {
+  effective_grad(g, gJ_extra, idx, w, V, E, g_eff);
+}
+
+// grid (blocks of V, N): g [N][V,3] or null, gJ [N][J + E, 3] or null (the extra joints' rows are read), g_eff [N][V,3]
+__global__ __launch_bounds__(kBlock) void smplx_effective_grad_batch_kernel(const float* __restrict__ g, const float* __restrict__ gJ, int J,
+                                                                           const int32_t* __restrict__ idx, const float* __restrict__ w, int V,
+                                                                           int E, int E_all, double* __restrict__ g_eff) {
+  const size_t n = blockIdx.y, n3 = 3 * (size_t)V;
+  effective_grad(g ? g + n * n3 : nullptr, gJ ? gJ + n * 3 * (size_t)(J + E_all) + 3 * (size_t)J : nullptr, idx, w, V, E, g_eff + n * n3);
 }
 
 // kBlock rows i = 3 v + c of the [3V] axis per workgroup.  dL/dv_shaped[i] = gvp[i] + sum_j J_regressor[j, v] dJ[j][c] (j ascending)
@@ -780,5 +999,156 @@ extern "C" int coma_smplx_extra_joints_f32(const float* vertices, const float* t
   if (V < 1 || V > kMaxV || E < 0 || E > kMaxV) return fail(COMA_E_INVALID, "%s: bad sizes V=%d E=%d", who, V, E);
   hipLaunchKernelGGL(smplx_gather_kernel, dim3((3 * E + kBlock - 1) / kBlock), dim3(kBlock), 0, (hipStream_t)stream, vertices, transl, vertex_index,
                      vertex_weight, V, E, out);
+  return check_launch(who);
+}
+
+// ---- the batched entry points ----
+namespace coma {
+namespace {
+
+// Body n's saved block is the single-body layout at n x saved_stride.  Forward workspace: feat [N][P], part [N][kPSplit][3V].
+// Backward workspace (one layout for both forms): gvp [N][3V], dA_part [N][tiles][12 J + 3], dfeat [N][P], g_eff [N][3V].
+struct BatchLayout {
+  Layout one;
+  size_t feat, part, total;
+  size_t gvp, dA_part, dfeat, g_eff, grad_total;
+  size_t saved_stride, saved_total;
+  int NT, chunks, skin_chunks;
+};
+
+bool batch_ok(int V, int J, int N) { return sizes_ok(V, J) && N >= 1 && N <= kMaxBatch; }
+
+BatchLayout batch_layout(int V, int J, int N) {
+  BatchLayout B = {};
+  B.one = layout(V, J);
+  const size_t n3 = (size_t)3 * V, d = sizeof(double), n = (size_t)N, P = (size_t)(B.one.P > 0 ? B.one.P : 1);
+  Carve ws, grad;
+  B.feat = ws.take(n * P * d);
+  B.part = ws.take(n * kPSplit * n3 * d);
+  B.total = ws.at;
+  B.gvp = grad.take(n * n3 * d);
+  B.dA_part = grad.take(n * B.one.nblk * (12 * J + 3) * d);
+  B.dfeat = grad.take(n * P * d);
+  B.g_eff = grad.take(n * n3 * d);
+  B.grad_total = grad.at;
+  B.saved_stride = B.one.saved_total;
+  B.saved_total = n * B.saved_stride;
+  B.chunks = (N + kChunk - 1) / kChunk;
+  B.skin_chunks = (N + kSkinChunk - 1) / kSkinChunk;
+  return B;
+}
+
+int check_batch(const char* who, int V, int J, int N, const void* shape_state, size_t shape_stride) {
+  if (N < 1 || N > kMaxBatch) return fail(COMA_E_INVALID, "%s: N=%d outside [1, %d]", who, N, kMaxBatch);
+  const size_t need = layout(V, J).shape_total;
+  if (shape_stride != 0 && (shape_stride < need || (shape_stride & 15) != 0))
+    return fail(COMA_E_INVALID, "%s: shape_stride=%zu must be 0 (one shape state for all bodies) or a multiple of 16 of at least %zu", who,
+                shape_stride, need);
+  if (((uintptr_t)shape_state & 15) != 0) return fail(COMA_E_INVALID, "%s: shape state must be 16-byte aligned", who);
+  return COMA_OK;
+}
+
+}  // namespace
+}  // namespace coma
+
+extern "C" size_t coma_smplx_batch_workspace_bytes(int V, int J, int N) { return batch_ok(V, J, N) ? batch_layout(V, J, N).total : 0; }
+extern "C" size_t coma_smplx_batch_saved_bytes(int V, int J, int N) { return batch_ok(V, J, N) ? batch_layout(V, J, N).saved_total : 0; }
+extern "C" size_t coma_smplx_batch_grad_workspace_bytes(int V, int J, int N) { return batch_ok(V, J, N) ? batch_layout(V, J, N).grad_total : 0; }
+
+extern "C" int coma_smplx_forward_batch_f32(const float* theta, const float* transl, const float* posedirs, const float* weights,
+                                            const int32_t* parents, const float* hand_components, const float* pose_mean, int V, int J,
+                                            int hand_dim, int n_pca, int N, const void* shape_state, size_t shape_stride, float* vertices,
+                                            float* joints, float* full_pose, void* saved, size_t saved_bytes, void* workspace,
+                                            size_t workspace_bytes, void* stream) {
+  const char* who = "coma_smplx_forward_batch_f32";
+  if (!theta || !posedirs || !weights || !parents || !shape_state || !vertices || !joints || !saved || !workspace)
+    return fail(COMA_E_INVALID, "%s: null pointer", who);
+  if (n_pca > 0 && hand_dim > 0 && !hand_components) return fail(COMA_E_INVALID, "%s: null pointer (hand_components with n_pca > 0)", who);
+  PoseArgs pa = {};
+  if (int rc = check_common(who, V, J, hand_dim, n_pca, parents, pa.tree)) return rc;
+  if (int rc = check_batch(who, V, J, N, shape_state, shape_stride)) return rc;
+  const BatchLayout B = batch_layout(V, J, N);
+  const Layout& L = B.one;
+  if (int rc = check_buffer(who, "saved state", saved, saved_bytes, B.saved_total)) return rc;
+  if (int rc = check_buffer(who, "workspace", workspace, workspace_bytes, B.total)) return rc;
+  const char* st = (const char*)shape_state;
+  char* sv = (char*)saved;
+  char* ws = (char*)workspace;
+  hipStream_t s = (hipStream_t)stream;
+  const BatchStrides bs = {N, n_pca > 0 ? 3 * J - 2 * hand_dim + 2 * n_pca : 3 * J, shape_stride, B.saved_stride};
+  pa.theta = theta; pa.comps = hand_components; pa.mean = pose_mean; pa.transl = transl; pa.j_rest = (const double*)(st + L.j_rest);
+  pa.J = J; pa.hd = hand_dim; pa.n_pca = n_pca; pa.s_pose = (double*)(sv + L.s_pose); pa.s_A = (double*)(sv + L.s_A);
+  pa.feat = (double*)(ws + B.feat); pa.joints = joints; pa.full_pose = full_pose;
+  hipLaunchKernelGGL(smplx_pose_batch_kernel, dim3(N), dim3(kBlock), 0, s, pa, bs);
+  hipLaunchKernelGGL(smplx_offsets_batch_kernel, dim3(L.nb3, kPSplit, B.chunks), dim3(kBlock), 0, s, posedirs, (const double*)(ws + B.feat), L.P,
+                     3 * V, L.rows, N, (double*)(ws + B.part));
+  SkinArgs sa = {};
+  sa.weights = weights; sa.A = pa.s_A; sa.v_shaped = (const double*)(st + L.v_shaped); sa.part = (const double*)(ws + B.part); sa.transl = transl;
+  sa.V = V; sa.J = J; sa.v_posed = (double*)(sv + L.s_vposed); sa.vertices = vertices;
+  hipLaunchKernelGGL(smplx_skin_batch_kernel, dim3(L.nblk, B.skin_chunks), dim3(kTile), 0, s, sa, bs);
+  return check_launch(who);
+}
+
+extern "C" int coma_smplx_backward_batch_f32(const float* grad_vertices, const float* grad_joints, const float* grad_full_pose,
+                                             const float* posedirs, const float* weights, const int32_t* parents, const float* hand_components,
+                                             const int32_t* extra_index, const float* extra_weight, int E, int V, int J, int hand_dim, int n_pca,
+                                             int N, const void* shape_state, size_t shape_stride, const void* saved, size_t saved_bytes,
+                                             float* grad_theta, float* grad_transl, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* who = "coma_smplx_backward_batch_f32";
+  if (!posedirs || !weights || !parents || !shape_state || !saved || !grad_theta || !grad_transl || !workspace)
+    return fail(COMA_E_INVALID, "%s: null pointer", who);
+  if (n_pca > 0 && hand_dim > 0 && !hand_components) return fail(COMA_E_INVALID, "%s: null pointer (hand_components with n_pca > 0)", who);
+  PoseBwdArgs pb = {};
+  if (int rc = check_common(who, V, J, hand_dim, n_pca, parents, pb.tree)) return rc;
+  if (int rc = check_batch(who, V, J, N, shape_state, shape_stride)) return rc;
+  if (E < 0 || E > kMaxE) return fail(COMA_E_INVALID, "%s: E=%d outside [0, %d]", who, E, kMaxE);
+  const bool scatter = grad_joints && E > 0;
+  if (scatter && (!extra_index || !extra_weight))
+    return fail(COMA_E_INVALID, "%s: null pointer (the extra-joint tables with grad_joints and E > 0)", who);
+  const BatchLayout B = batch_layout(V, J, N);
+  const Layout& L = B.one;
+  if (int rc = check_buffer(who, "saved state", saved, saved_bytes, B.saved_total)) return rc;
+  if (int rc = check_buffer(who, "workspace", workspace, workspace_bytes, B.grad_total)) return rc;
+  const char* st = (const char*)shape_state;
+  const char* sv = (const char*)saved;
+  char* ws = (char*)workspace;
+  hipStream_t s = (hipStream_t)stream;
+  const BatchStrides bs = {N, n_pca > 0 ? 3 * J - 2 * hand_dim + 2 * n_pca : 3 * J, shape_stride, B.saved_stride};
+  double* gvp = (double*)(ws + B.gvp);
+  double* dA_part = (double*)(ws + B.dA_part);
+  double* dfeat = (double*)(ws + B.dfeat);
+  if (scatter || !grad_vertices) {                          // as the single-body full backward: only then is an effective gradient built
+    double* g_eff = (double*)(ws + B.g_eff);
+    hipLaunchKernelGGL(smplx_effective_grad_batch_kernel, dim3((V + kBlock - 1) / kBlock, N), dim3(kBlock), 0, s, grad_vertices,
+                       scatter ? grad_joints : nullptr, J, extra_index, extra_weight, V, scatter ? E : 0, E, g_eff);
+    SkinBwdArgs<double> sb = {};
+    sb.weights = weights; sb.A = (const double*)(sv + L.s_A); sb.v_posed = (const double*)(sv + L.s_vposed); sb.grad = g_eff;
+    sb.V = V; sb.J = J; sb.gvp = gvp; sb.dA_part = dA_part;
+    hipLaunchKernelGGL(smplx_skin_bwd_batch_kernel<double>, dim3(L.nblk, B.skin_chunks), dim3(kTile), 0, s, sb, bs);
+  } else {
+    SkinBwdArgs<float> sb = {};
+    sb.weights = weights; sb.A = (const double*)(sv + L.s_A); sb.v_posed = (const double*)(sv + L.s_vposed); sb.grad = grad_vertices;
+    sb.V = V; sb.J = J; sb.gvp = gvp; sb.dA_part = dA_part;
+    hipLaunchKernelGGL(smplx_skin_bwd_batch_kernel<float>, dim3(L.nblk, B.skin_chunks), dim3(kTile), 0, s, sb, bs);
+  }
+  if (L.P > 0)
+    hipLaunchKernelGGL(smplx_feature_bwd_batch_kernel, dim3(L.P, B.chunks), dim3(kBlock), 0, s, posedirs, (const double*)gvp, 3 * V, L.P, N, dfeat);
+  pb.s_pose = (const double*)(sv + L.s_pose); pb.j_rest = (const double*)(st + L.j_rest); pb.comps = hand_components;
+  pb.dA_part = dA_part; pb.dfeat = dfeat; pb.J = J; pb.hd = hand_dim; pb.n_pca = n_pca; pb.nblk = L.nblk;
+  pb.grad_theta = grad_theta; pb.grad_transl = grad_transl;
+  pb.gJ = grad_joints; pb.gP = grad_full_pose; pb.extra_w = extra_weight; pb.E = scatter ? E : 0;
+  hipLaunchKernelGGL(smplx_pose_bwd_batch_kernel, dim3(N), dim3(kBlock), 0, s, pb, bs);
+  return check_launch(who);
+}
+
+extern "C" int coma_smplx_extra_joints_batch_f32(const float* vertices, const float* transl, const int32_t* vertex_index,
+                                                 const float* vertex_weight, int V, int E, int N, float* out, void* stream) {
+  const char* who = "coma_smplx_extra_joints_batch_f32";
+  if (N < 1 || N > kMaxBatch) return fail(COMA_E_INVALID, "%s: N=%d outside [1, %d]", who, N, kMaxBatch);
+  if (E == 0) return COMA_OK;
+  if (!vertices || !vertex_index || !vertex_weight || !out) return fail(COMA_E_INVALID, "%s: null pointer", who);
+  if (V < 1 || V > kMaxV || E < 0 || E > kMaxV) return fail(COMA_E_INVALID, "%s: bad sizes V=%d E=%d", who, V, E);
+  hipLaunchKernelGGL(smplx_gather_batch_kernel, dim3((3 * E + kBlock - 1) / kBlock, N), dim3(kBlock), 0, (hipStream_t)stream, vertices, transl,
+                     vertex_index, vertex_weight, V, E, out);
   return check_launch(who);
 }

@@ -494,7 +494,8 @@ int coma_app_objective_f32(const float* verts, const int32_t* faces, const int32
                            float* terms, float* grad_orientation, float* grad_contact, void* workspace, size_t workspace_bytes,
                            void* stream);
 
-/* The SMPL-X body model: linear blend skinning of a V-vertex template over a J-joint tree, forward and backward (batch size 1).
+/* The SMPL-X body model: linear blend skinning of a V-vertex template over a J-joint tree, forward and backward (one body per
+ * call; the batched calls follow this block).
  * replaces: the third-party `smplx` package behind the `body_model` hook of src/application/optimize.py (every iteration, forward
  *           and backward) and src/generation/optimize_depth.py (once per item), i.e. lbs / batch_rodrigues / batch_rigid_transform and
  *           the assembly of SMPLX.forward (use_face_contour=False, no joint mapper).
@@ -586,6 +587,52 @@ int coma_smplx_backward_full_f32(const float* grad_vertices, const float* grad_j
                                  void* stream);
 int coma_smplx_extra_joints_f32(const float* vertices, const float* transl, const int32_t* vertex_index, const float* vertex_weight, int V,
                                 int E, float* out, void* stream);
+
+/* The SMPL-X body model for a BATCH of N bodies in one call: the package's `batch_size=N`.
+ * Rule set: the one above, applied to every body.  Body n of a batched call has THE BITS of the single-body call on the same inputs:
+ * its pose offset is the eight ascending runs of rows added in ascending order, its sums over vertices are per workgroup of 128 in
+ * ascending order and then over the workgroups in ascending order, its P dot products are 256 strided partial sums and the tree, all in
+ * f64 on the f32 data without floating-point atomics.  What the batch changes is how often the operands move:
+ *   posedirs       bodies are served in chunks of C = 8.  Forward: a workgroup holds the chunk's features of its run of rows in LDS
+ *                  and eight f64 sums per thread, so an element of posedirs is loaded once per chunk; backward: the workgroup of row p
+ *                  forms the chunk's eight dot products from one read of the row.  ceil(N / 8) sweeps per direction.
+ *   weights        a skinning workgroup stages its 128 x J tile once and walks 2 bodies over it, each body's A in LDS in turn:
+ *                  ceil(N / 2) reads of the table (2.3 MB at V = 10 475, J = 55) per direction.
+ *   pose stage     one workgroup per body, forward and backward.
+ * Launches: forward 3 (pose, offsets, skinning), extra joints 1, backward 3 (skinning, features, chain), plus 1 when grad_joints reaches
+ * extra joints or grad_vertices is NULL (the effective gradient), whatever N is.
+ * Arrays: theta f32 [N, NT], transl f32 [N, 3] or NULL, vertices f32 [N, V, 3], joints f32 [N, J, 3], full_pose f32 [N, 3J] (may be
+ * NULL), grad_vertices f32 [N, V, 3], grad_joints f32 [N, J + E, 3], grad_full_pose f32 [N, 3J] (each gradient may be NULL = zeros),
+ * grad_theta f32 [N, NT], grad_transl f32 [N, 3]; the extra joints read vertices [N, V, 3] and write out f32 [N, E, 3] from ONE table.
+ * The model pointers are those of the single-body calls; `parents` stays a HOST pointer.
+ * shape_state / shape_stride: shape_stride = 0 is one shape state shared by all bodies; otherwise body n's state lies at shape_state +
+ * n shape_stride (bytes), each written by coma_smplx_shape_f32, which is unchanged.
+ * saved: coma_smplx_batch_saved_bytes(V, J, N) bytes, written by a forward and read by ITS backward: body n's block is the single-body
+ * layout at n coma_smplx_saved_bytes(V, J).  workspace: coma_smplx_batch_workspace_bytes(V, J, N) for the forward (features [N, P] and
+ * the partial offsets [N, 8, 3V] in f64: 2.0 MB per body at V = 10 475) and coma_smplx_batch_grad_workspace_bytes(V, J, N) for the
+ * backward, whichever gradients are given (g_vposed and the effective gradient [N, 3V], the workgroups' shares [N, tiles, 12 J + 3], the
+ * feature gradients [N, P]).  All three return 0 for sizes the calls refuse; all buffers 16-byte aligned.
+ * coma_smplx_backward_batch_f32: with grad_joints and grad_full_pose NULL body n has the bits of coma_smplx_backward_f32; otherwise those
+ * of coma_smplx_backward_full_f32 with grad_coefficients NULL.  DEVIATION: the gradient to the shape coefficients is not part of the
+ * batched call.
+ * Refused before any launch: N outside [1, 1024]; a shape_stride that is neither 0 nor a multiple of 16 of at least
+ * coma_smplx_shape_state_bytes(V, J); and everything the single-body calls refuse (a null pointer, V, J, n_pca, hand_dim, a bad
+ * parent, a buffer too small or misaligned, E outside [0, 4096], a NULL table with grad_joints and E > 0).  Caller's stream, no
+ * allocation, no host synchronisation. */
+size_t coma_smplx_batch_workspace_bytes(int V, int J, int N);
+size_t coma_smplx_batch_saved_bytes(int V, int J, int N);
+size_t coma_smplx_batch_grad_workspace_bytes(int V, int J, int N);
+int coma_smplx_forward_batch_f32(const float* theta, const float* transl, const float* posedirs, const float* weights, const int32_t* parents,
+                                 const float* hand_components, const float* pose_mean, int V, int J, int hand_dim, int n_pca, int N,
+                                 const void* shape_state, size_t shape_stride, float* vertices, float* joints, float* full_pose, void* saved,
+                                 size_t saved_bytes, void* workspace, size_t workspace_bytes, void* stream);
+int coma_smplx_backward_batch_f32(const float* grad_vertices, const float* grad_joints, const float* grad_full_pose, const float* posedirs,
+                                  const float* weights, const int32_t* parents, const float* hand_components, const int32_t* extra_index,
+                                  const float* extra_weight, int E, int V, int J, int hand_dim, int n_pca, int N, const void* shape_state,
+                                  size_t shape_stride, const void* saved, size_t saved_bytes, float* grad_theta, float* grad_transl,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+int coma_smplx_extra_joints_batch_f32(const float* vertices, const float* transl, const int32_t* vertex_index, const float* vertex_weight,
+                                      int V, int E, int N, float* out, void* stream);
 
 /* VPoser's pose decoder (forward and backward), its encoder (forward), and the SMPLify angle prior.
  * replaces: the `pose_decoder` and `angle_prior` hooks of src/application/optimize.py, i.e. the reference's vendored VPoser

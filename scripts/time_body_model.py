@@ -14,7 +14,12 @@ D  eager torch as B with the coefficients a leaf too: dL/dvertices to dL/dtheta,
 They alternate A B C D A B C D ... in rounds of --iters evaluations, each round timed by HIP events after --warmup untimed
 evaluations; the median, fastest and slowest rounds are printed.  Names the device.
 
-    python scripts/time_body_model.py [--rounds 7] [--iters 50] [--out file.json]
+--batch N times the batched path instead: A is ONE forward + backward of DeviceSMPLX(batch_size=N) over N bodies of distinct pose
+(coma_smplx_forward_batch_f32 + coma_smplx_extra_joints_batch_f32, then coma_smplx_backward_batch_f32), B is the only way to do the
+same work without it, a loop of N single-body forward + backward calls on the same build; A B A B in the same rounds, with the
+largest difference between their results (they must be bit-identical).
+
+    python scripts/time_body_model.py [--rounds 7] [--iters 50] [--batch N] [--out file.json]
 """
 import argparse
 import json
@@ -32,6 +37,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--batch", type=int, default=0, help="time one batched call of N bodies against N single-body calls")
     ap.add_argument("--out", type=str, default=None)
     a = ap.parse_args()
     import torch
@@ -53,6 +59,57 @@ def main():
           f"A B A B, {a.warmup} warm-up evaluations each")
 
     betas, expression = coef[None, :10], coef[None, 10:]
+
+    def round_ms(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(a.iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / a.iters
+
+    if a.batch:
+        N = a.batch
+        batched = DeviceSMPLX(model, n_pca=n_pca, device=dev, extra_joint_vertex_ids=list(range(21)), batch_size=N)
+        thetas, transls, gs = t(rng.normal(size=(N, S.n_theta(fm))) * 0.3), t(rng.uniform(-1, 1, (N, 3))), t(rng.normal(size=(N, V, 3)))
+
+        def batched_path():
+            th = thetas.clone().requires_grad_(True)
+            tr = transls.clone().requires_grad_(True)
+            out = batched(betas=betas, expression=expression, transl=tr, **dict(zip(keys, torch.split(th, sizes, 1))))
+            g_th, g_tr = torch.autograd.grad(out.vertices, (th, tr), gs)
+            return out.vertices.detach(), g_th, g_tr
+
+        def looped_path():
+            res = []
+            for n in range(N):
+                th = thetas[n].clone().requires_grad_(True)
+                tr = transls[n].clone().requires_grad_(True)
+                out = body(betas=betas, expression=expression, transl=tr[None], **dict(zip(keys, (x[None] for x in torch.split(th, sizes)))))
+                g_th, g_tr = torch.autograd.grad(out.vertices[0], (th, tr), gs[n])
+                res.append((out.vertices[0].detach(), g_th, g_tr))
+            return tuple(torch.stack(x) for x in zip(*res))
+
+        for fn in (batched_path, looped_path):
+            for _ in range(a.warmup):
+                fn()
+        torch.cuda.synchronize()
+        differ = [float((x - y).abs().max()) for x, y in zip(batched_path(), looped_path())]
+        times = dict(A=[], B=[])
+        for _ in range(a.rounds):
+            times["A"].append(round_ms(batched_path))
+            times["B"].append(round_ms(looped_path))
+        med = {n: float(np.median(x)) for n, x in times.items()}
+        print(f"batch {N}: A one batched call {1e3 * med['A']:9.1f} us (min {1e3 * min(times['A']):.1f}, max {1e3 * max(times['A']):.1f})   "
+              f"B {N} single-body calls {1e3 * med['B']:9.1f} us (min {1e3 * min(times['B']):.1f}, max {1e3 * max(times['B']):.1f})   B / A {med['B'] / med['A']:.2f}   "
+              f"max abs difference A vs B: vertices {differ[0]:.1e}, grad theta {differ[1]:.1e}, grad transl {differ[2]:.1e}")
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as fh:
+                json.dump(dict(device=torch.cuda.get_device_name(0), V=V, J=J, NB=NB, n_pca=n_pca, batch=N, rounds=a.rounds, iters=a.iters, ms=times,
+                               median_ms=med, difference=differ), fh, indent=1)
+        return
 
     def device_path():
         th = theta.clone().requires_grad_(True)
@@ -91,15 +148,6 @@ def main():
         verts = S.torch_forward(tm, cf, th, tr)
         g_th, g_tr, g_cf = torch.autograd.grad(verts, (th, tr, cf), g)
         return verts.detach(), g_th, g_tr, g_cf
-
-    def round_ms(fn):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(a.iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / a.iters
 
     for fn in (device_path, eager_path, device_full_path, eager_full_path):
         for _ in range(a.warmup):
