@@ -213,16 +213,19 @@ __global__ __launch_bounds__(256) void depth_init_kernel(const char* __restrict_
 
 // The multiview term of one epoch, by one workgroup: thread t adds up the views t, t + 256, ... in ascending order, each view its
 // joints in ascending order; the tree follows.  joints = J0 + d f; per view q = joints (R C) - t (R C), xy = q / scale max(res) +
-// res / 2 (view_record layout).  Every thread returns the mean loss and its derivative.
-__device__ __forceinline__ void multiview_term(const double* __restrict__ views, const double* __restrict__ joints0, double f0, double f1, double f2,
+// res / 2 (view_record layout).  Every thread returns the mean loss and its derivative.  A cand_view entry outside [0, n_views) is not
+// followed: status 3 and the epoch are recorded, and every thread returns true -- the caller then writes nothing for this epoch.
+__device__ __forceinline__ bool multiview_term(const double* __restrict__ views, const double* __restrict__ joints0, double f0, double f1, double f2,
                                                const int* __restrict__ cand_view, int n_views, const double* __restrict__ cand_xy, int N, int J, int e,
                                                double d, double* __restrict__ state, double* lds, double* loss_out, double* grad_out) {
   const double ox = d * f0, oy = d * f1, oz = d * f2;
   double loss = 0.0, grad = 0.0;
+  int bad = 0;
   for (int n = threadIdx.x; n < N; n += 256) {
     const int view = cand_view[n];
     if (view < 0 || view >= n_views) {   // not followed; recorded, and the later epochs idle
       ((long long*)state)[kStStatus] = 3, ((long long*)state)[kStEpoch] = e;   // every writer stores the same two values
+      bad = 1;
       continue;
     }
     const double* w = views + (int64_t)view * kViewDoubles;
@@ -248,6 +251,7 @@ __device__ __forceinline__ void multiview_term(const double* __restrict__ views,
   grad = block_sum<256>(grad, lds);
   if (N > 0) loss = loss / (double)N, grad = grad / (double)N;
   *loss_out = loss, *grad_out = grad;
+  return __syncthreads_or(bad) != 0;   // uniform: one bad entry anywhere stops the whole step
 }
 
 // Adam on the one parameter (thread 0): g = the objective's derivative at traj[e]; writes traj[e + 1] and the state block
@@ -274,7 +278,7 @@ __global__ __launch_bounds__(256) void depth_step_kernel(const char* __restrict_
   if (stopped) return;
   const double d = traj[e];
   double loss, grad;
-  multiview_term(views, joints0, f0, f1, f2, cand_view, n_views, cand_xy, N, J, e, d, state, lds, &loss, &grad);
+  if (multiview_term(views, joints0, f0, f1, f2, cand_view, n_views, cand_xy, N, J, e, d, state, lds, &loss, &grad)) return;   // status 3: losses, traj, Adam untouched
   if (threadIdx.x != 0) return;
   double ratio = 0.0, slope = 0.0;
   if (ws && w_collision != 0.0) {
@@ -301,7 +305,7 @@ __global__ __launch_bounds__(256) void depth_step_coap_kernel(const double* __re
   if (stopped) return;
   const double d = traj[e];
   double loss, grad;
-  multiview_term(views, joints0, f0, f1, f2, cand_view, n_views, cand_xy, N, J, e, d, state, lds, &loss, &grad);
+  if (multiview_term(views, joints0, f0, f1, f2, cand_view, n_views, cand_xy, N, J, e, d, state, lds, &loss, &grad)) return;   // status 3: losses, traj, Adam untouched
   if (threadIdx.x != 0) return;
   const double term = w_collision != 0.0 ? Ctraj[2 * e] : 0.0, slope = w_collision != 0.0 ? Ctraj[2 * e + 1] : 0.0;
   losses[2 * e] = loss, losses[2 * e + 1] = term;
@@ -461,7 +465,7 @@ extern "C" int coma_depth_optimize_status(const void* state, void* stream, int* 
   long long tail[2] = {0, 0};
   if (int rc = read_back(tail, (const long long*)state + kStStatus, sizeof(tail), stream, "coma_depth_optimize_status")) return rc;
   if (epoch) *epoch = (int)tail[1];
-  if (tail[0] == 3) return fail(COMA_E_INVALID, "coma_depth_optimize_f64: cand_view holds an index outside [0, n_views) (met in epoch %d; later epochs not run)", (int)tail[1]);
+  if (tail[0] == 3) return fail(COMA_E_INVALID, "coma_depth_optimize_f64: cand_view holds an index outside [0, n_views) (met in epoch %d; nothing written for it, later epochs not run)", (int)tail[1]);
   if (tail[0] == 2) return fail(COMA_E_INVALID, "coma_depth_optimize_f64: the columns workspace holds a refused call (nothing written)");
   if (tail[0]) return fail(COMA_E_INVALID, "coma_depth_optimize_f64: d is not finite after epoch %d (later epochs not run)", (int)tail[1]);
   return COMA_OK;

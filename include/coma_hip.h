@@ -338,7 +338,9 @@ int coma_intersection_status(const void* workspace, void* stream, int64_t* neede
  *                  (sqrt(v) / sqrt(1 - p2) + 1e-8); b1 = 0.9, b2 = 0.999.  w_refview of the reference is not in its loss (:757).
  * coma_shift_columns_prepare: arguments, capacity and refusals exactly as coma_intersection_columns; workspace:
  *   coma_shift_columns_workspace_bytes(...) bytes, 16-byte aligned; it holds the sorted lists until the next prepare.  lengths i64 [2]
- *   (device, may be NULL) = {L_A, L_B}.  Refusals are recorded on the device, the later kernels idle (lengths untouched), and
+ *   (device, may be NULL) = {L_A, L_B}, each mesh's list walked alone: for closed meshes these are sums[1] and sums[2] of
+ *   coma_intersection_columns; an OPEN mesh is still inside after its last crossing, which the joint sweep there counts up to the other
+ *   mesh's next crossing and the walk here does not, so the two may differ.  Refusals are recorded on the device, the later kernels idle (lengths untouched), and
  *   coma_shift_columns_status(workspace, stream, needed) is the one call that waits.
  * coma_shift_profile: d f64 [K] (device), K in [1, 64] -> L i64 [K,3] = L_AB at Delta - 1, Delta, Delta + 1 (device), integer atomics.
  *   Left untouched when the workspace holds a refused call.  No host synchronisation.
@@ -350,7 +352,17 @@ int coma_intersection_status(const void* workspace, void* stream, int64_t* neede
  *   ratio} at traj[e], unweighted.  state: coma_depth_optimize_state_bytes() bytes of device scratch, 8-byte aligned, where the step
  *   kernels keep m, v, p1, p2 between launches.  A d that is not finite is recorded there and the later epochs idle;
  *   coma_depth_optimize_status(state, stream, epoch) -- which waits -- then returns COMA_E_INVALID and the epoch (HOST pointer, may be
- *   NULL) after which it happened; so it does when the workspace holds a refused call (nothing is written then). */
+ *   NULL) after which it happened; so it does when the workspace holds a refused call (nothing is written then).
+ *   What a stopped call leaves: traj up to and including the non-finite d, losses and Ltraj up to the epoch that produced it; every
+ *   later slot of traj and losses keeps what it held.  Ltraj is zeroed as a whole before epoch 0 when the collision term is on.
+ *   cand_view: every entry must lie in [0, n_views).  The entries live on the device, so the step kernel tests each one before it
+ *   follows it; an entry outside the range is never followed.  The epoch that meets one (always epoch 0: cand_view does not change)
+ *   writes NOTHING: losses[0], traj[1] and the Adam state keep what they held, traj[0] = d0 and -- with the collision term on --
+ *   Ltraj[0], the profile at d0, which is taken before the step, are the only results; the later epochs idle, and
+ *   coma_depth_optimize_status returns COMA_E_INVALID with epoch 0.  coma_depth_optimize_coap_f64 does the same (Ctraj[0] written).
+ *   With L_A == 0 (the human off the grid) ratio and slope are both 0 and the collision term moves nothing.
+ *   The clamp of the shift: "nothing can overlap beyond" holds for closed meshes.  An OPEN mesh stays inside to the end of its
+ *   column, so L_AB at +2^42 and at -2^42 may be non-zero and differ; a NaN d takes +2^42.  Still deterministic, still restated. */
 size_t coma_shift_columns_workspace_bytes(int VA, int FA, int VB, int FB, int W, int H, int64_t capacity);
 int coma_shift_columns_prepare(const double* vertsA, int VA, const int32_t* facesA, int FA, const double* vertsB, int VB,
                                const int32_t* facesB, int FB, double x0, double y0, double s, int W, int H, int64_t capacity,

@@ -31,8 +31,11 @@ class Columns:
         self.s, self.W, self.H = float(s), W, H
         self.ca = VR.crossings(vertsA, facesA, x0, y0, s, W, H)
         self.cb = VR.crossings(vertsB, facesB, x0, y0, s, W, H)
-        sums, _, counts = VR.sweep(self.ca, self.cb, W, H)
-        self.L_A, self.L_B = int(sums[1]), int(sums[2])
+        _, _, counts = VR.sweep(self.ca, self.cb, W, H)
+        # "the sweep's, for one mesh at a time": each mesh walked alone.  For a closed mesh these are sums[1] and sums[2] of the joint
+        # sweep; an OPEN mesh is still inside after its last crossing, and the joint sweep counts that up to the other mesh's next one.
+        none = (np.zeros(0, np.int64),) * 3
+        self.L_A, self.L_B = int(VR.sweep(self.ca, none, W, H)[0][1]), int(VR.sweep(none, self.cb, W, H)[0][2])
         self.counts = counts
         self._lab = {}
 
@@ -96,6 +99,13 @@ def optimize(columns, views, joints0, front, cand_view, cand_xy, d0, lr, w_multi
     d, m, v, p1, p2 = np.float64(d0), np.float64(0.0), np.float64(0.0), np.float64(1.0), np.float64(1.0)
     b1, b2 = np.float64(BETA1), np.float64(BETA2)
     traj[0] = d
+    cv = np.asarray(cand_view, dtype=np.int64).reshape(-1)
+    if len(cv) and (cv.min() < 0 or cv.max() >= len(views)):
+        # the cand_view contract: the entry is not followed; epoch 0 stops with status 3 before it writes losses[0] or traj[1], the
+        # Adam state stays at its start.  The profile at traj[0] ran before the step: Ltraj[0] holds it when the collision term is on.
+        if collide:
+            Ltraj[0] = columns.profile([d])[0]
+        return dict(d=float(d), traj=traj[:1], Ltraj=Ltraj[:1], losses=losses[:0], status=3, epoch=0)
     with np.errstate(all="ignore"):
         for e in range(E):
             loss, g_mv = multiview(d, views, joints0, front, cand_view, cand_xy)
@@ -117,6 +127,14 @@ def optimize(columns, views, joints0, front, cand_view, cand_xy, d0, lr, w_multi
                 traj, Ltraj, losses = traj[:e + 2], Ltraj[:e + 1], losses[:e + 1]
                 break
     return dict(d=float(traj[-1]), traj=traj, Ltraj=Ltraj, losses=losses)
+
+
+def breakpoint_shifts(cols):
+    """EVERY shift at which a face of A meets a face of B (the breakpoints of the profile: all differences of a Z of B and a Z of
+    A), each with its two neighbours; 0 and +-1; and one far outside the overlap."""
+    diffs = np.unique(np.subtract.outer(np.unique(cols.cb[1]), np.unique(cols.ca[1])))
+    near = sorted({int(d) + k for d in diffs for k in (-1, 0, 1)} | {-1, 0, 1})
+    return near, int(diffs.max()) + 4096
 
 
 def box_pair_closed_form(a_lo, a_hi, b_lo, b_hi, delta):

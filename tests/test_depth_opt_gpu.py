@@ -59,12 +59,7 @@ def ref_columns(name, res):
     return _COLUMNS[(name, res)]
 
 
-def breakpoint_shifts(cols):
-    """EVERY shift at which a face of A meets a face of B (the breakpoints of the profile: all differences of a Z of B and a Z of
-    A), each with its two neighbours; 0 and +-1; and one far outside the overlap."""
-    diffs = np.unique(np.subtract.outer(np.unique(cols.cb[1]), np.unique(cols.ca[1])))
-    near = sorted({int(d) + k for d in diffs for k in (-1, 0, 1)} | {-1, 0, 1})
-    return near, int(diffs.max()) + 4096
+breakpoint_shifts = SR.breakpoint_shifts
 
 
 def to_d(delta, s):
