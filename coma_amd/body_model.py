@@ -11,8 +11,9 @@ a pose decoder or a prior on the other side of the hook keeps differentiating th
 By default `.joints` and `.full_pose` carry no gradient and betas / expression must not require grad.  `differentiable=` opts in, any
 subset of {"joints", "full_pose", "shape"}: with "joints" / "full_pose" those outputs take part in autograd too, with "shape" betas
 and expression may require grad and receive gradients from whichever outputs are differentiable (coma_smplx_backward_full_f32; the
-backward is once_differentiable: no double backward).  With any of them, every forward keeps the shape state it ran on, so a
-backward after the coefficients have changed still differentiates ITS forward; with "shape" the shape stage reads the coefficients
+backward is once_differentiable at every setting of `differentiable=`, the empty one included: a double backward raises).  With any
+of them, every forward keeps the shape state it ran on, so a backward after the coefficients have changed still differentiates ITS
+forward; with "shape" the shape stage reads the coefficients
 from the device tensors (nothing is copied to the host) and re-runs whenever a tensor or its version counter differs.
 
 Deviations from the package, all refused or stated rather than silently different:
@@ -55,19 +56,6 @@ def _package_vertex_ids():
         return None
     table = vertex_ids["smplx"]
     return [table[n] for n in _FACE_FEET] + [table[side + n] for side in ("l", "r") for n in _TIPS]
-
-
-def _row(x, n, name):
-    """A call argument as a host f32 vector [n] and whether it requires grad; batch size 1 only."""
-    if x is None:
-        return None
-    if not torch.is_tensor(x):
-        x = torch.as_tensor(np.asarray(x, dtype=np.float32))
-    if x.dim() == 2 and x.shape[0] != 1:
-        raise ValueError(f"{name}: batch size {x.shape[0]}; DeviceSMPLX handles batch size 1 only")
-    if x.numel() != n:
-        raise ValueError(f"{name}: expected {n} numbers ([1,{n}]), got shape {tuple(x.shape)}")
-    return x
 
 
 class DeviceSMPLX:
@@ -168,7 +156,7 @@ class DeviceSMPLX:
                          parents=parents, hand_components=comps, pose_mean=mean, extra_index=idx, extra_weight=w)
         self._parents = (C.c_int32 * J)(*[int(p) for p in parents])
         self._uploaded = False                                           # the device is first touched by the first call
-        self._shape_key, self._shape_source, self._shape_version = None, None, None
+        self._shape_keys, self._shape_source, self._shape_version = None, None, None    # the last shape stage: its rows of coefficients, its tensors
         self.shape_stage_runs = 0                                        # how often the shape stage ran (tests count it)
 
     @classmethod
@@ -193,122 +181,166 @@ class DeviceSMPLX:
         if self._uploaded:
             return
         self.device = _lib.need_device(self.device, "DeviceSMPLX")      # "cuda" means the current device; tensors report cuda:N
-        h, dev = self.host, self.device
+        h, dev, N = self.host, self.device, self.batch_size
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
         self._v_template, self._shapedirs, self._posedirs = up(h["v_template"]), up(h["shapedirs"]), up(h["posedirs"])
         self._J_regressor, self._weights, self._mean = up(h["J_regressor"]), up(h["weights"]), up(h["pose_mean"])
         self._comps = up(h["hand_components"]) if h["hand_components"] is not None and self.hand_dim else None
         self._extra_index, self._extra_weight = (up(h["extra_index"].astype(np.int32)), up(h["extra_weight"])) if self.num_extra else (None, None)
         L = _lib.lib()
-        self._ws_bytes, self._shape_bytes, self._saved_bytes = (int(f(self.V, self.J)) for f in (
-            L.coma_smplx_workspace_bytes, L.coma_smplx_shape_state_bytes, L.coma_smplx_saved_bytes))
-        self._ws = torch.empty([self._ws_bytes], dtype=torch.uint8, device=dev)
+        self._shape_bytes, self._saved_bytes = int(L.coma_smplx_shape_state_bytes(self.V, self.J)), int(L.coma_smplx_saved_bytes(self.V, self.J))
+        self._shape_stride = (self._shape_bytes + 15) // 16 * 16           # between the states of a batch with a row of coefficients per body
         self._shape_state = torch.empty([self._shape_bytes], dtype=torch.uint8, device=dev)
-        if self.differentiable:
-            self._grad_ws_bytes = int(L.coma_smplx_grad_workspace_bytes(self.V, self.J, self.num_betas + self.num_expression_coeffs))
-            self._grad_ws = torch.empty([self._grad_ws_bytes], dtype=torch.uint8, device=dev)
-        if self.batch_size > 1:                                          # scratch of the batched calls; `saved` is per forward
-            N = self.batch_size
-            self._batch_ws_bytes, self._batch_saved_bytes, self._batch_grad_ws_bytes = (int(f(self.V, self.J, N)) for f in (
-                L.coma_smplx_batch_workspace_bytes, L.coma_smplx_batch_saved_bytes, L.coma_smplx_batch_grad_workspace_bytes))
-            self._batch_ws = torch.empty([self._batch_ws_bytes], dtype=torch.uint8, device=dev)
-            self._batch_grad_ws = torch.empty([self._batch_grad_ws_bytes], dtype=torch.uint8, device=dev)
-            self._shape_stride = (self._shape_bytes + 15) // 16 * 16
-            self._batch_shape_state, self._batch_shape_keys = None, None
+        # scratch of the calls (`saved` is per forward): one body has the single-body entry points' sizes, and a backward workspace of
+        # its own only for the full backward
+        self._grad_ws_bytes = 0
+        if N > 1:
+            self._ws_bytes, self._grad_ws_bytes = (int(f(self.V, self.J, N)) for f in (
+                L.coma_smplx_batch_workspace_bytes, L.coma_smplx_batch_grad_workspace_bytes))
+        else:
+            self._ws_bytes = int(L.coma_smplx_workspace_bytes(self.V, self.J))
+            if self.differentiable:
+                self._grad_ws_bytes = int(L.coma_smplx_grad_workspace_bytes(self.V, self.J, self.num_betas + self.num_expression_coeffs))
+        self._ws = torch.empty([self._ws_bytes], dtype=torch.uint8, device=dev)
+        self._grad_ws = torch.empty([self._grad_ws_bytes], dtype=torch.uint8, device=dev) if self._grad_ws_bytes else None
         self._uploaded = True
 
-    # ---- the three device calls ----
+    def _rows(self, x, n, name):
+        """A call argument as a 2-D tensor [1 or batch_size, n] (None stays None); nothing here touches the device."""
+        if x is None:
+            return None
+        if not torch.is_tensor(x):
+            x = torch.as_tensor(np.asarray(x, dtype=np.float32))
+        if self.batch_size == 1:
+            if x.dim() == 2 and x.shape[0] != 1:
+                raise ValueError(f"{name}: batch size {x.shape[0]}; DeviceSMPLX handles batch size 1 only")
+            if x.numel() != n:
+                raise ValueError(f"{name}: expected {n} numbers ([1,{n}]), got shape {tuple(x.shape)}")
+            return x.reshape(1, n)
+        if x.dim() == 1:
+            x = x[None]
+        if x.dim() != 2 or x.shape[1] != n:
+            raise ValueError(f"{name}: expected [{self.batch_size},{n}] or [1,{n}], got shape {tuple(x.shape)}")
+        if x.shape[0] not in (1, self.batch_size):
+            raise ValueError(f"{name}: leading dimension {x.shape[0]} is neither 1 nor batch_size={self.batch_size}")
+        return x
+
+    # ---- the device calls ----
+    def _same_source(self, source):
+        """Whether `source` = (betas, expression) are the tensor objects of the last shape stage at the same version counters, and
+        those counters.  LIMITATION: a write that does not move the version counter -- through `.data`, or from outside torch -- is
+        not seen; pass a new tensor, or write in place through torch."""
+        version = tuple(x._version if torch.is_tensor(x) else None for x in source)
+        same = self._shape_source is not None and version == self._shape_version and all(
+            (x is None and y is None) or (torch.is_tensor(x) and x is y) for x, y in zip(source, self._shape_source))
+        return same, version
+
     def _shape_stage(self, betas, expression):
-        """Re-run only when the coefficients differ from the last call's.  The same tensor objects at the same version counter (the
-        app passes its fixed betas every iteration) are not looked at again, so nothing is read back from the device for them;
-        anything else is compared on the host copy made here (one device-to-host copy when the coefficients live on the device).
-        LIMITATION: a write that does not move the version counter -- through `.data`, or from outside torch -- is not seen on the
-        same-tensor path; pass a new tensor, or write in place through torch."""
+        """Leaves `_shape_state` ready for the call: ONE state when betas and expression are both [1, n] (or absent), else batch_size
+        states `_shape_stride` apart (`_stride()` says which).  A state is re-run only when ITS row of coefficients differs from the
+        last call's.  The same tensor objects at the same version counter (the app passes its fixed betas every iteration) are not
+        looked at again, so nothing is read back from the device for them; anything else is compared on the host copy made here (one
+        device-to-host copy when the coefficients live on the device).  -> the coefficients as a device tensor with differentiable
+        "shape", else None."""
         if "shape" in self.differentiable:
             return self._shape_stage_on_device(betas, expression)
         for x, name in ((betas, "betas"), (expression, "expression")):     # looked at on every call, whichever path follows
             if torch.is_tensor(x) and x.requires_grad:
-                raise _lib.ComaHipError(f"DeviceSMPLX: {name} requires grad, and the device body model has no gradient with respect to {name} "
-                                        f"unless it is built with \"shape\" in differentiable=")
+                raise _lib.ComaHipError(
+                    f"DeviceSMPLX: {name} requires grad, and the batched device body model has no gradient with respect to {name}" if self.batch_size > 1
+                    else f"DeviceSMPLX: {name} requires grad, and the device body model has no gradient with respect to {name} unless it is built "
+                         f"with \"shape\" in differentiable=")
         source = (betas, expression)
-        version = tuple(x._version if torch.is_tensor(x) else None for x in source)
-        if self._shape_source is not None and version == self._shape_version and all(
-                (x is None and y is None) or (torch.is_tensor(x) and x is y) for x, y in zip(source, self._shape_source)):
-            return
+        same, version = self._same_source(source)
+        if same:
+            return None
         parts = []
         for x, n, name in ((betas, self.num_betas, "betas"), (expression, self.num_expression_coeffs, "expression")):
-            x = _row(x, n, name)
-            if x is None:
-                parts.append(np.zeros(n, np.float32))
-                continue
-            parts.append(x.detach().to(torch.float32).reshape(-1).cpu().numpy())
-        coef = np.ascontiguousarray(np.concatenate(parts), dtype=np.float32)
+            x = self._rows(x, n, name)
+            parts.append(np.zeros([1, n], np.float32) if x is None else x.detach().to(torch.float32).cpu().numpy())
+        B = max(p.shape[0] for p in parts)
+        coef = np.ascontiguousarray(np.concatenate([np.broadcast_to(p, (B, p.shape[1])) for p in parts], 1), dtype=np.float32)
         self._upload()
-        key = coef.tobytes()
-        self._shape_source, self._shape_version = source, version
-        if key == self._shape_key:
-            return
-        self._run_shape(torch.from_numpy(coef).to(self.device))
-        self._shape_key = key
+        keys = [row.tobytes() for row in coef]
+        old = self._shape_keys if self._shape_keys is not None and len(self._shape_keys) == B else [None] * B
+        stale = [n for n in range(B) if keys[n] != old[n]]
+        if stale:
+            if self.differentiable or self._shape_state.numel() != B * self._shape_stride:
+                stale = list(range(B))          # all of them into a NEW buffer: with `differentiable`, forwards in flight keep the states they ran on
+                self._shape_state = torch.empty([B * self._shape_stride], dtype=torch.uint8, device=self.device)
+            d_coef = torch.from_numpy(coef).to(self.device)
+            with _lib.on_device(self.device) as stream:
+                for n in stale:
+                    self._run_shape(d_coef[n], n, stream)
+        self._shape_keys, self._shape_source, self._shape_version = keys, source, version
+        return None
 
-    def _run_shape(self, d_coef):
-        """The shape stage from device coefficients f32 [NB].  With anything in `differentiable`, into a NEW shape state: forwards that
-        ran on the previous one hold on to it for their backward."""
+    def _stride(self):
+        """The shape_stride of a call on the current shape states: 0 = one state for all bodies."""
+        return self._shape_stride if self._shape_keys is not None and len(self._shape_keys) > 1 else 0
+
+    def _run_shape(self, d_coef, n, stream):
+        """The shape stage from device coefficients f32 [NB] into state n of `_shape_state`, on the caller's `on_device` stream."""
         f32 = torch.float32
-        if self.differentiable:
-            self._shape_state = torch.empty([self._shape_bytes], dtype=torch.uint8, device=self.device)
-        with _lib.on_device(self.device) as stream:
-            rc = _lib.lib().coma_smplx_shape_f32(_lib.ptr(self._v_template, f32), _lib.ptr(self._shapedirs, f32), _lib.ptr(d_coef, f32),
-                                                 _lib.ptr(self._J_regressor, f32), self.V, self.J, int(d_coef.numel()), _lib.ptr(self._shape_state),
-                                                 self._shape_bytes, stream)
+        rc = _lib.lib().coma_smplx_shape_f32(_lib.ptr(self._v_template, f32), _lib.ptr(self._shapedirs, f32), _lib.ptr(d_coef, f32),
+                                             _lib.ptr(self._J_regressor, f32), self.V, self.J, int(d_coef.numel()),
+                                             C.c_void_p(self._shape_state.data_ptr() + n * self._shape_stride), self._shape_bytes, stream)
         _lib.check(rc, "coma_smplx_shape_f32")
         self.shape_stage_runs += 1
 
     def _shape_stage_on_device(self, betas, expression):
-        """differentiable "shape": the coefficients as ONE device tensor f32 [NB] that is part of the autograd graph (its gradient
-        splits back into betas and expression through torch), built without copying anything to the host.  The shape stage is
-        skipped for the same tensor objects at the same version counters and re-run otherwise: values are never compared, that
-        would take a read-back.  The LIMITATION of `_shape_stage` about writes that do not move the version counter holds here too."""
+        """differentiable "shape" (batch size 1): the coefficients as ONE device tensor f32 [NB] that is part of the autograd graph (its
+        gradient splits back into betas and expression through torch), built without copying anything to the host.  The shape stage
+        is skipped for the same tensor objects at the same version counters and re-run otherwise, into a NEW state (forwards that ran
+        on the previous one hold on to it for their backward): values are never compared, that would take a read-back."""
         self._upload()
         parts = []
         for x, n, name in ((betas, self.num_betas, "betas"), (expression, self.num_expression_coeffs, "expression")):
-            x = _row(x, n, name)
+            x = self._rows(x, n, name)
             parts.append(torch.zeros([n], dtype=torch.float32, device=self.device) if x is None
                          else x.reshape(-1).to(device=self.device, dtype=torch.float32))
         coef = torch.cat(parts)
         source = (betas, expression)
-        version = tuple(x._version if torch.is_tensor(x) else None for x in source)
-        if not (self._shape_source is not None and version == self._shape_version and all(
-                (x is None and y is None) or (torch.is_tensor(x) and x is y) for x, y in zip(source, self._shape_source))):
-            self._run_shape(coef.detach().contiguous())
-            self._shape_source, self._shape_version, self._shape_key = source, version, None
+        same, version = self._same_source(source)
+        if not same:
+            self._shape_state = torch.empty([self._shape_bytes], dtype=torch.uint8, device=self.device)
+            with _lib.on_device(self.device) as stream:
+                self._run_shape(coef.detach().contiguous(), 0, stream)
+            self._shape_source, self._shape_version, self._shape_keys = source, version, None
         return coef
 
     def _forward(self, theta, transl):
-        """theta f32 [num_theta], transl f32 [3] or None (device) -> vertices [V,3], joints [J + extra, 3], full_pose [3J], saved."""
-        f32, dev = torch.float32, self.device
-        vertices = torch.empty([self.V, 3], dtype=f32, device=dev)
-        joints = torch.empty([self.J + self.num_extra, 3], dtype=f32, device=dev)
-        full_pose = torch.empty([3 * self.J], dtype=f32, device=dev)
-        saved = torch.empty([self._saved_bytes], dtype=torch.uint8, device=dev)
+        """theta f32 [N, num_theta], transl f32 [N, 3] or None (device, contiguous), on the current shape states -> vertices [N,V,3],
+        joints [N, J + extra, 3], full_pose [N, 3J], saved: all new tensors."""
+        f32, dev, N, E = torch.float32, self.device, self.batch_size, self.num_extra
+        vertices = torch.empty([N, self.V, 3], dtype=f32, device=dev)
+        joints = torch.empty([N, self.J + (E if N == 1 else 0), 3], dtype=f32, device=dev)   # one body: the extra joints go in place behind the posed
+        full_pose = torch.empty([N, 3 * self.J], dtype=f32, device=dev)
+        saved = torch.empty([N * self._saved_bytes], dtype=torch.uint8, device=dev)
+        extra = torch.empty([N, E, 3], dtype=f32, device=dev) if N > 1 and E else None
         L = _lib.lib()
+        ins = (_lib.ptr(theta, f32, "theta"), _lib.ptr(transl, f32, "transl"), _lib.ptr(self._posedirs, f32), _lib.ptr(self._weights, f32),
+               self._parents, _lib.ptr(self._comps, f32), _lib.ptr(self._mean, f32), self.V, self.J, self.hand_dim, self.num_pca_comps)
+        table = (_lib.ptr(vertices), _lib.ptr(transl, f32), _lib.ptr(self._extra_index, torch.int32), _lib.ptr(self._extra_weight, f32), self.V, E)
         with _lib.on_device(dev) as stream:
-            rc = L.coma_smplx_forward_f32(_lib.ptr(theta, f32, "theta"), _lib.ptr(transl, f32, "transl"), _lib.ptr(self._posedirs, f32),
-                                          _lib.ptr(self._weights, f32), self._parents, _lib.ptr(self._comps, f32), _lib.ptr(self._mean, f32), self.V,
-                                          self.J, self.hand_dim, self.num_pca_comps, _lib.ptr(self._shape_state), _lib.ptr(vertices),
-                                          _lib.ptr(joints), _lib.ptr(full_pose), _lib.ptr(saved), self._saved_bytes, _lib.ptr(self._ws),
-                                          self._ws_bytes, stream)
-            if rc == 0 and self.num_extra:
-                rc = L.coma_smplx_extra_joints_f32(_lib.ptr(vertices), _lib.ptr(transl, f32), _lib.ptr(self._extra_index, torch.int32),
-                                                   _lib.ptr(self._extra_weight, f32), self.V, self.num_extra,
-                                                   C.c_void_p(joints.data_ptr() + 12 * self.J), stream)
-        _lib.check(rc, "coma_smplx_forward_f32")
+            outs = (_lib.ptr(vertices), _lib.ptr(joints), _lib.ptr(full_pose), _lib.ptr(saved), saved.numel(), _lib.ptr(self._ws), self._ws_bytes, stream)
+            if N == 1:
+                rc = L.coma_smplx_forward_f32(*ins, _lib.ptr(self._shape_state), *outs)
+                if rc == 0 and E:
+                    rc = L.coma_smplx_extra_joints_f32(*table, C.c_void_p(joints.data_ptr() + 12 * self.J), stream)
+                _lib.check(rc, "coma_smplx_forward_f32")
+            else:
+                _lib.check(L.coma_smplx_forward_batch_f32(*ins, N, _lib.ptr(self._shape_state), self._stride(), *outs), "coma_smplx_forward_batch_f32")
+                if E:
+                    _lib.check(L.coma_smplx_extra_joints_batch_f32(*table, N, _lib.ptr(extra), stream), "coma_smplx_extra_joints_batch_f32")
+                    joints = torch.cat([joints, extra], 1)
         return vertices, joints, full_pose, saved
 
     def _backward(self, grad_vertices, saved):
+        """The vertices-only backward of one body (coma_smplx_backward_f32, on the forward's workspace) -> (g_theta [1, NT], g_transl [1, 3])."""
         f32, dev = torch.float32, self.device
-        g_theta = torch.empty([self.num_theta], dtype=f32, device=dev)
-        g_transl = torch.empty([3], dtype=f32, device=dev)
+        g_theta = torch.empty([1, self.num_theta], dtype=f32, device=dev)
+        g_transl = torch.empty([1, 3], dtype=f32, device=dev)
         with _lib.on_device(dev) as stream:
             rc = _lib.lib().coma_smplx_backward_f32(_lib.ptr(grad_vertices, f32, "grad_vertices"), _lib.ptr(self._posedirs, f32),
                                                     _lib.ptr(self._weights, f32), self._parents, _lib.ptr(self._comps, f32), self.V, self.J,
@@ -318,192 +350,73 @@ class DeviceSMPLX:
         _lib.check(rc, "coma_smplx_backward_f32")
         return g_theta, g_transl
 
-    def _backward_full(self, grad_vertices, grad_joints, grad_full_pose, saved, shape_state, want_coefficients):
-        """The full backward of ONE forward (its saved state and the shape state it ran on); each gradient f32 on the device or None
-        = absent -> (g_theta, g_transl, g_coefficients or None)."""
-        f32, dev = torch.float32, self.device
+    def _backward_full(self, grad_vertices, grad_joints, grad_full_pose, saved, shape_state, want_coefficients, shape_stride=0):
+        """The backward of ONE forward (its saved state and the shape states it ran on) from every output: each gradient f32 on the
+        device or None = absent -> (g_theta [N, NT], g_transl [N, 3], g_coefficients [NB] or None).  One body: the full backward; a batch:
+        the batched one, which has no gradient to the coefficients."""
+        f32, dev, N = torch.float32, self.device, self.batch_size
         NB = self.num_betas + self.num_expression_coeffs
-        g_theta = torch.empty([self.num_theta], dtype=f32, device=dev)
-        g_transl = torch.empty([3], dtype=f32, device=dev)
+        g_theta = torch.empty([N, self.num_theta], dtype=f32, device=dev)
+        g_transl = torch.empty([N, 3], dtype=f32, device=dev)
         g_coef = torch.empty([NB], dtype=f32, device=dev) if want_coefficients else None
+        L = _lib.lib()
+        ins = (_lib.ptr(grad_vertices, f32, "grad_vertices"), _lib.ptr(grad_joints, f32, "grad_joints"), _lib.ptr(grad_full_pose, f32, "grad_full_pose"),
+               _lib.ptr(self._posedirs, f32), _lib.ptr(self._weights, f32), self._parents, _lib.ptr(self._comps, f32),
+               _lib.ptr(self._extra_index, torch.int32), _lib.ptr(self._extra_weight, f32), self.num_extra)
+        sizes = (self.V, self.J, self.hand_dim, self.num_pca_comps)
         with _lib.on_device(dev) as stream:
-            rc = _lib.lib().coma_smplx_backward_full_f32(
-                _lib.ptr(grad_vertices, f32, "grad_vertices"), _lib.ptr(grad_joints, f32, "grad_joints"), _lib.ptr(grad_full_pose, f32, "grad_full_pose"),
-                _lib.ptr(self._posedirs, f32), _lib.ptr(self._weights, f32), self._parents, _lib.ptr(self._comps, f32),
-                _lib.ptr(self._extra_index, torch.int32), _lib.ptr(self._extra_weight, f32), self.num_extra, _lib.ptr(self._shapedirs, f32),
-                _lib.ptr(self._J_regressor, f32), NB, self.V, self.J, self.hand_dim, self.num_pca_comps, _lib.ptr(shape_state), _lib.ptr(saved),
-                self._saved_bytes, _lib.ptr(g_theta), _lib.ptr(g_transl), _lib.ptr(g_coef, f32), _lib.ptr(self._grad_ws), self._grad_ws_bytes,
-                stream)
-        _lib.check(rc, "coma_smplx_backward_full_f32")
+            ws = (_lib.ptr(self._grad_ws), self._grad_ws_bytes, stream)
+            if N == 1:
+                name = "coma_smplx_backward_full_f32"
+                rc = L.coma_smplx_backward_full_f32(*ins, _lib.ptr(self._shapedirs, f32), _lib.ptr(self._J_regressor, f32), NB, *sizes,
+                                                    _lib.ptr(shape_state), _lib.ptr(saved), saved.numel(), _lib.ptr(g_theta), _lib.ptr(g_transl),
+                                                    _lib.ptr(g_coef, f32), *ws)
+            else:
+                name = "coma_smplx_backward_batch_f32"
+                rc = L.coma_smplx_backward_batch_f32(*ins, *sizes, N, _lib.ptr(shape_state), shape_stride, _lib.ptr(saved), saved.numel(),
+                                                     _lib.ptr(g_theta), _lib.ptr(g_transl), *ws)
+        _lib.check(rc, name)
         return g_theta, g_transl, g_coef
 
     def __call__(self, betas=None, global_orient=None, body_pose=None, left_hand_pose=None, right_hand_pose=None, transl=None, expression=None,
                  jaw_pose=None, leye_pose=None, reye_pose=None, return_verts=True, return_full_pose=False, **unused):
-        """The package's call: every argument [1, n] (None = zeros).  Gradients flow from .vertices to the seven pose arguments and
-        transl; betas and expression must not require grad.  `differentiable=` (constructor) adds .joints, .full_pose (ask for it with
-        return_full_pose=True) and the gradient to betas / expression."""
+        """The package's call: every argument [batch_size, n] or [1, n] (None = zeros).  Gradients flow from .vertices to the seven pose
+        arguments and transl; betas and expression must not require grad.  `differentiable=` (constructor) adds .joints, .full_pose (ask
+        for it with return_full_pose=True) and, at batch size 1, the gradient to betas / expression.  A [1, n] argument is expanded to
+        [batch_size, n] BEFORE the autograd function, so autograd sums its gradient over the bodies."""
+        N = self.batch_size
         sizes = (("global_orient", global_orient, 3), ("body_pose", body_pose, self.num_body), ("jaw_pose", jaw_pose, 3),
                  ("leye_pose", leye_pose, 3), ("reye_pose", reye_pose, 3), ("left_hand_pose", left_hand_pose, self.hand_size),
                  ("right_hand_pose", right_hand_pose, self.hand_size), ("transl", transl, 3))
-        if self.batch_size > 1:
-            return self._call_batch(sizes, betas, expression, return_verts, return_full_pose)
-        rows = [(name, _row(x, n, name), n) for name, x, n in sizes]          # shapes first: nothing has touched the device yet
-        coefficients = self._shape_stage(betas, expression)                 # a device tensor with differentiable "shape", else None
-        parts = []
-        for name, x, n in rows:
-            if x is None:
-                x = None if name == "transl" else torch.zeros([n], dtype=torch.float32, device=self.device)
-            elif not x.is_cuda or x.device != self.device:
-                raise _lib.ComaHipError(f"{name} must live on {self.device} (got {x.device}); there is no CPU path")
-            parts.append(x if x is None else x.reshape(-1).to(torch.float32))
-        transl = parts.pop()
-        theta = torch.cat(parts)
-        if self.differentiable:
-            vertices, joints, full_pose = _FullFunction.apply(self, theta, transl, coefficients)
-        else:
-            vertices, joints, full_pose = _SkinFunction.apply(self, theta, transl)
-        return SimpleNamespace(vertices=vertices[None] if return_verts else None, joints=joints[None],
-                               full_pose=full_pose[None] if return_full_pose else None, faces=self.faces, betas=betas, expression=expression,
-                               global_orient=global_orient, body_pose=body_pose, jaw_pose=jaw_pose, transl=transl)
-
-    # ---- batch_size > 1 ----
-    def _rows(self, x, n, name):
-        """A call argument of a batched object as a 2-D tensor [1 or batch_size, n] (None stays None)."""
-        if x is None:
-            return None
-        if not torch.is_tensor(x):
-            x = torch.as_tensor(np.asarray(x, dtype=np.float32))
-        if x.dim() == 1:
-            x = x[None]
-        if x.dim() != 2 or x.shape[1] != n:
-            raise ValueError(f"{name}: expected [{self.batch_size},{n}] or [1,{n}], got shape {tuple(x.shape)}")
-        if x.shape[0] not in (1, self.batch_size):
-            raise ValueError(f"{name}: leading dimension {x.shape[0]} is neither 1 nor batch_size={self.batch_size}")
-        return x
-
-    def _shape_stage_batch(self, betas, expression):
-        """The shape stage for a batch: ONE state when betas and expression are both [1, n] (or absent), else batch_size states,
-        each written by coma_smplx_shape_f32 and re-run only when ITS row of coefficients differs from the last call's (compared on
-        the host as at batch size 1; the same tensors at the same version counters are not looked at again) -> (buffer, stride)."""
-        for x, name in ((betas, "betas"), (expression, "expression")):
-            if torch.is_tensor(x) and x.requires_grad:
-                raise _lib.ComaHipError(f"DeviceSMPLX: {name} requires grad, and the batched device body model has no gradient with respect "
-                                        f"to {name}")
-        source = (betas, expression)
-        version = tuple(x._version if torch.is_tensor(x) else None for x in source)
-        if self._shape_source is not None and version == self._shape_version and all(
-                (x is None and y is None) or (torch.is_tensor(x) and x is y) for x, y in zip(source, self._shape_source)):
-            return self._batch_shape_state, (self._shape_stride if len(self._batch_shape_keys) > 1 else 0)
-        parts = []
-        for x, n, name in ((betas, self.num_betas, "betas"), (expression, self.num_expression_coeffs, "expression")):
-            x = self._rows(x, n, name)
-            parts.append(np.zeros([1, n], np.float32) if x is None else x.detach().to(torch.float32).cpu().numpy())
-        B = max(p.shape[0] for p in parts)
-        coef = np.ascontiguousarray(np.concatenate([np.broadcast_to(p, (B, p.shape[1])) for p in parts], 1), dtype=np.float32)
-        self._upload()
-        keys = [row.tobytes() for row in coef]
-        old = self._batch_shape_keys
-        stale = list(range(B)) if old is None or len(old) != B else [n for n in range(B) if keys[n] != old[n]]
-        if stale:
-            if self.differentiable or old is None or len(old) != B:     # with `differentiable`, forwards in flight keep the states they ran on
-                stale = list(range(B))
-                self._batch_shape_state = torch.empty([B * self._shape_stride], dtype=torch.uint8, device=self.device)
-            d_coef = torch.from_numpy(coef).to(self.device)
-            f32 = torch.float32
-            with _lib.on_device(self.device) as stream:
-                for n in stale:
-                    rc = _lib.lib().coma_smplx_shape_f32(_lib.ptr(self._v_template, f32), _lib.ptr(self._shapedirs, f32),
-                                                         C.c_void_p(d_coef.data_ptr() + 4 * n * coef.shape[1]), _lib.ptr(self._J_regressor, f32), self.V,
-                                                         self.J, coef.shape[1], C.c_void_p(self._batch_shape_state.data_ptr() + n * self._shape_stride),
-                                                         self._shape_bytes, stream)
-                    _lib.check(rc, "coma_smplx_shape_f32")
-                    self.shape_stage_runs += 1
-        self._batch_shape_keys, self._shape_source, self._shape_version = keys, source, version
-        return self._batch_shape_state, (self._shape_stride if B > 1 else 0)
-
-    def _forward_batch(self, theta, transl, shape_state, shape_stride):
-        """theta f32 [N, num_theta], transl f32 [N, 3] or None (device, contiguous) -> vertices [N,V,3], joints [N, J + extra, 3],
-        full_pose [N, 3J], saved: all new tensors."""
-        f32, dev, N = torch.float32, self.device, self.batch_size
-        vertices = torch.empty([N, self.V, 3], dtype=f32, device=dev)
-        joints = torch.empty([N, self.J, 3], dtype=f32, device=dev)
-        full_pose = torch.empty([N, 3 * self.J], dtype=f32, device=dev)
-        saved = torch.empty([self._batch_saved_bytes], dtype=torch.uint8, device=dev)
-        L = _lib.lib()
-        with _lib.on_device(dev) as stream:
-            rc = L.coma_smplx_forward_batch_f32(_lib.ptr(theta, f32, "theta"), _lib.ptr(transl, f32, "transl"), _lib.ptr(self._posedirs, f32),
-                                                _lib.ptr(self._weights, f32), self._parents, _lib.ptr(self._comps, f32), _lib.ptr(self._mean, f32),
-                                                self.V, self.J, self.hand_dim, self.num_pca_comps, N, _lib.ptr(shape_state), shape_stride,
-                                                _lib.ptr(vertices), _lib.ptr(joints), _lib.ptr(full_pose), _lib.ptr(saved), self._batch_saved_bytes,
-                                                _lib.ptr(self._batch_ws), self._batch_ws_bytes, stream)
-            _lib.check(rc, "coma_smplx_forward_batch_f32")
-            if self.num_extra:
-                extra = torch.empty([N, self.num_extra, 3], dtype=f32, device=dev)
-                rc = L.coma_smplx_extra_joints_batch_f32(_lib.ptr(vertices), _lib.ptr(transl, f32), _lib.ptr(self._extra_index, torch.int32),
-                                                         _lib.ptr(self._extra_weight, f32), self.V, self.num_extra, N, _lib.ptr(extra), stream)
-                _lib.check(rc, "coma_smplx_extra_joints_batch_f32")
-                joints = torch.cat([joints, extra], 1)
-        return vertices, joints, full_pose, saved
-
-    def _backward_batch(self, grad_vertices, grad_joints, grad_full_pose, saved, shape_state, shape_stride):
-        """The batched backward of ONE forward; each gradient f32 on the device or None = absent -> (g_theta [N, NT], g_transl [N, 3])."""
-        f32, dev, N = torch.float32, self.device, self.batch_size
-        g_theta = torch.empty([N, self.num_theta], dtype=f32, device=dev)
-        g_transl = torch.empty([N, 3], dtype=f32, device=dev)
-        with _lib.on_device(dev) as stream:
-            rc = _lib.lib().coma_smplx_backward_batch_f32(
-                _lib.ptr(grad_vertices, f32, "grad_vertices"), _lib.ptr(grad_joints, f32, "grad_joints"), _lib.ptr(grad_full_pose, f32, "grad_full_pose"),
-                _lib.ptr(self._posedirs, f32), _lib.ptr(self._weights, f32), self._parents, _lib.ptr(self._comps, f32),
-                _lib.ptr(self._extra_index, torch.int32), _lib.ptr(self._extra_weight, f32), self.num_extra, self.V, self.J, self.hand_dim,
-                self.num_pca_comps, N, _lib.ptr(shape_state), shape_stride, _lib.ptr(saved), self._batch_saved_bytes, _lib.ptr(g_theta),
-                _lib.ptr(g_transl), _lib.ptr(self._batch_grad_ws), self._batch_grad_ws_bytes, stream)
-        _lib.check(rc, "coma_smplx_backward_batch_f32")
-        return g_theta, g_transl
-
-    def _call_batch(self, sizes, betas, expression, return_verts, return_full_pose):
-        """__call__ at batch_size > 1: a [1, n] argument is expanded to [N, n] BEFORE the autograd function, so autograd sums its
-        gradient over the bodies."""
-        N = self.batch_size
         rows = [(name, self._rows(x, n, name), n) for name, x, n in sizes]     # shapes first: nothing has touched the device yet
-        shape_state, shape_stride = self._shape_stage_batch(betas, expression)
+        coefficients = self._shape_stage(betas, expression)                 # a device tensor with differentiable "shape", else None
         parts = []
         for name, x, n in rows:
             if x is None:
                 x = None if name == "transl" else torch.zeros([N, n], dtype=torch.float32, device=self.device)
             elif not x.is_cuda or x.device != self.device:
                 raise _lib.ComaHipError(f"{name} must live on {self.device} (got {x.device}); there is no CPU path")
-            parts.append(x if x is None else x.to(torch.float32).expand(N, n))
+            elif x.shape[0] != N:
+                x = x.expand(N, n)
+            parts.append(x if x is None else x.to(torch.float32))
         transl = parts.pop()
         theta = torch.cat(parts, 1)
-        vertices, joints, full_pose = _BatchFunction.apply(self, theta, transl, shape_state, shape_stride)
-        named = dict(zip((name for name, _, _ in sizes), (x for _, x, _ in sizes)))
+        vertices, joints, full_pose = _Function.apply(self, theta, transl, coefficients)
         return SimpleNamespace(vertices=vertices if return_verts else None, joints=joints, full_pose=full_pose if return_full_pose else None,
-                               faces=self.faces, betas=betas, expression=expression, global_orient=named["global_orient"],
-                               body_pose=named["body_pose"], jaw_pose=named["jaw_pose"], transl=transl)
+                               faces=self.faces, betas=betas, expression=expression, global_orient=global_orient, body_pose=body_pose,
+                               jaw_pose=jaw_pose, transl=transl)
 
 
-class _SkinFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, model, theta, transl):
-        vertices, joints, full_pose, saved = model._forward(theta.detach().contiguous(), None if transl is None else transl.detach().contiguous())
-        ctx.model, ctx.saved, ctx.has_transl = model, saved, transl is not None
-        ctx.mark_non_differentiable(joints, full_pose)
-        return vertices, joints, full_pose
-
-    @staticmethod
-    def backward(ctx, grad_vertices, _grad_joints, _grad_full_pose):
-        g_theta, g_transl = ctx.model._backward(grad_vertices.to(torch.float32).contiguous(), ctx.saved)
-        return None, g_theta, (g_transl if ctx.has_transl else None)
-
-
-class _FullFunction(torch.autograd.Function):
-    """The forward of _SkinFunction with the outputs named in `differentiable` left differentiable and the full device backward.  It
-    keeps the shape state its forward ran on: a later call with other coefficients writes a new one."""
+class _Function(torch.autograd.Function):
+    """The forward, with the outputs named in `differentiable` left differentiable, and the device backward from them.  The forward's
+    saved block and the shape states it ran on belong to this node: a second forward before the backward disturbs nothing, and a
+    later call with other coefficients writes new states."""
 
     @staticmethod
     def forward(ctx, model, theta, transl, coefficients):
         vertices, joints, full_pose, saved = model._forward(theta.detach().contiguous(), None if transl is None else transl.detach().contiguous())
-        ctx.model, ctx.saved, ctx.shape_state, ctx.has_transl = model, saved, model._shape_state, transl is not None
+        ctx.model, ctx.saved, ctx.has_transl = model, saved, transl is not None
+        ctx.shape_state, ctx.shape_stride = model._shape_state, model._stride()
         dead = [t for name, t in (("joints", joints), ("full_pose", full_pose)) if name not in model.differentiable]
         if dead:
             ctx.mark_non_differentiable(*dead)
@@ -514,41 +427,13 @@ class _FullFunction(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_vertices, grad_joints, grad_full_pose):
         model = ctx.model
-        if "joints" not in model.differentiable:
-            grad_joints = None
-        if "full_pose" not in model.differentiable:
-            grad_full_pose = None
         f32 = lambda g: None if g is None else g.to(torch.float32).contiguous()
-        want_coefficients = len(ctx.needs_input_grad) > 3 and ctx.needs_input_grad[3]
-        g_theta, g_transl, g_coef = model._backward_full(f32(grad_vertices), f32(grad_joints), f32(grad_full_pose), ctx.saved, ctx.shape_state,
-                                                         want_coefficients)
+        if model.batch_size == 1 and not model.differentiable:          # the fit loop's path: the backward on the forward's workspace
+            g_theta, g_transl = model._backward(f32(grad_vertices), ctx.saved)
+            return None, g_theta, (g_transl if ctx.has_transl else None), None
+        grad_joints = f32(grad_joints) if "joints" in model.differentiable else None
+        grad_full_pose = f32(grad_full_pose) if "full_pose" in model.differentiable else None
+        g_theta, g_transl, g_coef = model._backward_full(f32(grad_vertices), grad_joints, grad_full_pose, ctx.saved, ctx.shape_state,
+                                                         ctx.needs_input_grad[3], ctx.shape_stride)
         return None, g_theta, (g_transl if ctx.has_transl else None), g_coef
 
-
-class _BatchFunction(torch.autograd.Function):
-    """batch_size > 1: the batched forward, and the batched backward from whichever outputs `differentiable` names.  The forward's
-    saved block and the shape states it ran on belong to this node: a second forward before the backward disturbs nothing."""
-
-    @staticmethod
-    def forward(ctx, model, theta, transl, shape_state, shape_stride):
-        vertices, joints, full_pose, saved = model._forward_batch(theta.detach().contiguous(), None if transl is None else transl.detach().contiguous(),
-                                                                   shape_state, shape_stride)
-        ctx.model, ctx.saved, ctx.shape_state, ctx.shape_stride, ctx.has_transl = model, saved, shape_state, shape_stride, transl is not None
-        dead = [t for name, t in (("joints", joints), ("full_pose", full_pose)) if name not in model.differentiable]
-        if dead:
-            ctx.mark_non_differentiable(*dead)
-        ctx.set_materialize_grads(False)
-        return vertices, joints, full_pose
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_vertices, grad_joints, grad_full_pose):
-        model = ctx.model
-        if "joints" not in model.differentiable:
-            grad_joints = None
-        if "full_pose" not in model.differentiable:
-            grad_full_pose = None
-        f32 = lambda g: None if g is None else g.to(torch.float32).contiguous()
-        g_theta, g_transl = model._backward_batch(f32(grad_vertices), f32(grad_joints), f32(grad_full_pose), ctx.saved, ctx.shape_state,
-                                                  ctx.shape_stride)
-        return None, g_theta, (g_transl if ctx.has_transl else None), None, None

@@ -25,10 +25,12 @@
 // P dot products, one workgroup each.  No transposed copy.  No floating-point atomics: every sum over vertices is per-workgroup
 // (fixed order inside), then one fixed-order pass over the workgroups, so two calls give the same bits.
 //
-// The BATCHED forms (coma_smplx_*_batch_f32: N bodies in the launches of one) share the arithmetic of every stage with the
-// single-body kernels as device functions, so body n of a batch has the bits of the single-body call.  What changes is how often
-// the operands move: a sweep over posedirs serves kChunk bodies (their features in LDS, one f64 sum per body in registers), a
-// skinning workgroup stages its weights tile once and walks kSkinChunk bodies over it, the pose stage runs one workgroup per body.
+// There is ONE kernel per stage and it poses N bodies: body n is found from body 0's pointers through BatchStrides, and the
+// single-body entry points are the batch of one (N = 1, the same launches with grids of one body), so body n of a batch has the
+// bits of the single-body call.  N only changes how often the operands move: a sweep over posedirs serves C bodies (their features
+// in LDS, one f64 sum per body in registers), a skinning workgroup stages its weights tile once and walks B bodies over it, the pose
+// stage runs one workgroup per body.  C and B are template arguments: kChunk and kSkinChunk, and 1 at N = 1, where the compiler then
+// gives the code of a kernel written for one body (Layout picks them and the grids that go with them).
 #include "common.h"
 #include "coma_device.h"
 
@@ -43,8 +45,7 @@ constexpr int kTile = 128;        // vertices (and threads) per skinning workgro
 constexpr int kPSplit = 8;        // splits of the P rows of posedirs in the forward
 constexpr int kMaxRows = (9 * (kMaxJ - 1) + kPSplit - 1) / kPSplit;
 constexpr int kMaxPca = 64;
-// the batched forms (coma_smplx_*_batch_f32)
-constexpr int kMaxBatch = 1024;
+constexpr int kMaxBatch = 1024;   // N: bodies per call (coma_smplx_*_batch_f32; the single-body entry points are N = 1)
 constexpr int kChunk = 8;         // C: bodies served by one sweep over posedirs (16 VGPRs of f64 sums per thread; forward LDS 71 x 8 f64)
 constexpr int kSkinChunk = 2;     // bodies one skinning workgroup walks over its staged weights tile
 
@@ -157,7 +158,23 @@ __device__ __forceinline__ void pose_chain(const double* pose, const double* __r
   }
 }
 
-struct PoseArgs {
+// How a kernel finds body n of N from body 0's pointers: the f32 arrays and the workspace blocks are dense [N, ...]; the shape
+// states and saved blocks are `shape` / `saved` bytes apart.
+struct BatchStrides {
+  int N, NT;                // bodies; entries of one body's theta
+  size_t shape, saved;      // bytes; shape = 0: one shape state for all bodies
+};
+
+template <typename T>
+__device__ __forceinline__ T* at_bytes(T* p, size_t bytes) {
+  return (T*)((char*)p + bytes);
+}
+template <typename T>
+__device__ __forceinline__ const T* at_bytes(const T* p, size_t bytes) {
+  return (const T*)((const char*)p + bytes);
+}
+
+struct PoseArgs {           // the pointers are body 0's
   const float* theta;
   const float* comps;     // [2, n_pca, hd]
   const float* mean;      // [3J] or null
@@ -172,7 +189,7 @@ struct PoseArgs {
   float* full_pose;       // [3J] or null
 };
 
-// what differs from body to body of a batch; the single-body kernel passes PoseArgs' own pointers
+// what differs from body to body
 struct PoseBody {
   const float* theta;
   const float* transl;
@@ -217,27 +234,8 @@ __device__ __forceinline__ void pose_forward(const PoseArgs& a, const PoseBody& 
   for (int q = t; q < 9 * (J - 1); q += kBlock) b.feat[q] = R[9 + q] - ((q % 9) % 4 == 0 ? 1.0 : 0.0);
 }
 
-__global__ __launch_bounds__(kBlock) void smplx_pose_kernel(PoseArgs a) {
-  pose_forward(a, PoseBody{a.theta, a.transl, a.j_rest, a.s_pose, a.s_A, a.feat, a.joints, a.full_pose});
-}
-
-// How a batched call finds body n: the f32 arrays are dense [N, ...]; the shape states and saved blocks are `stride` bytes apart.
-struct BatchStrides {
-  int N, NT;
-  size_t shape, saved;      // bytes; shape = 0: one shape state for all bodies
-};
-
-template <typename T>
-__device__ __forceinline__ T* at_bytes(T* p, size_t bytes) {
-  return (T*)((char*)p + bytes);
-}
-template <typename T>
-__device__ __forceinline__ const T* at_bytes(const T* p, size_t bytes) {
-  return (const T*)((const char*)p + bytes);
-}
-
-// one workgroup per body; PoseArgs holds body 0's pointers
-__global__ __launch_bounds__(kBlock) void smplx_pose_batch_kernel(PoseArgs a, BatchStrides st) {
+// one workgroup per body
+__global__ __launch_bounds__(kBlock) void smplx_pose_kernel(PoseArgs a, BatchStrides st) {
   const size_t n = blockIdx.x;
   const int J = a.J;
   pose_forward(a, PoseBody{a.theta + n * st.NT, a.transl ? a.transl + 3 * n : nullptr, at_bytes(a.j_rest, n * st.shape), at_bytes(a.s_pose, n * st.saved),
@@ -246,55 +244,40 @@ __global__ __launch_bounds__(kBlock) void smplx_pose_batch_kernel(PoseArgs a, Ba
 }
 
 // ---- skinning stage ----
-// partial pose offsets: part[s][i] = sum over the rows p of split s (ascending) of feat[p] posedirs[p][i]
+// Partial pose offsets: part[n][s][i] = sum over the rows p of split s (ascending) of feat[n][p] posedirs[p][i].  Grid (column blocks,
+// kPSplit, chunks of C bodies).  The chunk's features of this split sit in LDS as [row][body]; every posedirs element is loaded once
+// and used for all bodies of the chunk, each body's sum in a register of its own.  With P = 0 (J = 1) it writes zeros.  C = 1 is the
+// instantiation for one body: no f64 work for absent bodies.
+template <int C>
 __global__ __launch_bounds__(kBlock) void smplx_offsets_kernel(const float* __restrict__ posedirs, const double* __restrict__ feat, int P, int n3,
-                                                              int rows, double* __restrict__ part) {
-  __shared__ double f[kMaxRows];
-  const int s = blockIdx.y;
+                                                              int rows, int N, double* __restrict__ part) {
+  __shared__ double f[kMaxRows * C];
+  const int s = blockIdx.y, n0 = blockIdx.z * C, nc = min(C, N - n0);
   const int p0 = s * rows, p1 = min(P, p0 + rows);
-  for (int p = p0 + threadIdx.x; p < p1; p += kBlock) f[p - p0] = feat[p];
-  __syncthreads();
-  const int i = blockIdx.x * kBlock + threadIdx.x;
-  if (i >= n3) return;
-  double acc = 0.0;
-  const float* col = posedirs + i;
-#pragma unroll 8
-  for (int p = p0; p < p1; ++p) acc = acc + f[p - p0] * (double)col[(int64_t)p * n3];
-  part[(int64_t)s * n3 + i] = acc;
-}
-
-// The batched form: grid (column blocks, kPSplit, chunks of kChunk bodies).  The chunk's features of this split sit in LDS as
-// [row][body]; every posedirs element is loaded once and used for all bodies of the chunk, each body's sum in a register of its own
-// and in the single-body kernel's order.  part is [N][kPSplit][3V].  With P = 0 it writes the zeros the single-body call memsets.
-__global__ __launch_bounds__(kBlock) void smplx_offsets_batch_kernel(const float* __restrict__ posedirs, const double* __restrict__ feat, int P,
-                                                                    int n3, int rows, int N, double* __restrict__ part) {
-  __shared__ double f[kMaxRows * kChunk];
-  const int s = blockIdx.y, n0 = blockIdx.z * kChunk, nc = min(kChunk, N - n0);
-  const int p0 = s * rows, p1 = min(P, p0 + rows);
-  for (int q = threadIdx.x; q < (p1 - p0) * kChunk; q += kBlock) {
-    const int r = q / kChunk, c = q % kChunk;
-    f[q] = c < nc ? feat[(int64_t)(n0 + c) * P + p0 + r] : 0.0;
+  for (int q = threadIdx.x; q < (p1 - p0) * C; q += kBlock) {
+    const int r = q / C, c = q % C;
+    f[q] = (C == 1 || c < nc) ? feat[(int64_t)(n0 + c) * P + p0 + r] : 0.0;
   }
   __syncthreads();
   const int i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= n3) return;
-  double acc[kChunk];
+  double acc[C];
 #pragma unroll
-  for (int c = 0; c < kChunk; ++c) acc[c] = 0.0;
+  for (int c = 0; c < C; ++c) acc[c] = 0.0;
   const float* col = posedirs + i;
-#pragma unroll 4
+#pragma unroll C == 1 ? 8 : 4
   for (int p = p0; p < p1; ++p) {
     const double x = (double)col[(int64_t)p * n3];
-    const double* fp = f + (p - p0) * kChunk;
+    const double* fp = f + (p - p0) * C;
 #pragma unroll
-    for (int c = 0; c < kChunk; ++c) acc[c] = acc[c] + fp[c] * x;
+    for (int c = 0; c < C; ++c) acc[c] = acc[c] + fp[c] * x;
   }
 #pragma unroll
-  for (int c = 0; c < kChunk; ++c)
-    if (c < nc) part[((int64_t)(n0 + c) * kPSplit + s) * n3 + i] = acc[c];
+  for (int c = 0; c < C; ++c)
+    if (C == 1 || c < nc) part[((int64_t)(n0 + c) * kPSplit + s) * n3 + i] = acc[c];
 }
 
-struct SkinArgs {
+struct SkinArgs {           // the pointers are body 0's
   const float* weights;     // [V,J]
   const double* A;          // [J,12]
   const double* v_shaped;   // [V,3]
@@ -305,14 +288,20 @@ struct SkinArgs {
   float* vertices;          // [V,3]
 };
 
-// the weights of a tile of vertices (one contiguous run of the [V,J] table) and the J transforms into LDS
-__device__ __forceinline__ int stage_tile(const float* __restrict__ weights, const double* __restrict__ A, int V, int J, float* Wt, double* Al) {
+// the weights of this workgroup's tile of vertices (one contiguous run of the [V,J] table) into LDS (no barrier: the first stage_A
+// gives it) -> the vertices in the tile
+__device__ __forceinline__ int stage_weights(const float* __restrict__ weights, int V, int J, float* Wt) {
   const int v0 = blockIdx.x * kTile, n = min(kTile, V - v0);
   const float* src = weights + (int64_t)v0 * J;
   for (int q = threadIdx.x; q < n * J; q += kTile) Wt[q] = src[q];
+  return n;
+}
+
+// the next body's transforms into LDS, once every thread is done with the previous body's (the chunk's first body has none before it)
+__device__ __forceinline__ void stage_A(const double* __restrict__ A, int J, double* Al, bool first) {
+  if (!first) __syncthreads();
   for (int q = threadIdx.x; q < 12 * J; q += kTile) Al[q] = A[q];
   __syncthreads();
-  return n;
 }
 
 __device__ __forceinline__ void blend(const float* w, const double* Al, int J, double* T) {
@@ -347,40 +336,20 @@ __device__ __forceinline__ void skin_vertex(const float* Wt, const double* Al, i
   }
 }
 
-__global__ __launch_bounds__(kTile) void smplx_skin_kernel(SkinArgs a) {
-  __shared__ float Wt[kTile * kMaxJ];
-  __shared__ double Al[12 * kMaxJ];
-  const int n = stage_tile(a.weights, a.A, a.V, a.J, Wt, Al);
-  const int t = threadIdx.x;
-  if (t >= n) return;
-  skin_vertex(Wt, Al, a.V, a.J, (int64_t)blockIdx.x * kTile + t, t, a.part, a.v_shaped, a.transl, a.v_posed, a.vertices);
-}
-
-// the weights of this workgroup's tile of vertices into LDS (no barrier: the first stage_A gives it) -> the vertices in the tile
-__device__ __forceinline__ int stage_weights(const float* __restrict__ weights, int V, int J, float* Wt) {
-  const int v0 = blockIdx.x * kTile, n = min(kTile, V - v0);
-  const float* src = weights + (int64_t)v0 * J;
-  for (int q = threadIdx.x; q < n * J; q += kTile) Wt[q] = src[q];
-  return n;
-}
-
-// the next body's transforms into LDS, once every thread is done with the previous body's
-__device__ __forceinline__ void stage_A(const double* __restrict__ A, int J, double* Al) {
-  __syncthreads();
-  for (int q = threadIdx.x; q < 12 * J; q += kTile) Al[q] = A[q];
-  __syncthreads();
-}
-
-// The batched form: grid (tiles, chunks of kSkinChunk bodies); SkinArgs holds body 0's pointers, part is [N][kPSplit][3V].  The
-// weights tile is staged once and the chunk's bodies walk over it.
-__global__ __launch_bounds__(kTile) void smplx_skin_batch_kernel(SkinArgs a, BatchStrides st) {
+// Grid (tiles, chunks of B bodies); part is [N][kPSplit][3V].  The weights tile is staged once and the chunk's bodies walk over it.
+// B = 1 is the instantiation for one body: no body loop, so the compiler gives it the code of a kernel written for one body.
+template <int B>
+__global__ __launch_bounds__(kTile) void smplx_skin_kernel(SkinArgs a, BatchStrides st) {
   __shared__ float Wt[kTile * kMaxJ];
   __shared__ double Al[12 * kMaxJ];
   const int n = stage_weights(a.weights, a.V, a.J, Wt);
-  const int t = threadIdx.x, b0 = blockIdx.y * kSkinChunk, b1 = min(st.N, b0 + kSkinChunk);
-  const size_t n3 = 3 * (size_t)a.V;
-  for (size_t b = b0; b < (size_t)b1; ++b) {
-    stage_A(at_bytes(a.A, b * st.saved), a.J, Al);
+  const int t = threadIdx.x;
+  const size_t n3 = 3 * (size_t)a.V, b0 = (size_t)blockIdx.y * B;
+#pragma unroll 1
+  for (int i = 0; i < B; ++i) {
+    const size_t b = b0 + i;
+    if (B > 1 && b >= (size_t)st.N) break;
+    stage_A(at_bytes(a.A, b * st.saved), a.J, Al, i == 0);
     if (t < n)
       skin_vertex(Wt, Al, a.V, a.J, (int64_t)blockIdx.x * kTile + t, t, a.part + b * kPSplit * n3, at_bytes(a.v_shaped, b * st.shape),
                   a.transl ? a.transl + 3 * b : nullptr, at_bytes(a.v_posed, b * st.saved), a.vertices + b * n3);
@@ -406,9 +375,9 @@ __device__ __forceinline__ void skin_bwd_tile(const float* Wt, const double* Al,
   const int t = threadIdx.x;
   if (t < n) {
     const int64_t v = (int64_t)blockIdx.x * kTile + t;
-    const double g[3] = {load(grad, 3 * v), load(grad, 3 * v + 1), load(grad, 3 * v + 2)};
     double T[12];
     blend(Wt + t * J, Al, J, T);
+    const double g[3] = {load(grad, 3 * v), load(grad, 3 * v + 1), load(grad, 3 * v + 2)};     // after the blend: not live across its loop
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       gvp[3 * v + c] = (T[c] * g[0] + T[4 + c] * g[1]) + T[8 + c] * g[2];
@@ -424,79 +393,63 @@ __device__ __forceinline__ void skin_bwd_tile(const float* Wt, const double* Al,
     double acc = 0.0;
     if (q < 12 * J) {
       const int j = q / 12, r = (q % 12) / 4, c = q % 4;
+#pragma unroll 8                                            // asked for: inside the body loop the compiler no longer unrolls these on its own
       for (int u = 0; u < n; ++u) acc = acc + ((double)Wt[u * J + j] * gl[3 * u + r]) * vl[4 * u + c];
     } else {
       const int r = q - 12 * J;
+#pragma unroll 8
       for (int u = 0; u < n; ++u) acc = acc + gl[3 * u + r];
     }
     out[q] = acc;
   }
 }
 
-template <typename TG>
-__global__ __launch_bounds__(kTile) void smplx_skin_bwd_kernel(SkinBwdArgs<TG> a) {
-  __shared__ float Wt[kTile * kMaxJ];
-  __shared__ double Al[12 * kMaxJ];
-  __shared__ double gl[3 * kTile], vl[4 * kTile];
-  const int n = stage_tile(a.weights, a.A, a.V, a.J, Wt, Al);
-  skin_bwd_tile(Wt, Al, gl, vl, n, a.J, a.grad, a.v_posed, a.gvp, a.dA_part);
-}
-
-// The batched form: grid (tiles, chunks of kSkinChunk bodies); the args hold body 0's pointers, grad and gvp are [N][3V], dA_part is
-// [N][tiles][12 J + 3].  stage_A's first barrier also keeps a body's gl / vl until every thread has summed over them.
-template <typename TG>
-__global__ __launch_bounds__(kTile) void smplx_skin_bwd_batch_kernel(SkinBwdArgs<TG> a, BatchStrides st) {
+// Grid (tiles, chunks of B bodies); grad and gvp are [N][3V], dA_part is [N][tiles][12 J + 3].  stage_A's barrier between two bodies
+// also keeps the first one's gl / vl until every thread has summed over them.  B = 1 as in smplx_skin_kernel.
+template <typename TG, int B>
+__global__ __launch_bounds__(kTile) void smplx_skin_bwd_kernel(SkinBwdArgs<TG> a, BatchStrides st) {
   __shared__ float Wt[kTile * kMaxJ];
   __shared__ double Al[12 * kMaxJ];
   __shared__ double gl[3 * kTile], vl[4 * kTile];
   const int n = stage_weights(a.weights, a.V, a.J, Wt);
-  const int b0 = blockIdx.y * kSkinChunk, b1 = min(st.N, b0 + kSkinChunk);
-  const size_t n3 = 3 * (size_t)a.V, per_body = (size_t)gridDim.x * (12 * a.J + 3);
-  for (size_t b = b0; b < (size_t)b1; ++b) {
-    stage_A(at_bytes(a.A, b * st.saved), a.J, Al);
+  const size_t n3 = 3 * (size_t)a.V, per_body = (size_t)gridDim.x * (12 * a.J + 3), b0 = (size_t)blockIdx.y * B;
+#pragma unroll 1
+  for (int i = 0; i < B; ++i) {
+    const size_t b = b0 + i;
+    if (B > 1 && b >= (size_t)st.N) break;
+    stage_A(at_bytes(a.A, b * st.saved), a.J, Al, i == 0);
     skin_bwd_tile(Wt, Al, gl, vl, n, a.J, a.grad + b * n3, at_bytes(a.v_posed, b * st.saved), a.gvp + b * n3, a.dA_part + b * per_body);
   }
 }
 
-// dL/dfeature_p = <posedirs[p, :], gvp>: one workgroup per row
+// dL/dfeature_p of body n = <posedirs[p, :], gvp[n]>.  Grid (P rows, chunks of C bodies); one read of the row serves the chunk's dot
+// products, each with 256 strided partial sums and the tree.  gvp is [N][3V], dfeat [N][P].  C = 1 is the instantiation for one body.
+template <int C>
 __global__ __launch_bounds__(kBlock) void smplx_feature_bwd_kernel(const float* __restrict__ posedirs, const double* __restrict__ gvp, int n3,
-                                                                  double* __restrict__ dfeat) {
+                                                                  int P, int N, double* __restrict__ dfeat) {
   __shared__ double lds[kBlock];
-  const float* row = posedirs + (int64_t)blockIdx.x * n3;
-  double acc = 0.0;
-#pragma unroll 4
-  for (int i = threadIdx.x; i < n3; i += kBlock) acc = acc + (double)row[i] * gvp[i];
-  const double s = block_sum<kBlock>(acc, lds);
-  if (threadIdx.x == 0) dfeat[blockIdx.x] = s;
-}
-
-// The batched form: grid (P rows, chunks of kChunk bodies); one read of the row serves the chunk's dot products, each with the
-// single-body kernel's 256 strided partial sums and tree.  gvp is [N][3V], dfeat [N][P].
-__global__ __launch_bounds__(kBlock) void smplx_feature_bwd_batch_kernel(const float* __restrict__ posedirs, const double* __restrict__ gvp, int n3,
-                                                                        int P, int N, double* __restrict__ dfeat) {
-  __shared__ double lds[kBlock];
-  const int n0 = blockIdx.y * kChunk, nc = min(kChunk, N - n0);
+  const int n0 = blockIdx.y * C, nc = min(C, N - n0);
   const float* row = posedirs + (int64_t)blockIdx.x * n3;
   const double* g0 = gvp + (int64_t)n0 * n3;
-  double acc[kChunk];
+  double acc[C];
 #pragma unroll
-  for (int c = 0; c < kChunk; ++c) acc[c] = 0.0;
-#pragma unroll 2
+  for (int c = 0; c < C; ++c) acc[c] = 0.0;
+#pragma unroll C == 1 ? 4 : 2
   for (int i = threadIdx.x; i < n3; i += kBlock) {
     const double x = (double)row[i];
 #pragma unroll
-    for (int c = 0; c < kChunk; ++c)
-      if (c < nc) acc[c] = acc[c] + x * g0[(int64_t)c * n3 + i];
+    for (int c = 0; c < C; ++c)
+      if (C == 1 || c < nc) acc[c] = acc[c] + x * g0[(int64_t)c * n3 + i];
   }
 #pragma unroll
-  for (int c = 0; c < kChunk; ++c)
-    if (c < nc) {                                           // nc is the workgroup's: every thread reaches the same barriers
+  for (int c = 0; c < C; ++c)
+    if (C == 1 || c < nc) {                                 // nc is the workgroup's: every thread reaches the same barriers
       const double s = block_sum<kBlock>(acc[c], lds);
       if (threadIdx.x == 0) dfeat[(int64_t)(n0 + c) * P + blockIdx.x] = s;
     }
 }
 
-struct PoseBwdArgs {
+struct PoseBwdArgs {        // the pointers are body 0's
   const double* s_pose;
   const double* j_rest;
   const float* comps;
@@ -514,7 +467,7 @@ struct PoseBwdArgs {
   double* dJ_out;           // dL/dJ_rest [J,3]
 };
 
-// what differs from body to body of a batch; the single-body kernel passes PoseBwdArgs' own pointers
+// what differs from body to body
 struct PoseBwdBody {
   const double* s_pose;
   const double* j_rest;
@@ -623,24 +576,27 @@ __device__ __forceinline__ void pose_backward(const PoseBwdArgs& a, const PoseBw
   }
 }
 
-__global__ __launch_bounds__(kBlock) void smplx_pose_bwd_kernel(PoseBwdArgs a) {
-  pose_backward(a, PoseBwdBody{a.s_pose, a.j_rest, a.dA_part, a.dfeat, a.grad_theta, a.grad_transl, a.gJ, a.gP, a.dJ_out});
-}
-
-// one workgroup per body; PoseBwdArgs holds body 0's pointers, gJ is [N][J + E, 3]; no gradient to the rest joints
-__global__ __launch_bounds__(kBlock) void smplx_pose_bwd_batch_kernel(PoseBwdArgs a, BatchStrides st) {
+// one workgroup per body; gJ is [N][J + E, 3]; the gradient to the rest joints is collected for a single body only
+__global__ __launch_bounds__(kBlock) void smplx_pose_bwd_kernel(PoseBwdArgs a, BatchStrides st) {
   const size_t n = blockIdx.x;
   const int J = a.J;
   pose_backward(a, PoseBwdBody{at_bytes(a.s_pose, n * st.saved), at_bytes(a.j_rest, n * st.shape), a.dA_part + n * a.nblk * (size_t)(12 * J + 3),
                                a.dfeat + n * (size_t)(9 * (J - 1)), a.grad_theta + n * st.NT, a.grad_transl + 3 * n,
-                               a.gJ ? a.gJ + n * (size_t)(3 * (J + a.E)) : nullptr, a.gP ? a.gP + n * (size_t)(3 * J) : nullptr, nullptr});
+                               a.gJ ? a.gJ + n * (size_t)(3 * (J + a.E)) : nullptr, a.gP ? a.gP + n * (size_t)(3 * J) : nullptr,
+                               st.N == 1 ? a.dJ_out : nullptr});
 }
 
 // ---- extra joints ----
-__device__ __forceinline__ void gather_extra(const float* __restrict__ vertices, const float* __restrict__ transl, const int32_t* __restrict__ idx,
-                                             const float* __restrict__ w, int V, int E, float* __restrict__ out) {
+// grid (blocks of 3E, N): vertices [N][V,3], transl [N][3] or null, out [N][E,3]; one table for all bodies
+__global__ __launch_bounds__(kBlock) void smplx_gather_kernel(const float* __restrict__ vertices, const float* __restrict__ transl,
+                                                             const int32_t* __restrict__ idx, const float* __restrict__ w, int V, int E,
+                                                             float* __restrict__ out) {
   const int q = blockIdx.x * kBlock + threadIdx.x;
   if (q >= 3 * E) return;
+  const size_t n = blockIdx.y;
+  vertices += n * 3 * (size_t)V;
+  out += n * 3 * (size_t)E;
+  if (transl) transl += 3 * n;
   const int e = q / 3, c = q % 3;
   const double tr = transl ? (double)transl[c] : 0.0;
   double acc = 0.0;
@@ -652,20 +608,6 @@ __device__ __forceinline__ void gather_extra(const float* __restrict__ vertices,
   out[q] = (float)(acc + tr);
 }
 
-__global__ __launch_bounds__(kBlock) void smplx_gather_kernel(const float* __restrict__ vertices, const float* __restrict__ transl,
-                                                             const int32_t* __restrict__ idx, const float* __restrict__ w, int V, int E,
-                                                             float* __restrict__ out) {
-  gather_extra(vertices, transl, idx, w, V, E, out);
-}
-
-// grid (blocks of 3E, N): vertices [N][V,3], transl [N][3] or null, out [N][E,3]; one table for all bodies
-__global__ __launch_bounds__(kBlock) void smplx_gather_batch_kernel(const float* __restrict__ vertices, const float* __restrict__ transl,
-                                                                   const int32_t* __restrict__ idx, const float* __restrict__ w, int V, int E,
-                                                                   float* __restrict__ out) {
-  const size_t n = blockIdx.y;
-  gather_extra(vertices + n * 3 * (size_t)V, transl ? transl + 3 * n : nullptr, idx, w, V, E, out + n * 3 * (size_t)E);
-}
-
 // ---- the full backward's own passes ----
 constexpr int kMaxE = 4096;       // extra joints whose gradient is scattered back
 constexpr int kEffChunk = 768;    // table entries in LDS per pass
@@ -673,10 +615,17 @@ constexpr int kEffChunk = 768;    // table entries in LDS per pass
 // The effective vertex gradient: g_eff[v] = g[v] (zeros without g) + the sum over the table entries (e, i) with index v, in ascending
 // (e, i), of w[e,i] gJ_extra[e].  Written as a gather -- every vertex scans the whole table from LDS -- so repeated indices (a vertex
 // pick is (i, i, i), landmark faces share vertices) add in the table's order without atomics; an index outside [0, V) matches nothing.
-__device__ __forceinline__ void effective_grad(const float* __restrict__ g, const float* __restrict__ gJ_extra, const int32_t* __restrict__ idx,
-                                               const float* __restrict__ w, int V, int E, double* __restrict__ g_eff) {
+// Grid (blocks of V, N): g [N][V,3] or null, g_eff [N][V,3]; gJ_extra is body 0's first extra-joint row of dL/djoints (or null), body
+// n's is gJ_stride = 3 (J + E) floats on.
+__global__ __launch_bounds__(kBlock) void smplx_effective_grad_kernel(const float* __restrict__ g, const float* __restrict__ gJ_extra,
+                                                                     size_t gJ_stride, const int32_t* __restrict__ idx,
+                                                                     const float* __restrict__ w, int V, int E, double* __restrict__ g_eff) {
   __shared__ int32_t li[kEffChunk];
   __shared__ double lw[3 * kEffChunk];
+  const size_t n = blockIdx.y;
+  if (g) g += n * 3 * (size_t)V;
+  if (gJ_extra) gJ_extra += n * gJ_stride;
+  g_eff += n * 3 * (size_t)V;
   const int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   D3 acc = {0.0, 0.0, 0.0};
   if (g && v < V) acc = load3(g, v);
@@ -695,20 +644,6 @@ __device__ __forceinline__ void effective_grad(const float* __restrict__ g, cons
         if (li[q] == (int32_t)v) acc = acc + D3{lw[3 * q], lw[3 * q + 1], lw[3 * q + 2]};
   }
   if (v < V) { g_eff[3 * v] = acc.x; g_eff[3 * v + 1] = acc.y; g_eff[3 * v + 2] = acc.z; }
-}
-
-__global__ __launch_bounds__(kBlock) void smplx_effective_grad_kernel(const float* __restrict__ g, const float* __restrict__ gJ_extra,
-                                                                     const int32_t* __restrict__ idx, const float* __restrict__ w, int V, int E,
-                                                                     double* __restrict__ g_eff) {
-  effective_grad(g, gJ_extra, idx, w, V, E, g_eff);
-}
-
-// grid (blocks of V, N): g [N][V,3] or null, gJ [N][J + E, 3] or null (the extra joints' rows are read), g_eff [N][V,3]
-__global__ __launch_bounds__(kBlock) void smplx_effective_grad_batch_kernel(const float* __restrict__ g, const float* __restrict__ gJ, int J,
-                                                                           const int32_t* __restrict__ idx, const float* __restrict__ w, int V,
-                                                                           int E, int E_all, double* __restrict__ g_eff) {
-  const size_t n = blockIdx.y, n3 = 3 * (size_t)V;
-  effective_grad(g ? g + n * n3 : nullptr, gJ ? gJ + n * 3 * (size_t)(J + E_all) + 3 * (size_t)J : nullptr, idx, w, V, E, g_eff + n * n3);
 }
 
 // kBlock rows i = 3 v + c of the [3V] axis per workgroup.  dL/dv_shaped[i] = gvp[i] + sum_j J_regressor[j, v] dJ[j][c] (j ascending)
@@ -751,63 +686,64 @@ __global__ __launch_bounds__(kBlock) void smplx_coef_sum_kernel(const double* __
   out[l] = (float)acc;
 }
 
+// ---- the host half ----
+constexpr int kMaxV = 1 << 24;
+constexpr int kMaxNB = 1024;
+
+// Every buffer of N bodies.  The forward workspace is feat [N][P], part [N][kPSplit][3V]; the backward workspace is gvp [N][3V],
+// dA_part [N][tiles][12 J + 3], dfeat [N][P], g_eff [N][3V] (the batched backward's ends here), then dJ and coef_part of the full
+// backward.  The single-body forward and vertices-only backward share ONE workspace: the forward blocks, then the backward blocks up
+// to dfeat, which therefore sit `fwd_total` further on.  Body n's saved block is the single-body one at n x saved_stride.
 struct Layout {
-  size_t feat, part, gvp, dA_part, dfeat, total;      // workspace
-  size_t v_shaped, j_rest, shape_total;               // shape state
-  size_t s_pose, s_A, s_vposed, saved_total;          // saved by a forward for its backward
+  size_t feat, part, fwd_total;                                                   // forward workspace
+  size_t gvp, dA_part, dfeat, g_eff, dJ, coef_part, grad_total;                   // backward workspace
+  size_t v_shaped, j_rest, shape_total;                                           // shape state
+  size_t s_pose, s_A, s_vposed, saved_stride;                                     // saved by a forward for its backward
   int P, rows, nblk, nb3;
+  int C, chunks, B, skin_chunks;                  // bodies per sweep over posedirs and per skinning workgroup (the instantiation), and their chunks
+  size_t batch_grad_total() const { return dJ; }
+  size_t single_total() const { return fwd_total + g_eff; }
 };
 
-Layout layout(int V, int J) {
+Layout layout(int V, int J, int N = 1, int NB = 0) {
   Layout L = {};
-  const size_t n3 = (size_t)3 * V, d = sizeof(double);
+  const size_t n3 = (size_t)3 * V, d = sizeof(double), n = (size_t)N;
   L.P = 9 * (J - 1);
   L.rows = (L.P + kPSplit - 1) / kPSplit;
   L.nblk = (V + kTile - 1) / kTile;
   L.nb3 = (int)((n3 + kBlock - 1) / kBlock);
-  Carve ws, shape, saved;
-  L.feat = ws.take((size_t)(L.P > 0 ? L.P : 1) * d);
-  L.part = ws.take((size_t)kPSplit * n3 * d);
-  L.gvp = ws.take(n3 * d);
-  L.dA_part = ws.take((size_t)L.nblk * (12 * J + 3) * d);
-  L.dfeat = ws.take((size_t)(L.P > 0 ? L.P : 1) * d);
-  L.total = ws.at;
+  L.C = N == 1 ? 1 : kChunk;          // one body: the instantiations that do no work for absent bodies
+  L.B = N == 1 ? 1 : kSkinChunk;
+  L.chunks = (N + L.C - 1) / L.C;
+  L.skin_chunks = (N + L.B - 1) / L.B;
+  const size_t P = (size_t)(L.P > 0 ? L.P : 1);
+  Carve fwd, bwd, shape, saved;
+  L.feat = fwd.take(n * P * d);
+  L.part = fwd.take(n * kPSplit * n3 * d);
+  L.fwd_total = fwd.at;
+  L.gvp = bwd.take(n * n3 * d);
+  L.dA_part = bwd.take(n * L.nblk * (12 * J + 3) * d);
+  L.dfeat = bwd.take(n * P * d);
+  L.g_eff = bwd.take(n * n3 * d);
+  L.dJ = bwd.take((size_t)3 * J * d);
+  L.coef_part = bwd.take((size_t)L.nb3 * (NB > 0 ? NB : 1) * d);
+  L.grad_total = bwd.at;
   L.v_shaped = shape.take(n3 * d);
   L.j_rest = shape.take((size_t)3 * J * d);
   L.shape_total = shape.at;
   L.s_pose = saved.take((size_t)3 * J * d);
   L.s_A = saved.take((size_t)12 * J * d);
   L.s_vposed = saved.take(n3 * d);
-  L.saved_total = saved.at;
+  L.saved_stride = saved.at;
   return L;
 }
 
-constexpr int kMaxV = 1 << 24;
-constexpr int kMaxNB = 1024;
+bool sizes_ok(int V, int J, int N = 1) { return V >= 1 && V <= kMaxV && J >= 1 && J <= kMaxJ && N >= 1 && N <= kMaxBatch; }
 
-bool sizes_ok(int V, int J) { return V >= 1 && V <= kMaxV && J >= 1 && J <= kMaxJ; }
-
-// the full backward's workspace: what the backward needs of the one above (at offsets of its own), then its additions
-struct GradLayout {
-  size_t gvp, dA_part, dfeat, g_eff, dJ, coef_part, total;
-};
-
-GradLayout grad_layout(int V, int J, int NB) {
-  const Layout L = layout(V, J);
-  GradLayout G = {};
-  const size_t n3 = (size_t)3 * V, d = sizeof(double);
-  Carve ws;
-  G.gvp = ws.take(n3 * d);
-  G.dA_part = ws.take((size_t)L.nblk * (12 * J + 3) * d);
-  G.dfeat = ws.take((size_t)(L.P > 0 ? L.P : 1) * d);
-  G.g_eff = ws.take(n3 * d);
-  G.dJ = ws.take((size_t)3 * J * d);
-  G.coef_part = ws.take((size_t)L.nb3 * (NB > 0 ? NB : 1) * d);
-  G.total = ws.at;
-  return G;
-}
-
-int check_common(const char* who, int V, int J, int hand_dim, int n_pca, const int32_t* parents, Tree& tree) {
+// what every forward and backward refuses after its null pointers; fills the tree and builds the call's layout (NB is only carved
+// with, its own refusal comes later)
+int check_common(const char* who, int V, int J, int hand_dim, int n_pca, const int32_t* parents, Tree& tree, int N, int NB,
+                 const void* shape_state, size_t shape_stride, Layout& L) {
   if (!sizes_ok(V, J)) return fail(COMA_E_INVALID, "%s: V=%d must lie in [1, %d] and J=%d in [1, %d]", who, V, kMaxV, J, kMaxJ);
   if (n_pca < 0 || n_pca > kMaxPca) return fail(COMA_E_INVALID, "%s: n_pca=%d outside [0, %d]", who, n_pca, kMaxPca);
   if (hand_dim < 0 || hand_dim % 3 != 0 || 2 * hand_dim > 3 * (J - 1))
@@ -817,7 +753,145 @@ int check_common(const char* who, int V, int J, int hand_dim, int n_pca, const i
     if (parents[i] < 0 || parents[i] >= i) return fail(COMA_E_INVALID, "%s: parent %d of joint %d outside [0, %d)", who, parents[i], i, i);
     tree.parent[i] = parents[i];
   }
+  if (N < 1 || N > kMaxBatch) return fail(COMA_E_INVALID, "%s: N=%d outside [1, %d]", who, N, kMaxBatch);
+  L = layout(V, J, N, NB);
+  if (shape_stride != 0 && (shape_stride < L.shape_total || (shape_stride & 15) != 0))
+    return fail(COMA_E_INVALID, "%s: shape_stride=%zu must be 0 (one shape state for all bodies) or a multiple of 16 of at least %zu", who,
+                shape_stride, L.shape_total);
+  if (((uintptr_t)shape_state & 15) != 0) return fail(COMA_E_INVALID, "%s: shape state must be 16-byte aligned", who);
   return COMA_OK;
+}
+
+// Both forward entry points.  `batched` only says which workspace the ABI gives the call: the single-body one also holds the
+// vertices-only backward's blocks.
+int forward_impl(const char* who, bool batched, int N, size_t shape_stride, const float* theta, const float* transl, const float* posedirs,
+                 const float* weights, const int32_t* parents, const float* hand_components, const float* pose_mean, int V, int J, int hand_dim,
+                 int n_pca, const void* shape_state, float* vertices, float* joints, float* full_pose, void* saved, size_t saved_bytes,
+                 void* workspace, size_t workspace_bytes, void* stream) {
+  if (!theta || !posedirs || !weights || !parents || !shape_state || !vertices || !joints || !saved || !workspace)
+    return fail(COMA_E_INVALID, "%s: null pointer", who);
+  if (n_pca > 0 && hand_dim > 0 && !hand_components) return fail(COMA_E_INVALID, "%s: null pointer (hand_components with n_pca > 0)", who);
+  PoseArgs pa = {};
+  Layout L;
+  if (int rc = check_common(who, V, J, hand_dim, n_pca, parents, pa.tree, N, 0, shape_state, shape_stride, L)) return rc;
+  if (int rc = check_buffer(who, "saved state", saved, saved_bytes, N * L.saved_stride)) return rc;
+  if (int rc = check_buffer(who, "workspace", workspace, workspace_bytes, batched ? L.fwd_total : L.single_total())) return rc;
+  const char* st = (const char*)shape_state;
+  char* sv = (char*)saved;
+  char* ws = (char*)workspace;
+  hipStream_t s = (hipStream_t)stream;
+  const BatchStrides bs = {N, n_pca > 0 ? 3 * J - 2 * hand_dim + 2 * n_pca : 3 * J, shape_stride, L.saved_stride};
+  pa.theta = theta; pa.comps = hand_components; pa.mean = pose_mean; pa.transl = transl; pa.j_rest = (const double*)(st + L.j_rest);
+  pa.J = J; pa.hd = hand_dim; pa.n_pca = n_pca; pa.s_pose = (double*)(sv + L.s_pose); pa.s_A = (double*)(sv + L.s_A);
+  pa.feat = (double*)(ws + L.feat); pa.joints = joints; pa.full_pose = full_pose;
+  hipLaunchKernelGGL(smplx_pose_kernel, dim3(N), dim3(kBlock), 0, s, pa, bs);
+  const auto offsets = L.C == 1 ? smplx_offsets_kernel<1> : smplx_offsets_kernel<kChunk>;       // one body: no sums for absent ones
+  hipLaunchKernelGGL(offsets, dim3(L.nb3, kPSplit, L.chunks), dim3(kBlock), 0, s, posedirs, (const double*)(ws + L.feat), L.P, 3 * V, L.rows, N,
+                     (double*)(ws + L.part));
+  SkinArgs sa = {};
+  sa.weights = weights; sa.A = pa.s_A; sa.v_shaped = (const double*)(st + L.v_shaped); sa.part = (const double*)(ws + L.part); sa.transl = transl;
+  sa.V = V; sa.J = J; sa.v_posed = (double*)(sv + L.s_vposed); sa.vertices = vertices;
+  const auto skin = L.B == 1 ? smplx_skin_kernel<1> : smplx_skin_kernel<kSkinChunk>;
+  hipLaunchKernelGGL(skin, dim3(L.nblk, L.skin_chunks), dim3(kTile), 0, s, sa, bs);
+  return check_launch(who);
+}
+
+// what the full and the batched backward take besides dL/dvertices; every pointer may be null
+struct FullBwd {
+  const float* grad_joints;
+  const float* grad_full_pose;
+  const int32_t* extra_index;
+  const float* extra_weight;
+  int E;
+  // the gradient to the coefficients, which the batched ABI does not have
+  const float* shapedirs;
+  const float* J_regressor;
+  int NB;
+  float* grad_coefficients;
+};
+
+template <typename TG>
+void launch_skin_bwd(const Layout& L, const BatchStrides& bs, const float* weights, const char* sv, const TG* grad, int V, int J, double* gvp,
+                     double* dA_part, hipStream_t s) {
+  SkinBwdArgs<TG> sb = {};
+  sb.weights = weights; sb.A = (const double*)(sv + L.s_A); sb.v_posed = (const double*)(sv + L.s_vposed); sb.grad = grad;
+  sb.V = V; sb.J = J; sb.gvp = gvp; sb.dA_part = dA_part;
+  const auto skin_bwd = L.B == 1 ? smplx_skin_bwd_kernel<TG, 1> : smplx_skin_bwd_kernel<TG, kSkinChunk>;
+  hipLaunchKernelGGL(skin_bwd, dim3(L.nblk, L.skin_chunks), dim3(kTile), 0, s, sb, bs);
+}
+
+// All three backward entry points.  `full` null is the vertices-only backward on the single-body workspace (its blocks behind the
+// forward's); otherwise the backward workspace from its start, up to g_eff for the batched ABI and whole for the full backward.
+int backward_impl(const char* who, bool batched, int N, size_t shape_stride, const float* grad_vertices, const float* posedirs,
+                  const float* weights, const int32_t* parents, const float* hand_components, int V, int J, int hand_dim, int n_pca,
+                  const void* shape_state, const void* saved, size_t saved_bytes, float* grad_theta, float* grad_transl, void* workspace,
+                  size_t workspace_bytes, void* stream, const FullBwd* full) {
+  if ((!full && !grad_vertices) || !posedirs || !weights || !parents || !shape_state || !saved || !grad_theta || !grad_transl || !workspace)
+    return fail(COMA_E_INVALID, "%s: null pointer", who);
+  if (n_pca > 0 && hand_dim > 0 && !hand_components) return fail(COMA_E_INVALID, "%s: null pointer (hand_components with n_pca > 0)", who);
+  PoseBwdArgs pb = {};
+  Layout L;
+  if (int rc = check_common(who, V, J, hand_dim, n_pca, parents, pb.tree, N, full ? full->NB : 0, shape_state, shape_stride, L)) return rc;
+  bool scatter = false, want_coef = false;
+  if (full) {
+    if (full->E < 0 || full->E > kMaxE) return fail(COMA_E_INVALID, "%s: E=%d outside [0, %d]", who, full->E, kMaxE);
+    scatter = full->grad_joints && full->E > 0;
+    if (scatter && (!full->extra_index || !full->extra_weight))
+      return fail(COMA_E_INVALID, "%s: null pointer (the extra-joint tables with grad_joints and E > 0)", who);
+    want_coef = full->grad_coefficients != nullptr;
+    if (full->NB < (want_coef ? 1 : 0) || full->NB > kMaxNB) return fail(COMA_E_INVALID, "%s: NB=%d outside [%d, %d]", who, full->NB, want_coef ? 1 : 0, kMaxNB);
+    if (want_coef && !full->shapedirs) return fail(COMA_E_INVALID, "%s: null pointer (shapedirs with grad_coefficients)", who);
+    if (want_coef && !full->J_regressor) return fail(COMA_E_INVALID, "%s: null pointer (J_regressor with grad_coefficients)", who);
+  }
+  if (int rc = check_buffer(who, "saved state", saved, saved_bytes, N * L.saved_stride)) return rc;
+  const size_t need = !full ? L.single_total() : batched ? L.batch_grad_total() : L.grad_total;
+  if (int rc = check_buffer(who, "workspace", workspace, workspace_bytes, need)) return rc;
+  const char* st = (const char*)shape_state;
+  const char* sv = (const char*)saved;
+  char* ws = (char*)workspace + (full ? 0 : L.fwd_total);
+  hipStream_t s = (hipStream_t)stream;
+  const BatchStrides bs = {N, n_pca > 0 ? 3 * J - 2 * hand_dim + 2 * n_pca : 3 * J, shape_stride, L.saved_stride};
+  double* gvp = (double*)(ws + L.gvp);
+  double* dA_part = (double*)(ws + L.dA_part);
+  double* dfeat = (double*)(ws + L.dfeat);
+  if (scatter || !grad_vertices) {                          // only then does the gradient at the vertices differ from the caller's
+    double* g_eff = (double*)(ws + L.g_eff);
+    hipLaunchKernelGGL(smplx_effective_grad_kernel, dim3((V + kBlock - 1) / kBlock, N), dim3(kBlock), 0, s, grad_vertices,
+                       scatter ? full->grad_joints + 3 * (size_t)J : nullptr, 3 * (size_t)(J + full->E), full->extra_index, full->extra_weight, V,
+                       scatter ? full->E : 0, g_eff);
+    launch_skin_bwd<double>(L, bs, weights, sv, g_eff, V, J, gvp, dA_part, s);
+  } else {
+    launch_skin_bwd<float>(L, bs, weights, sv, grad_vertices, V, J, gvp, dA_part, s);
+  }
+  const auto feature_bwd = L.C == 1 ? smplx_feature_bwd_kernel<1> : smplx_feature_bwd_kernel<kChunk>;
+  if (L.P > 0) hipLaunchKernelGGL(feature_bwd, dim3(L.P, L.chunks), dim3(kBlock), 0, s, posedirs, (const double*)gvp, 3 * V, L.P, N, dfeat);
+  pb.s_pose = (const double*)(sv + L.s_pose); pb.j_rest = (const double*)(st + L.j_rest); pb.comps = hand_components;
+  pb.dA_part = dA_part; pb.dfeat = dfeat; pb.J = J; pb.hd = hand_dim; pb.n_pca = n_pca; pb.nblk = L.nblk;
+  pb.grad_theta = grad_theta; pb.grad_transl = grad_transl;
+  if (full) {
+    pb.gJ = full->grad_joints; pb.gP = full->grad_full_pose; pb.extra_w = full->extra_weight; pb.E = scatter ? full->E : 0;
+    pb.dJ_out = want_coef ? (double*)(ws + L.dJ) : nullptr;
+  }
+  hipLaunchKernelGGL(smplx_pose_bwd_kernel, dim3(N), dim3(kBlock), 0, s, pb, bs);
+  if (want_coef) {
+    double* part = (double*)(ws + L.coef_part);
+    hipLaunchKernelGGL(smplx_shape_bwd_kernel, dim3(L.nb3), dim3(kBlock), 0, s, full->shapedirs, full->J_regressor, (const double*)gvp,
+                       (const double*)(ws + L.dJ), V, J, full->NB, part);
+    hipLaunchKernelGGL(smplx_coef_sum_kernel, dim3((full->NB + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (const double*)part, L.nb3, full->NB,
+                       full->grad_coefficients);
+  }
+  return check_launch(who);
+}
+
+int extra_joints_impl(const char* who, int N, const float* vertices, const float* transl, const int32_t* vertex_index, const float* vertex_weight,
+                      int V, int E, float* out, void* stream) {
+  if (N < 1 || N > kMaxBatch) return fail(COMA_E_INVALID, "%s: N=%d outside [1, %d]", who, N, kMaxBatch);
+  if (E == 0) return COMA_OK;
+  if (!vertices || !vertex_index || !vertex_weight || !out) return fail(COMA_E_INVALID, "%s: null pointer", who);
+  if (V < 1 || V > kMaxV || E < 0 || E > kMaxV) return fail(COMA_E_INVALID, "%s: bad sizes V=%d E=%d", who, V, E);
+  hipLaunchKernelGGL(smplx_gather_kernel, dim3((3 * E + kBlock - 1) / kBlock, N), dim3(kBlock), 0, (hipStream_t)stream, vertices, transl,
+                     vertex_index, vertex_weight, V, E, out);
+  return check_launch(who);
 }
 
 }  // namespace
@@ -825,9 +899,15 @@ int check_common(const char* who, int V, int J, int hand_dim, int n_pca, const i
 
 using namespace coma;
 
-extern "C" size_t coma_smplx_workspace_bytes(int V, int J) { return sizes_ok(V, J) ? layout(V, J).total : 0; }
+extern "C" size_t coma_smplx_workspace_bytes(int V, int J) { return sizes_ok(V, J) ? layout(V, J).single_total() : 0; }
 extern "C" size_t coma_smplx_shape_state_bytes(int V, int J) { return sizes_ok(V, J) ? layout(V, J).shape_total : 0; }
-extern "C" size_t coma_smplx_saved_bytes(int V, int J) { return sizes_ok(V, J) ? layout(V, J).saved_total : 0; }
+extern "C" size_t coma_smplx_saved_bytes(int V, int J) { return sizes_ok(V, J) ? layout(V, J).saved_stride : 0; }
+extern "C" size_t coma_smplx_grad_workspace_bytes(int V, int J, int NB) {
+  return sizes_ok(V, J) && NB >= 0 && NB <= kMaxNB ? layout(V, J, 1, NB).grad_total : 0;
+}
+extern "C" size_t coma_smplx_batch_workspace_bytes(int V, int J, int N) { return sizes_ok(V, J, N) ? layout(V, J, N).fwd_total : 0; }
+extern "C" size_t coma_smplx_batch_saved_bytes(int V, int J, int N) { return sizes_ok(V, J, N) ? N * layout(V, J, N).saved_stride : 0; }
+extern "C" size_t coma_smplx_batch_grad_workspace_bytes(int V, int J, int N) { return sizes_ok(V, J, N) ? layout(V, J, N).batch_grad_total() : 0; }
 
 extern "C" int coma_smplx_shape_f32(const float* v_template, const float* shapedirs, const float* coefficients, const float* J_regressor, int V,
                                     int J, int NB, void* shape_state, size_t shape_state_bytes, void* stream) {
@@ -848,136 +928,25 @@ extern "C" int coma_smplx_forward_f32(const float* theta, const float* transl, c
                                       const float* hand_components, const float* pose_mean, int V, int J, int hand_dim, int n_pca,
                                       const void* shape_state, float* vertices, float* joints, float* full_pose, void* saved, size_t saved_bytes,
                                       void* workspace, size_t workspace_bytes, void* stream) {
-  const char* who = "coma_smplx_forward_f32";
-  if (!theta || !posedirs || !weights || !parents || !shape_state || !vertices || !joints || !saved || !workspace)
-    return fail(COMA_E_INVALID, "%s: null pointer", who);
-  if (n_pca > 0 && hand_dim > 0 && !hand_components) return fail(COMA_E_INVALID, "%s: null pointer (hand_components with n_pca > 0)", who);
-  PoseArgs pa = {};
-  if (int rc = check_common(who, V, J, hand_dim, n_pca, parents, pa.tree)) return rc;
-  const Layout L = layout(V, J);
-  if (int rc = check_buffer(who, "saved state", saved, saved_bytes, L.saved_total)) return rc;
-  if (int rc = check_buffer(who, "workspace", workspace, workspace_bytes, L.total)) return rc;
-  if (((uintptr_t)shape_state & 15) != 0) return fail(COMA_E_INVALID, "%s: shape state must be 16-byte aligned", who);
-  const char* st = (const char*)shape_state;
-  char* sv = (char*)saved;
-  char* ws = (char*)workspace;
-  hipStream_t s = (hipStream_t)stream;
-  pa.theta = theta; pa.comps = hand_components; pa.mean = pose_mean; pa.transl = transl; pa.j_rest = (const double*)(st + L.j_rest);
-  pa.J = J; pa.hd = hand_dim; pa.n_pca = n_pca; pa.s_pose = (double*)(sv + L.s_pose); pa.s_A = (double*)(sv + L.s_A);
-  pa.feat = (double*)(ws + L.feat); pa.joints = joints; pa.full_pose = full_pose;
-  hipLaunchKernelGGL(smplx_pose_kernel, dim3(1), dim3(kBlock), 0, s, pa);
-  if (L.P > 0)
-    hipLaunchKernelGGL(smplx_offsets_kernel, dim3(L.nb3, kPSplit), dim3(kBlock), 0, s, posedirs, (const double*)(ws + L.feat), L.P, 3 * V, L.rows,
-                       (double*)(ws + L.part));
-  else if (hipMemsetAsync(ws + L.part, 0, (size_t)kPSplit * 3 * V * sizeof(double), s) != hipSuccess)
-    return fail(COMA_E_LAUNCH, "%s: memset failed", who);
-  SkinArgs sa = {};
-  sa.weights = weights; sa.A = pa.s_A; sa.v_shaped = (const double*)(st + L.v_shaped); sa.part = (const double*)(ws + L.part); sa.transl = transl;
-  sa.V = V; sa.J = J; sa.v_posed = (double*)(sv + L.s_vposed); sa.vertices = vertices;
-  hipLaunchKernelGGL(smplx_skin_kernel, dim3(L.nblk), dim3(kTile), 0, s, sa);
-  return check_launch(who);
+  return forward_impl("coma_smplx_forward_f32", false, 1, 0, theta, transl, posedirs, weights, parents, hand_components, pose_mean, V, J, hand_dim,
+                      n_pca, shape_state, vertices, joints, full_pose, saved, saved_bytes, workspace, workspace_bytes, stream);
 }
 
-namespace coma {
-namespace {
-
-// what coma_smplx_backward_full_f32 adds to coma_smplx_backward_f32; every pointer may be null
-struct FullBwd {
-  const float* grad_joints;
-  const float* grad_full_pose;
-  const int32_t* extra_index;
-  const float* extra_weight;
-  int E;
-  const float* shapedirs;
-  const float* J_regressor;
-  int NB;
-  float* grad_coefficients;
-};
-
-// Both backward entry points: `full` null is the vertices-only backward on the forward's workspace layout (its launches and bits are
-// those of the first release); otherwise the full backward on its own layout.
-int backward_impl(const char* who, const float* grad_vertices, const float* posedirs, const float* weights, const int32_t* parents,
-                  const float* hand_components, int V, int J, int hand_dim, int n_pca, const void* shape_state, const void* saved,
-                  size_t saved_bytes, float* grad_theta, float* grad_transl, void* workspace, size_t workspace_bytes, void* stream,
-                  const FullBwd* full) {
-  if ((!full && !grad_vertices) || !posedirs || !weights || !parents || !shape_state || !saved || !grad_theta || !grad_transl || !workspace)
-    return fail(COMA_E_INVALID, "%s: null pointer", who);
-  if (n_pca > 0 && hand_dim > 0 && !hand_components) return fail(COMA_E_INVALID, "%s: null pointer (hand_components with n_pca > 0)", who);
-  PoseBwdArgs pb = {};
-  if (int rc = check_common(who, V, J, hand_dim, n_pca, parents, pb.tree)) return rc;
-  const Layout L = layout(V, J);
-  size_t o_gvp = L.gvp, o_dA = L.dA_part, o_dfeat = L.dfeat, need = L.total;
-  GradLayout GL = {};
-  bool scatter = false, want_coef = false;
-  if (full) {
-    if (full->E < 0 || full->E > kMaxE) return fail(COMA_E_INVALID, "%s: E=%d outside [0, %d]", who, full->E, kMaxE);
-    scatter = full->grad_joints && full->E > 0;
-    if (scatter && (!full->extra_index || !full->extra_weight))
-      return fail(COMA_E_INVALID, "%s: null pointer (the extra-joint tables with grad_joints and E > 0)", who);
-    want_coef = full->grad_coefficients != nullptr;
-    if (full->NB < (want_coef ? 1 : 0) || full->NB > kMaxNB) return fail(COMA_E_INVALID, "%s: NB=%d outside [%d, %d]", who, full->NB, want_coef ? 1 : 0, kMaxNB);
-    if (want_coef && !full->shapedirs) return fail(COMA_E_INVALID, "%s: null pointer (shapedirs with grad_coefficients)", who);
-    if (want_coef && !full->J_regressor) return fail(COMA_E_INVALID, "%s: null pointer (J_regressor with grad_coefficients)", who);
-    GL = grad_layout(V, J, full->NB);
-    o_gvp = GL.gvp; o_dA = GL.dA_part; o_dfeat = GL.dfeat; need = GL.total;
-  }
-  if (int rc = check_buffer(who, "saved state", saved, saved_bytes, L.saved_total)) return rc;
-  if (int rc = check_buffer(who, "workspace", workspace, workspace_bytes, need)) return rc;
-  if (((uintptr_t)shape_state & 15) != 0) return fail(COMA_E_INVALID, "%s: shape state must be 16-byte aligned", who);
-  const char* st = (const char*)shape_state;
-  const char* sv = (const char*)saved;
-  char* ws = (char*)workspace;
-  hipStream_t s = (hipStream_t)stream;
-  double* gvp = (double*)(ws + o_gvp);
-  double* dA_part = (double*)(ws + o_dA);
-  if (scatter || !grad_vertices) {                          // only then does the gradient at the vertices differ from the caller's
-    double* g_eff = (double*)(ws + GL.g_eff);
-    const int E = scatter ? full->E : 0;
-    hipLaunchKernelGGL(smplx_effective_grad_kernel, dim3((V + kBlock - 1) / kBlock), dim3(kBlock), 0, s, grad_vertices,
-                       scatter ? full->grad_joints + 3 * (size_t)J : nullptr, full->extra_index, full->extra_weight, V, E, g_eff);
-    SkinBwdArgs<double> sb = {};
-    sb.weights = weights; sb.A = (const double*)(sv + L.s_A); sb.v_posed = (const double*)(sv + L.s_vposed); sb.grad = g_eff;
-    sb.V = V; sb.J = J; sb.gvp = gvp; sb.dA_part = dA_part;
-    hipLaunchKernelGGL(smplx_skin_bwd_kernel<double>, dim3(L.nblk), dim3(kTile), 0, s, sb);
-  } else {
-    SkinBwdArgs<float> sb = {};
-    sb.weights = weights; sb.A = (const double*)(sv + L.s_A); sb.v_posed = (const double*)(sv + L.s_vposed); sb.grad = grad_vertices;
-    sb.V = V; sb.J = J; sb.gvp = gvp; sb.dA_part = dA_part;
-    hipLaunchKernelGGL(smplx_skin_bwd_kernel<float>, dim3(L.nblk), dim3(kTile), 0, s, sb);
-  }
-  if (L.P > 0)
-    hipLaunchKernelGGL(smplx_feature_bwd_kernel, dim3(L.P), dim3(kBlock), 0, s, posedirs, (const double*)gvp, 3 * V, (double*)(ws + o_dfeat));
-  pb.s_pose = (const double*)(sv + L.s_pose); pb.j_rest = (const double*)(st + L.j_rest); pb.comps = hand_components;
-  pb.dA_part = dA_part; pb.dfeat = (const double*)(ws + o_dfeat); pb.J = J; pb.hd = hand_dim; pb.n_pca = n_pca; pb.nblk = L.nblk;
-  pb.grad_theta = grad_theta; pb.grad_transl = grad_transl;
-  if (full) {
-    pb.gJ = full->grad_joints; pb.gP = full->grad_full_pose; pb.extra_w = full->extra_weight; pb.E = scatter ? full->E : 0;
-    pb.dJ_out = want_coef ? (double*)(ws + GL.dJ) : nullptr;
-  }
-  hipLaunchKernelGGL(smplx_pose_bwd_kernel, dim3(1), dim3(kBlock), 0, s, pb);
-  if (want_coef) {
-    double* part = (double*)(ws + GL.coef_part);
-    hipLaunchKernelGGL(smplx_shape_bwd_kernel, dim3(L.nb3), dim3(kBlock), 0, s, full->shapedirs, full->J_regressor, (const double*)gvp,
-                       (const double*)(ws + GL.dJ), V, J, full->NB, part);
-    hipLaunchKernelGGL(smplx_coef_sum_kernel, dim3((full->NB + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (const double*)part, L.nb3, full->NB,
-                       full->grad_coefficients);
-  }
-  return check_launch(who);
+extern "C" int coma_smplx_forward_batch_f32(const float* theta, const float* transl, const float* posedirs, const float* weights,
+                                            const int32_t* parents, const float* hand_components, const float* pose_mean, int V, int J,
+                                            int hand_dim, int n_pca, int N, const void* shape_state, size_t shape_stride, float* vertices,
+                                            float* joints, float* full_pose, void* saved, size_t saved_bytes, void* workspace,
+                                            size_t workspace_bytes, void* stream) {
+  return forward_impl("coma_smplx_forward_batch_f32", true, N, shape_stride, theta, transl, posedirs, weights, parents, hand_components, pose_mean, V,
+                      J, hand_dim, n_pca, shape_state, vertices, joints, full_pose, saved, saved_bytes, workspace, workspace_bytes, stream);
 }
-
-}  // namespace
-}  // namespace coma
 
 extern "C" int coma_smplx_backward_f32(const float* grad_vertices, const float* posedirs, const float* weights, const int32_t* parents,
                                        const float* hand_components, int V, int J, int hand_dim, int n_pca, const void* shape_state,
                                        const void* saved, size_t saved_bytes, float* grad_theta, float* grad_transl, void* workspace,
                                        size_t workspace_bytes, void* stream) {
-  return backward_impl("coma_smplx_backward_f32", grad_vertices, posedirs, weights, parents, hand_components, V, J, hand_dim, n_pca, shape_state,
-                       saved, saved_bytes, grad_theta, grad_transl, workspace, workspace_bytes, stream, nullptr);
-}
-
-extern "C" size_t coma_smplx_grad_workspace_bytes(int V, int J, int NB) {
-  return sizes_ok(V, J) && NB >= 0 && NB <= kMaxNB ? grad_layout(V, J, NB).total : 0;
+  return backward_impl("coma_smplx_backward_f32", false, 1, 0, grad_vertices, posedirs, weights, parents, hand_components, V, J, hand_dim, n_pca,
+                       shape_state, saved, saved_bytes, grad_theta, grad_transl, workspace, workspace_bytes, stream, nullptr);
 }
 
 extern "C" int coma_smplx_backward_full_f32(const float* grad_vertices, const float* grad_joints, const float* grad_full_pose,
@@ -987,106 +956,8 @@ extern "C" int coma_smplx_backward_full_f32(const float* grad_vertices, const fl
                                             const void* saved, size_t saved_bytes, float* grad_theta, float* grad_transl,
                                             float* grad_coefficients, void* workspace, size_t workspace_bytes, void* stream) {
   const FullBwd full = {grad_joints, grad_full_pose, extra_index, extra_weight, E, shapedirs, J_regressor, NB, grad_coefficients};
-  return backward_impl("coma_smplx_backward_full_f32", grad_vertices, posedirs, weights, parents, hand_components, V, J, hand_dim, n_pca,
-                       shape_state, saved, saved_bytes, grad_theta, grad_transl, workspace, workspace_bytes, stream, &full);
-}
-
-extern "C" int coma_smplx_extra_joints_f32(const float* vertices, const float* transl, const int32_t* vertex_index, const float* vertex_weight,
-                                           int V, int E, float* out, void* stream) {
-  const char* who = "coma_smplx_extra_joints_f32";
-  if (E == 0) return COMA_OK;
-  if (!vertices || !vertex_index || !vertex_weight || !out) return fail(COMA_E_INVALID, "%s: null pointer", who);
-  if (V < 1 || V > kMaxV || E < 0 || E > kMaxV) return fail(COMA_E_INVALID, "%s: bad sizes V=%d E=%d", who, V, E);
-  hipLaunchKernelGGL(smplx_gather_kernel, dim3((3 * E + kBlock - 1) / kBlock), dim3(kBlock), 0, (hipStream_t)stream, vertices, transl, vertex_index,
-                     vertex_weight, V, E, out);
-  return check_launch(who);
-}
-
-// ---- the batched entry points ----
-namespace coma {
-namespace {
-
-// Body n's saved block is the single-body layout at n x saved_stride.  Forward workspace: feat [N][P], part [N][kPSplit][3V].
-// Backward workspace (one layout for both forms): gvp [N][3V], dA_part [N][tiles][12 J + 3], dfeat [N][P], g_eff [N][3V].
-struct BatchLayout {
-  Layout one;
-  size_t feat, part, total;
-  size_t gvp, dA_part, dfeat, g_eff, grad_total;
-  size_t saved_stride, saved_total;
-  int NT, chunks, skin_chunks;
-};
-
-bool batch_ok(int V, int J, int N) { return sizes_ok(V, J) && N >= 1 && N <= kMaxBatch; }
-
-BatchLayout batch_layout(int V, int J, int N) {
-  BatchLayout B = {};
-  B.one = layout(V, J);
-  const size_t n3 = (size_t)3 * V, d = sizeof(double), n = (size_t)N, P = (size_t)(B.one.P > 0 ? B.one.P : 1);
-  Carve ws, grad;
-  B.feat = ws.take(n * P * d);
-  B.part = ws.take(n * kPSplit * n3 * d);
-  B.total = ws.at;
-  B.gvp = grad.take(n * n3 * d);
-  B.dA_part = grad.take(n * B.one.nblk * (12 * J + 3) * d);
-  B.dfeat = grad.take(n * P * d);
-  B.g_eff = grad.take(n * n3 * d);
-  B.grad_total = grad.at;
-  B.saved_stride = B.one.saved_total;
-  B.saved_total = n * B.saved_stride;
-  B.chunks = (N + kChunk - 1) / kChunk;
-  B.skin_chunks = (N + kSkinChunk - 1) / kSkinChunk;
-  return B;
-}
-
-int check_batch(const char* who, int V, int J, int N, const void* shape_state, size_t shape_stride) {
-  if (N < 1 || N > kMaxBatch) return fail(COMA_E_INVALID, "%s: N=%d outside [1, %d]", who, N, kMaxBatch);
-  const size_t need = layout(V, J).shape_total;
-  if (shape_stride != 0 && (shape_stride < need || (shape_stride & 15) != 0))
-    return fail(COMA_E_INVALID, "%s: shape_stride=%zu must be 0 (one shape state for all bodies) or a multiple of 16 of at least %zu", who,
-                shape_stride, need);
-  if (((uintptr_t)shape_state & 15) != 0) return fail(COMA_E_INVALID, "%s: shape state must be 16-byte aligned", who);
-  return COMA_OK;
-}
-
-}  // namespace
-}  // namespace coma
-
-extern "C" size_t coma_smplx_batch_workspace_bytes(int V, int J, int N) { return batch_ok(V, J, N) ? batch_layout(V, J, N).total : 0; }
-extern "C" size_t coma_smplx_batch_saved_bytes(int V, int J, int N) { return batch_ok(V, J, N) ? batch_layout(V, J, N).saved_total : 0; }
-extern "C" size_t coma_smplx_batch_grad_workspace_bytes(int V, int J, int N) { return batch_ok(V, J, N) ? batch_layout(V, J, N).grad_total : 0; }
-
-extern "C" int coma_smplx_forward_batch_f32(const float* theta, const float* transl, const float* posedirs, const float* weights,
-                                            const int32_t* parents, const float* hand_components, const float* pose_mean, int V, int J,
-                                            int hand_dim, int n_pca, int N, const void* shape_state, size_t shape_stride, float* vertices,
-                                            float* joints, float* full_pose, void* saved, size_t saved_bytes, void* workspace,
-                                            size_t workspace_bytes, void* stream) {
-  const char* who = "coma_smplx_forward_batch_f32";
-  if (!theta || !posedirs || !weights || !parents || !shape_state || !vertices || !joints || !saved || !workspace)
-    return fail(COMA_E_INVALID, "%s: null pointer", who);
-  if (n_pca > 0 && hand_dim > 0 && !hand_components) return fail(COMA_E_INVALID, "%s: null pointer (hand_components with n_pca > 0)", who);
-  PoseArgs pa = {};
-  if (int rc = check_common(who, V, J, hand_dim, n_pca, parents, pa.tree)) return rc;
-  if (int rc = check_batch(who, V, J, N, shape_state, shape_stride)) return rc;
-  const BatchLayout B = batch_layout(V, J, N);
-  const Layout& L = B.one;
-  if (int rc = check_buffer(who, "saved state", saved, saved_bytes, B.saved_total)) return rc;
-  if (int rc = check_buffer(who, "workspace", workspace, workspace_bytes, B.total)) return rc;
-  const char* st = (const char*)shape_state;
-  char* sv = (char*)saved;
-  char* ws = (char*)workspace;
-  hipStream_t s = (hipStream_t)stream;
-  const BatchStrides bs = {N, n_pca > 0 ? 3 * J - 2 * hand_dim + 2 * n_pca : 3 * J, shape_stride, B.saved_stride};
-  pa.theta = theta; pa.comps = hand_components; pa.mean = pose_mean; pa.transl = transl; pa.j_rest = (const double*)(st + L.j_rest);
-  pa.J = J; pa.hd = hand_dim; pa.n_pca = n_pca; pa.s_pose = (double*)(sv + L.s_pose); pa.s_A = (double*)(sv + L.s_A);
-  pa.feat = (double*)(ws + B.feat); pa.joints = joints; pa.full_pose = full_pose;
-  hipLaunchKernelGGL(smplx_pose_batch_kernel, dim3(N), dim3(kBlock), 0, s, pa, bs);
-  hipLaunchKernelGGL(smplx_offsets_batch_kernel, dim3(L.nb3, kPSplit, B.chunks), dim3(kBlock), 0, s, posedirs, (const double*)(ws + B.feat), L.P,
-                     3 * V, L.rows, N, (double*)(ws + B.part));
-  SkinArgs sa = {};
-  sa.weights = weights; sa.A = pa.s_A; sa.v_shaped = (const double*)(st + L.v_shaped); sa.part = (const double*)(ws + B.part); sa.transl = transl;
-  sa.V = V; sa.J = J; sa.v_posed = (double*)(sv + L.s_vposed); sa.vertices = vertices;
-  hipLaunchKernelGGL(smplx_skin_batch_kernel, dim3(L.nblk, B.skin_chunks), dim3(kTile), 0, s, sa, bs);
-  return check_launch(who);
+  return backward_impl("coma_smplx_backward_full_f32", false, 1, 0, grad_vertices, posedirs, weights, parents, hand_components, V, J, hand_dim,
+                       n_pca, shape_state, saved, saved_bytes, grad_theta, grad_transl, workspace, workspace_bytes, stream, &full);
 }
 
 extern "C" int coma_smplx_backward_batch_f32(const float* grad_vertices, const float* grad_joints, const float* grad_full_pose,
@@ -1094,61 +965,18 @@ extern "C" int coma_smplx_backward_batch_f32(const float* grad_vertices, const f
                                              const int32_t* extra_index, const float* extra_weight, int E, int V, int J, int hand_dim, int n_pca,
                                              int N, const void* shape_state, size_t shape_stride, const void* saved, size_t saved_bytes,
                                              float* grad_theta, float* grad_transl, void* workspace, size_t workspace_bytes, void* stream) {
-  const char* who = "coma_smplx_backward_batch_f32";
-  if (!posedirs || !weights || !parents || !shape_state || !saved || !grad_theta || !grad_transl || !workspace)
-    return fail(COMA_E_INVALID, "%s: null pointer", who);
-  if (n_pca > 0 && hand_dim > 0 && !hand_components) return fail(COMA_E_INVALID, "%s: null pointer (hand_components with n_pca > 0)", who);
-  PoseBwdArgs pb = {};
-  if (int rc = check_common(who, V, J, hand_dim, n_pca, parents, pb.tree)) return rc;
-  if (int rc = check_batch(who, V, J, N, shape_state, shape_stride)) return rc;
-  if (E < 0 || E > kMaxE) return fail(COMA_E_INVALID, "%s: E=%d outside [0, %d]", who, E, kMaxE);
-  const bool scatter = grad_joints && E > 0;
-  if (scatter && (!extra_index || !extra_weight))
-    return fail(COMA_E_INVALID, "%s: null pointer (the extra-joint tables with grad_joints and E > 0)", who);
-  const BatchLayout B = batch_layout(V, J, N);
-  const Layout& L = B.one;
-  if (int rc = check_buffer(who, "saved state", saved, saved_bytes, B.saved_total)) return rc;
-  if (int rc = check_buffer(who, "workspace", workspace, workspace_bytes, B.grad_total)) return rc;
-  const char* st = (const char*)shape_state;
-  const char* sv = (const char*)saved;
-  char* ws = (char*)workspace;
-  hipStream_t s = (hipStream_t)stream;
-  const BatchStrides bs = {N, n_pca > 0 ? 3 * J - 2 * hand_dim + 2 * n_pca : 3 * J, shape_stride, B.saved_stride};
-  double* gvp = (double*)(ws + B.gvp);
-  double* dA_part = (double*)(ws + B.dA_part);
-  double* dfeat = (double*)(ws + B.dfeat);
-  if (scatter || !grad_vertices) {                          // as the single-body full backward: only then is an effective gradient built
-    double* g_eff = (double*)(ws + B.g_eff);
-    hipLaunchKernelGGL(smplx_effective_grad_batch_kernel, dim3((V + kBlock - 1) / kBlock, N), dim3(kBlock), 0, s, grad_vertices,
-                       scatter ? grad_joints : nullptr, J, extra_index, extra_weight, V, scatter ? E : 0, E, g_eff);
-    SkinBwdArgs<double> sb = {};
-    sb.weights = weights; sb.A = (const double*)(sv + L.s_A); sb.v_posed = (const double*)(sv + L.s_vposed); sb.grad = g_eff;
-    sb.V = V; sb.J = J; sb.gvp = gvp; sb.dA_part = dA_part;
-    hipLaunchKernelGGL(smplx_skin_bwd_batch_kernel<double>, dim3(L.nblk, B.skin_chunks), dim3(kTile), 0, s, sb, bs);
-  } else {
-    SkinBwdArgs<float> sb = {};
-    sb.weights = weights; sb.A = (const double*)(sv + L.s_A); sb.v_posed = (const double*)(sv + L.s_vposed); sb.grad = grad_vertices;
-    sb.V = V; sb.J = J; sb.gvp = gvp; sb.dA_part = dA_part;
-    hipLaunchKernelGGL(smplx_skin_bwd_batch_kernel<float>, dim3(L.nblk, B.skin_chunks), dim3(kTile), 0, s, sb, bs);
-  }
-  if (L.P > 0)
-    hipLaunchKernelGGL(smplx_feature_bwd_batch_kernel, dim3(L.P, B.chunks), dim3(kBlock), 0, s, posedirs, (const double*)gvp, 3 * V, L.P, N, dfeat);
-  pb.s_pose = (const double*)(sv + L.s_pose); pb.j_rest = (const double*)(st + L.j_rest); pb.comps = hand_components;
-  pb.dA_part = dA_part; pb.dfeat = dfeat; pb.J = J; pb.hd = hand_dim; pb.n_pca = n_pca; pb.nblk = L.nblk;
-  pb.grad_theta = grad_theta; pb.grad_transl = grad_transl;
-  pb.gJ = grad_joints; pb.gP = grad_full_pose; pb.extra_w = extra_weight; pb.E = scatter ? E : 0;
-  hipLaunchKernelGGL(smplx_pose_bwd_batch_kernel, dim3(N), dim3(kBlock), 0, s, pb, bs);
-  return check_launch(who);
+  const FullBwd full = {grad_joints, grad_full_pose, extra_index, extra_weight, E, nullptr, nullptr, 0, nullptr};
+  return backward_impl("coma_smplx_backward_batch_f32", true, N, shape_stride, grad_vertices, posedirs, weights, parents, hand_components, V, J,
+                       hand_dim, n_pca, shape_state, saved, saved_bytes, grad_theta, grad_transl, workspace, workspace_bytes, stream, &full);
+}
+
+extern "C" int coma_smplx_extra_joints_f32(const float* vertices, const float* transl, const int32_t* vertex_index, const float* vertex_weight,
+                                           int V, int E, float* out, void* stream) {
+  return extra_joints_impl("coma_smplx_extra_joints_f32", 1, vertices, transl, vertex_index, vertex_weight, V, E, out, stream);
 }
 
 extern "C" int coma_smplx_extra_joints_batch_f32(const float* vertices, const float* transl, const int32_t* vertex_index,
                                                  const float* vertex_weight, int V, int E, int N, float* out, void* stream) {
-  const char* who = "coma_smplx_extra_joints_batch_f32";
-  if (N < 1 || N > kMaxBatch) return fail(COMA_E_INVALID, "%s: N=%d outside [1, %d]", who, N, kMaxBatch);
-  if (E == 0) return COMA_OK;
-  if (!vertices || !vertex_index || !vertex_weight || !out) return fail(COMA_E_INVALID, "%s: null pointer", who);
-  if (V < 1 || V > kMaxV || E < 0 || E > kMaxV) return fail(COMA_E_INVALID, "%s: bad sizes V=%d E=%d", who, V, E);
-  hipLaunchKernelGGL(smplx_gather_batch_kernel, dim3((3 * E + kBlock - 1) / kBlock, N), dim3(kBlock), 0, (hipStream_t)stream, vertices, transl,
-                     vertex_index, vertex_weight, V, E, out);
-  return check_launch(who);
+  return extra_joints_impl("coma_smplx_extra_joints_batch_f32", N, vertices, transl, vertex_index, vertex_weight, V, E, out, stream);
 }
+

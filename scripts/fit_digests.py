@@ -90,6 +90,34 @@ def smplx_full():
             emit(f"smplx_full.{name}.grad_expression", kw["expression"].grad)
 
 
+def smplx_batch():
+    """One batched object at batch_size = kChunk + 1 (two sweeps over posedirs, the second with one body; an odd body count for the
+    skinning pairs) on the `moderate` model: the three outputs and, from a loss over all of them, the gradients to the pose and transl."""
+    import torch
+    from coma_amd.body_model import DeviceSMPLX
+    from tests import smplx_batch_ref as B
+    from tests import smplx_ref as S
+    N = B.C_CHUNK + 1
+    model, fm = S.case_model("moderate")
+    inp = S.case_inputs("moderate")
+    rng = np.random.RandomState(7)
+    t = lambda x: torch.as_tensor(np.asarray(x, dtype=np.float32)).to(DEV)
+    body = DeviceSMPLX(model, n_pca=fm["n_pca"], device=DEV, extra_joint_vertex_ids=[0, fm["V"] - 1], differentiable=("joints", "full_pose"),
+                       batch_size=N)
+    theta = t(inp["theta"] + 0.2 * rng.normal(size=(N, len(inp["theta"])))).requires_grad_(True)
+    transl = t(inp["transl"] + rng.normal(size=(N, 3))).requires_grad_(True)
+    coef = t(inp["coefficients"]).reshape(1, -1)
+    sizes = (3, body.num_body, 3, 3, 3, body.hand_size, body.hand_size)
+    out = body(betas=coef[:, :body.num_betas], expression=coef[:, body.num_betas:] if body.num_expression_coeffs else None, transl=transl, return_full_pose=True,
+               **dict(zip(POSE_KEYS, torch.split(theta, sizes, 1))))
+    ((out.vertices * t(rng.normal(size=out.vertices.shape))).sum() + (out.joints * t(rng.normal(size=out.joints.shape))).sum()
+     + (out.full_pose * t(rng.normal(size=out.full_pose.shape))).sum()).backward()
+    for q in ("vertices", "joints", "full_pose"):
+        emit(f"smplx_batch.{q}", getattr(out, q))
+    emit("smplx_batch.grad_theta", theta.grad)
+    emit("smplx_batch.grad_transl", transl.grad)
+
+
 def vposer():
     """Decode, decode-backward, encode at N = 1 and N = 3 (and the odd sizes H = 80, D = 7, NJ = 5); the angle prior and its backward."""
     import torch
@@ -231,7 +259,7 @@ def main():
     from coma_amd import _lib
     assert torch.cuda.is_available(), "the digests are of device results"
     print(f"# library: {_lib.LIB_PATH}", file=sys.stderr)
-    for part in (smplx, smplx_full, vposer, app_objective, app_fit, volumes_and_depth, row_reductions):
+    for part in (smplx, smplx_full, smplx_batch, vposer, app_objective, app_fit, volumes_and_depth, row_reductions):
         part()
     torch.cuda.synchronize()
 
