@@ -6,7 +6,9 @@ orientation bin -- and a contact term, the chamfer distance between the selected
 points.  `ComaObjective` evaluates both terms and their gradients with respect to the vertices in one device pass
 (coma_amd/csrc/app_objective.hip; rule set in include/coma_hip.h, restated in tests/app_ref.py); `.loss` wraps that in a
 torch.autograd.Function so that a caller's body model (SMPL-X, VPoser: third party, hooks of src/application/optimize.py) keeps
-differentiating from the vertices on.  `DeviceFit` goes one step further when the body model, the pose decoder and the angle prior are
+differentiating from the vertices on.  Both take N bodies [N,V,3] against the one set of constants -- several starts of one fit -- in
+the launches of one body (coma_app_objective_batch_f32; body n has the single call's bits); `DeviceFit` below is still one body.
+`DeviceFit` goes one step further when the body model, the pose decoder and the angle prior are
 the library's own too: the whole Adam loop of the app runs as one device call per 4096 iterations (coma_amd/csrc/app_fit.hip).  There
 is no CPU fallback.
 """
@@ -100,6 +102,7 @@ class ComaObjective:
         nbytes = int(_lib.lib().coma_app_objective_workspace_bytes(V, F, k))
         self._ws = torch.empty([max(16, nbytes)], dtype=torch.uint8, device=dev)
         self._ws_bytes = nbytes
+        self._batch_ws = {}                        # N -> (workspace, bytes) of coma_app_objective_batch_f32, made on first use and kept
         self.device = dev
 
     @classmethod
@@ -113,34 +116,49 @@ class ComaObjective:
         return cls(faces, gt, obj_normal, selected, target_points, principle_vec, sub_principle_vec, eps, device)
 
     def _vertices(self, vertices):
+        """-> (f32 contiguous [V,3] or, for N >= 2 bodies, [N,V,3]; N)."""
         v = vertices
         if v.dim() == 3 and v.shape[0] == 1:
             v = v[0]
-        if v.dim() != 2 or tuple(v.shape) != (self.V, 3):
-            raise ValueError(f"vertices: expected [{self.V},3] or [1,{self.V},3], got {tuple(vertices.shape)}")
+        if v.dim() not in (2, 3) or tuple(v.shape[-2:]) != (self.V, 3) or (v.dim() == 3 and v.shape[0] < 2):
+            raise ValueError(f"vertices: expected [{self.V},3], [1,{self.V},3] or [N,{self.V},3], got {tuple(vertices.shape)}")
         if not v.is_cuda or v.device != self.device:
             raise _lib.ComaHipError(f"vertices must live on {self.device} (got {v.device}); there is no CPU path")
-        return v.detach().to(torch.float32).contiguous()
+        return v.detach().to(torch.float32).contiguous(), (int(v.shape[0]) if v.dim() == 3 else 1)
+
+    def _batch_workspace(self, N):
+        if N not in self._batch_ws:
+            nbytes = int(_lib.lib().coma_app_objective_batch_workspace_bytes(self.V, self.F, self.k, N))
+            if not nbytes:
+                raise ValueError(f"vertices: {N} bodies are outside what coma_app_objective_batch_f32 accepts (at most 1024)")
+            self._batch_ws[N] = (torch.empty([nbytes], dtype=torch.uint8, device=self.device), nbytes)
+        return self._batch_ws[N]
 
     def evaluate(self, vertices):
         """vertices [V,3] or [1,V,3] on the device -> (terms f32 [2] = {orientation, contact} unweighted, grad_orientation f32 [V,3],
-        grad_contact f32 [V,3]), device tensors; nothing waits for the device."""
-        v = self._vertices(vertices)
-        terms = torch.empty([2], dtype=torch.float32, device=self.device)
-        g_o = torch.empty([self.V, 3], dtype=torch.float32, device=self.device)
-        g_c = torch.empty([self.V, 3], dtype=torch.float32, device=self.device)
+        grad_contact f32 [V,3]), device tensors; nothing waits for the device.  vertices [N,V,3], N >= 2 bodies against the same
+        constants -> (terms [N,2], grad_orientation [N,V,3], grad_contact [N,V,3]) from one coma_app_objective_batch_f32 call: body n
+        has the bits of evaluate(vertices[n])."""
+        v, N = self._vertices(vertices)
+        lead = [N] if v.dim() == 3 else []
+        terms = torch.empty(lead + [2], dtype=torch.float32, device=self.device)
+        g_o = torch.empty(lead + [self.V, 3], dtype=torch.float32, device=self.device)
+        g_c = torch.empty(lead + [self.V, 3], dtype=torch.float32, device=self.device)
         i32, f32 = torch.int32, torch.float32
+        batch = (N,) if lead else ()
+        entry = "coma_app_objective_batch_f32" if lead else "coma_app_objective_f32"
+        ws, ws_bytes = self._batch_workspace(N) if lead else (self._ws, self._ws_bytes)
         with _lib.on_device(self.device) as stream:
-            rc = _lib.lib().coma_app_objective_f32(
+            rc = getattr(_lib.lib(), entry)(
                 _lib.ptr(v, f32, "vertices"), _lib.ptr(self.faces, i32), _lib.ptr(self.vf_offsets, i32), _lib.ptr(self.vf_faces, i32),
                 self.V, self.F, _lib.ptr(self.orientation_gt, f32), self._b, self._p, self._s, self.eps, _lib.ptr(self.selected, i32),
-                _lib.ptr(self.targets, f32), self.k, _lib.ptr(terms), _lib.ptr(g_o), _lib.ptr(g_c), _lib.ptr(self._ws), self._ws_bytes,
-                stream)
-        _lib.check(rc, "coma_app_objective_f32")
+                _lib.ptr(self.targets, f32), self.k, *batch, _lib.ptr(terms), _lib.ptr(g_o), _lib.ptr(g_c), _lib.ptr(ws), ws_bytes, stream)
+        _lib.check(rc, entry)
         return terms, g_o, g_c
 
     def loss(self, vertices, orientation_weight, contact_weight):
-        """orientation_weight * orientation term + contact_weight * contact term as a scalar of the caller's graph."""
+        """orientation_weight * orientation term + contact_weight * contact term as a scalar of the caller's graph; for N >= 2 bodies
+        [N,V,3] a tensor [N], one weighted loss per body (its backward gives body n grad_output[n] times that body's gradient)."""
         return _ObjectiveFunction.apply(vertices, self, float(orientation_weight), float(contact_weight))
 
 
@@ -319,9 +337,11 @@ class _ObjectiveFunction(torch.autograd.Function):
         terms, g_o, g_c = objective.evaluate(vertices)
         ctx.save_for_backward(w_o * g_o + w_c * g_c)
         ctx.shape, ctx.dtype = vertices.shape, vertices.dtype
-        return (w_o * terms[0] + w_c * terms[1]).to(vertices.dtype)
+        return (w_o * terms[..., 0] + w_c * terms[..., 1]).to(vertices.dtype)
 
     @staticmethod
     def backward(ctx, grad_output):
         (g,) = ctx.saved_tensors
+        if g.dim() == 3:
+            grad_output = grad_output.reshape(-1, 1, 1)                # [N]: body n's gradient times its own factor
         return (grad_output * g).to(ctx.dtype).reshape(ctx.shape), None, None, None

@@ -21,7 +21,8 @@ Deviations from the package, all refused or stated rather than silently differen
     or `.full_pose`; each needs its entry in `differentiable=`;
   * no gradient with respect to the model's own tensors (shapedirs, posedirs, weights), no double backward;
   * at batch_size > 1 no gradient to betas or expression ("shape" is refused in the constructor), and betas / expression are one row
-    for all bodies or one row per body; DeviceVPoser, ComaObjective and DeviceFit are not batched and the CLIs pose one body;
+    for all bodies or one row per body; DeviceFit is not batched (ComaObjective takes N bodies, DeviceVPoser and DeviceAnglePrior up
+    to 64 rows, and src/application/optimize.py --num_starts N, a policy of this project, runs N starts of one fit through them);
   * the package's table of vertex ids for the extra joints (nose, eyes, ears, toes, heels, finger tips) is not shipped: it is taken
     from `smplx.vertex_ids` when that package imports, may be passed in, and otherwise `.joints` is [J posed joints | landmarks] and
     `extra_joint_source` says "landmarks only";

@@ -10,6 +10,10 @@
 // are merged in ascending split order, so the first minimum wins whatever the split.  No floating-point atomics: the normal
 // gradient returns to the vertices by a gather over the vertex->face CSR table, the contact term's second direction by a scan in
 // ascending j, and the two term sums by per-workgroup trees whose partials a single workgroup adds in block order.
+//
+// One kernel set for N bodies (coma_app_objective_batch_f32; coma_app_objective_f32 is N = 1): the last grid dimension is the body,
+// a workgroup moves its per-body pointers (vertices, gradients, every scratch array) to its body once and then runs the single
+// body's code, so body n has the single call's bits.  Topology, orientation targets, M, the selection and the targets are shared.
 #include "common.h"
 #include "coma_device.h"
 
@@ -31,9 +35,16 @@ struct AppArgs {
   int V, F;
   double M[9];     // f = M a (row-major), built on the host
   double eps;
-  double* gN;      // [V,3] d term / d N_h
-  double* part_o;  // [ceil(V / 256)]
+  double* gN;      // [N][V,3] d term / d N_h
+  double* part_o;  // [N][ceil(V / 256)]
 };
+
+// the per-body arrays of a workgroup whose body is n (the vertex kernels: blockIdx.y, gridDim.x = ceil(V / 256))
+__device__ __forceinline__ void to_body(AppArgs& A, int n) {
+  A.verts += (int64_t)n * A.V * 3;
+  A.gN += (int64_t)n * A.V * 3;
+  A.part_o += (int64_t)n * gridDim.x;
+}
 
 // one incident face of a vertex: its three indices, or false when the table points outside the mesh
 __device__ __forceinline__ bool face_of(const AppArgs& A, int e, int& i0, int& i1, int& i2) {
@@ -46,6 +57,7 @@ __device__ __forceinline__ bool face_of(const AppArgs& A, int e, int& i0, int& i
 // K1: per vertex the normal sum, the three normalisations, f = M a, the vertex's share of the orientation term and g_h = d term / d N_h
 __global__ __launch_bounds__(kBlock) void app_vertex_kernel(AppArgs A) {
   __shared__ double lds[kBlock];
+  to_body(A, blockIdx.y);
   const int h = blockIdx.x * kBlock + threadIdx.x;
   double t = 0.0;
   if (h < A.V) {
@@ -102,6 +114,8 @@ __global__ __launch_bounds__(kBlock) void app_vertex_kernel(AppArgs A) {
 __global__ __launch_bounds__(kBlock) void app_face_gather_kernel(AppArgs A, float* __restrict__ grad) {
   const int h = blockIdx.x * kBlock + threadIdx.x;
   if (h >= A.V) return;
+  to_body(A, blockIdx.y);
+  grad += (int64_t)blockIdx.y * A.V * 3;
   D3 acc = {0.0, 0.0, 0.0};
   const int e0 = max(A.off[h], 0), e1 = min(A.off[h + 1], 3 * A.F);
   for (int e = e0; e < e1; ++e) {
@@ -126,12 +140,16 @@ __device__ __forceinline__ bool point_row(const int32_t* idx, int t, int rows, i
   return r >= 0 && r < rows;
 }
 
-// K3 (run twice, sides swapped): for 64 rows of P the minimum and first argmin of sqrt((dx^2 + dy^2) + dz^2) over one split of Q
+// K3 (run twice, sides swapped): for 64 rows of P the minimum and first argmin of sqrt((dx^2 + dy^2) + dz^2) over one split of Q.
+// Body blockIdx.z: the side that is the vertices moves by its stride (the targets' stride is 0), the results by out_stride.
 __global__ __launch_bounds__(kRowTile) void app_rowmin_kernel(const float* __restrict__ P, const int32_t* __restrict__ idxP, int rowsP,
-                                                             const float* __restrict__ Q, const int32_t* __restrict__ idxQ, int rowsQ,
-                                                             int k, int chunk, float* __restrict__ pmin, int32_t* __restrict__ parg) {
+                                                             int64_t strideP, const float* __restrict__ Q, const int32_t* __restrict__ idxQ,
+                                                             int rowsQ, int64_t strideQ, int k, int chunk, float* __restrict__ pmin,
+                                                             int32_t* __restrict__ parg, int64_t out_stride) {
   __shared__ float4 tile[kRowTile];
   const int lane = threadIdx.x;
+  P += blockIdx.z * strideP; Q += blockIdx.z * strideQ;
+  pmin += blockIdx.z * out_stride; parg += blockIdx.z * out_stride;
   const int i = blockIdx.x * kRowTile + lane;
   const int split = blockIdx.y;
   float px = NAN, py = NAN, pz = NAN;
@@ -166,12 +184,22 @@ struct ContactArgs {
   const int32_t* sel;
   const float* targets;
   int V, k, nsplit;
-  const float* pmin;     // [2][nsplit][k]
-  const int32_t* parg;   // [2][nsplit][k]
-  double* dist;          // [2][k]  |A_i - B_argmin| and |A_argmin - B_j| in f64
-  int32_t* arg;          // [2][k]
-  double* part_c;        // [2][ceil(k / 256)]
+  const float* pmin;     // [N][2][nsplit][k]
+  const int32_t* parg;   // [N][2][nsplit][k]
+  double* dist;          // [N][2][k]  |A_i - B_argmin| and |A_argmin - B_j| in f64
+  int32_t* arg;          // [N][2][k]
+  double* part_c;        // [N][2][ceil(k / 256)]
 };
+
+// the per-body arrays of a workgroup whose body is n (the contact kernels: blockIdx.y, gridDim.x = ceil(k / 256))
+__device__ __forceinline__ void to_body(ContactArgs& C, int n) {
+  C.verts += (int64_t)n * C.V * 3;
+  C.pmin += (int64_t)n * 2 * C.nsplit * C.k;
+  C.parg += (int64_t)n * 2 * C.nsplit * C.k;
+  C.dist += (int64_t)n * 2 * C.k;
+  C.arg += (int64_t)n * 2 * C.k;
+  C.part_c += (int64_t)n * 2 * gridDim.x;
+}
 
 __device__ __forceinline__ D3 point_a(const ContactArgs& C, int i) {
   int r;
@@ -181,6 +209,7 @@ __device__ __forceinline__ D3 point_a(const ContactArgs& C, int i) {
 // K4: merge the splits in ascending order (first minimum wins), take the winning distance again in f64, partial sums of both directions
 __global__ __launch_bounds__(kBlock) void app_contact_merge_kernel(ContactArgs C) {
   __shared__ double lds[kBlock];
+  to_body(C, blockIdx.y);
   const int t = blockIdx.x * kBlock + threadIdx.x;
   double d[2] = {0.0, 0.0};
   if (t < C.k) {
@@ -211,6 +240,8 @@ __global__ __launch_bounds__(kBlock) void app_contact_merge_kernel(ContactArgs C
 // K5: contact gradient of selected row i: its own nearest target, then every target j (ascending) whose nearest selected row is i
 __global__ __launch_bounds__(kBlock) void app_contact_grad_kernel(ContactArgs C, float* __restrict__ grad) {
   __shared__ int32_t owner[kBlock];
+  to_body(C, blockIdx.y);
+  grad += (int64_t)blockIdx.y * C.V * 3;
   const int i = blockIdx.x * kBlock + threadIdx.x;
   const bool live = i < C.k;
   D3 a = {0.0, 0.0, 0.0}, g = {0.0, 0.0, 0.0};
@@ -241,10 +272,11 @@ __global__ __launch_bounds__(kBlock) void app_contact_grad_kernel(ContactArgs C,
   }
 }
 
-// K6: the partials in block order (thread t adds t, t + 256, ...; then the tree), the means, the two terms
+// K6, one workgroup per body: the partials in block order (thread t adds t, t + 256, ...; then the tree), the means, the two terms
 __global__ __launch_bounds__(kBlock) void app_finalize_kernel(const double* __restrict__ part_o, int nb_o, int V,
                                                              const double* __restrict__ part_c, int nb_c, int k, float* __restrict__ terms) {
   __shared__ double lds[kBlock];
+  part_o += (int64_t)blockIdx.x * nb_o; part_c += (int64_t)blockIdx.x * 2 * nb_c; terms += (int64_t)blockIdx.x * 2;
   double s[3] = {0.0, 0.0, 0.0};
   for (int b = threadIdx.x; b < nb_o; b += kBlock) s[0] = s[0] + part_o[b];
   for (int b = threadIdx.x; b < nb_c; b += kBlock) { s[1] = s[1] + part_c[b]; s[2] = s[2] + part_c[nb_c + b]; }
@@ -261,26 +293,28 @@ struct Layout {
   int nb_v, nb_k, row_blocks, chunk, nsplit;
 };
 
-Layout layout(int V, int k) {
+// the scratch of N bodies: every array is [N] of the single body's, so N = 1 is the single-body layout
+Layout layout(int V, int k, int N = 1) {
   Layout L = {};
   L.nb_v = (V + kBlock - 1) / kBlock;
   L.nb_k = (k + kBlock - 1) / kBlock;
   L.row_blocks = (k + kRowTile - 1) / kRowTile;
   if (k > 0) {
-    int want = kMinGrid / L.row_blocks;                 // splits of the columns, so that small k still fills the device
+    int want = kMinGrid / (L.row_blocks * N);           // splits of the columns, so that small k still fills the device; N bodies
+                                                        // fill it N times sooner (the merge does not depend on the split)
     if (want < 1) want = 1;
     if (want > L.row_blocks) want = L.row_blocks;
     L.chunk = (L.row_blocks + want - 1) / want;         // column tiles per split
     L.nsplit = (L.row_blocks + L.chunk - 1) / L.chunk;  // no split is empty
   }
   Carve ws;
-  L.gN = ws.take((size_t)V * 3 * sizeof(double));
-  L.part_o = ws.take((size_t)L.nb_v * sizeof(double));
-  L.part_c = ws.take((size_t)2 * L.nb_k * sizeof(double));
-  L.dist = ws.take((size_t)2 * k * sizeof(double));
-  L.arg = ws.take((size_t)2 * k * sizeof(int32_t));
-  L.pmin = ws.take((size_t)2 * L.nsplit * k * sizeof(float));
-  L.parg = ws.take((size_t)2 * L.nsplit * k * sizeof(int32_t));
+  L.gN = ws.take((size_t)N * V * 3 * sizeof(double));
+  L.part_o = ws.take((size_t)N * L.nb_v * sizeof(double));
+  L.part_c = ws.take((size_t)N * 2 * L.nb_k * sizeof(double));
+  L.dist = ws.take((size_t)N * 2 * k * sizeof(double));
+  L.arg = ws.take((size_t)N * 2 * k * sizeof(int32_t));
+  L.pmin = ws.take((size_t)N * 2 * L.nsplit * k * sizeof(float));
+  L.parg = ws.take((size_t)N * 2 * L.nsplit * k * sizeof(int32_t));
   L.total = ws.at;
   return L;
 }
@@ -291,22 +325,15 @@ void unit_host(const float* v, double eps, double* out) {   // utils/transformat
   out[0] = x / n; out[1] = y / n; out[2] = z / n;
 }
 
-}  // namespace
-}  // namespace coma
+constexpr int kMaxBatch = 1024;   // N: bodies per call, the body model's bound
 
-using namespace coma;
+bool sizes_ok(int V, int F, int k, int N) { return V > 0 && F > 0 && k >= 0 && k <= V && N >= 1 && N <= kMaxBatch; }
 
-extern "C" size_t coma_app_objective_workspace_bytes(int V, int F, int k) {
-  if (V <= 0 || F <= 0 || k < 0 || k > V) return 0;
-  return layout(V, k).total;
-}
-
-extern "C" int coma_app_objective_f32(const float* verts, const int32_t* faces, const int32_t* vf_offsets, const int32_t* vf_faces, int V,
-                                      int F, const float* orientation_gt, const float* obj_normal, const float* principle_vec,
-                                      const float* sub_principle_vec, double eps, const int32_t* selected, const float* targets, int k,
-                                      float* terms, float* grad_orientation, float* grad_contact, void* workspace,
-                                      size_t workspace_bytes, void* stream) {
-  const char* who = "coma_app_objective_f32";
+// both entry points: the refusals in one order, then the launches of one body over a grid that has the bodies as its last dimension
+int objective_impl(const char* who, bool batched, int N, const float* verts, const int32_t* faces, const int32_t* vf_offsets,
+                   const int32_t* vf_faces, int V, int F, const float* orientation_gt, const float* obj_normal, const float* principle_vec,
+                   const float* sub_principle_vec, double eps, const int32_t* selected, const float* targets, int k, float* terms,
+                   float* grad_orientation, float* grad_contact, void* workspace, size_t workspace_bytes, void* stream) {
   if (!verts || !faces || !vf_offsets || !vf_faces || !orientation_gt || !obj_normal || !principle_vec || !sub_principle_vec || !terms ||
       !grad_orientation || !grad_contact || !workspace)
     return fail(COMA_E_INVALID, "%s: null pointer", who);
@@ -314,7 +341,8 @@ extern "C" int coma_app_objective_f32(const float* verts, const int32_t* faces, 
   if (k < 0 || k > V) return fail(COMA_E_INVALID, "%s: k=%d outside [0, V=%d]", who, k, V);
   if (k > 0 && (!selected || !targets)) return fail(COMA_E_INVALID, "%s: null pointer (selected / targets with k > 0)", who);
   if (!(eps >= 0.0) || !std::isfinite(eps)) return fail(COMA_E_INVALID, "%s: eps must be finite and >= 0", who);
-  const Layout L = layout(V, k);
+  if (batched && (N < 1 || N > kMaxBatch)) return fail(COMA_E_INVALID, "%s: N=%d outside [1, %d]", who, N, kMaxBatch);
+  const Layout L = layout(V, k, N);
   if (int rc = check_buffer(who, "workspace", workspace, workspace_bytes, L.total)) return rc;
 
   // the canonicalisation of one column b is linear in the normalised vertex normal: f = M a
@@ -341,24 +369,53 @@ extern "C" int coma_app_objective_f32(const float* verts, const int32_t* faces, 
   A.gN = (double*)(ws + L.gN); A.part_o = (double*)(ws + L.part_o);
   hipStream_t st = (hipStream_t)stream;
 
-  if (hipMemsetAsync(grad_contact, 0, (size_t)V * 3 * sizeof(float), st) != hipSuccess) return fail(COMA_E_LAUNCH, "%s: memset failed", who);
-  hipLaunchKernelGGL(app_vertex_kernel, dim3(L.nb_v), dim3(kBlock), 0, st, A);
-  hipLaunchKernelGGL(app_face_gather_kernel, dim3(L.nb_v), dim3(kBlock), 0, st, A, grad_orientation);
+  if (hipMemsetAsync(grad_contact, 0, (size_t)N * V * 3 * sizeof(float), st) != hipSuccess) return fail(COMA_E_LAUNCH, "%s: memset failed", who);
+  hipLaunchKernelGGL(app_vertex_kernel, dim3(L.nb_v, N), dim3(kBlock), 0, st, A);
+  hipLaunchKernelGGL(app_face_gather_kernel, dim3(L.nb_v, N), dim3(kBlock), 0, st, A, grad_orientation);
   if (k > 0) {
     ContactArgs C = {};
     C.verts = verts; C.sel = selected; C.targets = targets; C.V = V; C.k = k; C.nsplit = L.nsplit;
     float* pmin = (float*)(ws + L.pmin);
     int32_t* parg = (int32_t*)(ws + L.parg);
     C.pmin = pmin; C.parg = parg; C.dist = (double*)(ws + L.dist); C.arg = (int32_t*)(ws + L.arg); C.part_c = (double*)(ws + L.part_c);
-    const dim3 grid(L.row_blocks, L.nsplit);
-    const size_t half = (size_t)L.nsplit * k;
-    hipLaunchKernelGGL(app_rowmin_kernel, grid, dim3(kRowTile), 0, st, verts, selected, V, targets, (const int32_t*)nullptr, k, k, L.chunk,
-                       pmin, parg);
-    hipLaunchKernelGGL(app_rowmin_kernel, grid, dim3(kRowTile), 0, st, targets, (const int32_t*)nullptr, k, verts, selected, V, k, L.chunk,
-                       pmin + half, parg + half);
-    hipLaunchKernelGGL(app_contact_merge_kernel, dim3(L.nb_k), dim3(kBlock), 0, st, C);
-    hipLaunchKernelGGL(app_contact_grad_kernel, dim3(L.nb_k), dim3(kBlock), 0, st, C, grad_contact);
+    const dim3 grid(L.row_blocks, L.nsplit, N);
+    const int64_t half = (int64_t)L.nsplit * k, body = (int64_t)V * 3;
+    hipLaunchKernelGGL(app_rowmin_kernel, grid, dim3(kRowTile), 0, st, verts, selected, V, body, targets, (const int32_t*)nullptr, k, (int64_t)0,
+                       k, L.chunk, pmin, parg, 2 * half);
+    hipLaunchKernelGGL(app_rowmin_kernel, grid, dim3(kRowTile), 0, st, targets, (const int32_t*)nullptr, k, (int64_t)0, verts, selected, V, body,
+                       k, L.chunk, pmin + half, parg + half, 2 * half);
+    hipLaunchKernelGGL(app_contact_merge_kernel, dim3(L.nb_k, N), dim3(kBlock), 0, st, C);
+    hipLaunchKernelGGL(app_contact_grad_kernel, dim3(L.nb_k, N), dim3(kBlock), 0, st, C, grad_contact);
   }
-  hipLaunchKernelGGL(app_finalize_kernel, dim3(1), dim3(kBlock), 0, st, A.part_o, L.nb_v, V, (const double*)(ws + L.part_c), L.nb_k, k, terms);
+  hipLaunchKernelGGL(app_finalize_kernel, dim3(N), dim3(kBlock), 0, st, A.part_o, L.nb_v, V, (const double*)(ws + L.part_c), L.nb_k, k, terms);
   return check_launch(who);
+}
+
+}  // namespace
+}  // namespace coma
+
+using namespace coma;
+
+extern "C" size_t coma_app_objective_workspace_bytes(int V, int F, int k) { return sizes_ok(V, F, k, 1) ? layout(V, k).total : 0; }
+extern "C" size_t coma_app_objective_batch_workspace_bytes(int V, int F, int k, int N) {
+  return sizes_ok(V, F, k, N) ? layout(V, k, N).total : 0;
+}
+
+extern "C" int coma_app_objective_f32(const float* verts, const int32_t* faces, const int32_t* vf_offsets, const int32_t* vf_faces, int V,
+                                      int F, const float* orientation_gt, const float* obj_normal, const float* principle_vec,
+                                      const float* sub_principle_vec, double eps, const int32_t* selected, const float* targets, int k,
+                                      float* terms, float* grad_orientation, float* grad_contact, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+  return objective_impl("coma_app_objective_f32", false, 1, verts, faces, vf_offsets, vf_faces, V, F, orientation_gt, obj_normal, principle_vec,
+                        sub_principle_vec, eps, selected, targets, k, terms, grad_orientation, grad_contact, workspace, workspace_bytes, stream);
+}
+
+extern "C" int coma_app_objective_batch_f32(const float* verts, const int32_t* faces, const int32_t* vf_offsets, const int32_t* vf_faces,
+                                            int V, int F, const float* orientation_gt, const float* obj_normal, const float* principle_vec,
+                                            const float* sub_principle_vec, double eps, const int32_t* selected, const float* targets, int k,
+                                            int N, float* terms, float* grad_orientation, float* grad_contact, void* workspace,
+                                            size_t workspace_bytes, void* stream) {
+  return objective_impl("coma_app_objective_batch_f32", true, N, verts, faces, vf_offsets, vf_faces, V, F, orientation_gt, obj_normal,
+                        principle_vec, sub_principle_vec, eps, selected, targets, k, terms, grad_orientation, grad_contact, workspace,
+                        workspace_bytes, stream);
 }

@@ -506,6 +506,25 @@ int coma_app_objective_f32(const float* verts, const int32_t* faces, const int32
                            float* terms, float* grad_orientation, float* grad_contact, void* workspace, size_t workspace_bytes,
                            void* stream);
 
+/* The same objective for N bodies in one call: N posed meshes of one topology against one set of constants (several starts of one
+ * fit).  Rule set: the one above, per body -- body n of the batch has the BITS of coma_app_objective_f32 on body n's vertices: terms,
+ * both gradients, NaN for NaN.  The kernels are the single-body call's (which is this call with N = 1): the body is the last grid
+ * dimension and every workgroup works on one body, so no sum changes its shape.  The column split of the double minimum is chosen
+ * from N k (N bodies fill the device N times sooner); the merge takes (min, first argmin) in ascending split order on exact f32
+ * comparisons, so its result does not depend on the split.  A body's NaN stays in that body.
+ * Shared by all bodies: faces, vf_offsets, vf_faces, orientation_gt, obj_normal / principle_vec / sub_principle_vec (M), eps, selected,
+ * targets.  Per body: verts f32 [N][V,3]; terms f32 [N][2]; grad_orientation, grad_contact f32 [N][V,3], overwritten; every scratch
+ * array.  N in [1, 1024].  workspace: coma_app_objective_batch_workspace_bytes(V, F, k, N) bytes, 16-byte aligned (0 for sizes the call
+ * would refuse; at N = 1 the single-body size).  Refused before any launch, in the single-body call's order: what it refuses, then
+ * (after eps) N outside [1, 1024], then the workspace.  Seven kernel launches and one memset (of N V 3 floats) whatever N; no host
+ * synchronisation.  Per-body constants (other targets or another object normal per body) are not offered. */
+size_t coma_app_objective_batch_workspace_bytes(int V, int F, int k, int N);
+int coma_app_objective_batch_f32(const float* verts, const int32_t* faces, const int32_t* vf_offsets, const int32_t* vf_faces, int V, int F,
+                                 const float* orientation_gt, const float* obj_normal, const float* principle_vec,
+                                 const float* sub_principle_vec, double eps, const int32_t* selected, const float* targets, int k, int N,
+                                 float* terms, float* grad_orientation, float* grad_contact, void* workspace, size_t workspace_bytes,
+                                 void* stream);
+
 /* The SMPL-X body model: linear blend skinning of a V-vertex template over a J-joint tree, forward and backward (one body per
  * call; the batched calls follow this block).
  * replaces: the third-party `smplx` package behind the `body_model` hook of src/application/optimize.py (every iteration, forward

@@ -160,6 +160,22 @@ def app_objective():
         emit(f"app.k{k}.grad_contact", g_c)
 
 
+def app_objective_batch():
+    """N = 9 bodies (more than 8) of the k = 333 case above in one coma_app_objective_batch_f32 call, and the last body once as a row
+    of the batch and once through the single-body call: those two digests are equal."""
+    import torch
+    from coma_amd.app import ComaObjective
+    from tests import app_batch_ref as AB
+    from tests import app_ref as A
+    c = A.make_case(A.grid_mesh(20, seed=31), 333, seed=40 + 333)
+    obj = ComaObjective(c["faces"], c["gt"], c["obj_normals"][c["ref_index"]], c["sel"], c["obj_verts"][c["objects"]], c["p"], c["sub_p"], c["eps"], device=DEV)
+    verts = torch.as_tensor(AB.batch_vertices(c, 9, seed=47)).to(DEV)
+    for name, batched, single in zip(("terms", "grad_orientation", "grad_contact"), obj.evaluate(verts), obj.evaluate(verts[8])):
+        emit(f"app_batch.k333.{name}", batched)
+        emit(f"app_batch.k333.body8.{name}", batched[8])
+        emit(f"app_batch.k333.single8.{name}", single)
+
+
 def app_fit():
     """The fitting app's whole loop (coma_app_fit_f32) on the golden cases: 45 and 6 hand components, and no selected vertices."""
     from coma_amd.app import ComaObjective, DeviceFit
@@ -259,7 +275,7 @@ def main():
     from coma_amd import _lib
     assert torch.cuda.is_available(), "the digests are of device results"
     print(f"# library: {_lib.LIB_PATH}", file=sys.stderr)
-    for part in (smplx, smplx_full, smplx_batch, vposer, app_objective, app_fit, volumes_and_depth, row_reductions):
+    for part in (smplx, smplx_full, smplx_batch, vposer, app_objective, app_objective_batch, app_fit, volumes_and_depth, row_reductions):
         part()
     torch.cuda.synchronize()
 
