@@ -1,7 +1,9 @@
 // The fitting app's Adam loop (gfx950): E iterations of decode -> skin -> objective -> backward -> Adam enqueued by ONE call.  The rule
 // set is stated in include/coma_hip.h ("The fitting app's whole Adam loop") and restated in NumPy by tests/fit_ref.py.  Every stage
-// is the existing entry point (vposer.hip, smplx.hip, app_objective.hip), called from here on the caller's stream with buffers
-// carved from one workspace; the kernels of this file only move numbers between them and take the step:
+// is the existing entry point's two halves (fit_stages.h: vposer.hip, smplx.hip, app_objective.hip): its plan is made ONCE per call, on
+// buffers carved from one workspace -- the plans make the stages' refusals, under this call's name, so every refusal comes before the
+// first launch and none of them is written out again here -- and the loop only enqueues, on the caller's stream.  The kernels of this
+// file move numbers between the stages and take the step:
 //   assemble   p (f64, state) -> theta, z, transl (f32)                       one workgroup
 //   pose       aa -> theta's body_pose slot; the angle prior and its sum (f64)  one workgroup
 //   scale      vs = raw vertices * scale_factor (f32)                          3V elements
@@ -11,7 +13,7 @@
 // All are latency-bound launches; sums have a fixed shape (block_sum) and nothing is contracted into FMAs (-ffp-contract=off), so two
 // calls give the same bits.
 #include "coma_device.h"
-#include "common.h"
+#include "fit_stages.h"
 
 #include <cmath>
 
@@ -192,13 +194,13 @@ struct FitLayout {
   size_t sx_saved_bytes, sx_ws_bytes, vp_saved_bytes, vp_ws_bytes, obj_ws_bytes;
 };
 
-bool fit_layout(int V, int F, int J, int k, int H, int NJ, int n_theta, FitLayout& L) {
+bool fit_layout(int V, int F, int J, int k, int H, int NJ, long long n_theta, FitLayout& L) {
   L = FitLayout{};
   L.sx_saved_bytes = coma_smplx_saved_bytes(V, J), L.sx_ws_bytes = coma_smplx_workspace_bytes(V, J);
   L.vp_saved_bytes = coma_vposer_saved_bytes(1, H, NJ), L.vp_ws_bytes = coma_vposer_workspace_bytes(1, H, NJ);
   L.obj_ws_bytes = coma_app_objective_workspace_bytes(V, F, k);
   if (!L.sx_saved_bytes || !L.sx_ws_bytes || !L.vp_saved_bytes || !L.vp_ws_bytes || !L.obj_ws_bytes) return false;
-  if (n_theta < 3 * NJ + 3 + kLeadFixed || n_theta > 3 * NJ + 3 + kLeadFixed + 2 * kFitMaxHand) return false;
+  if (n_theta < 3 * NJ + 3 + kLeadFixed || n_theta > 3 * NJ + 3 + kLeadFixed + 2 * kFitMaxHand) return false;   // NJ <= 64 by now
   const size_t f = sizeof(float), n3 = (size_t)3 * V;
   Carve ws;
   L.theta = ws.take((size_t)n_theta * f);
@@ -253,58 +255,21 @@ extern "C" int coma_app_fit_f32(const coma_app_fit_desc* d, void* state, size_t 
                                 void* stream) {
   const char* who = "coma_app_fit_f32";
   if (!d || !state || !workspace) return fail(COMA_E_INVALID, "%s: null pointer", who);
-  if (!d->posedirs || !d->weights || !d->parents || !d->shape_state || !d->lead_fixed || !d->W1 || !d->b1 || !d->W2 || !d->b2 || !d->W3 || !d->b3 ||
-      !d->prior_index || !d->prior_sign || !d->faces || !d->vf_offsets || !d->vf_faces || !d->orientation_gt || !d->obj_normal ||
-      !d->principle_vec || !d->sub_principle_vec || !d->losses || !d->vertices)
+  if (!d->lead_fixed || !d->prior_index || !d->prior_sign || !d->losses)     // the fit's own; the stages' pointers are refused by their plans
     return fail(COMA_E_INVALID, "%s: null pointer", who);
   if (d->E < 1 || d->E > kFitMaxEpochs) return fail(COMA_E_INVALID, "%s: E=%d outside [1, %d]", who, d->E, kFitMaxEpochs);
   const int V = d->V, J = d->J, hd = d->hand_dim, n_pca = d->n_pca, D = d->D, H = d->H, NJ = d->NJ, K = d->prior_K, k = d->k, P = d->P;
   if (D < 1 || D > kFitMaxD) return fail(COMA_E_INVALID, "%s: D=%d outside [1, %d]", who, D, kFitMaxD);
-  if (J < 1 || n_pca < 0 || n_pca > 64 || hd < 0 || hd % 3 != 0 || 2 * (long long)hd > 3 * ((long long)J - 1))
-    return fail(COMA_E_INVALID, "%s: J=%d, hand_dim=%d (a multiple of 3 with 2 hand_dim <= 3 (J - 1)) or n_pca=%d (in [0, 64]) not accepted", who, J,
-                hd, n_pca);
-  if (n_pca > 0 && hd > 0 && !d->hand_components) return fail(COMA_E_INVALID, "%s: null pointer (hand_components with n_pca > 0)", who);
-  if (k > 0 && (!d->selected || !d->targets)) return fail(COMA_E_INVALID, "%s: null pointer (selected / targets with k > 0)", who);
   const int hs = (n_pca > 0 && hd > 0) ? n_pca : hd;
-  if (hs > kFitMaxHand) return fail(COMA_E_INVALID, "%s: %d entries per hand, at most %d", who, hs, kFitMaxHand);
-  if (NJ < 1 || 3 * (long long)NJ + 3 + kLeadFixed != 3 * (long long)J - 2 * (long long)hd)
-    return fail(COMA_E_INVALID, "%s: the decoder's 3 NJ = %d body-pose entries do not fill the model's 3 J - 2 hand_dim - 12 = %d", who, 3 * NJ,
-                3 * J - 2 * hd - 3 - kLeadFixed);
-  const int n_body = 3 * NJ, n_theta = n_body + 3 + kLeadFixed + 2 * hs;
-  if (P != 6 + 2 * hs + D) return fail(COMA_E_INVALID, "%s: P=%d, but 6 + 2 hs + D = %d (hs=%d, D=%d)", who, P, 6 + 2 * hs + D, hs, D);
+  if (hs < 0 || hs > kFitMaxHand) return fail(COMA_E_INVALID, "%s: %d entries per hand, outside [0, %d]", who, hs, kFitMaxHand);
+  // every carved field has the alignment of the block it is carved from: said of the caller's two blocks, not of a field
+  if (((uintptr_t)state & 15) != 0) return fail(COMA_E_INVALID, "%s: state must be 16-byte aligned", who);
+  if (((uintptr_t)workspace & 15) != 0) return fail(COMA_E_INVALID, "%s: workspace must be 16-byte aligned", who);
   FitLayout L;
-  if (!fit_layout(V, d->F, J, k, H, NJ, n_theta, L))
+  if (!fit_layout(V, d->F, J, k, H, NJ, 3 * (long long)NJ + 3 + kLeadFixed + 2 * hs, L))
     return fail(COMA_E_INVALID, "%s: sizes V=%d F=%d J=%d k=%d H=%d NJ=%d outside what the body model, the decoder or the objective accept", who, V,
                 d->F, J, k, H, NJ);
-  for (int i = 1; i < J; ++i)
-    if (d->parents[i] < 0 || d->parents[i] >= i) return fail(COMA_E_INVALID, "%s: parent %d of joint %d outside [0, %d)", who, d->parents[i], i, i);
-  PriorVec pv = {};
-  if (K < 1 || K > kFitMaxK) return fail(COMA_E_INVALID, "%s: prior_K=%d outside [1, %d]", who, K, kFitMaxK);
-  pv.K = K;
-  for (int i = 0; i < K; ++i) {
-    if (d->prior_index[i] < 0 || d->prior_index[i] >= n_body)
-      return fail(COMA_E_INVALID, "%s: prior_index[%d]=%d outside [0, %d)", who, i, d->prior_index[i], n_body);
-    pv.index[i] = d->prior_index[i], pv.sign[i] = d->prior_sign[i];
-  }
-  if (!(d->eps >= 0.0) || !std::isfinite(d->eps)) return fail(COMA_E_INVALID, "%s: eps must be finite and >= 0", who);
-  {   // the objective's own refusal, met here so that nothing has been launched when it is given
-    double u[2][3];
-    const float* src[2] = {d->principle_vec, d->sub_principle_vec};
-    for (int i = 0; i < 2; ++i) {
-      const double x = src[i][0], y = src[i][1], z = src[i][2];
-      const double n = std::sqrt((x * x + y * y) + z * z) + d->eps;
-      u[i][0] = x / n, u[i][1] = y / n, u[i][2] = z / n;
-    }
-    const double ps = (u[0][0] * u[1][0] + u[0][1] * u[1][1]) + u[0][2] * u[1][2];
-    if (!(std::fabs(ps) <= 1e-8)) return fail(COMA_E_INVALID, "%s: principle_vec and sub_principle_vec are not orthogonal", who);
-  }
-  for (double x : {d->lr, d->body_pose_weight, d->bending_prior_weight, d->pprior_weight, d->orientation_weight, d->contact_weight, d->scale_factor})
-    if (!std::isfinite(x)) return fail(COMA_E_INVALID, "%s: lr, the weights and scale_factor must be finite", who);
-  if (int rc = check_buffer(who, "state", state, state_bytes_, state_bytes(P))) return rc;
-  if (int rc = check_buffer(who, "workspace", workspace, workspace_bytes, L.total)) return rc;
-  if (((uintptr_t)d->shape_state & 15) != 0) return fail(COMA_E_INVALID, "%s: shape state must be 16-byte aligned", who);
-  if (((uintptr_t)d->traj & 7) || ((uintptr_t)d->losses & 7) || ((uintptr_t)d->grad0 & 7) || !f32_aligned({d->vertices, d->lead_fixed}))
-    return fail(COMA_E_INVALID, "%s: traj, losses, grad0 must be 8-byte and vertices, lead_fixed 4-byte aligned", who);
+  const int n_body = 3 * NJ;
 
   char* ws = (char*)workspace;
   hipStream_t st = (hipStream_t)stream;
@@ -313,6 +278,50 @@ extern "C" int coma_app_fit_f32(const coma_app_fit_desc* d, void* state, size_t 
   float *g_o = (float*)(ws + L.g_o), *g_c = (float*)(ws + L.g_c), *g = (float*)(ws + L.g);
   float *g_theta = (float*)(ws + L.g_theta), *g_transl = (float*)(ws + L.g_transl), *g_aa = (float*)(ws + L.g_aa), *g_z = (float*)(ws + L.g_z);
   double* prior = (double*)(ws + L.prior);
+
+  // the stages' plans, once: each makes its entry point's refusals; nothing is launched, no address is followed on the device
+  VposerDecodePlan decode;
+  SmplxForwardPlan forward;
+  AppObjectivePlan objective;
+  SmplxBackwardPlan backward;
+  VposerDecodeBackwardPlan decode_bwd;
+  if (int rc = vposer_decode_plan(who, z, d->W1, d->b1, d->W2, d->b2, d->W3, d->b3, 1, D, H, NJ, aa, nullptr, nullptr, ws + L.vp_saved, L.vp_saved_bytes,
+                                  decode))
+    return rc;
+  if (int rc = smplx_forward_plan(who, false, 1, 0, theta, transl, d->posedirs, d->weights, d->parents, d->hand_components, d->pose_mean, V, J, hd,
+                                  n_pca, d->shape_state, raw, joints, nullptr, ws + L.sx_saved, L.sx_saved_bytes, ws + L.sx_ws, L.sx_ws_bytes, forward))
+    return rc;
+  if (int rc = app_objective_plan(who, false, 1, d->vertices, d->faces, d->vf_offsets, d->vf_faces, V, d->F, d->orientation_gt, d->obj_normal,
+                                  d->principle_vec, d->sub_principle_vec, d->eps, d->selected, d->targets, k, terms, g_o, g_c, ws + L.obj_ws,
+                                  L.obj_ws_bytes, objective))
+    return rc;
+  if (int rc = smplx_backward_plan(who, false, 1, 0, g, d->posedirs, d->weights, d->parents, d->hand_components, V, J, hd, n_pca, d->shape_state,
+                                   ws + L.sx_saved, L.sx_saved_bytes, g_theta, g_transl, ws + L.sx_ws, L.sx_ws_bytes, nullptr, backward))
+    return rc;
+  if (int rc = vposer_decode_backward_plan(who, g_aa, d->W1, d->W2, d->W3, 1, D, H, NJ, ws + L.vp_saved, L.vp_saved_bytes, g_z, ws + L.vp_ws,
+                                           L.vp_ws_bytes, decode_bwd))
+    return rc;
+
+  // what ties the stages together, and the fit's own arguments
+  if (3 * (long long)NJ + 3 + kLeadFixed != 3 * (long long)J - 2 * (long long)hd)
+    return fail(COMA_E_INVALID, "%s: the decoder's 3 NJ = %d body-pose entries do not fill the model's 3 J - 2 hand_dim - 12 = %d", who, 3 * NJ,
+                3 * J - 2 * hd - 3 - kLeadFixed);
+  if (P != 6 + 2 * hs + D) return fail(COMA_E_INVALID, "%s: P=%d, but 6 + 2 hs + D = %d (hs=%d, D=%d)", who, P, 6 + 2 * hs + D, hs, D);
+  PriorVec pv = {};
+  if (K < 1 || K > kFitMaxK) return fail(COMA_E_INVALID, "%s: prior_K=%d outside [1, %d]", who, K, kFitMaxK);
+  pv.K = K;
+  for (int i = 0; i < K; ++i) {
+    if (d->prior_index[i] < 0 || d->prior_index[i] >= n_body)
+      return fail(COMA_E_INVALID, "%s: prior_index[%d]=%d outside [0, %d)", who, i, d->prior_index[i], n_body);
+    pv.index[i] = d->prior_index[i], pv.sign[i] = d->prior_sign[i];
+  }
+  for (double x : {d->lr, d->body_pose_weight, d->bending_prior_weight, d->pprior_weight, d->orientation_weight, d->contact_weight, d->scale_factor})
+    if (!std::isfinite(x)) return fail(COMA_E_INVALID, "%s: lr, the weights and scale_factor must be finite", who);
+  if (int rc = check_buffer(who, "state", state, state_bytes_, state_bytes(P))) return rc;
+  if (int rc = check_buffer(who, "workspace", workspace, workspace_bytes, L.total)) return rc;
+  if (((uintptr_t)d->traj & 7) || ((uintptr_t)d->losses & 7) || ((uintptr_t)d->grad0 & 7) || !f32_aligned({d->vertices, d->lead_fixed}))
+    return fail(COMA_E_INVALID, "%s: traj, losses, grad0 must be 8-byte and vertices, lead_fixed 4-byte aligned", who);
+
   const int n3 = 3 * V;
   const dim3 grid3((unsigned)((n3 + kFitBlock - 1) / kFitBlock)), block(kFitBlock);
   const float scale = (float)d->scale_factor, w_o = (float)d->orientation_weight, w_c = (float)d->contact_weight;
@@ -326,30 +335,20 @@ extern "C" int coma_app_fit_f32(const coma_app_fit_desc* d, void* state, size_t 
   for (int e = 0; e < d->E; ++e) {
     hipLaunchKernelGGL(fit_assemble_kernel, dim3(1), block, 0, st, (double*)state, P, hs, D, n_body, d->lead_fixed, theta, z, transl);
     if (int rc = check_launch("fit_assemble_kernel")) return rc;
-    if (int rc = coma_vposer_decode_f32(z, d->W1, d->b1, d->W2, d->b2, d->W3, d->b3, 1, D, H, NJ, aa, nullptr, nullptr, ws + L.vp_saved,
-                                        L.vp_saved_bytes, stream))
-      return rc;
+    if (int rc = vposer_decode_enqueue(decode, st)) return rc;
     hipLaunchKernelGGL(fit_pose_kernel, dim3(1), block, 0, st, (const float*)aa, n_body, pv, theta, prior);
     if (int rc = check_launch("fit_pose_kernel")) return rc;
-    if (int rc = coma_smplx_forward_f32(theta, transl, d->posedirs, d->weights, d->parents, d->hand_components, d->pose_mean, V, J, hd, n_pca,
-                                        d->shape_state, raw, joints, nullptr, ws + L.sx_saved, L.sx_saved_bytes, ws + L.sx_ws, L.sx_ws_bytes, stream))
-      return rc;
+    if (int rc = smplx_forward_enqueue(forward, st)) return rc;
     hipLaunchKernelGGL(fit_scale_kernel, grid3, block, 0, st, (const float*)raw, n3, scale, d->vertices);
     if (int rc = check_launch("fit_scale_kernel")) return rc;
-    if (int rc = coma_app_objective_f32(d->vertices, d->faces, d->vf_offsets, d->vf_faces, V, d->F, d->orientation_gt, d->obj_normal, d->principle_vec,
-                                        d->sub_principle_vec, d->eps, d->selected, d->targets, k, terms, g_o, g_c, ws + L.obj_ws, L.obj_ws_bytes, stream))
-      return rc;
+    if (int rc = app_objective_enqueue(objective, st)) return rc;
     hipLaunchKernelGGL(fit_seed_kernel, grid3, block, 0, st, (const float*)g_o, (const float*)g_c, n3, w_o, w_c, scale, g);
     if (int rc = check_launch("fit_seed_kernel")) return rc;
-    if (int rc = coma_smplx_backward_f32(g, d->posedirs, d->weights, d->parents, d->hand_components, V, J, hd, n_pca, d->shape_state, ws + L.sx_saved,
-                                         L.sx_saved_bytes, g_theta, g_transl, ws + L.sx_ws, L.sx_ws_bytes, stream))
-      return rc;
+    if (int rc = smplx_backward_enqueue(backward, st)) return rc;
     hipLaunchKernelGGL(fit_prior_grad_kernel, dim3((unsigned)((n_body + kFitBlock - 1) / kFitBlock)), block, 0, st, (const float*)aa,
                        (const float*)g_theta, n_body, pv, d->bending_prior_weight, g_aa);
     if (int rc = check_launch("fit_prior_grad_kernel")) return rc;
-    if (int rc = coma_vposer_decode_backward_f32(g_aa, d->W1, d->W2, d->W3, 1, D, H, NJ, ws + L.vp_saved, L.vp_saved_bytes, g_z, ws + L.vp_ws,
-                                                 L.vp_ws_bytes, stream))
-      return rc;
+    if (int rc = vposer_decode_backward_enqueue(decode_bwd, st)) return rc;
     sa.e = e;
     hipLaunchKernelGGL(fit_step_kernel, dim3(1), block, 0, st, sa);
     if (int rc = check_launch("fit_step_kernel")) return rc;

@@ -14,8 +14,8 @@
 // One kernel set for N bodies (coma_app_objective_batch_f32; coma_app_objective_f32 is N = 1): the last grid dimension is the body,
 // a workgroup moves its per-body pointers (vertices, gradients, every scratch array) to its body once and then runs the single
 // body's code, so body n has the single call's bits.  Topology, orientation targets, M, the selection and the targets are shared.
-#include "common.h"
 #include "coma_device.h"
+#include "fit_stages.h"
 
 #include <cmath>
 
@@ -25,19 +25,6 @@ namespace {
 constexpr int kRowTile = 64;      // rows per workgroup (one wave) and points per LDS stage of the double minimum
 constexpr int kBlock = 256;       // every other kernel
 constexpr int kMinGrid = 1024;    // workgroups the double minimum aims for (256 CUs x 4 SIMDs, one wave each)
-
-struct AppArgs {
-  const float* verts;
-  const int32_t* faces;
-  const int32_t* off;
-  const int32_t* vf;
-  const float* gt;
-  int V, F;
-  double M[9];     // f = M a (row-major), built on the host
-  double eps;
-  double* gN;      // [N][V,3] d term / d N_h
-  double* part_o;  // [N][ceil(V / 256)]
-};
 
 // the per-body arrays of a workgroup whose body is n (the vertex kernels: blockIdx.y, gridDim.x = ceil(V / 256))
 __device__ __forceinline__ void to_body(AppArgs& A, int n) {
@@ -179,18 +166,6 @@ __global__ __launch_bounds__(kRowTile) void app_rowmin_kernel(const float* __res
   }
 }
 
-struct ContactArgs {
-  const float* verts;
-  const int32_t* sel;
-  const float* targets;
-  int V, k, nsplit;
-  const float* pmin;     // [N][2][nsplit][k]
-  const int32_t* parg;   // [N][2][nsplit][k]
-  double* dist;          // [N][2][k]  |A_i - B_argmin| and |A_argmin - B_j| in f64
-  int32_t* arg;          // [N][2][k]
-  double* part_c;        // [N][2][ceil(k / 256)]
-};
-
 // the per-body arrays of a workgroup whose body is n (the contact kernels: blockIdx.y, gridDim.x = ceil(k / 256))
 __device__ __forceinline__ void to_body(ContactArgs& C, int n) {
   C.verts += (int64_t)n * C.V * 3;
@@ -329,11 +304,13 @@ constexpr int kMaxBatch = 1024;   // N: bodies per call, the body model's bound
 
 bool sizes_ok(int V, int F, int k, int N) { return V > 0 && F > 0 && k >= 0 && k <= V && N >= 1 && N <= kMaxBatch; }
 
-// both entry points: the refusals in one order, then the launches of one body over a grid that has the bodies as its last dimension
-int objective_impl(const char* who, bool batched, int N, const float* verts, const int32_t* faces, const int32_t* vf_offsets,
-                   const int32_t* vf_faces, int V, int F, const float* orientation_gt, const float* obj_normal, const float* principle_vec,
-                   const float* sub_principle_vec, double eps, const int32_t* selected, const float* targets, int k, float* terms,
-                   float* grad_orientation, float* grad_contact, void* workspace, size_t workspace_bytes, void* stream) {
+}  // namespace
+
+// both entry points: the refusals in one order, M, and the arguments of one body's launches
+int app_objective_plan(const char* who, bool batched, int N, const float* verts, const int32_t* faces, const int32_t* vf_offsets,
+                       const int32_t* vf_faces, int V, int F, const float* orientation_gt, const float* obj_normal, const float* principle_vec,
+                       const float* sub_principle_vec, double eps, const int32_t* selected, const float* targets, int k, float* terms,
+                       float* grad_orientation, float* grad_contact, void* workspace, size_t workspace_bytes, AppObjectivePlan& p) {
   if (!verts || !faces || !vf_offsets || !vf_faces || !orientation_gt || !obj_normal || !principle_vec || !sub_principle_vec || !terms ||
       !grad_orientation || !grad_contact || !workspace)
     return fail(COMA_E_INVALID, "%s: null pointer", who);
@@ -346,52 +323,59 @@ int objective_impl(const char* who, bool batched, int N, const float* verts, con
   if (int rc = check_buffer(who, "workspace", workspace, workspace_bytes, L.total)) return rc;
 
   // the canonicalisation of one column b is linear in the normalised vertex normal: f = M a
-  double b[3], p[3], s[3];
+  double b[3], pv[3], s[3];
   unit_host(obj_normal, eps, b);
-  unit_host(principle_vec, eps, p);
+  unit_host(principle_vec, eps, pv);
   unit_host(sub_principle_vec, eps, s);
-  const double ps = (p[0] * s[0] + p[1] * s[1]) + p[2] * s[2];
+  const double ps = (pv[0] * s[0] + pv[1] * s[1]) + pv[2] * s[2];
   if (!(std::fabs(ps) <= 1e-8)) return fail(COMA_E_INVALID, "%s: principle_vec and sub_principle_vec are not orthogonal", who);
-  const double bp = (b[0] * p[0] + b[1] * p[1]) + b[2] * p[2];
-  AppArgs A = {};
+  const double bp = (b[0] * pv[0] + b[1] * pv[1]) + b[2] * pv[2];
+  p = {};
+  AppArgs& A = p.vertex;
   if (1.0 + bp < eps) {                                 // b opposite to p: 2 (a.s) s - a
     for (int i = 0; i < 3; ++i)
       for (int j = 0; j < 3; ++j) A.M[3 * i + j] = 2.0 * s[i] * s[j] - (i == j ? 1.0 : 0.0);
   } else {
     // the reference's b_cross as written: [0][0] = b0 is set and [2][1] = b0 is not
-    const double c[3] = {(b[0] * p[0] - b[2] * p[1]) + b[1] * p[2], b[2] * p[0] - b[0] * p[2], -b[1] * p[0]};
+    const double c[3] = {(b[0] * pv[0] - b[2] * pv[1]) + b[1] * pv[2], b[2] * pv[0] - b[0] * pv[2], -b[1] * pv[0]};
     for (int i = 0; i < 3; ++i)
       for (int j = 0; j < 3; ++j)
-        A.M[3 * i + j] = c[i] * c[j] / (1.0 + bp) + (i == j ? bp : 0.0) + p[i] * b[j] - b[i] * p[j];
+        A.M[3 * i + j] = c[i] * c[j] / (1.0 + bp) + (i == j ? bp : 0.0) + pv[i] * b[j] - b[i] * pv[j];
   }
   char* ws = (char*)workspace;
   A.verts = verts; A.faces = faces; A.off = vf_offsets; A.vf = vf_faces; A.gt = orientation_gt; A.V = V; A.F = F; A.eps = eps;
   A.gN = (double*)(ws + L.gN); A.part_o = (double*)(ws + L.part_o);
-  hipStream_t st = (hipStream_t)stream;
-
-  if (hipMemsetAsync(grad_contact, 0, (size_t)N * V * 3 * sizeof(float), st) != hipSuccess) return fail(COMA_E_LAUNCH, "%s: memset failed", who);
-  hipLaunchKernelGGL(app_vertex_kernel, dim3(L.nb_v, N), dim3(kBlock), 0, st, A);
-  hipLaunchKernelGGL(app_face_gather_kernel, dim3(L.nb_v, N), dim3(kBlock), 0, st, A, grad_orientation);
-  if (k > 0) {
-    ContactArgs C = {};
-    C.verts = verts; C.sel = selected; C.targets = targets; C.V = V; C.k = k; C.nsplit = L.nsplit;
-    float* pmin = (float*)(ws + L.pmin);
-    int32_t* parg = (int32_t*)(ws + L.parg);
-    C.pmin = pmin; C.parg = parg; C.dist = (double*)(ws + L.dist); C.arg = (int32_t*)(ws + L.arg); C.part_c = (double*)(ws + L.part_c);
-    const dim3 grid(L.row_blocks, L.nsplit, N);
-    const int64_t half = (int64_t)L.nsplit * k, body = (int64_t)V * 3;
-    hipLaunchKernelGGL(app_rowmin_kernel, grid, dim3(kRowTile), 0, st, verts, selected, V, body, targets, (const int32_t*)nullptr, k, (int64_t)0,
-                       k, L.chunk, pmin, parg, 2 * half);
-    hipLaunchKernelGGL(app_rowmin_kernel, grid, dim3(kRowTile), 0, st, targets, (const int32_t*)nullptr, k, (int64_t)0, verts, selected, V, body,
-                       k, L.chunk, pmin + half, parg + half, 2 * half);
-    hipLaunchKernelGGL(app_contact_merge_kernel, dim3(L.nb_k, N), dim3(kBlock), 0, st, C);
-    hipLaunchKernelGGL(app_contact_grad_kernel, dim3(L.nb_k, N), dim3(kBlock), 0, st, C, grad_contact);
-  }
-  hipLaunchKernelGGL(app_finalize_kernel, dim3(N), dim3(kBlock), 0, st, A.part_o, L.nb_v, V, (const double*)(ws + L.part_c), L.nb_k, k, terms);
-  return check_launch(who);
+  p.who = who; p.N = N; p.nb_v = L.nb_v; p.nb_k = L.nb_k; p.row_blocks = L.row_blocks; p.chunk = L.chunk;
+  p.pmin = (float*)(ws + L.pmin); p.parg = (int32_t*)(ws + L.parg);
+  p.terms = terms; p.grad_orientation = grad_orientation; p.grad_contact = grad_contact;
+  ContactArgs& C = p.contact;
+  C.verts = verts; C.sel = selected; C.targets = targets; C.V = V; C.k = k; C.nsplit = L.nsplit;
+  C.pmin = p.pmin; C.parg = p.parg; C.dist = (double*)(ws + L.dist); C.arg = (int32_t*)(ws + L.arg); C.part_c = (double*)(ws + L.part_c);
+  return COMA_OK;
 }
 
-}  // namespace
+// the launches of one body over a grid that has the bodies as its last dimension
+int app_objective_enqueue(const AppObjectivePlan& p, hipStream_t st) {
+  const AppArgs& A = p.vertex;
+  const ContactArgs& C = p.contact;
+  const int N = p.N, V = A.V, k = C.k;
+  if (hipMemsetAsync(p.grad_contact, 0, (size_t)N * V * 3 * sizeof(float), st) != hipSuccess) return fail(COMA_E_LAUNCH, "%s: memset failed", p.who);
+  hipLaunchKernelGGL(app_vertex_kernel, dim3(p.nb_v, N), dim3(kBlock), 0, st, A);
+  hipLaunchKernelGGL(app_face_gather_kernel, dim3(p.nb_v, N), dim3(kBlock), 0, st, A, p.grad_orientation);
+  if (k > 0) {
+    const dim3 grid(p.row_blocks, C.nsplit, N);
+    const int64_t half = (int64_t)C.nsplit * k, body = (int64_t)V * 3;
+    hipLaunchKernelGGL(app_rowmin_kernel, grid, dim3(kRowTile), 0, st, C.verts, C.sel, V, body, C.targets, (const int32_t*)nullptr, k, (int64_t)0,
+                       k, p.chunk, p.pmin, p.parg, 2 * half);
+    hipLaunchKernelGGL(app_rowmin_kernel, grid, dim3(kRowTile), 0, st, C.targets, (const int32_t*)nullptr, k, (int64_t)0, C.verts, C.sel, V, body,
+                       k, p.chunk, p.pmin + half, p.parg + half, 2 * half);
+    hipLaunchKernelGGL(app_contact_merge_kernel, dim3(p.nb_k, N), dim3(kBlock), 0, st, C);
+    hipLaunchKernelGGL(app_contact_grad_kernel, dim3(p.nb_k, N), dim3(kBlock), 0, st, C, p.grad_contact);
+  }
+  hipLaunchKernelGGL(app_finalize_kernel, dim3(N), dim3(kBlock), 0, st, (const double*)A.part_o, p.nb_v, V, (const double*)C.part_c, p.nb_k, k, p.terms);
+  return check_launch(p.who);
+}
+
 }  // namespace coma
 
 using namespace coma;
@@ -406,8 +390,11 @@ extern "C" int coma_app_objective_f32(const float* verts, const int32_t* faces, 
                                       const float* sub_principle_vec, double eps, const int32_t* selected, const float* targets, int k,
                                       float* terms, float* grad_orientation, float* grad_contact, void* workspace,
                                       size_t workspace_bytes, void* stream) {
-  return objective_impl("coma_app_objective_f32", false, 1, verts, faces, vf_offsets, vf_faces, V, F, orientation_gt, obj_normal, principle_vec,
-                        sub_principle_vec, eps, selected, targets, k, terms, grad_orientation, grad_contact, workspace, workspace_bytes, stream);
+  AppObjectivePlan p;
+  if (int rc = app_objective_plan("coma_app_objective_f32", false, 1, verts, faces, vf_offsets, vf_faces, V, F, orientation_gt, obj_normal, principle_vec,
+                                  sub_principle_vec, eps, selected, targets, k, terms, grad_orientation, grad_contact, workspace, workspace_bytes, p))
+    return rc;
+  return app_objective_enqueue(p, (hipStream_t)stream);
 }
 
 extern "C" int coma_app_objective_batch_f32(const float* verts, const int32_t* faces, const int32_t* vf_offsets, const int32_t* vf_faces,
@@ -415,7 +402,10 @@ extern "C" int coma_app_objective_batch_f32(const float* verts, const int32_t* f
                                             const float* sub_principle_vec, double eps, const int32_t* selected, const float* targets, int k,
                                             int N, float* terms, float* grad_orientation, float* grad_contact, void* workspace,
                                             size_t workspace_bytes, void* stream) {
-  return objective_impl("coma_app_objective_batch_f32", true, N, verts, faces, vf_offsets, vf_faces, V, F, orientation_gt, obj_normal,
-                        principle_vec, sub_principle_vec, eps, selected, targets, k, terms, grad_orientation, grad_contact, workspace,
-                        workspace_bytes, stream);
+  AppObjectivePlan p;
+  if (int rc = app_objective_plan("coma_app_objective_batch_f32", true, N, verts, faces, vf_offsets, vf_faces, V, F, orientation_gt, obj_normal,
+                                  principle_vec, sub_principle_vec, eps, selected, targets, k, terms, grad_orientation, grad_contact, workspace,
+                                  workspace_bytes, p))
+    return rc;
+  return app_objective_enqueue(p, (hipStream_t)stream);
 }

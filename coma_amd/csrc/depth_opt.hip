@@ -266,11 +266,38 @@ __device__ __forceinline__ void adam_step(double g, double d, double lr, int e, 
   if (!__builtin_isfinite(next) && !((long long*)state)[kStStatus]) ((long long*)state)[kStStatus] = 1, ((long long*)state)[kStEpoch] = e + 1;
 }
 
-__global__ __launch_bounds__(256) void depth_step_kernel(const char* __restrict__ ws, const double* __restrict__ views,
-                                                         const double* __restrict__ joints0, double f0, double f1, double f2,
-                                                         const int* __restrict__ cand_view, int n_views, const double* __restrict__ cand_xy,
-                                                         int N, int J, double lr, double w_multiview, double w_collision, int e, double* __restrict__ traj,
-                                                         const long long* __restrict__ Ltraj, double* __restrict__ losses,
+// Where an epoch's collision term {value, d value / d d} comes from; each source's arithmetic is its own.
+// The shift profile: Ltraj[e] = the three lengths of this epoch, written by the profile launch; L_A and the scale from the workspace
+struct ShiftSource {
+  const char* ws;            // null: no collision term
+  const long long* Ltraj;
+  __device__ __forceinline__ void term(int e, double w_collision, double* value, double* slope) const {
+    double ratio = 0.0, sl = 0.0;
+    if (ws && w_collision != 0.0) {
+      const long long la = ((const long long*)(ws + kParamBytes))[kHdrSums + 1];
+      if (la != 0) {
+        const long long* l = Ltraj + 3 * (int64_t)e;
+        ratio = (double)l[1] / (double)la;
+        sl = ((double)(l[2] - l[0]) * (256.0 * ((const ShiftParams*)ws)->s)) / (2.0 * (double)la);
+      }
+    }
+    *value = ratio, *slope = sl;
+  }
+};
+
+// COAP: Ctraj[e] = {loss, d loss / d d} of this epoch, written by the collision launches
+struct CoapSource {
+  const double* Ctraj;
+  __device__ __forceinline__ void term(int e, double w_collision, double* value, double* slope) const {
+    *value = w_collision != 0.0 ? Ctraj[2 * e] : 0.0, *slope = w_collision != 0.0 ? Ctraj[2 * e + 1] : 0.0;
+  }
+};
+
+template <typename Source>
+__global__ __launch_bounds__(256) void depth_step_kernel(Source source, const double* __restrict__ views, const double* __restrict__ joints0, double f0,
+                                                         double f1, double f2, const int* __restrict__ cand_view, int n_views,
+                                                         const double* __restrict__ cand_xy, int N, int J, double lr, double w_multiview,
+                                                         double w_collision, int e, double* __restrict__ traj, double* __restrict__ losses,
                                                          double* __restrict__ state) {
   __shared__ double lds[256];
   const long long stopped = ((const long long*)state)[kStStatus];
@@ -280,36 +307,26 @@ __global__ __launch_bounds__(256) void depth_step_kernel(const char* __restrict_
   double loss, grad;
   if (multiview_term(views, joints0, f0, f1, f2, cand_view, n_views, cand_xy, N, J, e, d, state, lds, &loss, &grad)) return;   // status 3: losses, traj, Adam untouched
   if (threadIdx.x != 0) return;
-  double ratio = 0.0, slope = 0.0;
-  if (ws && w_collision != 0.0) {
-    const long long la = ((const long long*)(ws + kParamBytes))[kHdrSums + 1];
-    if (la != 0) {
-      const long long* l = Ltraj + 3 * (int64_t)e;
-      ratio = (double)l[1] / (double)la;
-      slope = ((double)(l[2] - l[0]) * (256.0 * ((const ShiftParams*)ws)->s)) / (2.0 * (double)la);
-    }
-  }
-  losses[2 * e] = loss, losses[2 * e + 1] = ratio;
+  double value, slope;
+  source.term(e, w_collision, &value, &slope);
+  losses[2 * e] = loss, losses[2 * e + 1] = value;
   adam_step(w_multiview * grad + w_collision * slope, d, lr, e, traj, state);
 }
 
-// The same step with COAP's collision term: Ctraj[e] = {loss, d loss / d d} of this epoch, written by the collision launches
-__global__ __launch_bounds__(256) void depth_step_coap_kernel(const double* __restrict__ views, const double* __restrict__ joints0, double f0, double f1,
-                                                              double f2, const int* __restrict__ cand_view, int n_views,
-                                                              const double* __restrict__ cand_xy, int N, int J, double lr, double w_multiview,
-                                                              double w_collision, int e, double* __restrict__ traj, const double* __restrict__ Ctraj,
-                                                              double* __restrict__ losses, double* __restrict__ state) {
-  __shared__ double lds[256];
-  const long long stopped = ((const long long*)state)[kStStatus];
-  __syncthreads();
-  if (stopped) return;
-  const double d = traj[e];
-  double loss, grad;
-  if (multiview_term(views, joints0, f0, f1, f2, cand_view, n_views, cand_xy, N, J, e, d, state, lds, &loss, &grad)) return;   // status 3: losses, traj, Adam untouched
-  if (threadIdx.x != 0) return;
-  const double term = w_collision != 0.0 ? Ctraj[2 * e] : 0.0, slope = w_collision != 0.0 ? Ctraj[2 * e + 1] : 0.0;
-  losses[2 * e] = loss, losses[2 * e + 1] = term;
-  adam_step(w_multiview * grad + w_collision * slope, d, lr, e, traj, state);
+// what both optimisers refuse of the arguments they share (no launch)
+static int depth_optimize_check(const char* who, const double* views, int n_views, const double* joints0, const double* front, const int32_t* cand_view,
+                                const double* cand_xy, int N, int J, double d0, double lr, double w_multiview, double w_collision, int E,
+                                const double* traj, const double* losses, const void* state) {
+  if (!front || !traj || !losses || !state) return fail(COMA_E_INVALID, "%s: null pointer", who);
+  if (E < 1 || E > kMaxEpochs) return fail(COMA_E_INVALID, "%s: E=%d outside [1, %d]", who, E, kMaxEpochs);
+  if (N < 0 || N > kMaxInliers || J < 1 || J > kMaxJoints || n_views < 0)
+    return fail(COMA_E_INVALID, "%s: N=%d outside [0, %d], J=%d outside [1, %d] or n_views=%d < 0", who, N, kMaxInliers, J, kMaxJoints, n_views);
+  if (N > 0 && (!views || !joints0 || !cand_view || !cand_xy || n_views < 1))
+    return fail(COMA_E_INVALID, "%s: null pointer (views, joints0, cand_view, cand_xy are read when N > 0)", who);
+  if (!__builtin_isfinite(d0) || !__builtin_isfinite(lr) || !__builtin_isfinite(w_multiview) || !__builtin_isfinite(w_collision) ||
+      !__builtin_isfinite(front[0]) || !__builtin_isfinite(front[1]) || !__builtin_isfinite(front[2]))
+    return fail(COMA_E_INVALID, "%s: d0, lr, the weights and front must be finite", who);
+  return COMA_OK;
 }
 
 static int read_status(const void* hdr, void* stream, int64_t* needed, const char* who) {
@@ -396,27 +413,20 @@ extern "C" size_t coma_depth_optimize_state_bytes(void) { return 64; }
 extern "C" int coma_depth_optimize_f64(const void* workspace, const double* views, int n_views, const double* joints0, const double* front,
                                        const int32_t* cand_view, const double* cand_xy, int N, int J, double d0, double lr, double w_multiview,
                                        double w_collision, int E, double* traj, int64_t* Ltraj, double* losses, void* state, void* stream) {
-  if (!front || !traj || !losses || !state) return fail(COMA_E_INVALID, "coma_depth_optimize_f64: null pointer");
-  if (E < 1 || E > kMaxEpochs) return fail(COMA_E_INVALID, "coma_depth_optimize_f64: E=%d outside [1, %d]", E, kMaxEpochs);
-  if (N < 0 || N > kMaxInliers || J < 1 || J > kMaxJoints || n_views < 0)
-    return fail(COMA_E_INVALID, "coma_depth_optimize_f64: N=%d outside [0, %d], J=%d outside [1, %d] or n_views=%d < 0", N, kMaxInliers, J, kMaxJoints,
-                n_views);
-  if (N > 0 && (!views || !joints0 || !cand_view || !cand_xy || n_views < 1))
-    return fail(COMA_E_INVALID, "coma_depth_optimize_f64: null pointer (views, joints0, cand_view, cand_xy are read when N > 0)");
-  if (!__builtin_isfinite(d0) || !__builtin_isfinite(lr) || !__builtin_isfinite(w_multiview) || !__builtin_isfinite(w_collision) ||
-      !__builtin_isfinite(front[0]) || !__builtin_isfinite(front[1]) || !__builtin_isfinite(front[2]))
-    return fail(COMA_E_INVALID, "coma_depth_optimize_f64: d0, lr, the weights and front must be finite");
+  const char* who = "coma_depth_optimize_f64";
+  if (int rc = depth_optimize_check(who, views, n_views, joints0, front, cand_view, cand_xy, N, J, d0, lr, w_multiview, w_collision, E, traj, losses, state))
+    return rc;
   const char* ws = (workspace && w_collision != 0.0) ? (const char*)workspace : nullptr;
-  if (ws && !Ltraj) return fail(COMA_E_INVALID, "coma_depth_optimize_f64: Ltraj is written when the collision term is on");
-  if (((uintptr_t)workspace % 16) || ((uintptr_t)state % 8)) return fail(COMA_E_INVALID, "coma_depth_optimize_f64: workspace 16-byte, state 8-byte aligned");
+  if (ws && !Ltraj) return fail(COMA_E_INVALID, "%s: Ltraj is written when the collision term is on", who);
+  if (((uintptr_t)workspace % 16) || ((uintptr_t)state % 8)) return fail(COMA_E_INVALID, "%s: workspace 16-byte, state 8-byte aligned", who);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(depth_init_kernel, dim3(1), dim3(256), 0, st, ws, d0, traj, (long long*)Ltraj, E, (double*)state);
   if (int rc = check_launch("depth_init_kernel")) return rc;
   for (int e = 0; e < E; ++e) {
     if (ws)
       if (int rc = profile_launch(ws, traj + e, 1, (long long*)Ltraj + 3 * (int64_t)e, (const long long*)state, st)) return rc;
-    hipLaunchKernelGGL(depth_step_kernel, dim3(1), dim3(256), 0, st, ws, views, joints0, front[0], front[1], front[2], cand_view, n_views, cand_xy, N, J, lr,
-                       w_multiview, w_collision, e, traj, (const long long*)Ltraj, losses, (double*)state);
+    hipLaunchKernelGGL(depth_step_kernel<ShiftSource>, dim3(1), dim3(256), 0, st, ShiftSource{ws, (const long long*)Ltraj}, views, joints0, front[0], front[1],
+                       front[2], cand_view, n_views, cand_xy, N, J, lr, w_multiview, w_collision, e, traj, losses, (double*)state);
     if (int rc = check_launch("depth_step_kernel")) return rc;
   }
   return COMA_OK;
@@ -428,15 +438,8 @@ extern "C" int coma_depth_optimize_coap_f64(const float* weights, size_t weights
                                             double d0, double lr, double w_multiview, double w_collision, int E, double* traj, double* Ctraj,
                                             double* losses, void* state, void* stream) {
   const char* who = "coma_depth_optimize_coap_f64";
-  if (!front || !traj || !losses || !state) return fail(COMA_E_INVALID, "%s: null pointer", who);
-  if (E < 1 || E > kMaxEpochs) return fail(COMA_E_INVALID, "%s: E=%d outside [1, %d]", who, E, kMaxEpochs);
-  if (N < 0 || N > kMaxInliers || J < 1 || J > kMaxJoints || n_views < 0)
-    return fail(COMA_E_INVALID, "%s: N=%d outside [0, %d], J=%d outside [1, %d] or n_views=%d < 0", who, N, kMaxInliers, J, kMaxJoints, n_views);
-  if (N > 0 && (!views || !joints0 || !cand_view || !cand_xy || n_views < 1))
-    return fail(COMA_E_INVALID, "%s: null pointer (views, joints0, cand_view, cand_xy are read when N > 0)", who);
-  if (!__builtin_isfinite(d0) || !__builtin_isfinite(lr) || !__builtin_isfinite(w_multiview) || !__builtin_isfinite(w_collision) ||
-      !__builtin_isfinite(front[0]) || !__builtin_isfinite(front[1]) || !__builtin_isfinite(front[2]))
-    return fail(COMA_E_INVALID, "%s: d0, lr, the weights and front must be finite", who);
+  if (int rc = depth_optimize_check(who, views, n_views, joints0, front, cand_view, cand_xy, N, J, d0, lr, w_multiview, w_collision, E, traj, losses, state))
+    return rc;
   const bool collide = w_collision != 0.0;
   if (collide) {
     if (!Ctraj) return fail(COMA_E_INVALID, "%s: Ctraj is written when the collision term is on", who);
@@ -453,9 +456,9 @@ extern "C" int coma_depth_optimize_coap_f64(const float* weights, size_t weights
       if (int rc = coap_collision_launch(weights, code, K, points, T, traj + e, front, filter_threshold, Ctraj + 2 * (int64_t)e, nullptr, coap_workspace,
                                          (const long long*)state, st))
         return rc;
-    hipLaunchKernelGGL(depth_step_coap_kernel, dim3(1), dim3(256), 0, st, views, joints0, front[0], front[1], front[2], cand_view, n_views, cand_xy, N, J, lr,
-                       w_multiview, w_collision, e, traj, (const double*)Ctraj, losses, (double*)state);
-    if (int rc = check_launch("depth_step_coap_kernel")) return rc;
+    hipLaunchKernelGGL(depth_step_kernel<CoapSource>, dim3(1), dim3(256), 0, st, CoapSource{Ctraj}, views, joints0, front[0], front[1], front[2], cand_view,
+                       n_views, cand_xy, N, J, lr, w_multiview, w_collision, e, traj, losses, (double*)state);
+    if (int rc = check_launch("depth_step_kernel")) return rc;
   }
   return COMA_OK;
 }

@@ -31,15 +31,14 @@
 // in LDS, one f64 sum per body in registers), a skinning workgroup stages its weights tile once and walks B bodies over it, the pose
 // stage runs one workgroup per body.  C and B are template arguments: kChunk and kSkinChunk, and 1 at N = 1, where the compiler then
 // gives the code of a kernel written for one body (Layout picks them and the grids that go with them).
-#include "common.h"
 #include "coma_device.h"
+#include "fit_stages.h"
 
 #include <cmath>
 
 namespace coma {
 namespace {
 
-constexpr int kMaxJ = 64;         // joints (the chain kernels keep the whole tree in LDS)
 constexpr int kBlock = 256;
 constexpr int kTile = 128;        // vertices (and threads) per skinning workgroup: weights tile 128 x 64 f32 = 32 KB of LDS
 constexpr int kPSplit = 8;        // splits of the P rows of posedirs in the forward
@@ -48,8 +47,6 @@ constexpr int kMaxPca = 64;
 constexpr int kMaxBatch = 1024;   // N: bodies per call (coma_smplx_*_batch_f32; the single-body entry points are N = 1)
 constexpr int kChunk = 8;         // C: bodies served by one sweep over posedirs (16 VGPRs of f64 sums per thread; forward LDS 71 x 8 f64)
 constexpr int kSkinChunk = 2;     // bodies one skinning workgroup walks over its staged weights tile
-
-struct Tree { int32_t parent[kMaxJ]; };
 
 // ---- shape stage ----
 __global__ __launch_bounds__(kBlock) void smplx_shape_kernel(const float* __restrict__ v_template, const float* __restrict__ shapedirs,
@@ -158,13 +155,6 @@ __device__ __forceinline__ void pose_chain(const double* pose, const double* __r
   }
 }
 
-// How a kernel finds body n of N from body 0's pointers: the f32 arrays and the workspace blocks are dense [N, ...]; the shape
-// states and saved blocks are `shape` / `saved` bytes apart.
-struct BatchStrides {
-  int N, NT;                // bodies; entries of one body's theta
-  size_t shape, saved;      // bytes; shape = 0: one shape state for all bodies
-};
-
 template <typename T>
 __device__ __forceinline__ T* at_bytes(T* p, size_t bytes) {
   return (T*)((char*)p + bytes);
@@ -173,21 +163,6 @@ template <typename T>
 __device__ __forceinline__ const T* at_bytes(const T* p, size_t bytes) {
   return (const T*)((const char*)p + bytes);
 }
-
-struct PoseArgs {           // the pointers are body 0's
-  const float* theta;
-  const float* comps;     // [2, n_pca, hd]
-  const float* mean;      // [3J] or null
-  const float* transl;    // [3] or null
-  const double* j_rest;
-  int J, hd, n_pca;
-  Tree tree;
-  double* s_pose;         // saved [3J]
-  double* s_A;            // saved [J,12]
-  double* feat;           // workspace [9 (J - 1)]
-  float* joints;          // [J,3]
-  float* full_pose;       // [3J] or null
-};
 
 // what differs from body to body
 struct PoseBody {
@@ -276,17 +251,6 @@ __global__ __launch_bounds__(kBlock) void smplx_offsets_kernel(const float* __re
   for (int c = 0; c < C; ++c)
     if (C == 1 || c < nc) part[((int64_t)(n0 + c) * kPSplit + s) * n3 + i] = acc[c];
 }
-
-struct SkinArgs {           // the pointers are body 0's
-  const float* weights;     // [V,J]
-  const double* A;          // [J,12]
-  const double* v_shaped;   // [V,3]
-  const double* part;       // [kPSplit][3V]
-  const float* transl;      // [3] or null
-  int V, J;
-  double* v_posed;          // saved [V,3]
-  float* vertices;          // [V,3]
-};
 
 // the weights of this workgroup's tile of vertices (one contiguous run of the [V,J] table) into LDS (no barrier: the first stage_A
 // gives it) -> the vertices in the tile
@@ -448,24 +412,6 @@ __global__ __launch_bounds__(kBlock) void smplx_feature_bwd_kernel(const float* 
       if (threadIdx.x == 0) dfeat[(int64_t)(n0 + c) * P + blockIdx.x] = s;
     }
 }
-
-struct PoseBwdArgs {        // the pointers are body 0's
-  const double* s_pose;
-  const double* j_rest;
-  const float* comps;
-  const double* dA_part;
-  const double* dfeat;
-  int J, hd, n_pca, nblk;
-  Tree tree;
-  float* grad_theta;
-  float* grad_transl;
-  // the full backward's additions; each pointer may be null and then changes nothing
-  const float* gJ;          // dL/djoints [J + E, 3]
-  const float* gP;          // dL/dfull_pose [3J]
-  const float* extra_w;     // [E,3]: the extra joints' weights, for the direct transl term (read only with gJ)
-  int E;
-  double* dJ_out;           // dL/dJ_rest [J,3]
-};
 
 // what differs from body to body
 struct PoseBwdBody {
@@ -694,13 +640,11 @@ constexpr int kMaxNB = 1024;
 // dA_part [N][tiles][12 J + 3], dfeat [N][P], g_eff [N][3V] (the batched backward's ends here), then dJ and coef_part of the full
 // backward.  The single-body forward and vertices-only backward share ONE workspace: the forward blocks, then the backward blocks up
 // to dfeat, which therefore sit `fwd_total` further on.  Body n's saved block is the single-body one at n x saved_stride.
-struct Layout {
+struct Layout : SmplxGrids {
   size_t feat, part, fwd_total;                                                   // forward workspace
   size_t gvp, dA_part, dfeat, g_eff, dJ, coef_part, grad_total;                   // backward workspace
   size_t v_shaped, j_rest, shape_total;                                           // shape state
   size_t s_pose, s_A, s_vposed, saved_stride;                                     // saved by a forward for its backward
-  int P, rows, nblk, nb3;
-  int C, chunks, B, skin_chunks;                  // bodies per sweep over posedirs and per skinning workgroup (the instantiation), and their chunks
   size_t batch_grad_total() const { return dJ; }
   size_t single_total() const { return fwd_total + g_eff; }
 };
@@ -762,16 +706,38 @@ int check_common(const char* who, int V, int J, int hand_dim, int n_pca, const i
   return COMA_OK;
 }
 
-// Both forward entry points.  `batched` only says which workspace the ABI gives the call: the single-body one also holds the
-// vertices-only backward's blocks.
-int forward_impl(const char* who, bool batched, int N, size_t shape_stride, const float* theta, const float* transl, const float* posedirs,
-                 const float* weights, const int32_t* parents, const float* hand_components, const float* pose_mean, int V, int J, int hand_dim,
-                 int n_pca, const void* shape_state, float* vertices, float* joints, float* full_pose, void* saved, size_t saved_bytes,
-                 void* workspace, size_t workspace_bytes, void* stream) {
+int extra_joints_impl(const char* who, int N, const float* vertices, const float* transl, const int32_t* vertex_index, const float* vertex_weight,
+                      int V, int E, float* out, void* stream) {
+  if (N < 1 || N > kMaxBatch) return fail(COMA_E_INVALID, "%s: N=%d outside [1, %d]", who, N, kMaxBatch);
+  if (E == 0) return COMA_OK;
+  if (!vertices || !vertex_index || !vertex_weight || !out) return fail(COMA_E_INVALID, "%s: null pointer", who);
+  if (V < 1 || V > kMaxV || E < 0 || E > kMaxV) return fail(COMA_E_INVALID, "%s: bad sizes V=%d E=%d", who, V, E);
+  hipLaunchKernelGGL(smplx_gather_kernel, dim3((3 * E + kBlock - 1) / kBlock, N), dim3(kBlock), 0, (hipStream_t)stream, vertices, transl,
+                     vertex_index, vertex_weight, V, E, out);
+  return check_launch(who);
+}
+
+// the skinning backward on the caller's f32 gradient or on the f64 effective one
+template <typename TG>
+void launch_skin_bwd(const SmplxBackwardPlan& p, const TG* grad, hipStream_t s) {
+  SkinBwdArgs<TG> sb = {};
+  sb.weights = p.weights; sb.A = p.s_A; sb.v_posed = p.s_vposed; sb.grad = grad;
+  sb.V = p.V; sb.J = p.pose.J; sb.gvp = p.gvp; sb.dA_part = p.dA_part;
+  const auto skin_bwd = p.g.B == 1 ? smplx_skin_bwd_kernel<TG, 1> : smplx_skin_bwd_kernel<TG, kSkinChunk>;
+  hipLaunchKernelGGL(skin_bwd, dim3(p.g.nblk, p.g.skin_chunks), dim3(kTile), 0, s, sb, p.strides);
+}
+
+}  // namespace
+
+int smplx_forward_plan(const char* who, bool batched, int N, size_t shape_stride, const float* theta, const float* transl, const float* posedirs,
+                       const float* weights, const int32_t* parents, const float* hand_components, const float* pose_mean, int V, int J,
+                       int hand_dim, int n_pca, const void* shape_state, float* vertices, float* joints, float* full_pose, void* saved,
+                       size_t saved_bytes, void* workspace, size_t workspace_bytes, SmplxForwardPlan& p) {
   if (!theta || !posedirs || !weights || !parents || !shape_state || !vertices || !joints || !saved || !workspace)
     return fail(COMA_E_INVALID, "%s: null pointer", who);
   if (n_pca > 0 && hand_dim > 0 && !hand_components) return fail(COMA_E_INVALID, "%s: null pointer (hand_components with n_pca > 0)", who);
-  PoseArgs pa = {};
+  p = {};
+  PoseArgs& pa = p.pose;
   Layout L;
   if (int rc = check_common(who, V, J, hand_dim, n_pca, parents, pa.tree, N, 0, shape_state, shape_stride, L)) return rc;
   if (int rc = check_buffer(who, "saved state", saved, saved_bytes, N * L.saved_stride)) return rc;
@@ -779,57 +745,38 @@ int forward_impl(const char* who, bool batched, int N, size_t shape_stride, cons
   const char* st = (const char*)shape_state;
   char* sv = (char*)saved;
   char* ws = (char*)workspace;
-  hipStream_t s = (hipStream_t)stream;
-  const BatchStrides bs = {N, n_pca > 0 ? 3 * J - 2 * hand_dim + 2 * n_pca : 3 * J, shape_stride, L.saved_stride};
+  p.who = who; p.g = L; p.posedirs = posedirs; p.part = (double*)(ws + L.part);
+  p.strides = {N, n_pca > 0 ? 3 * J - 2 * hand_dim + 2 * n_pca : 3 * J, shape_stride, L.saved_stride};
   pa.theta = theta; pa.comps = hand_components; pa.mean = pose_mean; pa.transl = transl; pa.j_rest = (const double*)(st + L.j_rest);
   pa.J = J; pa.hd = hand_dim; pa.n_pca = n_pca; pa.s_pose = (double*)(sv + L.s_pose); pa.s_A = (double*)(sv + L.s_A);
   pa.feat = (double*)(ws + L.feat); pa.joints = joints; pa.full_pose = full_pose;
-  hipLaunchKernelGGL(smplx_pose_kernel, dim3(N), dim3(kBlock), 0, s, pa, bs);
-  const auto offsets = L.C == 1 ? smplx_offsets_kernel<1> : smplx_offsets_kernel<kChunk>;       // one body: no sums for absent ones
-  hipLaunchKernelGGL(offsets, dim3(L.nb3, kPSplit, L.chunks), dim3(kBlock), 0, s, posedirs, (const double*)(ws + L.feat), L.P, 3 * V, L.rows, N,
-                     (double*)(ws + L.part));
-  SkinArgs sa = {};
-  sa.weights = weights; sa.A = pa.s_A; sa.v_shaped = (const double*)(st + L.v_shaped); sa.part = (const double*)(ws + L.part); sa.transl = transl;
+  SkinArgs& sa = p.skin;
+  sa.weights = weights; sa.A = pa.s_A; sa.v_shaped = (const double*)(st + L.v_shaped); sa.part = p.part; sa.transl = transl;
   sa.V = V; sa.J = J; sa.v_posed = (double*)(sv + L.s_vposed); sa.vertices = vertices;
+  return COMA_OK;
+}
+
+int smplx_forward_enqueue(const SmplxForwardPlan& p, hipStream_t s) {
+  const SmplxGrids& L = p.g;
+  const int N = p.strides.N;
+  hipLaunchKernelGGL(smplx_pose_kernel, dim3(N), dim3(kBlock), 0, s, p.pose, p.strides);
+  const auto offsets = L.C == 1 ? smplx_offsets_kernel<1> : smplx_offsets_kernel<kChunk>;       // one body: no sums for absent ones
+  hipLaunchKernelGGL(offsets, dim3(L.nb3, kPSplit, L.chunks), dim3(kBlock), 0, s, p.posedirs, (const double*)p.pose.feat, L.P, 3 * p.skin.V, L.rows, N,
+                     p.part);
   const auto skin = L.B == 1 ? smplx_skin_kernel<1> : smplx_skin_kernel<kSkinChunk>;
-  hipLaunchKernelGGL(skin, dim3(L.nblk, L.skin_chunks), dim3(kTile), 0, s, sa, bs);
-  return check_launch(who);
+  hipLaunchKernelGGL(skin, dim3(L.nblk, L.skin_chunks), dim3(kTile), 0, s, p.skin, p.strides);
+  return check_launch(p.who);
 }
 
-// what the full and the batched backward take besides dL/dvertices; every pointer may be null
-struct FullBwd {
-  const float* grad_joints;
-  const float* grad_full_pose;
-  const int32_t* extra_index;
-  const float* extra_weight;
-  int E;
-  // the gradient to the coefficients, which the batched ABI does not have
-  const float* shapedirs;
-  const float* J_regressor;
-  int NB;
-  float* grad_coefficients;
-};
-
-template <typename TG>
-void launch_skin_bwd(const Layout& L, const BatchStrides& bs, const float* weights, const char* sv, const TG* grad, int V, int J, double* gvp,
-                     double* dA_part, hipStream_t s) {
-  SkinBwdArgs<TG> sb = {};
-  sb.weights = weights; sb.A = (const double*)(sv + L.s_A); sb.v_posed = (const double*)(sv + L.s_vposed); sb.grad = grad;
-  sb.V = V; sb.J = J; sb.gvp = gvp; sb.dA_part = dA_part;
-  const auto skin_bwd = L.B == 1 ? smplx_skin_bwd_kernel<TG, 1> : smplx_skin_bwd_kernel<TG, kSkinChunk>;
-  hipLaunchKernelGGL(skin_bwd, dim3(L.nblk, L.skin_chunks), dim3(kTile), 0, s, sb, bs);
-}
-
-// All three backward entry points.  `full` null is the vertices-only backward on the single-body workspace (its blocks behind the
-// forward's); otherwise the backward workspace from its start, up to g_eff for the batched ABI and whole for the full backward.
-int backward_impl(const char* who, bool batched, int N, size_t shape_stride, const float* grad_vertices, const float* posedirs,
-                  const float* weights, const int32_t* parents, const float* hand_components, int V, int J, int hand_dim, int n_pca,
-                  const void* shape_state, const void* saved, size_t saved_bytes, float* grad_theta, float* grad_transl, void* workspace,
-                  size_t workspace_bytes, void* stream, const FullBwd* full) {
+int smplx_backward_plan(const char* who, bool batched, int N, size_t shape_stride, const float* grad_vertices, const float* posedirs,
+                        const float* weights, const int32_t* parents, const float* hand_components, int V, int J, int hand_dim, int n_pca,
+                        const void* shape_state, const void* saved, size_t saved_bytes, float* grad_theta, float* grad_transl, void* workspace,
+                        size_t workspace_bytes, const FullBwd* full, SmplxBackwardPlan& p) {
   if ((!full && !grad_vertices) || !posedirs || !weights || !parents || !shape_state || !saved || !grad_theta || !grad_transl || !workspace)
     return fail(COMA_E_INVALID, "%s: null pointer", who);
   if (n_pca > 0 && hand_dim > 0 && !hand_components) return fail(COMA_E_INVALID, "%s: null pointer (hand_components with n_pca > 0)", who);
-  PoseBwdArgs pb = {};
+  p = {};
+  PoseBwdArgs& pb = p.pose;
   Layout L;
   if (int rc = check_common(who, V, J, hand_dim, n_pca, parents, pb.tree, N, full ? full->NB : 0, shape_state, shape_stride, L)) return rc;
   bool scatter = false, want_coef = false;
@@ -849,52 +796,51 @@ int backward_impl(const char* who, bool batched, int N, size_t shape_stride, con
   const char* st = (const char*)shape_state;
   const char* sv = (const char*)saved;
   char* ws = (char*)workspace + (full ? 0 : L.fwd_total);
-  hipStream_t s = (hipStream_t)stream;
-  const BatchStrides bs = {N, n_pca > 0 ? 3 * J - 2 * hand_dim + 2 * n_pca : 3 * J, shape_stride, L.saved_stride};
-  double* gvp = (double*)(ws + L.gvp);
-  double* dA_part = (double*)(ws + L.dA_part);
-  double* dfeat = (double*)(ws + L.dfeat);
+  p.who = who; p.g = L; p.V = V; p.posedirs = posedirs; p.weights = weights;
+  p.strides = {N, n_pca > 0 ? 3 * J - 2 * hand_dim + 2 * n_pca : 3 * J, shape_stride, L.saved_stride};
+  p.s_A = (const double*)(sv + L.s_A); p.s_vposed = (const double*)(sv + L.s_vposed); p.grad_vertices = grad_vertices;
+  p.gvp = (double*)(ws + L.gvp); p.dA_part = (double*)(ws + L.dA_part); p.dfeat = (double*)(ws + L.dfeat);
   if (scatter || !grad_vertices) {                          // only then does the gradient at the vertices differ from the caller's
-    double* g_eff = (double*)(ws + L.g_eff);
-    hipLaunchKernelGGL(smplx_effective_grad_kernel, dim3((V + kBlock - 1) / kBlock, N), dim3(kBlock), 0, s, grad_vertices,
-                       scatter ? full->grad_joints + 3 * (size_t)J : nullptr, 3 * (size_t)(J + full->E), full->extra_index, full->extra_weight, V,
-                       scatter ? full->E : 0, g_eff);
-    launch_skin_bwd<double>(L, bs, weights, sv, g_eff, V, J, gvp, dA_part, s);
-  } else {
-    launch_skin_bwd<float>(L, bs, weights, sv, grad_vertices, V, J, gvp, dA_part, s);
+    p.g_eff = (double*)(ws + L.g_eff);
+    p.gJ_extra = scatter ? full->grad_joints + 3 * (size_t)J : nullptr; p.gJ_stride = 3 * (size_t)(J + full->E);
+    p.extra_index = full->extra_index; p.extra_weight = full->extra_weight; p.E = scatter ? full->E : 0;
   }
-  const auto feature_bwd = L.C == 1 ? smplx_feature_bwd_kernel<1> : smplx_feature_bwd_kernel<kChunk>;
-  if (L.P > 0) hipLaunchKernelGGL(feature_bwd, dim3(L.P, L.chunks), dim3(kBlock), 0, s, posedirs, (const double*)gvp, 3 * V, L.P, N, dfeat);
   pb.s_pose = (const double*)(sv + L.s_pose); pb.j_rest = (const double*)(st + L.j_rest); pb.comps = hand_components;
-  pb.dA_part = dA_part; pb.dfeat = dfeat; pb.J = J; pb.hd = hand_dim; pb.n_pca = n_pca; pb.nblk = L.nblk;
+  pb.dA_part = p.dA_part; pb.dfeat = p.dfeat; pb.J = J; pb.hd = hand_dim; pb.n_pca = n_pca; pb.nblk = L.nblk;
   pb.grad_theta = grad_theta; pb.grad_transl = grad_transl;
   if (full) {
     pb.gJ = full->grad_joints; pb.gP = full->grad_full_pose; pb.extra_w = full->extra_weight; pb.E = scatter ? full->E : 0;
     pb.dJ_out = want_coef ? (double*)(ws + L.dJ) : nullptr;
   }
-  hipLaunchKernelGGL(smplx_pose_bwd_kernel, dim3(N), dim3(kBlock), 0, s, pb, bs);
   if (want_coef) {
-    double* part = (double*)(ws + L.coef_part);
-    hipLaunchKernelGGL(smplx_shape_bwd_kernel, dim3(L.nb3), dim3(kBlock), 0, s, full->shapedirs, full->J_regressor, (const double*)gvp,
-                       (const double*)(ws + L.dJ), V, J, full->NB, part);
-    hipLaunchKernelGGL(smplx_coef_sum_kernel, dim3((full->NB + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (const double*)part, L.nb3, full->NB,
-                       full->grad_coefficients);
+    p.shapedirs = full->shapedirs; p.J_regressor = full->J_regressor; p.NB = full->NB;
+    p.coef_part = (double*)(ws + L.coef_part); p.grad_coefficients = full->grad_coefficients;
   }
-  return check_launch(who);
+  return COMA_OK;
 }
 
-int extra_joints_impl(const char* who, int N, const float* vertices, const float* transl, const int32_t* vertex_index, const float* vertex_weight,
-                      int V, int E, float* out, void* stream) {
-  if (N < 1 || N > kMaxBatch) return fail(COMA_E_INVALID, "%s: N=%d outside [1, %d]", who, N, kMaxBatch);
-  if (E == 0) return COMA_OK;
-  if (!vertices || !vertex_index || !vertex_weight || !out) return fail(COMA_E_INVALID, "%s: null pointer", who);
-  if (V < 1 || V > kMaxV || E < 0 || E > kMaxV) return fail(COMA_E_INVALID, "%s: bad sizes V=%d E=%d", who, V, E);
-  hipLaunchKernelGGL(smplx_gather_kernel, dim3((3 * E + kBlock - 1) / kBlock, N), dim3(kBlock), 0, (hipStream_t)stream, vertices, transl,
-                     vertex_index, vertex_weight, V, E, out);
-  return check_launch(who);
+int smplx_backward_enqueue(const SmplxBackwardPlan& p, hipStream_t s) {
+  const SmplxGrids& L = p.g;
+  const int N = p.strides.N, V = p.V, J = p.pose.J;
+  if (p.g_eff) {
+    hipLaunchKernelGGL(smplx_effective_grad_kernel, dim3((V + kBlock - 1) / kBlock, N), dim3(kBlock), 0, s, p.grad_vertices, p.gJ_extra, p.gJ_stride,
+                       p.extra_index, p.extra_weight, V, p.E, p.g_eff);
+    launch_skin_bwd<double>(p, p.g_eff, s);
+  } else {
+    launch_skin_bwd<float>(p, p.grad_vertices, s);
+  }
+  const auto feature_bwd = L.C == 1 ? smplx_feature_bwd_kernel<1> : smplx_feature_bwd_kernel<kChunk>;
+  if (L.P > 0) hipLaunchKernelGGL(feature_bwd, dim3(L.P, L.chunks), dim3(kBlock), 0, s, p.posedirs, (const double*)p.gvp, 3 * V, L.P, N, p.dfeat);
+  hipLaunchKernelGGL(smplx_pose_bwd_kernel, dim3(N), dim3(kBlock), 0, s, p.pose, p.strides);
+  if (p.grad_coefficients) {
+    hipLaunchKernelGGL(smplx_shape_bwd_kernel, dim3(L.nb3), dim3(kBlock), 0, s, p.shapedirs, p.J_regressor, (const double*)p.gvp,
+                       (const double*)p.pose.dJ_out, V, J, p.NB, p.coef_part);
+    hipLaunchKernelGGL(smplx_coef_sum_kernel, dim3((p.NB + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (const double*)p.coef_part, L.nb3, p.NB,
+                       p.grad_coefficients);
+  }
+  return check_launch(p.who);
 }
 
-}  // namespace
 }  // namespace coma
 
 using namespace coma;
@@ -928,8 +874,11 @@ extern "C" int coma_smplx_forward_f32(const float* theta, const float* transl, c
                                       const float* hand_components, const float* pose_mean, int V, int J, int hand_dim, int n_pca,
                                       const void* shape_state, float* vertices, float* joints, float* full_pose, void* saved, size_t saved_bytes,
                                       void* workspace, size_t workspace_bytes, void* stream) {
-  return forward_impl("coma_smplx_forward_f32", false, 1, 0, theta, transl, posedirs, weights, parents, hand_components, pose_mean, V, J, hand_dim,
-                      n_pca, shape_state, vertices, joints, full_pose, saved, saved_bytes, workspace, workspace_bytes, stream);
+  SmplxForwardPlan p;
+  if (int rc = smplx_forward_plan("coma_smplx_forward_f32", false, 1, 0, theta, transl, posedirs, weights, parents, hand_components, pose_mean, V, J,
+                                  hand_dim, n_pca, shape_state, vertices, joints, full_pose, saved, saved_bytes, workspace, workspace_bytes, p))
+    return rc;
+  return smplx_forward_enqueue(p, (hipStream_t)stream);
 }
 
 extern "C" int coma_smplx_forward_batch_f32(const float* theta, const float* transl, const float* posedirs, const float* weights,
@@ -937,16 +886,23 @@ extern "C" int coma_smplx_forward_batch_f32(const float* theta, const float* tra
                                             int hand_dim, int n_pca, int N, const void* shape_state, size_t shape_stride, float* vertices,
                                             float* joints, float* full_pose, void* saved, size_t saved_bytes, void* workspace,
                                             size_t workspace_bytes, void* stream) {
-  return forward_impl("coma_smplx_forward_batch_f32", true, N, shape_stride, theta, transl, posedirs, weights, parents, hand_components, pose_mean, V,
-                      J, hand_dim, n_pca, shape_state, vertices, joints, full_pose, saved, saved_bytes, workspace, workspace_bytes, stream);
+  SmplxForwardPlan p;
+  if (int rc = smplx_forward_plan("coma_smplx_forward_batch_f32", true, N, shape_stride, theta, transl, posedirs, weights, parents, hand_components,
+                                  pose_mean, V, J, hand_dim, n_pca, shape_state, vertices, joints, full_pose, saved, saved_bytes, workspace,
+                                  workspace_bytes, p))
+    return rc;
+  return smplx_forward_enqueue(p, (hipStream_t)stream);
 }
 
 extern "C" int coma_smplx_backward_f32(const float* grad_vertices, const float* posedirs, const float* weights, const int32_t* parents,
                                        const float* hand_components, int V, int J, int hand_dim, int n_pca, const void* shape_state,
                                        const void* saved, size_t saved_bytes, float* grad_theta, float* grad_transl, void* workspace,
                                        size_t workspace_bytes, void* stream) {
-  return backward_impl("coma_smplx_backward_f32", false, 1, 0, grad_vertices, posedirs, weights, parents, hand_components, V, J, hand_dim, n_pca,
-                       shape_state, saved, saved_bytes, grad_theta, grad_transl, workspace, workspace_bytes, stream, nullptr);
+  SmplxBackwardPlan p;
+  if (int rc = smplx_backward_plan("coma_smplx_backward_f32", false, 1, 0, grad_vertices, posedirs, weights, parents, hand_components, V, J, hand_dim,
+                                   n_pca, shape_state, saved, saved_bytes, grad_theta, grad_transl, workspace, workspace_bytes, nullptr, p))
+    return rc;
+  return smplx_backward_enqueue(p, (hipStream_t)stream);
 }
 
 extern "C" int coma_smplx_backward_full_f32(const float* grad_vertices, const float* grad_joints, const float* grad_full_pose,
@@ -956,8 +912,11 @@ extern "C" int coma_smplx_backward_full_f32(const float* grad_vertices, const fl
                                             const void* saved, size_t saved_bytes, float* grad_theta, float* grad_transl,
                                             float* grad_coefficients, void* workspace, size_t workspace_bytes, void* stream) {
   const FullBwd full = {grad_joints, grad_full_pose, extra_index, extra_weight, E, shapedirs, J_regressor, NB, grad_coefficients};
-  return backward_impl("coma_smplx_backward_full_f32", false, 1, 0, grad_vertices, posedirs, weights, parents, hand_components, V, J, hand_dim,
-                       n_pca, shape_state, saved, saved_bytes, grad_theta, grad_transl, workspace, workspace_bytes, stream, &full);
+  SmplxBackwardPlan p;
+  if (int rc = smplx_backward_plan("coma_smplx_backward_full_f32", false, 1, 0, grad_vertices, posedirs, weights, parents, hand_components, V, J,
+                                   hand_dim, n_pca, shape_state, saved, saved_bytes, grad_theta, grad_transl, workspace, workspace_bytes, &full, p))
+    return rc;
+  return smplx_backward_enqueue(p, (hipStream_t)stream);
 }
 
 extern "C" int coma_smplx_backward_batch_f32(const float* grad_vertices, const float* grad_joints, const float* grad_full_pose,
@@ -966,8 +925,12 @@ extern "C" int coma_smplx_backward_batch_f32(const float* grad_vertices, const f
                                              int N, const void* shape_state, size_t shape_stride, const void* saved, size_t saved_bytes,
                                              float* grad_theta, float* grad_transl, void* workspace, size_t workspace_bytes, void* stream) {
   const FullBwd full = {grad_joints, grad_full_pose, extra_index, extra_weight, E, nullptr, nullptr, 0, nullptr};
-  return backward_impl("coma_smplx_backward_batch_f32", true, N, shape_stride, grad_vertices, posedirs, weights, parents, hand_components, V, J,
-                       hand_dim, n_pca, shape_state, saved, saved_bytes, grad_theta, grad_transl, workspace, workspace_bytes, stream, &full);
+  SmplxBackwardPlan p;
+  if (int rc = smplx_backward_plan("coma_smplx_backward_batch_f32", true, N, shape_stride, grad_vertices, posedirs, weights, parents, hand_components,
+                                   V, J, hand_dim, n_pca, shape_state, saved, saved_bytes, grad_theta, grad_transl, workspace, workspace_bytes, &full,
+                                   p))
+    return rc;
+  return smplx_backward_enqueue(p, (hipStream_t)stream);
 }
 
 extern "C" int coma_smplx_extra_joints_f32(const float* vertices, const float* transl, const int32_t* vertex_index, const float* vertex_weight,

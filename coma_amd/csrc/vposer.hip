@@ -18,8 +18,8 @@
 // per workgroup, one per lane; wave w of the 16 adds the rows o = w, w + 16, ... of its column in ascending order (a row's 64 columns
 // are consecutive in memory), and the 16 partial sums are added in ascending w through LDS.  No floating-point atomics: two calls
 // give the same bits.
-#include "common.h"
 #include "coma_device.h"
+#include "fit_stages.h"
 
 #include <cmath>
 
@@ -320,6 +320,56 @@ int prior_args(const char* who, int N, int P, const int32_t* index, const float*
 }
 
 }  // namespace
+
+int vposer_decode_plan(const char* who, const float* z, const float* W1, const float* b1, const float* W2, const float* b2, const float* W3,
+                       const float* b3, int N, int D, int H, int NJ, float* aa, float* matrices, int8_t* branch, void* saved, size_t saved_bytes,
+                       VposerDecodePlan& p) {
+  if (!z || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !aa || !saved) return fail(COMA_E_INVALID, "%s: null pointer", who);
+  if (int rc = check_sizes(who, N, D, H, NJ)) return rc;
+  if (!f32_aligned({z, W1, b1, W2, b2, W3, b3, aa, matrices})) return fail(COMA_E_INVALID, "%s: an f32 buffer is not 4-byte aligned", who);
+  const Layout L = layout(N, H, NJ);
+  if (int rc = check_buffer(who, "saved state", saved, saved_bytes, L.saved_total)) return rc;
+  char* sv = (char*)saved;
+  p = {who, z, W1, b1, W2, b2, W3, b3, N, D, H, NJ, (double*)(sv + L.h1), (double*)(sv + L.h2), (double*)(sv + L.o), (int8_t*)(sv + L.branch),
+       aa, matrices, branch};
+  return COMA_OK;
+}
+
+int vposer_decode_enqueue(const VposerDecodePlan& p, hipStream_t s) {
+  linear(s, p.z, p.W1, p.b1, p.N, p.D, p.H, 1, p.h1);
+  linear(s, (const double*)p.h1, p.W2, p.b2, p.N, p.H, p.H, 1, p.h2);
+  linear(s, (const double*)p.h2, p.W3, p.b3, p.N, p.H, 6 * p.NJ, 0, p.o);
+  const int total = p.N * p.NJ;
+  hipLaunchKernelGGL(vposer_tail_kernel, dim3((total + 255) / 256), dim3(256), 0, s, (const double*)p.o, total, p.aa, p.matrices, p.branch,
+                     p.saved_branch);
+  return check_launch(p.who);
+}
+
+int vposer_decode_backward_plan(const char* who, const float* grad_aa, const float* W1, const float* W2, const float* W3, int N, int D, int H,
+                                int NJ, const void* saved, size_t saved_bytes, float* grad_z, void* workspace, size_t workspace_bytes,
+                                VposerDecodeBackwardPlan& p) {
+  if (!grad_aa || !W1 || !W2 || !W3 || !saved || !grad_z || !workspace) return fail(COMA_E_INVALID, "%s: null pointer", who);
+  if (int rc = check_sizes(who, N, D, H, NJ)) return rc;
+  if (!f32_aligned({grad_aa, W1, W2, W3, grad_z})) return fail(COMA_E_INVALID, "%s: an f32 buffer is not 4-byte aligned", who);
+  const Layout L = layout(N, H, NJ);
+  if (int rc = check_buffer(who, "saved state", saved, saved_bytes, L.saved_total)) return rc;
+  if (int rc = check_buffer(who, "workspace", workspace, workspace_bytes, L.total)) return rc;
+  const char* sv = (const char*)saved;
+  char* ws = (char*)workspace;
+  p = {who, grad_aa, W1, W2, W3, N, D, H, NJ, (const double*)(sv + L.h1), (const double*)(sv + L.h2), (const double*)(sv + L.o),
+       (const int8_t*)(sv + L.branch), (double*)(ws + L.a), (double*)(ws + L.b), (double*)(ws + L.c), grad_z};
+  return COMA_OK;
+}
+
+int vposer_decode_backward_enqueue(const VposerDecodeBackwardPlan& p, hipStream_t s) {
+  const int total = p.N * p.NJ;
+  hipLaunchKernelGGL(vposer_tail_bwd_kernel, dim3((total + 255) / 256), dim3(256), 0, s, p.o, p.saved_branch, p.grad_aa, total, p.go);
+  linear_t(s, p.go, p.W3, p.h2, p.N, p.H, 6 * p.NJ, p.gh2, nullptr);
+  linear_t(s, p.gh2, p.W2, p.h1, p.N, p.H, p.H, p.gh1, nullptr);
+  linear_t(s, p.gh1, p.W1, nullptr, p.N, p.D, p.H, nullptr, p.grad_z);
+  return check_launch(p.who);
+}
+
 }  // namespace coma
 
 using namespace coma;
@@ -330,45 +380,19 @@ extern "C" size_t coma_vposer_workspace_bytes(int N, int H, int NJ) { return siz
 extern "C" int coma_vposer_decode_f32(const float* z, const float* W1, const float* b1, const float* W2, const float* b2, const float* W3,
                                       const float* b3, int N, int D, int H, int NJ, float* aa, float* matrices, int8_t* branch, void* saved,
                                       size_t saved_bytes, void* stream) {
-  const char* who = "coma_vposer_decode_f32";
-  if (!z || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !aa || !saved) return fail(COMA_E_INVALID, "%s: null pointer", who);
-  if (int rc = check_sizes(who, N, D, H, NJ)) return rc;
-  if (!f32_aligned({z, W1, b1, W2, b2, W3, b3, aa, matrices})) return fail(COMA_E_INVALID, "%s: an f32 buffer is not 4-byte aligned", who);
-  const Layout L = layout(N, H, NJ);
-  if (int rc = check_buffer(who, "saved state", saved, saved_bytes, L.saved_total)) return rc;
-  char* sv = (char*)saved;
-  hipStream_t s = (hipStream_t)stream;
-  double *h1 = (double*)(sv + L.h1), *h2 = (double*)(sv + L.h2), *o = (double*)(sv + L.o);
-  linear(s, z, W1, b1, N, D, H, 1, h1);
-  linear(s, (const double*)h1, W2, b2, N, H, H, 1, h2);
-  linear(s, (const double*)h2, W3, b3, N, H, 6 * NJ, 0, o);
-  const int total = N * NJ;
-  hipLaunchKernelGGL(vposer_tail_kernel, dim3((total + 255) / 256), dim3(256), 0, s, (const double*)o, total, aa, matrices, branch,
-                     (int8_t*)(sv + L.branch));
-  return check_launch(who);
+  VposerDecodePlan p;
+  if (int rc = vposer_decode_plan("coma_vposer_decode_f32", z, W1, b1, W2, b2, W3, b3, N, D, H, NJ, aa, matrices, branch, saved, saved_bytes, p)) return rc;
+  return vposer_decode_enqueue(p, (hipStream_t)stream);
 }
 
 extern "C" int coma_vposer_decode_backward_f32(const float* grad_aa, const float* W1, const float* W2, const float* W3, int N, int D, int H,
                                                int NJ, const void* saved, size_t saved_bytes, float* grad_z, void* workspace,
                                                size_t workspace_bytes, void* stream) {
-  const char* who = "coma_vposer_decode_backward_f32";
-  if (!grad_aa || !W1 || !W2 || !W3 || !saved || !grad_z || !workspace) return fail(COMA_E_INVALID, "%s: null pointer", who);
-  if (int rc = check_sizes(who, N, D, H, NJ)) return rc;
-  if (!f32_aligned({grad_aa, W1, W2, W3, grad_z})) return fail(COMA_E_INVALID, "%s: an f32 buffer is not 4-byte aligned", who);
-  const Layout L = layout(N, H, NJ);
-  if (int rc = check_buffer(who, "saved state", saved, saved_bytes, L.saved_total)) return rc;
-  if (int rc = check_buffer(who, "workspace", workspace, workspace_bytes, L.total)) return rc;
-  const char* sv = (const char*)saved;
-  char* ws = (char*)workspace;
-  hipStream_t s = (hipStream_t)stream;
-  const double *h1 = (const double*)(sv + L.h1), *h2 = (const double*)(sv + L.h2), *o = (const double*)(sv + L.o);
-  double *go = (double*)(ws + L.a), *gh2 = (double*)(ws + L.b), *gh1 = (double*)(ws + L.c);
-  const int total = N * NJ;
-  hipLaunchKernelGGL(vposer_tail_bwd_kernel, dim3((total + 255) / 256), dim3(256), 0, s, o, (const int8_t*)(sv + L.branch), grad_aa, total, go);
-  linear_t(s, go, W3, h2, N, H, 6 * NJ, gh2, nullptr);
-  linear_t(s, gh2, W2, h1, N, H, H, gh1, nullptr);
-  linear_t(s, gh1, W1, nullptr, N, D, H, nullptr, grad_z);
-  return check_launch(who);
+  VposerDecodeBackwardPlan p;
+  if (int rc = vposer_decode_backward_plan("coma_vposer_decode_backward_f32", grad_aa, W1, W2, W3, N, D, H, NJ, saved, saved_bytes, grad_z, workspace,
+                                           workspace_bytes, p))
+    return rc;
+  return vposer_decode_backward_enqueue(p, (hipStream_t)stream);
 }
 
 extern "C" int coma_vposer_encode_f32(const float* pose, const float* bn1, const float* W1, const float* b1, const float* bn2, const float* W2,

@@ -730,8 +730,9 @@ int coma_angle_prior_backward_f32(const float* pose, const float* grad_out, int 
 /* The fitting app's whole Adam loop: E iterations of decode -> skin -> objective -> backward -> Adam enqueued by one call (N = 1).
  * replaces: the loop of src/application/optimize.py:252-307 with the parameter set of :236-250 and torch.optim.Adam, i.e. what
  *           this repository's fit() drives from Python through four autograd Functions and torch's optimiser.
- * Every stage is the existing entry point, called from C on the caller's stream with buffers carved from ONE workspace; the new
- * kernels only move numbers between them and take the step.  PINNED against the reference's own parts (its vendored SMPLX class and
+ * Every stage is the existing entry point in two halves (csrc/fit_stages.h): its argument checks, made ONCE per call on buffers
+ * carved from ONE workspace, and its launches, enqueued per iteration on the caller's stream; the new kernels only move numbers
+ * between the stages and take the step.  PINNED against the reference's own parts (its vendored SMPLX class and
  * VPoser class, SMPLifyAnglePrior, the objective's own lines, torch.optim.Adam) run on the CPU in f64
  * (tests/golden/app_fit_golden.npz), through the f64 restatement tests/fit_ref.py.
  *   parameters     p f64 [P] = [global_orient 3 | transl 3 | left hand hs | right hand hs | embedding D], hs = n_pca when n_pca > 0,
@@ -781,9 +782,12 @@ int coma_angle_prior_backward_f32(const float* pose, const float* grad_out, int 
  * refuse the sizes or n_theta = 3 NJ + 12 + 2 hs is outside [3 NJ + 12, 3 NJ + 12 + 192]: hs <= 96); it holds theta, z, aa, the raw vertices, both models' saved
  * blocks and workspaces, the objective's workspace, terms, g_o, g_c, g and every gradient: no allocation inside the call.
  * Refused before any launch (COMA_E_INVALID, nothing written): a NULL descriptor, state or workspace, or required pointer; E outside
- * [1, 4096]; sizes the called entry points refuse (V, F, J, k, hand_dim, n_pca, a bad parent, D, H, NJ, the prior's K or an index
- * outside [0, 3 NJ)); 3 NJ + 12 != 3 J - 2 hand_dim; P != 6 + 2 hs + D; eps < 0 or principle vectors that are not orthogonal; a
- * non-finite lr, weight or scale_factor; a state or workspace too small or misaligned. */
+ * [1, 4096]; D outside [1, 256]; more than 96 entries per hand; EVERYTHING the five called entry points refuse of their own arguments,
+ * by their own checks and in their own words under this call's name (V, F, J, k, hand_dim, n_pca, a bad parent, H, NJ, a misaligned
+ * f32 buffer or shape state, eps < 0, principle vectors that are not orthogonal, ...): those checks are made once, before the loop,
+ * and not again per iteration; 3 NJ + 12 != 3 J - 2 hand_dim; P != 6 + 2 hs + D; the prior's K outside [1, 16] or an index outside
+ * [0, 3 NJ); a non-finite lr, weight or scale_factor; a state or workspace too small or misaligned; traj, losses, grad0 not 8-byte or
+ * vertices, lead_fixed not 4-byte aligned. */
 typedef struct coma_app_fit_desc {
   /* body model: coma_smplx_forward_f32 / coma_smplx_backward_f32 */
   const float* posedirs;

@@ -967,7 +967,8 @@ _optrows = lambda: [("null pointer", dict(front=0)), ("null pointer", dict(traj=
                     ("outside [0, 65536]", dict(J=0)), ("outside [0, 65536]", dict(J=1025)), ("outside [0, 65536]", dict(n_views=-1)),
                     ("are read when N > 0", dict(views=0)), ("are read when N > 0", dict(joints0=0)), ("are read when N > 0", dict(cand_view=0)),
                     ("are read when N > 0", dict(cand_xy=0)), ("are read when N > 0", dict(n_views=0)),
-                    ("must be finite", dict(d0=NAN)), ("must be finite", dict(lr=INF)), ("must be finite", dict(w_multiview=NAN)), ("must be finite", dict(w_collision=-INF))]
+                    ("must be finite", dict(d0=NAN)), ("must be finite", dict(lr=INF)), ("must be finite", dict(w_multiview=NAN)), ("must be finite", dict(w_collision=-INF)),
+                    ("must be finite", dict(lr=NAN))]       # the rows above are one check function's: the same words after either name
 REFUSALS = {
     "coma_raster_depth_f64": (_RAST, [
         ("null pointer", dict(verts=0)), ("null pointer", dict(faces=0)), ("null pointer", dict(R=0)), ("null pointer", dict(t=0)), ("null pointer", dict(workspace=0)),
@@ -1043,6 +1044,10 @@ def argument_check_sites():
     import re
     root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "coma_amd", "csrc")
     sites = sum(len(re.findall(r"fail\(COMA_E_INVALID", open(os.path.join(root, f)).read())) for f in ("raster.hip", "mesh_volume.hip", "depth_opt.hip"))
+    # the two depth optimisers share one check function that takes their name: each of its sites is one site of either entry point
+    depth = open(os.path.join(root, "depth_opt.hip")).read()
+    shared = re.search(r"\nstatic int depth_optimize_check\(.*?\n}\n", depth, re.S).group(0)
+    sites += (len(re.findall(r"depth_optimize_check\(who,", depth)) - 1) * len(re.findall(r"fail\(COMA_E_INVALID", shared))
     host = {(e, t) for e, (_, rows) in REFUSALS.items() for t, _ in rows}
     return len(host) + CAMERA_ROWS + len(STATUS_REFUSALS) + sum(len(v) for v in STATUS_TEXTS.values()), sites
 

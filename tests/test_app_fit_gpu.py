@@ -287,7 +287,11 @@ def test_refusals_write_nothing(golden):
              (dict(vertices=None), "null pointer"), (dict(parents=None), "null pointer"), (dict(targets=None), "selected / targets"),
              (dict(state_bytes=fit._state_bytes - 16), "state of"), (dict(ws_bytes=fit._ws_bytes - 16), "workspace of"),
              (dict(state_at=C.c_void_p(state.data_ptr() + 8)), "state must be 16-byte aligned"), (dict(ws_at=C.c_void_p(ws.data_ptr() + 4)), "workspace must be 16-byte aligned"),
-             (dict(state_at=None, ws_at=C.c_void_p(0)), "null pointer")]
+             (dict(state_at=None, ws_at=C.c_void_p(0)), "null pointer"),
+             # refusals of a stage alone (the decoder's alignment, the objective's bound on F): from its plan, before the first launch
+             (dict(W1=fit.decoder._w["bodyprior_dec_fc1.weight"].data_ptr() + 2), "4-byte aligned"),
+             (dict(b3=fit.decoder._w["bodyprior_dec_out.bias"].data_ptr() + 2), "4-byte aligned"),
+             (dict(F=715827883), "F=715827883")]
     for kw, text in cases:
         rc, said = call(**kw)
         assert rc == -1 and text in said and said.startswith("coma_app_fit_f32: "), (kw, said)

@@ -150,7 +150,9 @@ REFUSALS = [(dict(E=0), "E=0 outside [1, 4096]"), (dict(E=4097), "E=4097 outside
             (dict(posedirs=None), "null pointer"), (dict(shape_state=None), "null pointer"), (dict(lead_fixed=None), "null pointer"),
             (dict(W3=None), "null pointer"), (dict(prior_sign=None), "null pointer"), (dict(vf_faces=None), "null pointer"),
             (dict(losses=None), "null pointer"), (dict(vertices=None), "null pointer"), (dict(hand_components=None), "hand_components"),
-            (dict(selected=None), "selected / targets"), (dict(shape_state=24), "shape state must be 16-byte aligned"), (dict(traj=20), "8-byte")]
+            (dict(selected=None), "selected / targets"), (dict(shape_state=24), "shape state must be 16-byte aligned"), (dict(traj=20), "8-byte"),
+            # refusals of a stage alone, which the fit never restated: they come from the stage's plan, before the first launch
+            (dict(W1=18), "4-byte aligned"), (dict(b3=18), "4-byte aligned"), (dict(F=715827883), "F=715827883")]
 
 
 @pytest.mark.parametrize("over, text", REFUSALS, ids=[",".join(f"{k}={v}" for k, v in o.items()) for o, _ in REFUSALS])
